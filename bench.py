@@ -48,6 +48,7 @@ ALGO_BYTES_PER_IMAGE = C * H * W * 4 + N_MC * H * W * 4 + 8
 K1_BOUNDARY_BYTES_PER_IMAGE = C * H * W * 4 + N_MC * (H * W + 2) * 4 + C * 8
 
 
+DUMP_MAX_BYTES = 64 << 20  # --dump-outputs: all .npy files of one run together
 CONTRACT_MAX_BYTES = 4096  # the driver keeps ~8 KB of stdout: the contract line stays well inside it
 DETAIL_FILE = "bench_detail.json"
 _TOP_KEYS = ("metric", "value", "unit", "n_gpus", "steps", "warmup", "ms_per_step", "higher_is_better", "scaling",
@@ -155,6 +156,32 @@ def emit_record(full, saved_stdout=None):
     return text
 
 
+def dump_outputs(d, arrays, seed=0):
+    """--dump-outputs DIR: every array of `arrays` ({name: ndarray}) -> DIR/<name>.npy, float32 kept and every other dtype as
+    float64, at most DUMP_MAX_BYTES in all.  An array larger than its even share of that budget is replaced by a fixed,
+    seeded sample of its rows (same rows on every run with the same shape).  Returns what was written, for the record."""
+    import numpy as np
+
+    os.makedirs(d, exist_ok=True)
+    share = (DUMP_MAX_BYTES - 1024 * len(arrays)) // max(1, len(arrays))  # 1 KB per file for the .npy header
+    info = {}
+    for name, a in arrays.items():
+        a = np.asarray(a)
+        a = a.astype(np.float32 if a.dtype == np.float32 else np.float64, copy=False)
+        rows = a.shape[0] if a.ndim else 1
+        row_bytes = max(1, a.nbytes // max(1, rows))
+        rec = {"file": f"{name}.npy", "shape": list(a.shape), "dtype": str(a.dtype)}
+        if a.nbytes > share:
+            keep = max(1, share // row_bytes)
+            idx = np.sort(np.random.default_rng(seed).choice(rows, size=keep, replace=False))
+            a = a[idx]
+            rec["sampled_rows"] = {"kept": int(keep), "of": int(rows), "seed": seed,
+                                   "how": "np.sort(np.random.default_rng(seed).choice(rows, kept, replace=False))"}
+        np.save(os.path.join(d, f"{name}.npy"), np.ascontiguousarray(a))
+        info[name] = rec
+    return {"dir": os.path.abspath(d), "arrays": info}
+
+
 def parse_args():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -207,7 +234,14 @@ def parse_args():
                          "p2p (opt-in, never chosen by auto): the one-shot gather of csrc/p2p.hip instead of RCCL - every "
                          "rank writes its shard into the peers' IPC-mapped buffers over xGMI, two launches on the compute "
                          "stream (runia_core_amd.distributed.OneShotGather)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last timed step computed (cfg2: the (N,) float64 LaREM "
+                         "scores, all ranks gathered) as DIR/<name>.npy; inputs are seeded, so two builds compare output for output")
     args = ap.parse_args()
+    if args.dump_outputs is not None and args.workload != "cfg2":
+        ap.error("--dump-outputs is implemented for --workload cfg2 only")
+    if args.steps is not None and args.steps < 1:
+        ap.error("--steps must be at least 1")
     if args.steps is None:
         args.steps = {"cfg2": 200, "cfg3": 3, "larex_eval": 1, "baselines_eval": 1}[args.workload]
     if args.warmup is None:
@@ -741,6 +775,8 @@ def main():
 
     ms_per_step = 1e3 * elapsed / args.steps
     value = world * n * args.steps / elapsed
+    # the last timed step's scores (a fresh tensor per step; with N > 1 the gathered buffer, not rewritten since)
+    dumped = dump_outputs(args.dump_outputs, {"scores": scores.cpu().numpy()}) if args.dump_outputs else None
 
     # ---------------- API level: the public batched entry point, no caller-supplied draws ---------------------------
     api = None
@@ -870,6 +906,8 @@ def main():
                              (" (chosen by the warm-up trial)" if (use_dist and args.gather_stream == "auto") else "")},
         "roofline": roofline,
     }
+    if dumped is not None:
+        out["dumped_outputs"] = dumped
     if gather_info is not None:
         out["gather"] = gather_info
     if api is not None:

@@ -98,7 +98,9 @@ def test_argument_checks_come_before_any_launch():
     assert lib.runia_error_string(WORKSPACE) and lib.runia_error_string(INVALID)
 
 
-def test_product_path_fails_loudly_without_gpu():
+def test_product_path_fails_loudly_without_gpu(monkeypatch):
+    # no HIP device visible, also on a box that has one: every check of the product reads torch.cuda.is_available()
+    monkeypatch.setattr(torch.cuda, "is_available", lambda: False)
     with pytest.raises(_hip.RuniaHipError, match="no CPU fallback"):
         _hip.require_gpu()
     md = MDLatentSpace()

@@ -84,7 +84,9 @@ def test_oracle_all_baselines_reference_means(golden_means):
 
 @pytest.mark.parametrize("tag", ["unit", "wide"])
 def test_oracle_all_baselines_vs_the_reference_run(tag):
-    """The oracle's loop against what the reference's own calculate_all_baselines returned here (by-path run)."""
+    """The oracle's loop against what the reference's own calculate_all_baselines returned here (by-path run).  ddu of the
+    "unit" case is the reference's ill-posed test recipe (see _close): its float32 Cholesky round-off, and so the scores, move
+    by a few per cent with the host CPU's LAPACK code path, for the oracle as for the product (test_calculate_all_baselines_vs_the_reference_run)."""
     g, ind, ood, fc, classes = _ref_case(tag)
     with warnings.catch_warnings():
         warnings.simplefilter("ignore")
@@ -96,7 +98,7 @@ def test_oracle_all_baselines_vs_the_reference_run(tag):
                     ind["valid features"] if split == "valid" else ood[f"{split} features"], copy=True), 90), fc["weight"], fc["bias"])
                 assert _close(e, g[f"{tag}/{split}/{name}"], name), (name, split)
                 continue
-            assert _close(got[name][split], g[f"{tag}/{split}/{name}"], name), (name, split)
+            assert _close(got[name][split], g[f"{tag}/{split}/{name}"], name, ill_posed=(tag == "unit")), (name, split)
 
 
 def test_get_labels_from_logits_branches():

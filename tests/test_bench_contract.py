@@ -180,3 +180,37 @@ def test_world_size_must_match_gpus(monkeypatch):
     with pytest.raises(SystemExit) as e:
         bench.main()
     assert "WORLD_SIZE=2" in str(e.value.code)
+
+
+def test_dump_outputs_writes_float_npy_within_budget_and_samples_the_same_rows(tmp_path, monkeypatch):
+    """--dump-outputs: float32 stays float32, everything else becomes float64; an array over its share of the budget is
+    cut to a seeded sample of rows that is the same on every call, and the files together stay inside the budget."""
+    import numpy as np
+
+    small = np.arange(10, dtype=np.float64) * 0.5
+    half = np.arange(6, dtype=np.float32)
+    big = np.random.default_rng(1).standard_normal((5000, 8))
+    monkeypatch.setattr(bench, "DUMP_MAX_BYTES", 3 * 1024 + 3 * 64 * 1024)
+    a = bench.dump_outputs(str(tmp_path / "a"), {"scores": small, "half": half, "ints": np.arange(4), "big": big})
+    got = {n: np.load(tmp_path / "a" / f"{n}.npy") for n in ("scores", "half", "ints", "big")}
+    assert np.array_equal(got["scores"], small) and got["scores"].dtype == np.float64
+    assert np.array_equal(got["half"], half) and got["half"].dtype == np.float32
+    assert got["ints"].dtype == np.float64 and np.array_equal(got["ints"], np.arange(4))
+    assert got["big"].shape[1] == 8 and 0 < got["big"].shape[0] < 5000 and "sampled_rows" in a["arrays"]["big"]
+    assert "sampled_rows" not in a["arrays"]["scores"]
+    assert sum(os.path.getsize(tmp_path / "a" / f"{n}.npy") for n in got) <= bench.DUMP_MAX_BYTES
+    rows = {tuple(r) for r in big.tolist()}
+    assert all(tuple(r) in rows for r in got["big"].tolist())
+    bench.dump_outputs(str(tmp_path / "b"), {"big": big})
+    bench.dump_outputs(str(tmp_path / "c"), {"big": big})
+    assert np.array_equal(np.load(tmp_path / "b" / "big.npy"), np.load(tmp_path / "c" / "big.npy"))
+
+
+def test_steps_and_dump_outputs_arguments(monkeypatch):
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--gpus", "1", "--steps", "7", "--warmup", "2", "--dump-outputs", "out"])
+    a = bench.parse_args()
+    assert (a.steps, a.warmup, a.dump_outputs, a.workload) == (7, 2, "out", "cfg2")
+    for bad in (["--steps", "0"], ["--workload", "cfg3", "--dump-outputs", "out"]):
+        monkeypatch.setattr(sys, "argv", ["bench.py"] + bad)
+        with pytest.raises(SystemExit):
+            bench.parse_args()

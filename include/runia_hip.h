@@ -502,6 +502,43 @@ int runia_proj_norm_f32(const float* x, const float* u, const double* packed_ns,
 int runia_proj_norm_f64(const double* x, const double* u, const double* packed_ns, double* norm, int64_t N,
                         int64_t D, int64_t n, runia_stream_t stream);
 
+/* ---- RAUQ  attention-based uncertainty of one LLM generation -------------- *
+ * Replaces rauq_uncertainty / rauq_uncertainty_mean_heads / rauq_uncertainty_rollout / RAUQ
+ * (llm_uncertainty/scores.py:155-344) and their helpers (llm_uncertainty/attention_aggregation.py).
+ *   table  device array of n_gen * L map descriptors, step-major, 6 int64 each: {pointer to batch 0 of the step's
+ *          (B, H, q, k) attention tensor, head stride, row stride, column stride (elements), k, q}.  The caller checks
+ *          the shapes (the kernels trust the table): every step has H heads; "original" gathers need k >= 2 from step 1 on;
+ *          rollout needs step 0 = (H, input_length or 1, input_length) and step g >= 1 = (H, 1, input_length + g).
+ *   dtype  0 f32, 1 f16, 2 bf16 (all maps of one call).  token_agg 0 "original", 1 "mean_all_tokens".
+ * runia_rauq_gather: w [L, H, N] f32, N = n_gen - 1 ("original": attn[0, h, 0, -2] of steps 1 .. n_gen-1) or n_gen
+ *   ("mean_all_tokens": mean of query row 0 over k, formed in f32 and rounded to the map dtype).  One launch.
+ * runia_rauq_score: one launch.  head_mode 0: per layer the head argmax_h mean(w[l, h, 1:]) (NaN counts as the maximum,
+ *   the first index wins; heads [L] int32 receives it), 1: mean over heads, 2: att is one series [N] (rollout; L = H = 1).
+ *   Then per layer and alpha conf[0] = exp(lp[0]), conf[i] = a exp(lp[i]) + (1 - a) att[i] conf[i-1] in f32 in the
+ *   reference's order, u = -mean log conf; scores [n_alpha] f32 = max over layers.  log_probs [>= N] f32, alphas
+ *   [n_alpha] f64.  workspace: runia_rauq_workspace_bytes(L, N, 0, 0, 0, n_alpha).
+ * runia_rauq_rollout_rows: the row pass over every layer's T x T reconstructed map (T = input_length + n_gen): row sums
+ *   of mean_h A + I and the diagonal / sub-diagonal of its row normalisation into the workspace; *upper_flag (device
+ *   int) = 1 when some prompt-block entry above the diagonal is non-zero.  workspace as for runia_rauq_rollout_att.
+ * runia_rauq_rollout_att: att [n] f32 of the rollout joint = A^_{L-1} ... A^_0 after the row pass:
+ *   token_agg 0: joint.diagonal(-1)[-n:], token_agg 1: joint[:, -n:].mean(0).
+ *   route 0: one pass over the diagonals (token_agg 0 and a clear upper_flag only); route 1: the chain over causal maps
+ *   (clear upper_flag: prompt rows are read up to the diagonal); route 2: the chain over general maps.  The chain
+ *   carries k = 1 (token_agg 1) or n (token_agg 0) rows.
+ *   workspace: runia_rauq_workspace_bytes(L, n_gen, input_length, n, k, 1), k = 0 for route 0, 16-byte aligned. */
+size_t runia_rauq_workspace_bytes(int64_t L, int64_t n_gen, int64_t input_length, int64_t n, int64_t chain_rows,
+                                  int n_alpha);
+int runia_rauq_gather(const void* table, int dtype, int64_t n_gen, int64_t L, int64_t H, int token_agg, float* w,
+                      runia_stream_t stream);
+int runia_rauq_score(const float* att, int64_t L, int64_t H, int64_t N, int head_mode, const float* log_probs,
+                     const double* alphas, int n_alpha, float* scores, int* heads, void* workspace, size_t workspace_bytes,
+                     runia_stream_t stream);
+int runia_rauq_rollout_rows(const void* table, int dtype, int64_t n_gen, int64_t L, int64_t H, int64_t input_length,
+                            int* upper_flag, void* workspace, size_t workspace_bytes, runia_stream_t stream);
+int runia_rauq_rollout_att(const void* table, int dtype, int64_t n_gen, int64_t L, int64_t H, int64_t input_length,
+                           int token_agg, int route, int64_t n, float* att, void* workspace, size_t workspace_bytes,
+                           runia_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

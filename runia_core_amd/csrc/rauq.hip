@@ -1,0 +1,443 @@
+// RAUQ - recurrent attention-based uncertainty of one LLM generation (Vazhentsev et al. 2025), from the attention maps of
+// HuggingFace `generate(output_attentions=True)` (reference llm_uncertainty/scores.py:155-344, attention_aggregation.py).
+//
+// The maps are read where they lie: a device table of n_gen x L descriptors (pointer, head / row / column strides in
+// elements, k = last dimension, q = query rows) describes batch 0 of every step's tensor, so the caller's tensors are
+// neither copied nor made contiguous.  Four kernels:
+//   gather  (L, H, N) f32 token-aggregation values, one wave per (token, layer, head) row: attn[0, h, 0, -2] of steps
+//           1 .. n_gen-1 ("original") or the row mean of step g's row 0 rounded to the map dtype ("mean_all_tokens")
+//   score   one workgroup: head choice (argmax of the mean over tokens 1.. / mean over heads), exp of the log-probs, the
+//           sequential confidence recurrence in f32 in the reference's operation order, -mean log, max over layers
+//   rows    rollout row pass, one workgroup per (layer, row of the reconstructed T x T map): row sum of mean_h A + I, the
+//           diagonal and sub-diagonal of A^ = rownorm(mean_h A + I), and a flag "a prompt-block entry above the diagonal
+//           is non-zero"
+//   chain   rollout for general maps: a k-row block R (1^T, or the last n rows of I) left-multiplied through the layers,
+//           R <- (R diag(1/r_l)) M_l + R diag(1/r_l), column partials per row block written to a ping-pong buffer and
+//           reduced in a fixed order by the next layer's workgroups (no atomics: repeated calls are bitwise equal)
+// When no layer sets the flag every A^_l is lower-triangular and the sub-diagonal of the product needs only the
+// diagonals and sub-diagonals of the factors (one_pass_kernel): "original" rollout then reads the maps once.
+#include "common.hpp"
+
+namespace {
+
+struct MapDesc {  // one (step, layer) map, batch 0; strides and sizes in elements
+  int64_t ptr, head_stride, row_stride, col_stride, k, q;
+};
+
+enum { kF32 = 0, kF16 = 1, kBF16 = 2 };
+
+template <int DT>
+__device__ __forceinline__ float ld(const MapDesc& m, int64_t off) {
+  if constexpr (DT == kF32) return reinterpret_cast<const float*>(m.ptr)[off];
+  else if constexpr (DT == kF16) return (float)reinterpret_cast<const _Float16*>(m.ptr)[off];
+  else return __uint_as_float((unsigned)reinterpret_cast<const unsigned short*>(m.ptr)[off] << 16);
+}
+
+// an f32 value rounded to the map dtype (round to nearest even, as torch's casts) and widened back
+template <int DT>
+__device__ __forceinline__ float round_to(float x) {
+  if constexpr (DT == kF32) return x;
+  else if constexpr (DT == kF16) return (float)(_Float16)x;
+  else {
+    unsigned u = __float_as_uint(x);
+    if ((u & 0x7fffffffu) > 0x7f800000u) return x;  // NaN
+    u += 0x7fffu + ((u >> 16) & 1u);
+    return __uint_as_float(u & 0xffff0000u);
+  }
+}
+
+// ---- gather ------------------------------------------------------------------------------------------------------------
+template <int DT>
+__global__ __launch_bounds__(256) void gather_kernel(const MapDesc* __restrict__ tab, int L, int H, int N, int mean_all,
+                                                     float* __restrict__ w) {
+  const int64_t row = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
+  const int lane = threadIdx.x & 63;
+  if (row >= (int64_t)N * L * H) return;
+  const int i = (int)(row / ((int64_t)L * H)), l = (int)((row / H) % L), h = (int)(row % H);
+  const int g = mean_all ? i : i + 1;  // "original" reads steps 1 .. n_gen-1
+  const MapDesc m = tab[(int64_t)g * L + l];
+  const int64_t base = (int64_t)h * m.head_stride;  // query row 0
+  float v;
+  if (!mean_all) {
+    v = ld<DT>(m, base + (m.k - 2) * m.col_stride);
+  } else if (m.k < 512) {
+    // torch's own summation order (ATen cascade_sum): the head choice of the per-head mode compares row means that all
+    // sit near 1/k for softmax rows, and is decided in their last bits
+    v = round_to<DT>(torch_row_sum([&](int j) { return ld<DT>(m, base + (int64_t)j * m.col_stride); }, (int)m.k) / (float)m.k);
+  } else {
+    float s = 0.f;
+    for (int64_t j = lane; j < m.k; j += 64) s += ld<DT>(m, base + j * m.col_stride);
+    s = wave_sum_f32(s);
+    v = round_to<DT>(s / (float)m.k);
+  }
+  if (lane == 0) w[((int64_t)l * H + h) * N + i] = v;
+}
+
+// ---- score -------------------------------------------------------------------------------------------------------------
+// head_mode 0: argmax head of each layer, 1: mean over heads, 2: one series att[N] (rollout; 1-D mean of the logs)
+__global__ __launch_bounds__(256) void score_kernel(const float* __restrict__ att, int L, int H, int N, int head_mode,
+                                                    const float* __restrict__ log_probs, const double* __restrict__ alphas,
+                                                    int n_alpha, float* __restrict__ scores, int* __restrict__ heads,
+                                                    float* __restrict__ series, float* __restrict__ unc) {
+  const int t = threadIdx.x;
+  if (head_mode == 0) {
+    for (int l = t; l < L; l += blockDim.x) {
+      int best = 0;
+      float bv = 0.f;
+      for (int h = 0; h < H; ++h) {
+        const float* r = att + ((int64_t)l * H + h) * N + 1;
+        const float mu = torch_row_sum([&](int i) { return r[i]; }, N - 1) / (float)(N - 1);  // NaN for N == 1
+        // torch.argmax: NaN is the maximum, the first index wins ties
+        if (h == 0 || (!(bv != bv) && ((mu != mu) || mu > bv))) { best = h; bv = mu; }
+      }
+      if (heads) heads[l] = best;
+      for (int i = 0; i < N; ++i) series[(int64_t)l * N + i] = att[((int64_t)l * H + best) * N + i];
+    }
+  } else if (head_mode == 1) {
+    for (int64_t e = t; e < (int64_t)L * N; e += blockDim.x) {
+      const int l = (int)(e / N), i = (int)(e % N);
+      float s = 0.f;
+      for (int h = 0; h < H; ++h) s += att[((int64_t)l * H + h) * N + i];
+      series[e] = s / (float)H;
+    }
+  } else {
+    for (int i = t; i < N; i += blockDim.x) series[i] = att[i];
+  }
+  __syncthreads();
+  for (int e = t; e < L * n_alpha; e += blockDim.x) {
+    const int l = e / n_alpha, a = e % n_alpha;
+    const float* s = series + (int64_t)l * N;
+    const float ca = (float)alphas[a], cb = (float)(1.0 - alphas[a]);
+    float conf = expf(log_probs[0]);
+    float acc = logf(conf);  // (N, L) mean over dim 0: one running f32 sum per layer
+    double acc_d = (double)acc;
+    for (int i = 1; i < N; ++i) {
+      const float t1 = ca * expf(log_probs[i]);
+      const float t2 = cb * s[i];
+      const float t3 = t2 * conf;
+      conf = t1 + t3;
+      const float lg = logf(conf);
+      acc += lg;
+      acc_d += (double)lg;
+    }
+    unc[e] = head_mode == 2 ? -(float)(acc_d / (double)N) : -(acc / (float)N);
+  }
+  __syncthreads();
+  for (int a = t; a < n_alpha; a += blockDim.x) {
+    float m = unc[a];
+    for (int l = 1; l < L; ++l) {
+      const float u = unc[l * n_alpha + a];
+      if (m != m || u != u) m = __builtin_nanf("");  // torch.max propagates NaN
+      else m = fmaxf(m, u);
+    }
+    scores[a] = m;
+  }
+}
+
+// ---- rollout -----------------------------------------------------------------------------------------------------------
+// Row i of the reconstructed (T x T) map of a layer (reference _reconstruct_attention_matrix): i < in - row i of step 0's
+// block (row 0 when step 0 has one query row: torch broadcasts it), in columns; i == in - never written (zero); i > in -
+// step i - in, in + (i - in) = i columns.
+struct RowRef {
+  MapDesc m;
+  int64_t off;  // element offset of (head 0, the row, column 0)
+  int64_t k;    // stored columns (0: zero row)
+};
+
+__device__ __forceinline__ RowRef row_ref(const MapDesc* tab, int L, int l, int in, int i) {
+  RowRef r;
+  if (i < in) {
+    r.m = tab[l];
+    r.off = (r.m.q == 1 ? 0 : (int64_t)i) * r.m.row_stride;
+    r.k = in;
+  } else if (i == in) {
+    r.m = tab[l];
+    r.off = 0;
+    r.k = 0;
+  } else {
+    r.m = tab[(int64_t)(i - in) * L + l];
+    r.off = 0;
+    r.k = i;
+  }
+  return r;
+}
+
+// sum over heads of column j (head order 0 .. H-1, as torch's mean over dim 0 of (H, T, T)); nz: a non-zero entry
+template <int DT>
+__device__ __forceinline__ float head_sum(const RowRef& r, int H, int64_t j, bool& nz) {
+  const int64_t off = r.off + j * r.m.col_stride;
+  float acc = 0.f;
+  int h0 = 0;
+  for (; h0 + 8 <= H; h0 += 8) {
+    float v[8];
+#pragma unroll
+    for (int u = 0; u < 8; ++u) v[u] = ld<DT>(r.m, off + (int64_t)(h0 + u) * r.m.head_stride);
+#pragma unroll
+    for (int u = 0; u < 8; ++u) {
+      acc += v[u];
+      nz |= v[u] != 0.f;
+    }
+  }
+  for (; h0 < H; ++h0) {
+    const float v = ld<DT>(r.m, off + (int64_t)h0 * r.m.head_stride);
+    acc += v;
+    nz |= v != 0.f;
+  }
+  return acc;
+}
+
+template <int DT>
+__global__ __launch_bounds__(256) void rows_kernel(const MapDesc* __restrict__ tab, int L, int H, int in, int T,
+                                                   float* __restrict__ rsum, float* __restrict__ diag,
+                                                   float* __restrict__ sub, int* __restrict__ upper_flag) {
+  const int i = blockIdx.x, l = blockIdx.y, t = threadIdx.x;
+  __shared__ float part[4];
+  __shared__ float m_diag, m_sub;
+  if (t == 0) { m_diag = 0.f; m_sub = 0.f; }
+  __syncthreads();
+  const RowRef r = row_ref(tab, L, l, in, i);
+  float s = 0.f;
+  bool upper = false;
+  const float inv_h_div = (float)H;
+  for (int64_t j = t; j < r.k; j += 256) {
+    bool nz = false;
+    const float m = head_sum<DT>(r, H, j, nz) / inv_h_div;
+    s += m;
+    if (j > i) upper |= nz;
+    if (j == i) m_diag = m;
+    if (j == i - 1) m_sub = m;
+  }
+  s = wave_sum_f32(s);
+  if ((t & 63) == 0) part[t >> 6] = s;
+  if (upper) atomicOr(upper_flag, 1);
+  __syncthreads();
+  if (t == 0) {
+    const float rs = ((part[0] + part[1]) + (part[2] + part[3])) + 1.0f;  // + the identity's 1
+    const int64_t e = (int64_t)l * T + i;
+    rsum[e] = rs;
+    diag[e] = (m_diag + 1.0f) / rs;
+    sub[e] = m_sub / rs;  // A^[i, i-1] (0 for i == 0)
+  }
+}
+
+// causal maps: joint[i+1, i] of A^_{L-1} ... A^_0 from the diagonals and sub-diagonals, for i = T-n-1 .. T-2
+__global__ __launch_bounds__(256) void one_pass_kernel(const float* __restrict__ diag, const float* __restrict__ sub, int L,
+                                                       int T, int n, float* __restrict__ att) {
+  const int c = blockIdx.x * 256 + threadIdx.x;
+  if (c >= n) return;
+  const int i = T - n - 1 + c;
+  double d = 1.0, s = 0.0;
+  for (int l = 0; l < L; ++l) {
+    const int64_t e = (int64_t)l * T + i;
+    s = (double)diag[e + 1] * s + (double)sub[e + 1] * d;
+    d = (double)diag[e] * d;
+  }
+  att[c] = (float)s;
+}
+
+constexpr int kChainRows = 8;     // rows of the map per chain workgroup
+constexpr int kChainCols = 256;   // columns per chain workgroup (one per thread)
+
+// One layer of the chain, R row `r` = blockIdx.z, rows [b*8, b*8+8) = blockIdx.y, columns [c*256, c*256+256) = blockIdx.x.
+// State in:  v_prev[k][T] (R diag(1/r) of the previous layer) and p_prev[k][nb][T] (its column partials); first layer: the
+// initial R.  Out: v_cur (rows of this block, written by the column-0 workgroups), p_cur[r][b][columns].
+template <int DT>
+__global__ __launch_bounds__(256) void chain_kernel(const MapDesc* __restrict__ tab, int L, int H, int in, int T, int l,
+                                                    int first, int init_ones, int n, int causal, int nb,
+                                                    const float* __restrict__ rsum, const double* __restrict__ v_prev,
+                                                    const double* __restrict__ p_prev, double* __restrict__ v_cur,
+                                                    double* __restrict__ p_cur) {
+  const int c0 = blockIdx.x * kChainCols, b = blockIdx.y, r = blockIdx.z, t = threadIdx.x;
+  const int i0 = b * kChainRows;
+  __shared__ double vp[kChainRows];
+  if (t < kChainRows) {
+    const int i = i0 + t;
+    double v = 0.0;
+    if (i < T) {
+      if (first) {
+        v = init_ones ? 1.0 : (i == T - n + r ? 1.0 : 0.0);
+      } else {
+        const double* pp = p_prev + (int64_t)r * nb * T + i;
+        for (int bb = 0; bb < nb; ++bb) v += pp[(int64_t)bb * T];
+        v += v_prev[(int64_t)r * T + i];
+      }
+      v /= (double)rsum[(int64_t)l * T + i];
+      if (blockIdx.x == 0) v_cur[(int64_t)r * T + i] = v;
+    }
+    vp[t] = v;
+  }
+  __syncthreads();
+  const int64_t j = c0 + t;
+  if (j >= T) return;
+  double acc = 0.0;
+  for (int u = 0; u < kChainRows; ++u) {
+    const int i = i0 + u;
+    if (i >= T) break;
+    const RowRef rr = row_ref(tab, L, l, in, i);
+    const int64_t kk = (causal && i < in) ? (int64_t)i + 1 : rr.k;  // causal maps: nothing above the diagonal
+    if (j >= kk || vp[u] == 0.0) continue;
+    bool nz = false;
+    const float m = head_sum<DT>(rr, H, j, nz) / (float)H;
+    acc += vp[u] * (double)m;
+  }
+  p_cur[((int64_t)r * nb + b) * T + j] = acc;
+}
+
+// att[c]: "mean_all_tokens" - column T-n+c of 1^T joint over T; "original" - entry (r = c, column T-n-1+c) of the n-row R
+__global__ __launch_bounds__(256) void chain_final_kernel(int T, int n, int mean_all, int nb, const double* __restrict__ v,
+                                                          const double* __restrict__ p, float* __restrict__ att) {
+  const int c = blockIdx.x * 256 + threadIdx.x;
+  if (c >= n) return;
+  const int r = mean_all ? 0 : c;
+  const int64_t j = mean_all ? T - n + c : T - n - 1 + c;
+  double s = 0.0;
+  for (int bb = 0; bb < nb; ++bb) s += p[((int64_t)r * nb + bb) * T + j];
+  s += v[(int64_t)r * T + j];
+  att[c] = mean_all ? (float)(s / (double)T) : (float)s;
+}
+
+// ---- workspace layout --------------------------------------------------------------------------------------------------
+static size_t al(size_t b) { return (b + 255) & ~(size_t)255; }
+
+struct Layout {
+  size_t series, unc, rsum, diag, sub, v0, v1, p0, p1, total;
+  int64_t nb;
+};
+
+static Layout layout(int64_t L, int64_t n_gen, int64_t in, int64_t n, int64_t chain_rows, int n_alpha) {
+  Layout o{};
+  const int64_t T = in > 0 ? in + n_gen : 0;
+  const int64_t N = n_gen > n ? n_gen : n;
+  o.nb = T > 0 ? (T + kChainRows - 1) / kChainRows : 0;
+  size_t at = 0;  // the rollout regions first: their offsets depend on (L, T) only
+  o.rsum = at;   at += al((size_t)(L * T) * 4);
+  o.diag = at;   at += al((size_t)(L * T) * 4);
+  o.sub = at;    at += al((size_t)(L * T) * 4);
+  o.series = at; at += al((size_t)(L * N) * 4);
+  o.unc = at;    at += al((size_t)(L * n_alpha) * 4);
+  const int64_t k = T > 0 ? chain_rows : 0;
+  o.v0 = at;     at += al((size_t)(k * T) * 8);
+  o.v1 = at;     at += al((size_t)(k * T) * 8);
+  o.p0 = at;     at += al((size_t)(k * o.nb * T) * 8);
+  o.p1 = at;     at += al((size_t)(k * o.nb * T) * 8);
+  o.total = at;
+  return o;
+}
+
+static bool bad_ws(const void* ws, size_t bytes, size_t need) {
+  return !ws || bytes < need || (((uintptr_t)ws) & 15) != 0;
+}
+
+template <class F>
+static int dispatch_dtype(int dtype, F f) {
+  switch (dtype) {
+    case kF32: f(std::integral_constant<int, kF32>{}); break;
+    case kF16: f(std::integral_constant<int, kF16>{}); break;
+    default: f(std::integral_constant<int, kBF16>{}); break;
+  }
+  return runia_check_launch();
+}
+
+constexpr int64_t kMaxDim = 1 << 20;
+static bool dims_ok(int64_t n_gen, int64_t L, int64_t H) {
+  return n_gen >= 1 && n_gen <= kMaxDim && L >= 1 && L <= 4096 && H >= 1 && H <= 4096;
+}
+
+}  // namespace
+
+extern "C" size_t runia_rauq_workspace_bytes(int64_t L, int64_t n_gen, int64_t input_length, int64_t n, int64_t chain_rows,
+                                             int n_alpha) {
+  if (L < 1 || n_gen < 1 || input_length < 0 || n < 0 || chain_rows < 0 || n_alpha < 0) return 0;
+  return layout(L, n_gen, input_length, n, chain_rows, n_alpha).total;
+}
+
+extern "C" int runia_rauq_gather(const void* table, int dtype, int64_t n_gen, int64_t L, int64_t H, int token_agg, float* w,
+                                 runia_stream_t stream) {
+  if (!table || !w || dtype < kF32 || dtype > kBF16 || (token_agg != 0 && token_agg != 1) || !dims_ok(n_gen, L, H))
+    return RUNIA_E_INVALID;
+  const int64_t N = token_agg ? n_gen : n_gen - 1;
+  if (N < 1) return RUNIA_E_INVALID;
+  const int64_t rows = N * L * H;
+  const unsigned grid = (unsigned)((rows + 3) / 4);
+  const MapDesc* tab = reinterpret_cast<const MapDesc*>(table);
+  return dispatch_dtype(dtype, [&](auto dt) {
+    gather_kernel<decltype(dt)::value><<<grid, 256, 0, as_stream(stream)>>>(tab, (int)L, (int)H, (int)N, token_agg, w);
+  });
+}
+
+extern "C" int runia_rauq_score(const float* att, int64_t L, int64_t H, int64_t N, int head_mode, const float* log_probs,
+                                const double* alphas, int n_alpha, float* scores, int* heads, void* workspace,
+                                size_t workspace_bytes, runia_stream_t stream) {
+  if (!att || !log_probs || !alphas || !scores || n_alpha < 1 || N < 1 || N > kMaxDim || head_mode < 0 || head_mode > 2 ||
+      L < 1 || L > 4096 || H < 1 || H > 4096 || (head_mode == 2 && (L != 1 || H != 1)))
+    return RUNIA_E_INVALID;
+  // the layout's series region holds L * max(n_gen, n) floats: N of them per layer
+  const Layout o = layout(L, N, 0, 0, 0, n_alpha);
+  if (bad_ws(workspace, workspace_bytes, o.total)) return RUNIA_E_WORKSPACE;
+  char* ws = reinterpret_cast<char*>(workspace);
+  score_kernel<<<1, 256, 0, as_stream(stream)>>>(att, (int)L, (int)H, (int)N, head_mode, log_probs, alphas, n_alpha, scores,
+                                                 head_mode == 0 ? heads : nullptr, reinterpret_cast<float*>(ws + o.series),
+                                                 reinterpret_cast<float*>(ws + o.unc));
+  return runia_check_launch();
+}
+
+extern "C" int runia_rauq_rollout_rows(const void* table, int dtype, int64_t n_gen, int64_t L, int64_t H,
+                                       int64_t input_length, int* upper_flag, void* workspace, size_t workspace_bytes,
+                                       runia_stream_t stream) {
+  if (!table || !upper_flag || dtype < kF32 || dtype > kBF16 || !dims_ok(n_gen, L, H) || n_gen < 2 || input_length < 1 ||
+      input_length + n_gen > kMaxDim)
+    return RUNIA_E_INVALID;
+  const Layout o = layout(L, n_gen, input_length, 0, 0, 1);
+  if (bad_ws(workspace, workspace_bytes, o.total)) return RUNIA_E_WORKSPACE;
+  char* ws = reinterpret_cast<char*>(workspace);
+  const int T = (int)(input_length + n_gen);
+  if (hipMemsetAsync(upper_flag, 0, sizeof(int), as_stream(stream)) != hipSuccess) return RUNIA_E_LAUNCH;
+  const MapDesc* tab = reinterpret_cast<const MapDesc*>(table);
+  return dispatch_dtype(dtype, [&](auto dt) {
+    rows_kernel<decltype(dt)::value><<<dim3((unsigned)T, (unsigned)L), 256, 0, as_stream(stream)>>>(
+        tab, (int)L, (int)H, (int)input_length, T, reinterpret_cast<float*>(ws + o.rsum),
+        reinterpret_cast<float*>(ws + o.diag), reinterpret_cast<float*>(ws + o.sub), upper_flag);
+  });
+}
+
+extern "C" int runia_rauq_rollout_att(const void* table, int dtype, int64_t n_gen, int64_t L, int64_t H,
+                                      int64_t input_length, int token_agg, int route, int64_t n, float* att, void* workspace,
+                                      size_t workspace_bytes, runia_stream_t stream) {
+  if (!table || !att || dtype < kF32 || dtype > kBF16 || !dims_ok(n_gen, L, H) || n_gen < 2 || input_length < 1 ||
+      input_length + n_gen > kMaxDim || (token_agg != 0 && token_agg != 1) || route < 0 || route > 2 ||
+      (route == 0 && token_agg != 0) || n < 1)
+    return RUNIA_E_INVALID;
+  const int64_t T = input_length + n_gen;
+  if ((token_agg == 0 && n > T - 1) || (token_agg == 1 && n > T)) return RUNIA_E_INVALID;
+  const int64_t k = route == 0 ? 0 : (token_agg ? 1 : n);
+  const Layout o = layout(L, n_gen, input_length, n, k, 1);
+  if (bad_ws(workspace, workspace_bytes, o.total)) return RUNIA_E_WORKSPACE;
+  if (k > 65535) return RUNIA_E_INVALID;
+  char* ws = reinterpret_cast<char*>(workspace);
+  const float* rsum = reinterpret_cast<const float*>(ws + o.rsum);
+  const unsigned out_grid = (unsigned)((n + 255) / 256);
+  hipStream_t s = as_stream(stream);
+  if (route == 0) {
+    one_pass_kernel<<<out_grid, 256, 0, s>>>(reinterpret_cast<const float*>(ws + o.diag),
+                                             reinterpret_cast<const float*>(ws + o.sub), (int)L, (int)T, (int)n, att);
+    return runia_check_launch();
+  }
+  const MapDesc* tab = reinterpret_cast<const MapDesc*>(table);
+  double* v[2] = {reinterpret_cast<double*>(ws + o.v0), reinterpret_cast<double*>(ws + o.v1)};
+  double* p[2] = {reinterpret_cast<double*>(ws + o.p0), reinterpret_cast<double*>(ws + o.p1)};
+  const dim3 grid((unsigned)((T + kChainCols - 1) / kChainCols), (unsigned)o.nb, (unsigned)k);
+  int cur = 0;
+  int rc = RUNIA_OK;
+  for (int64_t l = L - 1; l >= 0 && rc == RUNIA_OK; --l) {
+    const int first = l == L - 1;
+    rc = dispatch_dtype(dtype, [&](auto dt) {
+      chain_kernel<decltype(dt)::value><<<grid, 256, 0, s>>>(tab, (int)L, (int)H, (int)input_length, (int)T, (int)l, first,
+                                                           token_agg, (int)n, route == 1, (int)o.nb, rsum, v[cur ^ 1],
+                                                           p[cur ^ 1], v[cur], p[cur]);
+    });
+    cur ^= 1;
+  }
+  if (rc != RUNIA_OK) return rc;
+  chain_final_kernel<<<out_grid, 256, 0, s>>>((int)T, (int)n, token_agg, (int)o.nb, v[cur ^ 1], p[cur ^ 1], att);
+  return runia_check_launch();
+}

@@ -387,7 +387,7 @@ int runia_centred_gram_f32(const float* E, double* G, int64_t n, int64_t H, doub
  * AUROC, FPR@95 and AUPR of in-distribution (positive) against out-of-distribution scores as get_auroc_results
  * computes them (evaluation/metrics.py:37-100: torchmetrics binary auroc / roc / precision_recall_curve +
  * sklearn.metrics.auc): sigmoid in the dtype of the scores when any score is outside [0, 1], descending sort, one
- * curve point per run of equal scores, float32 curve points and trapezoid terms.  Device-resident: radix sort + scans.
+ * curve point per run of equal scores, float32 curve points and trapezoid terms.  Device-resident: bucket sort + scans.
  *   ind_scores [n_ind], ood_scores [n_ood] (device), out3 [3] f64 (device) = {auroc, fpr@95, aupr} (float32 values);
  *   workspace: runia_ood_metrics_workspace_bytes(n_ind + n_ood) bytes, 256-byte aligned. */
 size_t runia_ood_metrics_workspace_bytes(int64_t n_total);

@@ -1223,6 +1223,14 @@ def proj_sq_score(h: torch.Tensor, packed_m: torch.Tensor, c: torch.Tensor, r: i
     return s
 
 
+def _ood_metrics_buffers(lib, n: int, device):
+    """The workspace of a runia_ood_metrics_* / runia_ood_clf_curve_* call over n scores, and its [3] f64 result:
+    ``(ws, ws_ptr, ws_bytes, out)`` - ``ws`` owns the memory, ``ws_ptr`` is its first 256-byte aligned address."""
+    ws_bytes = int(lib.runia_ood_metrics_workspace_bytes(n))
+    ws = torch.empty(ws_bytes + 256, dtype=torch.uint8, device=device)
+    return ws, ws.data_ptr() + (-ws.data_ptr()) % 256, ws_bytes, torch.empty(3, dtype=torch.float64, device=device)
+
+
 @_device_guard()
 def ood_metrics(ind_scores: torch.Tensor, ood_scores: torch.Tensor) -> torch.Tensor:
     """Device scores (both f32 or both f64) -> device tensor [3] f64 = (auroc, fpr@95, aupr), InD = positive class
@@ -1233,13 +1241,9 @@ def ood_metrics(ind_scores: torch.Tensor, ood_scores: torch.Tensor) -> torch.Ten
     assert ind_scores.dtype in (torch.float32, torch.float64)
     a, b = ind_scores.reshape(-1).contiguous(), ood_scores.reshape(-1).contiguous()
     n = a.numel() + b.numel()
-    ws_bytes = int(lib.runia_ood_metrics_workspace_bytes(n))
-    ws = torch.empty(ws_bytes + 256, dtype=torch.uint8, device=a.device)
-    off = (-ws.data_ptr()) % 256
-    out = torch.empty(3, dtype=torch.float64, device=a.device)
+    ws, ws_ptr, ws_bytes, out = _ood_metrics_buffers(lib, n, a.device)
     fn = lib.runia_ood_metrics_f64 if a.dtype == torch.float64 else lib.runia_ood_metrics_f32
-    _check(fn(a.data_ptr(), a.numel(), b.data_ptr(), b.numel(), out.data_ptr(), ws.data_ptr() + off, ws_bytes, _stream()),
-           "runia_ood_metrics")
+    _check(fn(a.data_ptr(), a.numel(), b.data_ptr(), b.numel(), out.data_ptr(), ws_ptr, ws_bytes, _stream()), "runia_ood_metrics")
     return out
 
 
@@ -1254,15 +1258,12 @@ def ood_clf_curve(ind_scores: torch.Tensor, ood_scores: torch.Tensor):
     assert ind_scores.dtype in (torch.float32, torch.float64)
     a, b = ind_scores.reshape(-1).contiguous(), ood_scores.reshape(-1).contiguous()
     n = a.numel() + b.numel()
-    ws_bytes = int(lib.runia_ood_metrics_workspace_bytes(n))
-    ws = torch.empty(ws_bytes + 256, dtype=torch.uint8, device=a.device)
-    off = (-ws.data_ptr()) % 256
-    out = torch.empty(3, dtype=torch.float64, device=a.device)
+    ws, ws_ptr, ws_bytes, out = _ood_metrics_buffers(lib, n, a.device)
     curve = torch.empty((2, n), dtype=torch.int32, device=a.device)  # u32 counts < 2^31 (n is limited to 2^31 - 1)
     n_points = torch.zeros(1, dtype=torch.int64, device=a.device)
     fn = lib.runia_ood_clf_curve_f64 if a.dtype == torch.float64 else lib.runia_ood_clf_curve_f32
     _check(fn(a.data_ptr(), a.numel(), b.data_ptr(), b.numel(), out.data_ptr(), curve[0].data_ptr(), curve[1].data_ptr(),
-              n_points.data_ptr(), ws.data_ptr() + off, ws_bytes, _stream()), "runia_ood_clf_curve")
+              n_points.data_ptr(), ws_ptr, ws_bytes, _stream()), "runia_ood_clf_curve")
     m = int(n_points.item())
     host = to_host(curve[:, :m].contiguous()).astype(np.int64)
     return out, host[0], host[1]

@@ -2,11 +2,11 @@
 // out-of-distribution (negative) score set, as get_auroc_results computes them through torchmetrics' binary
 // auroc / roc / precision_recall_curve and sklearn.metrics.auc (reference evaluation/metrics.py:37-100; torchmetrics'
 // _binary_clf_curve: descending sort, one curve point per run of equal scores, cumulative true / false positives).
-// Everything stays on the device: the sort of the 64-bit keys (round 4: one split into 4 096 buckets that are linear in the
-// score + a sort per bucket, 10 launches; the stable LSD radix sort of rounds 2-3, 8 passes of 8 bits and ~31 launches, is
-// kept behind -DMETRICS_MSD=0), a scan of the labels and of the run ends, and the trapezoid sums.  Round 6: the three scalars
-// alone take six launches (four without the sketch) - buckets by splitter keys, bucket sort and curve terms in one launch
-// (msd_keys_split_kernel, msd_sort_curve_kernel below); the curve API keeps the eight-launch chain.
+// Everything stays on the device: the sort of the 64-bit keys (one split into 4 096 buckets + a sort per bucket; it replaced
+// the stable LSD radix sort of rounds 2-3, 8 passes of 8 bits and ~31 launches, which is gone), a scan of the labels and of
+// the run ends, and the trapezoid sums.  The three scalars alone take six launches (four without the sketch) - buckets by
+// splitter keys, bucket sort and curve terms in one launch (msd_keys_split_kernel, msd_sort_curve_kernel below); the curve
+// API takes eight: probe | [sketch | splitters] | keys | scatter | bucket sort | tile summary | tile prefix | curve terms.
 //
 // Reference behaviour that is reproduced on purpose (the oracle pins it with the reference's goldens):
 //   * if any score lies outside [0, 1] (or is NaN) every score goes through a sigmoid first - in the dtype of the
@@ -29,147 +29,6 @@ __device__ __forceinline__ uint64_t sortable_desc(double v) {
   uint64_t b = (uint64_t)__double_as_longlong(v);
   b = (b >> 63) ? ~b : (b | 0x8000000000000000ull);  // ascending-sortable
   return ~b;
-}
-
-template <typename T>
-__global__ __launch_bounds__(256) void range_check_kernel(const T* __restrict__ ind, int64_t n_ind,
-                                                          const T* __restrict__ ood, int64_t n_ood,
-                                                          unsigned* __restrict__ any_outside) {
-  bool bad = false;
-  const int64_t n = n_ind + n_ood;
-  for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (int64_t)gridDim.x * 256) {
-    const T v = (i < n_ind) ? ind[i] : ood[i - n_ind];
-    bad = bad || !(v >= (T)0 && v <= (T)1);
-  }
-  // one word for the whole launch: atomics on it retire at ~88 per microsecond (31 000 waves of out-of-range scores took
-  // 0.36 ms), so: one candidate per workgroup, a bounded grid, and only while the flag is still clear
-  if (__syncthreads_or(bad) && threadIdx.x == 0 && __atomic_load_n(any_outside, __ATOMIC_RELAXED) == 0u)
-    atomicOr(any_outside, 1u);
-}
-
-template <typename T>
-__global__ __launch_bounds__(256) void make_keys_kernel(const T* __restrict__ ind, int64_t n_ind,
-                                                        const T* __restrict__ ood, int64_t n_ood,
-                                                        const unsigned* __restrict__ any_outside,
-                                                        uint64_t* __restrict__ keys, uint8_t* __restrict__ labels) {
-  const bool squash = *any_outside != 0u;
-  const int64_t n = n_ind + n_ood;
-  for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (int64_t)gridDim.x * 256) {
-    T v = (i < n_ind) ? ind[i] : ood[i - n_ind];
-    if (squash) v = (T)1 / ((T)1 + exp(-v));  // torch.sigmoid in the dtype of the scores
-    // + 0.0: -0.0 becomes +0.0, so that the two zeros share a key and form ONE curve point, as torchmetrics' run
-    // detection (preds[1:] - preds[:-1] != 0) has it
-    keys[i] = sortable_desc((double)v + 0.0);
-    labels[i] = (i < n_ind) ? 1 : 0;
-  }
-}
-
-// ---- LSD radix sort, one 8-bit digit per pass ----------------------------------------------------------------
-__global__ __launch_bounds__(256) void radix_hist_kernel(const uint64_t* __restrict__ keys, int64_t n, int shift,
-                                                         unsigned* __restrict__ table, unsigned nblocks) {
-  __shared__ unsigned hist[256];
-  hist[threadIdx.x] = 0u;
-  __syncthreads();
-  const int64_t t0 = (int64_t)blockIdx.x * kTile;
-#pragma unroll
-  for (int c = 0; c < kItems; ++c) {
-    const int64_t i = t0 + c * 256 + threadIdx.x;
-    if (i < n) atomicAdd(&hist[(unsigned)(keys[i] >> shift) & 255u], 1u);
-  }
-  __syncthreads();
-  table[(size_t)threadIdx.x * nblocks + blockIdx.x] = hist[threadIdx.x];  // digit-major: scan order = (digit, block)
-}
-
-// Offsets of a radix pass in two levels, both parallel: workgroup d scans row d of the digit-major table (the counts of
-// digit d in every tile) in place and leaves the row total in dtot[d]; every scatter workgroup then scans the 256 totals
-// itself.  (One workgroup scanning all 256 x tiles counters took 139 us of a 2 M-key pass's 180 - 52 us once staged
-// through LDS; the row scans take a few us.)
-__global__ __launch_bounds__(256) void radix_row_scan_kernel(unsigned* __restrict__ table, unsigned nblocks,
-                                                              unsigned* __restrict__ dtot) {
-  __shared__ unsigned wsum[4];
-  __shared__ unsigned carry_s;
-  unsigned* row = table + (size_t)blockIdx.x * nblocks;
-  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-  if (tid == 0) carry_s = 0u;
-  __syncthreads();
-  for (unsigned base = 0; base < nblocks; base += 256) {
-    const unsigned i = base + tid;
-    const unsigned v = (i < nblocks) ? row[i] : 0u;
-    unsigned x = v;
-#pragma unroll
-    for (int o = 1; o < 64; o <<= 1) {
-      const unsigned y = __shfl_up(x, o, 64);
-      if (lane >= o) x += y;
-    }
-    if (lane == 63) wsum[wave] = x;
-    __syncthreads();
-    unsigned woff = 0u;
-    for (int w = 0; w < wave; ++w) woff += wsum[w];
-    const unsigned carry = carry_s;
-    if (i < nblocks) row[i] = carry + woff + x - v;
-    __syncthreads();
-    if (tid == 255) carry_s = carry + woff + x;
-    __syncthreads();
-  }
-  if (tid == 0) dtot[blockIdx.x] = carry_s;
-}
-
-__global__ __launch_bounds__(256) void radix_scatter_kernel(const uint64_t* __restrict__ keys_in,
-                                                            const uint8_t* __restrict__ lab_in,
-                                                            uint64_t* __restrict__ keys_out, uint8_t* __restrict__ lab_out,
-                                                            int64_t n, int shift, const unsigned* __restrict__ table,
-                                                            unsigned nblocks, const unsigned* __restrict__ dtot) {
-  __shared__ unsigned base[256];       // next free global slot of every digit for this workgroup
-  __shared__ unsigned wcnt[4][256];    // per-wave digit counts of the current chunk
-  __shared__ unsigned dsum[4];
-  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-  {
-    // first slot of digit `tid` = number of keys with a smaller digit (exclusive scan of the 256 row totals) ...
-    const unsigned v = dtot[tid];
-    unsigned x = v;
-#pragma unroll
-    for (int o = 1; o < 64; o <<= 1) {
-      const unsigned y = __shfl_up(x, o, 64);
-      if (lane >= o) x += y;
-    }
-    if (lane == 63) dsum[wave] = x;
-    __syncthreads();
-    unsigned woff = 0u;
-    for (int w = 0; w < wave; ++w) woff += dsum[w];
-    // ... plus the keys of this digit in earlier tiles
-    base[tid] = woff + x - v + table[(size_t)tid * nblocks + blockIdx.x];
-  }
-#pragma unroll
-  for (int w = 0; w < 4; ++w) wcnt[w][tid] = 0u;
-  __syncthreads();
-  const int64_t t0 = (int64_t)blockIdx.x * kTile;
-  const uint64_t lt_mask = (lane == 0) ? 0ull : (~0ull >> (64 - lane));
-  for (int c = 0; c < kItems; ++c) {  // chunks in order: the pass is stable
-    const int64_t i = t0 + c * 256 + tid;
-    const bool valid = i < n;
-    const uint64_t key = valid ? keys_in[i] : 0ull;
-    const unsigned d = (unsigned)(key >> shift) & 255u;
-    uint64_t same = __ballot(valid);  // lanes of this wave holding the same digit
-#pragma unroll
-    for (int b = 0; b < 8; ++b) {
-      const uint64_t bal = __ballot((d >> b) & 1u);
-      same &= ((d >> b) & 1u) ? bal : ~bal;
-    }
-    const unsigned rank_in_wave = (unsigned)__popcll(same & lt_mask);
-    if (valid && rank_in_wave == 0u) wcnt[wave][d] = (unsigned)__popcll(same);
-    __syncthreads();
-    if (valid) {
-      unsigned off = base[d] + rank_in_wave;
-      for (int w = 0; w < wave; ++w) off += wcnt[w][d];
-      keys_out[off] = key;
-      lab_out[off] = lab_in[i];
-    }
-    __syncthreads();
-    base[tid] += wcnt[0][tid] + wcnt[1][tid] + wcnt[2][tid] + wcnt[3][tid];
-#pragma unroll
-    for (int w = 0; w < 4; ++w) wcnt[w][tid] = 0u;
-    __syncthreads();
-  }
 }
 
 // ---- curve: cumulative positives and the previous run end of every run end ------------------------------------------------
@@ -212,46 +71,8 @@ __global__ __launch_bounds__(256) void tile_summary_kernel(const uint64_t* __res
   tile_summary_body(keys, lab, n, tile_sum, tile_end, tile_cnt, blockIdx.x);
 }
 
-// exclusive scan of the tile summaries (sum: +, end: max) by one wave, 64 tiles per trip
-__device__ __forceinline__ void tile_scan_body(unsigned* __restrict__ tile_sum, int* __restrict__ tile_end,
-                                               unsigned* __restrict__ tile_cnt, int64_t ntiles) {
-  if (threadIdx.x >= 64) return;
-  const int lane = threadIdx.x;
-  unsigned cs = 0u, cc = 0u;
-  int ce = -1;
-  for (int64_t base = 0; base < ntiles; base += 64) {
-    const int64_t i = base + lane;
-    const unsigned ts = (i < ntiles) ? tile_sum[i] : 0u;
-    const unsigned tc = (i < ntiles) ? tile_cnt[i] : 0u;
-    const int te = (i < ntiles) ? tile_end[i] : -1;
-    unsigned x = ts, k = tc;
-    int m = te;
-#pragma unroll
-    for (int o = 1; o < 64; o <<= 1) {
-      const unsigned y = __shfl_up(x, o, 64);
-      const unsigned q = __shfl_up(k, o, 64);
-      const int z = __shfl_up(m, o, 64);
-      if (lane >= o) { x += y; k += q; m = max(m, z); }
-    }
-    int em = __shfl_up(m, 1, 64);  // exclusive maximum
-    if (lane == 0) em = -1;
-    if (i < ntiles) {
-      tile_sum[i] = cs + x - ts;
-      tile_cnt[i] = cc + k - tc;
-      tile_end[i] = max(ce, em);
-    }
-    cs += __shfl(x, 63, 64);
-    cc += __shfl(k, 63, 64);
-    ce = max(ce, __shfl(m, 63, 64));
-  }
-}
-__global__ void tile_scan_kernel(unsigned* __restrict__ tile_sum, int* __restrict__ tile_end,
-                                 unsigned* __restrict__ tile_cnt, int64_t ntiles) {
-  if (blockIdx.x == 0) tile_scan_body(tile_sum, tile_end, tile_cnt, ntiles);
-}
-
-// tile pass 2: tps[i] (inclusive) for every element; prev_end[i] for every run end
-template <bool RAW = false>  // RAW: the tile summaries as tile_summary_kernel left them - the carries are added up here
+// tile pass 2: tps[i] (inclusive) for every element; prev_end[i] for every run end.  The tile summaries are read as
+// tile_summary_kernel left them - the carries are added up here
 __device__ __forceinline__ void tile_prefix_body(const uint64_t* __restrict__ keys, const uint8_t* __restrict__ lab,
                                                  int64_t n, const unsigned* __restrict__ tile_sum,
                                                  const int* __restrict__ tile_end, const unsigned* __restrict__ tile_cnt,
@@ -267,7 +88,7 @@ __device__ __forceinline__ void tile_prefix_body(const uint64_t* __restrict__ ke
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const int64_t t0 = (int64_t)tile * kTile;
   __syncthreads();  // (a caller that loops over tiles reuses the carries)
-  if constexpr (RAW) {
+  {
     // every workgroup adds up the summaries of the tiles before its own (<= 1 024 x 12 bytes from L2, ~1 us side by side)
     // instead of one wave scanning them in a launch of its own in front of this one (5.6 us + a launch boundary)
     unsigned ps = 0u, pc = 0u;
@@ -286,8 +107,6 @@ __device__ __forceinline__ void tile_prefix_body(const uint64_t* __restrict__ ke
       carry_cnt = wcnt[0] + wcnt[1] + wcnt[2] + wcnt[3];
       carry_end = max(max(wend[0], wend[1]), max(wend[2], wend[3]));
     }
-  } else {
-    if (tid == 0) { carry_sum = tile_sum[tile]; carry_end = tile_end[tile]; carry_cnt = tile_cnt[tile]; }
   }
   __syncthreads();
   for (int c = 0; c < kItems; ++c) {
@@ -338,21 +157,13 @@ __device__ __forceinline__ void tile_prefix_body(const uint64_t* __restrict__ ke
   }
 }
 
-__global__ __launch_bounds__(256) void tile_prefix_kernel(const uint64_t* __restrict__ keys, const uint8_t* __restrict__ lab,
-                                                          int64_t n, const unsigned* __restrict__ tile_sum,
-                                                          const int* __restrict__ tile_end,
-                                                          const unsigned* __restrict__ tile_cnt, unsigned* __restrict__ tps,
-                                                          int* __restrict__ prev_end, unsigned* __restrict__ tps_out,
-                                                          unsigned* __restrict__ fps_out, int64_t* __restrict__ n_points) {
-  tile_prefix_body(keys, lab, n, tile_sum, tile_end, tile_cnt, tps, prev_end, tps_out, fps_out, n_points, blockIdx.x);
-}
 __global__ __launch_bounds__(256) void tile_prefix_raw_kernel(const uint64_t* __restrict__ keys, const uint8_t* __restrict__ lab,
                                                               int64_t n, const unsigned* __restrict__ tile_sum,
                                                               const int* __restrict__ tile_end,
                                                               const unsigned* __restrict__ tile_cnt, unsigned* __restrict__ tps,
                                                               int* __restrict__ prev_end, unsigned* __restrict__ tps_out,
                                                               unsigned* __restrict__ fps_out, int64_t* __restrict__ n_points) {
-  tile_prefix_body<true>(keys, lab, n, tile_sum, tile_end, tile_cnt, tps, prev_end, tps_out, fps_out, n_points, blockIdx.x);
+  tile_prefix_body(keys, lab, n, tile_sum, tile_end, tile_cnt, tps, prev_end, tps_out, fps_out, n_points, blockIdx.x);
 }
 
 struct MetricsAccum {
@@ -361,10 +172,10 @@ struct MetricsAccum {
   unsigned long long fpr95_idx;  // smallest run-end index with tpr >= 0.95
 };
 
+// the curve terms of the run ends in this workgroup's share of the keys -> its record parts[block]
 __device__ __forceinline__ void curve_terms_body(const uint64_t* __restrict__ keys, int64_t n,
                                                  const unsigned* __restrict__ tps, const int* __restrict__ prev_end,
-                                                 MetricsAccum* __restrict__ acc, unsigned block, unsigned blocks,
-                                                 MetricsAccum* __restrict__ parts = nullptr) {
+                                                 MetricsAccum* __restrict__ parts, unsigned block, unsigned blocks) {
   __shared__ double sroc[4], spr[4];
   __shared__ unsigned long long sidx[4];
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
@@ -430,27 +241,8 @@ __device__ __forceinline__ void curve_terms_body(const uint64_t* __restrict__ ke
   if (tid == 0) {
     const double r = ((sroc[0] + sroc[1]) + sroc[2]) + sroc[3], q = ((spr[0] + spr[1]) + spr[2]) + spr[3];
     const unsigned long long f = min(min(sidx[0], sidx[1]), min(sidx[2], sidx[3]));
-    if (parts) {  // the workgroup's own record: the last workgroup adds the records up in index order
-      parts[block].roc_sum = r; parts[block].pr_sum = q; parts[block].fpr95_idx = f;
-    } else {
-      unsafeAtomicAdd(&acc->roc_sum, r);
-      unsafeAtomicAdd(&acc->pr_sum, q);
-      atomicMin(&acc->fpr95_idx, f);
-    }
+    parts[block].roc_sum = r; parts[block].pr_sum = q; parts[block].fpr95_idx = f;  // the last workgroup adds them up in index order
   }
-}
-__global__ __launch_bounds__(256) void curve_terms_kernel(const uint64_t* __restrict__ keys, int64_t n,
-                                                          const unsigned* __restrict__ tps, const int* __restrict__ prev_end,
-                                                          MetricsAccum* __restrict__ acc) {
-  curve_terms_body(keys, n, tps, prev_end, acc, blockIdx.x, gridDim.x);
-}
-
-__device__ __forceinline__ void finalize_body(const MetricsAccum* __restrict__ acc, const unsigned* __restrict__ tps, int64_t n,
-                                              double* __restrict__ out);
-__global__ void finalize_kernel(const MetricsAccum* __restrict__ acc, const unsigned* __restrict__ tps, int64_t n,
-                                double* __restrict__ out) {
-  if (threadIdx.x != 0 || blockIdx.x != 0) return;
-  finalize_body(acc, tps, n, out);
 }
 __device__ __forceinline__ void finalize_body(const MetricsAccum* __restrict__ acc, const unsigned* __restrict__ tps, int64_t n,
                                               double* __restrict__ out) {
@@ -792,7 +584,7 @@ __global__ __launch_bounds__(256) void msd_split_kernel(unsigned* __restrict__ a
 }
 
 constexpr int kScatItems = METRICS_SCAT_ITEMS, kScatTile = 256 * kScatItems;  // 8 192 keys per workgroup: ~2 per (tile, bucket)
-template <typename T, int ITEMS = kScatItems>  // small sets: 8 keys per thread (20 000 scores: 10 workgroups instead of 3)
+template <int ITEMS = kScatItems>  // small sets: 8 keys per thread (20 000 scores: 10 workgroups instead of 3)
 __global__ __launch_bounds__(256) void msd_scatter_kernel(const uint64_t* __restrict__ keys_in, const uint8_t* __restrict__ lab_in,
                                                           uint64_t* __restrict__ keys_out, uint8_t* __restrict__ lab_out, int64_t n,
                                                           const uint16_t* __restrict__ bucket_of, MsdState* st) {
@@ -869,9 +661,6 @@ __global__ __launch_bounds__(256) void msd_scatter_kernel(const uint64_t* __rest
 // the bytes in which a bucket's keys differ (two LDS copies of the bucket: half the occupancy) 168 us.  Then the workgroup
 // together takes each of its buckets that is larger.
 constexpr int kMsdWaveCap = 1024;
-#ifndef METRICS_REG_SORT
-#define METRICS_REG_SORT 1
-#endif
 // A bucket of up to 64 * PER keys sorted by ONE wave in registers: element e = lane * PER + r, a bitonic network whose
 // exchanges at distance j < PER are compare-and-selects between two of the lane's own registers and whose exchanges at
 // distance j >= PER are two shuffles + a select per element with the lane at distance j / PER (21 of the 45 stages at
@@ -945,23 +734,107 @@ __device__ __forceinline__ void wave_sort_in_registers(uint64_t* __restrict__ ke
   }
 }
 
-template <typename T>
+// A bucket beyond a wave's kMsdWaveCap keys is sorted by the whole workgroup: stable 8-bit radix passes over the bytes in which
+// its keys differ, in global memory between the bucket's range in `keys` and the same range of the other buffer - slow but
+// bounded.  Both kernels below run it through the two helpers that follow; they work in the caller's LDS (so a kernel's LDS is
+// what it declares) and every thread of the workgroup calls them.
+
+// the bits in which the bucket's nb keys differ at all: OR of key ^ first key over the bucket (0: one run of equal keys -
+// saturated sigmoids, a constant score set - which needs no pass)
+__device__ __forceinline__ unsigned long long bucket_diff_bits(const uint64_t* __restrict__ k, unsigned nb,
+                                                               unsigned long long& diff_s) {
+  const int tid = threadIdx.x, lane = tid & 63;
+  __syncthreads();
+  if (tid == 0) diff_s = 0ull;
+  __syncthreads();
+  {
+    const uint64_t k0 = k[0];
+    unsigned long long d = 0ull;
+    for (unsigned i = tid; i < nb; i += 256) d |= k[i] ^ k0;
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1)
+      d |= ((unsigned long long)__shfl_xor((unsigned)(d >> 32), o, 64) << 32) | __shfl_xor((unsigned)d, o, 64);
+    if (lane == 0 && d) atomicOr(&diff_s, d);
+  }
+  __syncthreads();
+  return diff_s;
+}
+
+// the passes over the bytes that `diff` (non-zero) covers, between (src_k, src_l) and (dst_k, dst_l), nb keys and labels each;
+// on return (src_k, src_l) point at the sorted bucket - (dst_k, dst_l) as passed after an odd number of passes
+__device__ __forceinline__ void bucket_radix_sort(uint64_t*& src_k, uint8_t*& src_l, uint64_t* dst_k, uint8_t* dst_l, unsigned nb,
+                                                  unsigned long long diff, unsigned* base, unsigned (*wcnt)[256], unsigned* dsum) {
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int low_bits = 64 - __builtin_clzll(diff);
+  const int first_bit = __builtin_ctzll(diff) & ~7;
+  const uint64_t lt_mask = (lane == 0) ? 0ull : (~0ull >> (64 - lane));
+  for (int shift = first_bit; shift < low_bits; shift += 8) {
+    __syncthreads();
+    base[tid] = 0u;
+    __syncthreads();
+    for (unsigned i = tid; i < nb; i += 256) atomicAdd(&base[(unsigned)(src_k[i] >> shift) & 255u], 1u);
+    __syncthreads();
+    {
+      const unsigned v = base[tid];
+      unsigned x = v;
+#pragma unroll
+      for (int o = 1; o < 64; o <<= 1) {
+        const unsigned y = __shfl_up(x, o, 64);
+        if (lane >= o) x += y;
+      }
+      if (lane == 63) dsum[wave] = x;
+      __syncthreads();
+      unsigned woff = 0u;
+      for (int w = 0; w < wave; ++w) woff += dsum[w];
+      base[tid] = woff + x - v;
+    }
+#pragma unroll
+    for (int w = 0; w < 4; ++w) wcnt[w][tid] = 0u;
+    __syncthreads();
+    for (unsigned i0 = 0; i0 < nb; i0 += 256) {  // chunks in order: the pass is stable
+      const unsigned i = i0 + tid;
+      const bool valid = i < nb;
+      const uint64_t key = valid ? src_k[i] : 0ull;
+      const unsigned d = (unsigned)(key >> shift) & 255u;
+      uint64_t same = __ballot(valid);
+#pragma unroll
+      for (int bb = 0; bb < 8; ++bb) {
+        const uint64_t bal = __ballot((d >> bb) & 1u);
+        same &= ((d >> bb) & 1u) ? bal : ~bal;
+      }
+      const unsigned rank_in_wave = (unsigned)__popcll(same & lt_mask);
+      if (valid && rank_in_wave == 0u) wcnt[wave][d] = (unsigned)__popcll(same);
+      __syncthreads();
+      if (valid) {
+        unsigned off = base[d] + rank_in_wave;
+        for (int w = 0; w < wave; ++w) off += wcnt[w][d];
+        dst_k[off] = key;
+        dst_l[off] = src_l[i];
+      }
+      __syncthreads();
+      base[tid] += wcnt[0][tid] + wcnt[1][tid] + wcnt[2][tid] + wcnt[3][tid];
+#pragma unroll
+      for (int w = 0; w < 4; ++w) wcnt[w][tid] = 0u;
+      __syncthreads();
+    }
+    __threadfence_block();
+    uint64_t* tk = src_k; src_k = dst_k; dst_k = tk;
+    uint8_t* tl = src_l; src_l = dst_l; dst_l = tl;
+  }
+  __syncthreads();
+}
+
 __global__ __launch_bounds__(256) void msd_bucket_sort_kernel(uint64_t* __restrict__ keys, uint8_t* __restrict__ labs,
                                                               uint64_t* __restrict__ alt_keys, uint8_t* __restrict__ alt_labs,
-                                                              const unsigned* __restrict__ any_outside, const MsdState* st) {
-#if !METRICS_REG_SORT
-  __shared__ uint64_t sk_all[4][kMsdWaveCap];
-  __shared__ uint8_t sl_all[4][kMsdWaveCap];
-#endif
+                                                              const MsdState* st) {
   __shared__ unsigned base[256];
   __shared__ unsigned wcnt[4][256];
   __shared__ unsigned dsum[4];
+  __shared__ unsigned long long diff_s;
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-  (void)any_outside;
   {
     const int b = 4 * blockIdx.x + wave;
     const unsigned lo = st->start[b], nb = st->start[b + 1] - lo;
-#if METRICS_REG_SORT
     if (nb >= 2u && nb <= (unsigned)kMsdWaveCap) {  // (wave-uniform)
       if (nb <= 64u) wave_sort_in_registers<1>(keys, labs, lo, nb, lane);
       else if (nb <= 128u) wave_sort_in_registers<2>(keys, labs, lo, nb, lane);
@@ -969,123 +842,16 @@ __global__ __launch_bounds__(256) void msd_bucket_sort_kernel(uint64_t* __restri
       else if (nb <= 512u) wave_sort_in_registers<8>(keys, labs, lo, nb, lane);
       else wave_sort_in_registers<16>(keys, labs, lo, nb, lane);
     }
-#else  // the LDS form of the network (round 4's first cut), kept for comparison
-    if (nb >= 2u && nb <= (unsigned)kMsdWaveCap) {  // (wave-uniform)
-      uint64_t* sk = sk_all[wave];
-      uint8_t* sl = sl_all[wave];
-      unsigned m = 2u;
-      while (m < nb) m <<= 1;  // network size: the next power of two, padded with the largest key
-      for (unsigned i = lane; i < m; i += 64) {
-        sk[i] = (i < nb) ? keys[lo + i] : ~0ull;
-        sl[i] = (i < nb) ? labs[lo + i] : 0;
-      }
-      __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-      __builtin_amdgcn_wave_barrier();
-      for (unsigned k2 = 2u; k2 <= m; k2 <<= 1) {
-        for (unsigned j = k2 >> 1; j > 0u; j >>= 1) {
-          for (unsigned t = lane; t < (m >> 1); t += 64) {  // pair t: i = the index with bit j clear
-            const unsigned i = ((t & ~(j - 1u)) << 1) | (t & (j - 1u)), p = i | j;
-            const bool up = (i & k2) == 0u;
-            const uint64_t a = sk[i], c = sk[p];
-            if ((a > c) == up) {
-              sk[i] = c; sk[p] = a;
-              const uint8_t la = sl[i]; sl[i] = sl[p]; sl[p] = la;
-            }
-          }
-          __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
-          __builtin_amdgcn_wave_barrier();
-        }
-      }
-      for (unsigned i = lane; i < nb; i += 64) { keys[lo + i] = sk[i]; labs[lo + i] = sl[i]; }
-    }
-#endif
   }
   for (int b = 4 * blockIdx.x; b < 4 * (int)blockIdx.x + 4; ++b) {
     const unsigned lo = st->start[b], nb = st->start[b + 1] - lo;
     if (nb <= (unsigned)kMsdWaveCap) continue;  // (uniform)
-    // a bucket that does not fit a wave's LDS slice: stable 8-bit radix passes over the bits below the bucket digit, by this
-    // workgroup alone, between the bucket's range in `keys` and the same range of the other buffer
-    // the bits in which the bucket's keys differ at all (a bucket of equal keys - saturated sigmoids, a constant score set -
-    // needs no pass): OR of key ^ first key over the bucket
-    __shared__ unsigned long long diff_s;
-    __syncthreads();
-    if (tid == 0) diff_s = 0ull;
-    __syncthreads();
-    {
-      const uint64_t k0 = keys[lo];
-      unsigned long long d = 0ull;
-      for (unsigned i = tid; i < nb; i += 256) d |= keys[lo + i] ^ k0;
-#pragma unroll
-      for (int o = 32; o > 0; o >>= 1)
-        d |= ((unsigned long long)__shfl_xor((unsigned)(d >> 32), o, 64) << 32) | __shfl_xor((unsigned)d, o, 64);
-      if (lane == 0 && d) atomicOr(&diff_s, d);
-    }
-    __syncthreads();
-    const unsigned long long diff = diff_s;
-    const int low_bits = diff ? 64 - __builtin_clzll(diff) : 0;
-    const int first_bit = diff ? (__builtin_ctzll(diff) & ~7) : 0;
+    const unsigned long long diff = bucket_diff_bits(keys + lo, nb, diff_s);
+    if (diff == 0ull) continue;  // equal keys: in order as they lie
     uint64_t* src_k = keys + lo;
     uint8_t* src_l = labs + lo;
-    uint64_t* dst_k = alt_keys + lo;
-    uint8_t* dst_l = alt_labs + lo;
-    int moved = 0;
-    const uint64_t lt_mask = (lane == 0) ? 0ull : (~0ull >> (64 - lane));
-    for (int shift = first_bit; shift < low_bits; shift += 8) {
-      __syncthreads();
-      base[tid] = 0u;
-      __syncthreads();
-      for (unsigned i = tid; i < nb; i += 256) atomicAdd(&base[(unsigned)(src_k[i] >> shift) & 255u], 1u);
-      __syncthreads();
-      {
-        const unsigned v = base[tid];
-        unsigned x = v;
-#pragma unroll
-        for (int o = 1; o < 64; o <<= 1) {
-          const unsigned y = __shfl_up(x, o, 64);
-          if (lane >= o) x += y;
-        }
-        if (lane == 63) dsum[wave] = x;
-        __syncthreads();
-        unsigned woff = 0u;
-        for (int w = 0; w < wave; ++w) woff += dsum[w];
-        base[tid] = woff + x - v;
-      }
-#pragma unroll
-      for (int w = 0; w < 4; ++w) wcnt[w][tid] = 0u;
-      __syncthreads();
-      for (unsigned i0 = 0; i0 < nb; i0 += 256) {  // chunks in order: the pass is stable
-        const unsigned i = i0 + tid;
-        const bool valid = i < nb;
-        const uint64_t key = valid ? src_k[i] : 0ull;
-        const unsigned d = (unsigned)(key >> shift) & 255u;
-        uint64_t same = __ballot(valid);
-#pragma unroll
-        for (int bb = 0; bb < 8; ++bb) {
-          const uint64_t bal = __ballot((d >> bb) & 1u);
-          same &= ((d >> bb) & 1u) ? bal : ~bal;
-        }
-        const unsigned rank_in_wave = (unsigned)__popcll(same & lt_mask);
-        if (valid && rank_in_wave == 0u) wcnt[wave][d] = (unsigned)__popcll(same);
-        __syncthreads();
-        if (valid) {
-          unsigned off = base[d] + rank_in_wave;
-          for (int w = 0; w < wave; ++w) off += wcnt[w][d];
-          dst_k[off] = key;
-          dst_l[off] = src_l[i];
-        }
-        __syncthreads();
-        base[tid] += wcnt[0][tid] + wcnt[1][tid] + wcnt[2][tid] + wcnt[3][tid];
-#pragma unroll
-        for (int w = 0; w < 4; ++w) wcnt[w][tid] = 0u;
-        __syncthreads();
-      }
-      __threadfence_block();
-      uint64_t* tk = src_k; src_k = dst_k; dst_k = tk;
-      uint8_t* tl = src_l; src_l = dst_l; dst_l = tl;
-      moved ^= 1;
-    }
-    __syncthreads();
-    if (moved)  // an odd number of passes left the bucket in the other buffer
+    bucket_radix_sort(src_k, src_l, alt_keys + lo, alt_labs + lo, nb, diff, base, wcnt, dsum);
+    if (src_k != keys + lo)  // an odd number of passes left the bucket in the other buffer
       for (unsigned i = tid; i < nb; i += 256) { keys[lo + i] = src_k[i]; labs[lo + i] = src_l[i]; }
     __syncthreads();
   }
@@ -1105,7 +871,7 @@ __global__ __launch_bounds__(256) void curve_terms_finalize_kernel(const uint64_
   __shared__ int last;
   __shared__ double sroc[4], spr[4];
   __shared__ unsigned long long sidx[4];
-  curve_terms_body(keys, n, tps, prev_end, nullptr, blockIdx.x, gridDim.x, parts);
+  curve_terms_body(keys, n, tps, prev_end, parts, blockIdx.x, gridDim.x);
   // (thread 0 wrote the record: it alone fences, below - a release fence is an L2 write-back, and four waves of every
   // workgroup issuing one was ~70 ns per workgroup of this launch)
   // "last one out": atomics on ONE word retire at ~60 ns each - 512 workgroups finishing together spent 30 us in that queue.
@@ -1326,7 +1092,6 @@ __device__ __forceinline__ void wave_bucket_curve(const uint64_t* __restrict__ k
   }
 }
 
-template <typename T>
 __global__ __launch_bounds__(256) void msd_sort_curve_kernel(uint64_t* __restrict__ keys, uint8_t* __restrict__ labs,
                                                              uint64_t* __restrict__ alt_keys, uint8_t* __restrict__ alt_labs,
                                                              MsdState* st, FusedPart* __restrict__ parts, float P, float Nn,
@@ -1375,88 +1140,16 @@ __global__ __launch_bounds__(256) void msd_sort_curve_kernel(uint64_t* __restric
     if (nb <= (unsigned)kMsdWaveCap) continue;  // (uniform)
     unsigned base_pos = before_pos;
     for (int c = b0; c < b; ++c) base_pos += (unsigned)(st->cursor64[c] >> 32);
-    // the bits in which the bucket's keys differ at all: OR of key ^ first key over the bucket
-    __syncthreads();
-    if (tid == 0) diff_s = 0ull;
-    __syncthreads();
-    {
-      const uint64_t k0 = keys[lo];
-      unsigned long long d = 0ull;
-      for (unsigned i = tid; i < nb; i += 256) d |= keys[lo + i] ^ k0;
-#pragma unroll
-      for (int o = 32; o > 0; o >>= 1)
-        d |= ((unsigned long long)__shfl_xor((unsigned)(d >> 32), o, 64) << 32) | __shfl_xor((unsigned)d, o, 64);
-      if (lane == 0 && d) atomicOr(&diff_s, d);
-    }
-    __syncthreads();
-    const unsigned long long diff = diff_s;
+    const unsigned long long diff = bucket_diff_bits(keys + lo, nb, diff_s);
     if (diff == 0ull) {  // one run: its end carries the bucket's counts (nothing else of it is read)
       if (tid == 0)
         curve_term(acc, (unsigned long long)lo + nb - 1u, base_pos + (unsigned)(st->cursor64[b] >> 32), base_pos, lo - base_pos, lo != 0u, P, Nn);
       continue;
     }
-    const int low_bits = 64 - __builtin_clzll(diff);
-    const int first_bit = __builtin_ctzll(diff) & ~7;
     uint64_t* src_k = keys + lo;
     uint8_t* src_l = labs + lo;
-    uint64_t* dst_k = alt_keys + lo;
-    uint8_t* dst_l = alt_labs + lo;
-    const uint64_t lt_mask = (lane == 0) ? 0ull : (~0ull >> (64 - lane));
-    for (int shift = first_bit; shift < low_bits; shift += 8) {  // stable 8-bit radix passes, as msd_bucket_sort_kernel
-      __syncthreads();
-      base[tid] = 0u;
-      __syncthreads();
-      for (unsigned i = tid; i < nb; i += 256) atomicAdd(&base[(unsigned)(src_k[i] >> shift) & 255u], 1u);
-      __syncthreads();
-      {
-        const unsigned v = base[tid];
-        unsigned x = v;
-#pragma unroll
-        for (int o = 1; o < 64; o <<= 1) {
-          const unsigned y = __shfl_up(x, o, 64);
-          if (lane >= o) x += y;
-        }
-        if (lane == 63) dsum[wave] = x;
-        __syncthreads();
-        unsigned woff = 0u;
-        for (int w = 0; w < wave; ++w) woff += dsum[w];
-        base[tid] = woff + x - v;
-      }
-#pragma unroll
-      for (int w = 0; w < 4; ++w) wcnt[w][tid] = 0u;
-      __syncthreads();
-      for (unsigned i0 = 0; i0 < nb; i0 += 256) {  // chunks in order: the pass is stable
-        const unsigned i = i0 + tid;
-        const bool valid = i < nb;
-        const uint64_t key = valid ? src_k[i] : 0ull;
-        const unsigned d = (unsigned)(key >> shift) & 255u;
-        uint64_t same = __ballot(valid);
-#pragma unroll
-        for (int bb = 0; bb < 8; ++bb) {
-          const uint64_t bal = __ballot((d >> bb) & 1u);
-          same &= ((d >> bb) & 1u) ? bal : ~bal;
-        }
-        const unsigned rank_in_wave = (unsigned)__popcll(same & lt_mask);
-        if (valid && rank_in_wave == 0u) wcnt[wave][d] = (unsigned)__popcll(same);
-        __syncthreads();
-        if (valid) {
-          unsigned o2 = base[d] + rank_in_wave;
-          for (int w = 0; w < wave; ++w) o2 += wcnt[w][d];
-          dst_k[o2] = key;
-          dst_l[o2] = src_l[i];
-        }
-        __syncthreads();
-        base[tid] += wcnt[0][tid] + wcnt[1][tid] + wcnt[2][tid] + wcnt[3][tid];
-#pragma unroll
-        for (int w = 0; w < 4; ++w) wcnt[w][tid] = 0u;
-        __syncthreads();
-      }
-      __threadfence_block();
-      uint64_t* tk = src_k; src_k = dst_k; dst_k = tk;
-      uint8_t* tl = src_l; src_l = dst_l; dst_l = tl;
-    }
-    __syncthreads();
-    // the sorted bucket lies at src_k / src_l: chunks of 1 024 (four consecutive keys per thread) with carries
+    bucket_radix_sort(src_k, src_l, alt_keys + lo, alt_labs + lo, nb, diff, base, wcnt, dsum);
+    // the sorted bucket, read where it lies: chunks of 1 024 (four consecutive keys per thread) with carries
     if (tid == 0) { carry_tp_s = 0u; carry_prev_s = 0ull; }
     __syncthreads();
     for (unsigned c0 = 0; c0 < nb; c0 += 1024u) {
@@ -1608,7 +1301,7 @@ __global__ __launch_bounds__(256) void msd_sort_curve_kernel(uint64_t* __restric
 size_t align256(size_t v) { return (v + 255) & ~(size_t)255; }
 
 struct Layout {
-  size_t keys_a, keys_b, lab_a, lab_b, tps, prev_end, table, dtot, tile_sum, tile_end, tile_cnt, accum, flag, msd, parts, bucket_of, parts2, total;
+  size_t keys_a, keys_b, lab_a, lab_b, tps, prev_end, tile_sum, tile_end, tile_cnt, flag, msd, parts, bucket_of, parts2, total;
   unsigned nblocks;
 };
 
@@ -1622,14 +1315,11 @@ Layout make_layout(int64_t n) {
   L.lab_b = o; o += align256((size_t)n);
   L.tps = o; o += align256((size_t)n * 4);
   L.prev_end = o; o += align256((size_t)n * 4);
-  L.table = o; o += align256((size_t)256 * L.nblocks * 4);
-  L.dtot = o; o += align256(256 * 4);
   L.tile_sum = o; o += align256((size_t)L.nblocks * 4);
   L.tile_end = o; o += align256((size_t)L.nblocks * 4);
   L.tile_cnt = o; o += align256((size_t)L.nblocks * 4);
-  L.accum = o; o += align256(sizeof(MetricsAccum));
   L.flag = o; o += 256;
-  L.msd = o; o += align256(sizeof(MsdState));  // (accum, flag and msd are contiguous: one memset clears them)
+  L.msd = o; o += align256(sizeof(MsdState));
   L.parts = o; o += align256(kCurveBlocks * sizeof(MetricsAccum));  // per-workgroup records of the curve-term launch (written before read)
   L.bucket_of = o; o += align256((size_t)n * 2);                     // bucket of every key (key launch -> scatter)
   L.parts2 = o; o += align256((size_t)(kMsdBuckets / 4) * sizeof(FusedPart));  // per-workgroup records of the fused sort + curve launch
@@ -1651,92 +1341,55 @@ int ood_metrics(const T* ind, int64_t n_ind, const T* ood, int64_t n_ood, double
   uint8_t* labs[2] = {reinterpret_cast<uint8_t*>(w + L.lab_a), reinterpret_cast<uint8_t*>(w + L.lab_b)};
   unsigned* tps = reinterpret_cast<unsigned*>(w + L.tps);
   int* prev_end = reinterpret_cast<int*>(w + L.prev_end);
-  unsigned* table = reinterpret_cast<unsigned*>(w + L.table);
-  unsigned* dtot = reinterpret_cast<unsigned*>(w + L.dtot);
   unsigned* tile_sum = reinterpret_cast<unsigned*>(w + L.tile_sum);
   int* tile_end = reinterpret_cast<int*>(w + L.tile_end);
   unsigned* tile_cnt = reinterpret_cast<unsigned*>(w + L.tile_cnt);
-  MetricsAccum* acc = reinterpret_cast<MetricsAccum*>(w + L.accum);
   unsigned* flag = reinterpret_cast<unsigned*>(w + L.flag);
+  MsdState* st = reinterpret_cast<MsdState*>(w + L.msd);
+  uint16_t* bucket_of = reinterpret_cast<uint16_t*>(w + L.bucket_of);
   hipStream_t s = as_stream(stream);
-  // f32 scores widened to f64 have 29 zero mantissa bits at the bottom: the three lowest digits are the same for every
-  // key, so those passes would move nothing
-  const int first_pass = (sizeof(T) == 4) ? 3 : 0;
-#ifndef METRICS_MSD
-#define METRICS_MSD 1
-#endif
-#ifndef METRICS_FUSED
-#define METRICS_FUSED 1
-#endif
-  if (METRICS_MSD) {
-    MsdState* st = reinterpret_cast<MsdState*>(w + L.msd);
-    // eight launches, nothing cleared beforehand (MsdState)
-    const unsigned sgrid = runia_stream_grid(n, 256);
-    const unsigned pgrid = sgrid < kProbeBlocks ? sgrid : kProbeBlocks;
-    msd_probe_kernel<T><<<pgrid, 256, 0, s>>>(ind, n_ind, ood, n_ood, st);
-    // Small sets (<= 64 keys per bucket on average) skip the sketch: a raw-linear bin of a bell-shaped set holds a few times
-    // the mean, far below the wave sort's 1 024, and the launch would cost them 10 us of their 80
-    const int equalise = n > (int64_t)64 * kMsdBuckets;
-    if (equalise) {
-      const int64_t sketch_n = (n > kSketchAll) ? (n + kSketchStride - 1) / kSketchStride : n;
-      msd_lin_hist_kernel<T><<<(unsigned)((sketch_n + kScatTileHist - 1) / kScatTileHist), 256, 0, s>>>(ind, n_ind, ood, n_ood, flag, st, pgrid);
-      msd_split_kernel<T><<<kMsdBuckets / 256, 256, 0, s>>>(flag, st, pgrid);
-    }
-    uint16_t* bucket_of = reinterpret_cast<uint16_t*>(w + L.bucket_of);
-    // Front half of both forms (round 6): keys + buckets by splitter keys, scatter.  Buckets: 4 096 (equalised by the sketch) for
-    // large sets; for small ones raw-linear bins, ~64 keys each - every (tile, bucket) pair costs the scatter an atomic and every
-    // four buckets the sort launch a workgroup (20 000 scores in 4 096 buckets: 28 + 28 us for those two launches)
-    int nbk = kMsdBuckets;
-    if (!equalise) {
-      nbk = 64;
-      while (nbk < kMsdBuckets && (int64_t)nbk * 64 < n) nbk <<= 1;
-    }
-    if (n <= 65536) {  // small sets: smaller tiles, more workgroups (the two launches are latency-bound there)
-      msd_keys_split_kernel<T, 4><<<(unsigned)((n + 1023) / 1024), 256, 0, s>>>(ind, n_ind, ood, n_ood, flag, st, pgrid, keys[0], labs[0], bucket_of, equalise, nbk);
-      msd_scatter_kernel<T, 8><<<(unsigned)((n + 2047) / 2048), 256, 0, s>>>(keys[0], labs[0], keys[1], labs[1], n, bucket_of, st);
-    } else if (n <= 524288) {  // mid-sized sets: 16 keys per thread in the scatter (200 000 scores: 85 -> 73 us; 2 M: 230 -> 240)
-      msd_keys_split_kernel<T><<<L.nblocks, 256, 0, s>>>(ind, n_ind, ood, n_ood, flag, st, pgrid, keys[0], labs[0], bucket_of, equalise, nbk);
-      msd_scatter_kernel<T, 16><<<(unsigned)((n + 4095) / 4096), 256, 0, s>>>(keys[0], labs[0], keys[1], labs[1], n, bucket_of, st);
-    } else {
-      msd_keys_split_kernel<T><<<L.nblocks, 256, 0, s>>>(ind, n_ind, ood, n_ood, flag, st, pgrid, keys[0], labs[0], bucket_of, equalise, nbk);
-      msd_scatter_kernel<T><<<(unsigned)((n + kScatTile - 1) / kScatTile), 256, 0, s>>>(keys[0], labs[0], keys[1], labs[1], n, bucket_of, st);
-    }
-    if (METRICS_FUSED && !tps_out) {  // the three scalars alone: bucket sort + curve terms + finalise in ONE launch (six launches, four without the sketch)
-      msd_sort_curve_kernel<T><<<(unsigned)(nbk / 4), 256, 0, s>>>(keys[1], labs[1], keys[0], labs[0], st,
-                                                                   reinterpret_cast<FusedPart*>(w + L.parts2), (float)n_ind, (float)n_ood, out3);
-      return runia_check_launch();
-    }
-    // the curve API: every run's cumulative counts have to land in memory - bucket sort, tile summary, tile prefix, terms
-    msd_bucket_sort_kernel<T><<<kMsdBuckets / 4, 256, 0, s>>>(keys[1], labs[1], keys[0], labs[0], flag, st);  // (four buckets per workgroup)
-    tile_summary_kernel<<<L.nblocks, 256, 0, s>>>(keys[1], labs[1], n, tile_sum, tile_end, tile_cnt);
-    tile_prefix_raw_kernel<<<L.nblocks, 256, 0, s>>>(keys[1], labs[1], n, tile_sum, tile_end, tile_cnt, tps, prev_end, tps_out,
-                                                     fps_out, n_points);
-    curve_terms_finalize_kernel<<<(sgrid < kCurveBlocks ? sgrid : kCurveBlocks), 256, 0, s>>>(
-        keys[1], n, tps, prev_end, reinterpret_cast<MetricsAccum*>(w + L.parts), st, out3);
+  // nothing cleared beforehand (MsdState)
+  const unsigned sgrid = runia_stream_grid(n, 256);
+  const unsigned pgrid = sgrid < kProbeBlocks ? sgrid : kProbeBlocks;
+  msd_probe_kernel<T><<<pgrid, 256, 0, s>>>(ind, n_ind, ood, n_ood, st);
+  // Small sets (<= 64 keys per bucket on average) skip the sketch: a raw-linear bin of a bell-shaped set holds a few times
+  // the mean, far below the wave sort's 1 024, and the launch would cost them 10 us of their 80
+  const int equalise = n > (int64_t)64 * kMsdBuckets;
+  if (equalise) {
+    const int64_t sketch_n = (n > kSketchAll) ? (n + kSketchStride - 1) / kSketchStride : n;
+    msd_lin_hist_kernel<T><<<(unsigned)((sketch_n + kScatTileHist - 1) / kScatTileHist), 256, 0, s>>>(ind, n_ind, ood, n_ood, flag, st, pgrid);
+    msd_split_kernel<T><<<kMsdBuckets / 256, 256, 0, s>>>(flag, st, pgrid);
+  }
+  // Front half of both forms (round 6): keys + buckets by splitter keys, scatter.  Buckets: 4 096 (equalised by the sketch) for
+  // large sets; for small ones raw-linear bins, ~64 keys each - every (tile, bucket) pair costs the scatter an atomic and every
+  // four buckets the sort launch a workgroup (20 000 scores in 4 096 buckets: 28 + 28 us for those two launches)
+  int nbk = kMsdBuckets;
+  if (!equalise) {
+    nbk = 64;
+    while (nbk < kMsdBuckets && (int64_t)nbk * 64 < n) nbk <<= 1;
+  }
+  if (n <= 65536) {  // small sets: smaller tiles, more workgroups (the two launches are latency-bound there)
+    msd_keys_split_kernel<T, 4><<<(unsigned)((n + 1023) / 1024), 256, 0, s>>>(ind, n_ind, ood, n_ood, flag, st, pgrid, keys[0], labs[0], bucket_of, equalise, nbk);
+    msd_scatter_kernel<8><<<(unsigned)((n + 2047) / 2048), 256, 0, s>>>(keys[0], labs[0], keys[1], labs[1], n, bucket_of, st);
+  } else if (n <= 524288) {  // mid-sized sets: 16 keys per thread in the scatter (200 000 scores: 85 -> 73 us; 2 M: 230 -> 240)
+    msd_keys_split_kernel<T><<<L.nblocks, 256, 0, s>>>(ind, n_ind, ood, n_ood, flag, st, pgrid, keys[0], labs[0], bucket_of, equalise, nbk);
+    msd_scatter_kernel<16><<<(unsigned)((n + 4095) / 4096), 256, 0, s>>>(keys[0], labs[0], keys[1], labs[1], n, bucket_of, st);
+  } else {
+    msd_keys_split_kernel<T><<<L.nblocks, 256, 0, s>>>(ind, n_ind, ood, n_ood, flag, st, pgrid, keys[0], labs[0], bucket_of, equalise, nbk);
+    msd_scatter_kernel<kScatItems><<<(unsigned)((n + kScatTile - 1) / kScatTile), 256, 0, s>>>(keys[0], labs[0], keys[1], labs[1], n, bucket_of, st);
+  }
+  if (!tps_out) {  // the three scalars alone: bucket sort + curve terms + finalise in ONE launch (six launches, four without the sketch)
+    msd_sort_curve_kernel<<<(unsigned)(nbk / 4), 256, 0, s>>>(keys[1], labs[1], keys[0], labs[0], st,
+                                                              reinterpret_cast<FusedPart*>(w + L.parts2), (float)n_ind, (float)n_ood, out3);
     return runia_check_launch();
   }
-  if (hipMemsetAsync(flag, 0, 4, s) != hipSuccess) return RUNIA_E_LAUNCH;
-  if (hipMemsetAsync(acc, 0, 16, s) != hipSuccess) return RUNIA_E_LAUNCH;
-  if (hipMemsetAsync(&acc->fpr95_idx, 0xFF, 8, s) != hipSuccess) return RUNIA_E_LAUNCH;
-  const unsigned sgrid = runia_stream_grid(n, 256);
-  range_check_kernel<T><<<(sgrid < 1024u ? sgrid : 1024u), 256, 0, s>>>(ind, n_ind, ood, n_ood, flag);
-  make_keys_kernel<T><<<sgrid, 256, 0, s>>>(ind, n_ind, ood, n_ood, flag, keys[0], labs[0]);
-  int cur = 0;
-  for (int pass = first_pass; pass < 8; ++pass) {
-    const int shift = 8 * pass;
-    radix_hist_kernel<<<L.nblocks, 256, 0, s>>>(keys[cur], n, shift, table, L.nblocks);
-    radix_row_scan_kernel<<<256, 256, 0, s>>>(table, L.nblocks, dtot);
-    radix_scatter_kernel<<<L.nblocks, 256, 0, s>>>(keys[cur], labs[cur], keys[cur ^ 1], labs[cur ^ 1], n, shift, table,
-                                                   L.nblocks, dtot);
-    cur ^= 1;
-  }
-  tile_summary_kernel<<<L.nblocks, 256, 0, s>>>(keys[cur], labs[cur], n, tile_sum, tile_end, tile_cnt);
-  tile_scan_kernel<<<1, 64, 0, s>>>(tile_sum, tile_end, tile_cnt, L.nblocks);
-  tile_prefix_kernel<<<L.nblocks, 256, 0, s>>>(keys[cur], labs[cur], n, tile_sum, tile_end, tile_cnt, tps, prev_end, tps_out,
-                                               fps_out, n_points);
-  // bounded grid: every workgroup ends with three atomics on ONE record
-  curve_terms_kernel<<<(sgrid < 512u ? sgrid : 512u), 256, 0, s>>>(keys[cur], n, tps, prev_end, acc);
-  finalize_kernel<<<1, 64, 0, s>>>(acc, tps, n, out3);
+  // the curve API: every run's cumulative counts have to land in memory - bucket sort, tile summary, tile prefix, terms
+  msd_bucket_sort_kernel<<<kMsdBuckets / 4, 256, 0, s>>>(keys[1], labs[1], keys[0], labs[0], st);  // (four buckets per workgroup)
+  tile_summary_kernel<<<L.nblocks, 256, 0, s>>>(keys[1], labs[1], n, tile_sum, tile_end, tile_cnt);
+  tile_prefix_raw_kernel<<<L.nblocks, 256, 0, s>>>(keys[1], labs[1], n, tile_sum, tile_end, tile_cnt, tps, prev_end, tps_out,
+                                                   fps_out, n_points);
+  curve_terms_finalize_kernel<<<(sgrid < kCurveBlocks ? sgrid : kCurveBlocks), 256, 0, s>>>(
+      keys[1], n, tps, prev_end, reinterpret_cast<MetricsAccum*>(w + L.parts), st, out3);
   return runia_check_launch();
 }
 

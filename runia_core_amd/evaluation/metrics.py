@@ -1,7 +1,7 @@
 """Detection metrics after the scoring path (reference
 ``runia_core/evaluation/metrics.py:37-100`` ``get_auroc_results``).
 
-``auroc_fpr95_aupr_device`` keeps the whole step on the GPU (``runia_ood_metrics_*``: radix sort of the scores, scan of
+``auroc_fpr95_aupr_device`` keeps the whole step on the GPU (``runia_ood_metrics_*``: bucket sort of the scores, scan of
 the labels and run ends, trapezoid sums - ``csrc/metrics.hip``).  ``get_auroc_results`` / ``auroc_fpr95_aupr`` are the
 harness-facing forms: they also return the ROC curve as lists for the results table, which is host data by nature.  The
 O(N log N) part - torchmetrics' ``_binary_clf_curve``: sigmoid of scores outside [0, 1], descending sort, cumulative

@@ -106,15 +106,10 @@ add("f4.pred_h_mi", f4["pred_h_mi"]["ms"], [("mcd_uncertainty_kernel<16>", 7813)
 g1, _ = med("gemm_rows_kernel<float, float, 1, 2, 4>", 8192)
 rows.append(("f4.gmm_ddu (10 components)", f4["gmm_ddu"]["ms"], None if g1 is None else 10 * g1, "10 x the per-component launch"))
 mt = stg["metrics"]
-msum = sum((med(k, g)[0] or 0) for k, g in (("msd_probe_kernel<double>", 256), ("msd_lin_hist_kernel<double>", 245), ("msd_keys_kernel<double>", 489),
-                                            ("msd_scatter_kernel<double>", 245), ("msd_bucket_sort_kernel<double>", 1024), ("tile_summary_kernel", 489),
-                                            ("tile_prefix_raw_kernel", 489), ("curve_terms_finalize_kernel", 512)))
-# the bucket sort has the same grid (1 024 workgroups) for 20 000 and for 2 M scores: take its launches that belong to 2 M-score calls
-n_big = med("msd_scatter_kernel<double>", 245)[1]
-sorts = sorted(d for (n, x, y, z), v in groups.items() if "msd_bucket_sort_kernel<double>" in n for d in v)
-if n_big and len(sorts) >= n_big:
-    msum += st.median(sorts[-n_big:]) - (med("msd_bucket_sort_kernel<double>", 1024)[0] or 0)
-rows.append(("metrics.larem_f64_2m (8 launches)", mt["larem_f64_2m"]["ms"], msum, "sum of the eight kernels of a 2 M-score call"))
+msum = sum((med(k, g)[0] or 0) for k, g in (("msd_probe_kernel<double>", 256), ("msd_lin_hist_kernel<double>", 245), ("msd_split_kernel<double>", 16),
+                                            ("msd_keys_split_kernel<double, 16>", 489), ("msd_scatter_kernel<32>", 245), ("msd_sort_curve_kernel", 1024)))
+# (the last two serve f32 and f64 scores alike: their medians are over every 2 M-score call of the leg)
+rows.append(("metrics.larem_f64_2m (6 launches)", mt["larem_f64_2m"]["ms"], msum, "sum of the six kernels of a 2 M-score call"))
 
 print("| leg | in-run ms (events) | trace ms (sum of kernel medians) | in-run / trace | note |")
 print("|---|---|---|---|---|")

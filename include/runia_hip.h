@@ -539,6 +539,33 @@ int runia_rauq_rollout_att(const void* table, int dtype, int64_t n_gen, int64_t 
                            int token_agg, int route, int64_t n, float* att, void* workspace, size_t workspace_bytes,
                            runia_stream_t stream);
 
+/* ---- logit scores  per-token log-probabilities and entropies of an LLM generation -------------------------- *
+ * Replaces HuggingFace model.compute_transition_scores(sequences, scores, normalize_logits) as compute_uncertainties calls it
+ * (llm_uncertainty/scores.py:452-456, 495-499), generation_entropy's softmax per step (scores.py:135-152, utils.py:83-99),
+ * perplexity and normalized_entropy (scores.py:69-85, 121-132), for every row of a generate() output in one pass.
+ *   table   device array of n_steps step descriptors, 2 int64 each: {pointer to row 0 of the step's (B, V) or (B, 1, V)
+ *           logits, row stride (elements)}.  The vocabulary axis has unit stride.  dtype 0 f32, 1 f16, 2 bf16 (one per call).
+ *   tokens  int64, row b of the generated token ids at tokens + b * token_stride (>= n_steps when B > 1), each in [0, V)
+ *           (the caller checks the range: the kernels trust it).  Needed for log_prob only.
+ * Outputs (any may be NULL, not all), [B, n_steps] f32 row-major:
+ *   lse       log-sum-exp of the row;
+ *   log_prob  x[tok] - lse (normalize != 0) or x[tok];  a -inf logit gives -inf exactly;
+ *   entropy   -sum p log p / log V with p = softmax(x), as H = log1p(s') + u / (1 + s') from the max m, s' = sum e^(x-m)
+ *             without the max's own term and u = sum e^(x-m) (m - x): no cancellation.  The reference's clamp of p at 1e-12
+ *             (at most V e^-1 1e-12 nats) is not applied.
+ *   A row holding NaN or +inf, or only -inf, gives NaN in lse, entropy and the normalised log_prob.
+ *   seq       [3B + 1] f64 (needs log_prob and entropy): mean over steps of entropy (generation entropy), -mean of log_prob
+ *             (perplexity), the mean of the log_prob values that are not -inf, then normalized_entropy = -mean over rows of
+ *             those means.
+ * Rows are split into chunks of 4 096 logits, one workgroup each; partials merge in chunk order (f64), no atomics: two calls
+ * give equal bits and a row's outputs depend on its own logits only.  Three launches (two without seq), no synchronisation.
+ * workspace: runia_logit_stats_workspace_bytes(n_steps, B, V) bytes, 16-byte aligned (16 bytes per row and chunk); 0 for
+ * sizes the kernels do not take. */
+size_t runia_logit_stats_workspace_bytes(int64_t n_steps, int64_t B, int64_t V);
+int runia_logit_stats(const void* table, int dtype, int64_t n_steps, int64_t B, int64_t V, const int64_t* tokens,
+                      int64_t token_stride, int normalize, float* lse, float* log_prob, float* entropy, double* seq,
+                      void* workspace, size_t workspace_bytes, runia_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

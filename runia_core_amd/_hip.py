@@ -198,6 +198,12 @@ _SIGNATURES = {
         c_int,
         [c_void_p, c_int, c_int64, c_int64, c_int64, c_int64, c_int, c_int, c_int64, c_void_p, c_void_p, c_size_t, c_void_p],
     ),
+    "runia_logit_stats_workspace_bytes": (c_size_t, [c_int64, c_int64, c_int64]),
+    "runia_logit_stats": (
+        c_int,
+        [c_void_p, c_int, c_int64, c_int64, c_int64, c_void_p, c_int64, c_int, c_void_p, c_void_p, c_void_p, c_void_p,
+         c_void_p, c_size_t, c_void_p],
+    ),
     "runia_pca_md_score_f64": (
         c_int,
         [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_int64, c_int64,

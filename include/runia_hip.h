@@ -539,6 +539,42 @@ int runia_rauq_rollout_att(const void* table, int dtype, int64_t n_gen, int64_t 
                            int token_agg, int route, int64_t n, float* att, void* workspace, size_t workspace_bytes,
                            runia_stream_t stream);
 
+/* ---- batched RAUQ  every row of a left-padded batch of generations ---------- *
+ * Row b is scored as the runia_rauq_* calls score its own slices: step 0 [b, :, pad_b:, pad_b:], step g >= 1
+ * [b, :, :, pad_b:] for g < n_b, with input_length - pad_b as its input length (llm_uncertainty.rauq_batch).
+ *   table  device array of n_gen * L descriptors, step-major, 7 int64 each: {pointer to batch 0 of the step's (B, H, q, k)
+ *          tensor, batch stride, head stride, row stride, column stride (elements), k, q}.  Shapes as for runia_rauq_*,
+ *          with k = input_length at step 0 and input_length + g at step g; a step 0 of one query row only without padding.
+ *   rows   device array of B {pad_b, n_b} int64 pairs, 0 <= pad_b < input_length, 1 <= n_b <= n_gen (the kernels trust
+ *          it; runia_rauqb_rollout_att checks host_rows, its host copy).
+ * Outputs keep the one-row summation orders, roundings and fixed-order chain reductions, so row b's bits equal the one-row
+ * calls' on its slices and depend on that row alone.
+ * runia_rauqb_gather: w [B, L, H, N] f32, N = n_gen - 1 (token_agg 0) or n_gen; row b fills N_b = n_b - 1 or n_b tokens.
+ * runia_rauqb_score: one workgroup per row.  att [B, L, H, N] (head_mode 0 / 1) or [B, N] (head_mode 2, L = H = 1);
+ *   log_probs row b at log_probs + b * lp_stride; scores [B, n_alpha] f32.  A row with N_b < 1, or n_b < 2 for head_mode
+ *   2, gets NaN (its one-row call raises).  workspace: runia_rauqb_workspace_bytes(B, L, N, 0, 0, n_alpha).
+ * runia_rauqb_rollout_rows: the row pass of every row with n_b >= 2 over its T_b = input_length - pad_b + n_b rows;
+ *   upper_flags [B] device int.  workspace: runia_rauqb_workspace_bytes(B, L, n_gen, input_length, 0, 1) or larger.
+ * runia_rauqb_rollout_att: att [B, n_gen] f32, row b's n_b values first.  host_upper is the host copy of upper_flags.
+ *   token_agg 0: one launch over the rows with a clear flag (one pass), the n_b-row chain for the others; token_agg 1: the
+ *   1-row chain (causal or general, by the flag).  Chains run row after row in one workspace, each the one-row chain
+ *   over the row's own map table, which one small launch writes into the workspace first:
+ *   runia_rauqb_workspace_bytes(B, L, n_gen, input_length, k, 1), k the largest chain's rows (0 when there is none). */
+size_t runia_rauqb_workspace_bytes(int64_t B, int64_t L, int64_t n_gen, int64_t input_length, int64_t chain_rows,
+                                   int n_alpha);
+int runia_rauqb_gather(const void* table, const void* rows, int dtype, int64_t B, int64_t n_gen, int64_t L, int64_t H,
+                       int token_agg, float* w, runia_stream_t stream);
+int runia_rauqb_score(const float* att, const void* rows, int64_t B, int64_t L, int64_t H, int64_t N, int head_mode,
+                      int token_agg, const float* log_probs, int64_t lp_stride, const double* alphas, int n_alpha,
+                      float* scores, void* workspace, size_t workspace_bytes, runia_stream_t stream);
+int runia_rauqb_rollout_rows(const void* table, const void* rows, int dtype, int64_t B, int64_t n_gen, int64_t L, int64_t H,
+                             int64_t input_length, int* upper_flags, void* workspace, size_t workspace_bytes,
+                             runia_stream_t stream);
+int runia_rauqb_rollout_att(const void* table, const void* rows, const int64_t* host_rows, const int* upper_flags,
+                            const int* host_upper, int dtype, int64_t B, int64_t n_gen, int64_t L, int64_t H,
+                            int64_t input_length, int token_agg, float* att, void* workspace, size_t workspace_bytes,
+                            runia_stream_t stream);
+
 /* ---- logit scores  per-token log-probabilities and entropies of an LLM generation -------------------------- *
  * Replaces HuggingFace model.compute_transition_scores(sequences, scores, normalize_logits) as compute_uncertainties calls it
  * (llm_uncertainty/scores.py:452-456, 495-499), generation_entropy's softmax per step (scores.py:135-152, utils.py:83-99),

@@ -198,6 +198,20 @@ _SIGNATURES = {
         c_int,
         [c_void_p, c_int, c_int64, c_int64, c_int64, c_int64, c_int, c_int, c_int64, c_void_p, c_void_p, c_size_t, c_void_p],
     ),
+    "runia_rauqb_workspace_bytes": (c_size_t, [c_int64, c_int64, c_int64, c_int64, c_int64, c_int]),
+    "runia_rauqb_gather": (c_int, [c_void_p, c_void_p, c_int, c_int64, c_int64, c_int64, c_int64, c_int, c_void_p, c_void_p]),
+    "runia_rauqb_score": (
+        c_int,
+        [c_void_p, c_void_p, c_int64, c_int64, c_int64, c_int64, c_int, c_int, c_void_p, c_int64, c_void_p, c_int, c_void_p,
+         c_void_p, c_size_t, c_void_p],
+    ),
+    "runia_rauqb_rollout_rows": (
+        c_int, [c_void_p, c_void_p, c_int, c_int64, c_int64, c_int64, c_int64, c_int64, c_void_p, c_void_p, c_size_t, c_void_p]),
+    "runia_rauqb_rollout_att": (
+        c_int,
+        [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int64, c_int64, c_int64, c_int64, c_int64, c_int, c_void_p,
+         c_void_p, c_size_t, c_void_p],
+    ),
     "runia_logit_stats_workspace_bytes": (c_size_t, [c_int64, c_int64, c_int64]),
     "runia_logit_stats": (
         c_int,

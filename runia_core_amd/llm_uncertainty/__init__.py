@@ -1,6 +1,8 @@
 from .logits import GenerationScores, generation_scores, token_entropies, transition_scores  # noqa: F401
-from .rauq import RAUQ, rauq_uncertainty, rauq_uncertainty_mean_heads, rauq_uncertainty_rollout  # noqa: F401
+from .rauq import (RAUQ, generated_lengths, rauq_batch, rauq_uncertainty, rauq_uncertainty_mean_heads,  # noqa: F401
+                   rauq_uncertainty_rollout)
 from .scores import eigen_score, semantic_entropy  # noqa: F401
 
 __all__ = ["eigen_score", "semantic_entropy", "rauq_uncertainty", "rauq_uncertainty_mean_heads", "rauq_uncertainty_rollout",
-           "RAUQ", "GenerationScores", "generation_scores", "token_entropies", "transition_scores"]
+           "RAUQ", "rauq_batch", "generated_lengths", "GenerationScores", "generation_scores", "token_entropies",
+           "transition_scores"]

@@ -17,7 +17,11 @@ the device in ONE copy of the rows the mode reads.  All arithmetic is in ``csrc/
   the maps, no matrix product); otherwise a 1-row ("mean_all_tokens") or n-row ("original") block is left-multiplied
   through the layers, O(k T^2 L) instead of the reference's O(T^3 L) host products, and ``joint`` is never formed.
 
-The four names live on ``runia_core_amd.llm_uncertainty`` (the reference's package path, whose ``__init__`` star-imports
+``rauq_batch`` scores every row of a batched, left-padded generation in one walk over the maps: row b is scored as the
+one-row functions score its own slices (its left padding stripped, its steps after ``lengths[b]`` cut), and the
+kernels take all rows at once.  ``generated_lengths`` gives those lengths from a sampled generation's eos tokens.
+
+The four one-row names and the two batched ones live on ``runia_core_amd.llm_uncertainty`` (the reference's package path, whose ``__init__`` star-imports
 ``scores``), not on ``.scores``.  Without a GPU a valid call raises ``RuniaHipError``: there is no host fallback.
 """
 from __future__ import annotations
@@ -28,11 +32,13 @@ import torch
 
 from .. import _hip
 
-__all__ = ["rauq_uncertainty", "rauq_uncertainty_mean_heads", "rauq_uncertainty_rollout", "RAUQ"]
+__all__ = ["rauq_uncertainty", "rauq_uncertainty_mean_heads", "rauq_uncertainty_rollout", "RAUQ", "rauq_batch",
+           "generated_lengths"]
 
 _DTYPE_CODES = {torch.float32: 0, torch.float16: 1, torch.bfloat16: 2}
 _TOKEN_AGGREGATION = {"original": 0, "mean_all_tokens": 1}
 _HEAD_ARGMAX, _HEAD_MEAN, _SERIES = 0, 1, 2
+_HEAD_AGGREGATION = {"original": _HEAD_ARGMAX, "mean_heads": _HEAD_MEAN, "rollout": _SERIES}
 
 
 class _UnknownTokenAggregation(KeyError, UnboundLocalError):
@@ -231,3 +237,162 @@ def RAUQ(log_probs, attentions, input_length, token_aggregation, head_aggregatio
         "rollout": lambda: rauq_uncertainty_rollout(log_probs, attentions, token_aggregation, input_length, alphas, ablation),
     }
     return modes[head_aggregation]()
+
+
+# ---- batched ---------------------------------------------------------------------------------------------------------------
+def generated_lengths(sequences: torch.Tensor, input_length: int, eos_token_id: Union[int, List[int]]) -> torch.Tensor:
+    """(B,) int64: per row, the generated tokens up to and including the first eos in ``sequences[:, input_length:]``, or
+    all of them when the row has none (the ``lengths`` of ``rauq_batch`` for a sampled generation)."""
+    gen = torch.as_tensor(sequences)[:, int(input_length):]
+    ids = torch.as_tensor([eos_token_id] if isinstance(eos_token_id, int) else list(eos_token_id), device=gen.device)
+    hit = torch.isin(gen, ids.to(gen.dtype))
+    first = hit.to(torch.int8).argmax(dim=1).to(torch.int64) + 1
+    full = torch.full_like(first, int(gen.shape[1]))
+    return torch.where(hit.any(dim=1), first, full)
+
+
+def _batch_table(attentions, dev: torch.device, pads: List[int], first_row_only: bool):
+    """Device int64 table [n_gen * L, 7] of batched descriptors (batch 0 and the batch stride) and what it points into.
+    Host maps go up in one copy of the rows the mode reads: query row 0 of every row's own view, or everything."""
+    flat = [t for step in attentions for t in step]
+    if flat[0].is_cuda:
+        rows = [[t.data_ptr(), t.stride(0), t.stride(1), t.stride(2), t.stride(3), t.shape[3], t.shape[2]] for t in flat]
+        return torch.tensor(rows, dtype=torch.int64).to(dev), flat
+    parts = flat
+    if first_row_only:
+        # step 0: query row pad_b of row b, stored as one query row (which the kernels do not slice by rows again)
+        parts = [torch.stack([t[b, :, p:p + 1, :] for b, p in enumerate(pads)]) if t.shape[2] > 1 else t
+                 for t in attentions[0]] + [t[:, :, :1, :] for t in flat[len(attentions[0]):]]
+    total = sum(p.numel() for p in parts)
+    try:
+        host = torch.empty(total, dtype=flat[0].dtype, pin_memory=True)
+    except RuntimeError:
+        host = torch.empty(total, dtype=flat[0].dtype)
+    rows, at = [], 0
+    for p in parts:
+        b, h, q, k = p.shape
+        host[at:at + p.numel()].view(b, h, q, k).copy_(p)
+        rows.append([at, h * q * k, q * k, k, 1, k, q])
+        at += p.numel()
+    dmaps = host.to(dev)
+    base, size = dmaps.data_ptr(), dmaps.element_size()
+    for r in rows:
+        r[0] = base + r[0] * size
+    return torch.tensor(rows, dtype=torch.int64).to(dev), dmaps
+
+
+def _row_pads(attention_mask, batch: int, in_len: int) -> List[int]:
+    """Leading zeros of every mask row; ValueError unless the mask is left padding with a non-empty prompt per row."""
+    if attention_mask is None:
+        return [0] * batch
+    m = torch.as_tensor(attention_mask).detach().cpu()
+    if m.dim() != 2 or tuple(m.shape) != (batch, in_len):
+        raise ValueError(f"attention_mask must be ({batch}, {in_len}), got {tuple(m.shape)}")
+    on = m != 0
+    if not bool(on.any(dim=1).all()):
+        raise ValueError("attention_mask has a row of zeros: every row needs at least one prompt token")
+    pads = on.to(torch.int8).argmax(dim=1)
+    if not bool((on == (torch.arange(in_len)[None, :] >= pads[:, None])).all()):
+        raise ValueError("attention_mask is not left padding: a zero follows a one")
+    return [int(p) for p in pads]
+
+
+def _row_lengths(lengths, batch: int, n_gen: int) -> List[int]:
+    if lengths is None:
+        return [n_gen] * batch
+    n = torch.as_tensor(lengths).detach().cpu().reshape(-1)
+    if n.numel() != batch or n.is_floating_point() or n.is_complex():
+        raise ValueError(f"lengths must hold {batch} integers, got {tuple(torch.as_tensor(lengths).shape)}")
+    out = [int(v) for v in n.tolist()]
+    if any(v < 1 or v > n_gen for v in out):
+        raise ValueError(f"lengths must lie in [1, {n_gen}], got {out}")
+    return out
+
+
+@_hip._device_guard()
+def rauq_batch(log_probs: torch.Tensor, attentions: Tuple[Tuple[torch.Tensor, ...], ...], input_length: int,
+               token_aggregation: str, head_aggregation: str, alphas: List[float], attention_mask=None,
+               lengths=None) -> torch.Tensor:
+    """RAUQ of every row of a batched, left-padded generation: ``(B, len(alphas))`` f32, on the maps' GPU (on the host for
+    host maps).  Row b is bit for bit ``RAUQ(<its log-probs>, <its maps>, in_b, token_aggregation, head_aggregation,
+    alphas, True)`` on its own slices: pad_b = the leading zeros of ``attention_mask[b]`` (0 without a mask), in_b =
+    input_length - pad_b, n_b = ``lengths[b]`` (default: every step); step 0 ``[b:b+1, :, pad_b:, pad_b:]``, step 1 <= g <
+    n_b ``[b:b+1, :, :, pad_b:]``, log-probs ``log_probs[b, :n_b]``.  A row whose one-row call raises (n_b < 2 for
+    "original" token aggregation or the rollout) is NaN.  The maps are walked once for all rows."""
+    head_mode = _HEAD_AGGREGATION[head_aggregation]
+    tok = _TOKEN_AGGREGATION[token_aggregation]
+    n_gen, n_layers, heads, dtype, map_dev = _map_shapes(attentions)
+    in_len = int(input_length)
+    batch = int(attentions[0][0].shape[0])
+    if in_len < 1:
+        raise ValueError(f"input_length must be positive, got {input_length}")
+    for g, step in enumerate(attentions):
+        for t in step:
+            b, _, q, k = (int(v) for v in t.shape)
+            if b != batch:
+                raise ValueError(f"every map must have batch size {batch}, got {b} at step {g}")
+            ok = (k == in_len and q in (1, in_len)) if g == 0 else (k == in_len + g and q == 1)
+            if not ok:
+                raise ValueError(f"step {g} map {tuple(t.shape)} does not fit input_length={in_len}")
+    pads = _row_pads(attention_mask, batch, in_len)
+    if int(attentions[0][0].shape[2]) == 1 and any(pads):
+        raise ValueError("step 0 holds one query row: padded rows need the whole prompt block")
+    ns = _row_lengths(lengths, batch, n_gen)
+    lp = torch.as_tensor(log_probs)
+    if lp.dim() != 2 or int(lp.shape[0]) != batch or int(lp.shape[1]) < max(ns):
+        raise ValueError(f"log_probs must be ({batch}, >= {max(ns)}), got {tuple(lp.shape)}")
+    lib = _hip.load_library()
+    dev = _hip.require_gpu()
+    n_alpha = len(alphas)
+    out_dev = map_dev if map_dev is not None else dev
+    scores = torch.full((batch, n_alpha), float("nan"), dtype=torch.float32, device=dev)
+    if n_alpha == 0:
+        return scores if map_dev is not None else scores.cpu()
+    code = _DTYPE_CODES[dtype]
+    rows_h = torch.tensor([[p, n] for p, n in zip(pads, ns)], dtype=torch.int64)
+    rows_d = rows_h.to(dev)
+    lp_d = _hip.to_device(lp, torch.float32)
+    al = torch.tensor([float(a) for a in alphas], dtype=torch.float64).to(dev)
+    stream = _hip._stream()
+
+    def score(att, n_l, n_h, width, mode, ws):
+        _hip._check(lib.runia_rauqb_score(att.data_ptr(), rows_d.data_ptr(), batch, n_l, n_h, width, mode, tok, lp_d.data_ptr(),
+                                          lp_d.stride(0), al.data_ptr(), n_alpha, scores.data_ptr(), ws.data_ptr(), ws.numel(),
+                                          stream), "runia_rauqb_score")
+
+    if head_mode != _SERIES:
+        width = n_gen if tok else n_gen - 1
+        if width >= 1:
+            table, keep = _batch_table(attentions, dev, pads, first_row_only=True)
+            w = torch.empty((batch, n_layers, heads, width), dtype=torch.float32, device=dev)
+            _hip._check(lib.runia_rauqb_gather(table.data_ptr(), rows_d.data_ptr(), code, batch, n_gen, n_layers, heads, tok,
+                                               w.data_ptr(), stream), "runia_rauqb_gather")
+            ws = torch.empty(int(lib.runia_rauqb_workspace_bytes(batch, n_layers, width, 0, 0, n_alpha)), dtype=torch.uint8,
+                             device=dev)
+            score(w, n_layers, heads, width, head_mode, ws)
+            del keep
+    elif n_gen >= 2 and max(ns) >= 2:
+        table, keep = _batch_table(attentions, dev, pads, first_row_only=False)
+        flags = torch.zeros(batch, dtype=torch.int32, device=dev)
+
+        def row_pass(chain_rows):
+            ws = torch.empty(int(lib.runia_rauqb_workspace_bytes(batch, n_layers, n_gen, in_len, chain_rows, 1)),
+                             dtype=torch.uint8, device=dev)
+            _hip._check(lib.runia_rauqb_rollout_rows(table.data_ptr(), rows_d.data_ptr(), code, batch, n_gen, n_layers, heads,
+                                                     in_len, flags.data_ptr(), ws.data_ptr(), ws.numel(), stream),
+                        "runia_rauqb_rollout_rows")
+            return ws
+
+        ws = row_pass(1 if tok else 0)
+        upper = flags.cpu()  # the B flags in one copy
+        chained = [n for n, u in zip(ns, upper.tolist()) if n >= 2 and (tok or u)]
+        k = 0 if not chained else (1 if tok else max(chained))
+        if k > (1 if tok else 0):
+            ws = row_pass(k)  # the n-row chains need the larger workspace: the row pass runs again into it
+        att = torch.empty((batch, n_gen), dtype=torch.float32, device=dev)
+        _hip._check(lib.runia_rauqb_rollout_att(table.data_ptr(), rows_d.data_ptr(), rows_h.data_ptr(), flags.data_ptr(),
+                                                upper.data_ptr(), code, batch, n_gen, n_layers, heads, in_len, tok,
+                                                att.data_ptr(), ws.data_ptr(), ws.numel(), stream), "runia_rauqb_rollout_att")
+        score(att, 1, 1, n_gen, _SERIES, ws)
+        del keep
+    return scores if map_dev is not None else scores.cpu()

@@ -12,17 +12,27 @@ finds its inputs in a cache.
 `python bench.py --gpus N` with N > 1 and no WORLD_SIZE starts its own N ranks (torch.distributed.run as a child
 process, before this process makes any GPU call) and exits with the child's code.
 
-Prints ONE JSON line of < 4 KB (rank 0; contract_line below) with the driver's contract plus `roofline`, `cpu_baseline`,
-`parity` and `stages` as {leg: [ms, frac]} pairs.  The full record (everything listed below, per-step lists, notes, the harness
-table) goes to stderr and to bench_detail.json next to this file (and under gpurun_out/ when that directory exists):
+Prints ONE JSON line of < 4 KB (rank 0; contract_line below) with the contract keys plus `roofline`, and with --full
+`cpu_baseline`, `parity` and `stages` as {leg: [ms, frac]} pairs.  The full record (everything listed below, per-step lists,
+notes, the harness table) goes to stderr and to bench_detail.json (emit_record below).
+
+A plain run (`--gpus N --steps K --warmup W`) does what its headline figure needs and nothing else: setup, warm-up, the K
+timed steps, --dump-outputs, the line.  Its record carries, beside the headline:
   `roofline`      dominant kernel (K1, sampler + entropy), timed inside the timed region with HIP events attached to its
                   dispatch on its launch stream (the kernel's own start / end timestamps, as rocprofv3's kernel trace
-                  reports them; runia_time_next_launch); `achieved` uses BASELINE.md section 4's algorithmic 33 800 B/image;
+                  reports them; runia_time_next_launch); `achieved` uses BASELINE.md section 4's algorithmic 33 800 B/image.
+--full adds everything else the benchmark measures or checks (each leg can still be left out with its --no-* option):
   `cpu_baseline`  the CPU oracle in the reference's algorithmic form on a bounded sample, 1 core;
   `cpu_baseline_all_cores`  the same work fanned out per image over a process pool, as the reference's
                   parallel_run=True does (evaluation/entropy.py:86-91);
+  `parity`        the last timed step's scores against the oracle on that sample, and counter vs host draws over 12 seeds;
   `api_level`     the same workload through the public batched API with NO caller-supplied draws
-                  (LaRExInference.get_scores_from_latents, sampler in counter-draw mode).
+                  (LaRExInference.get_scores_from_latents, sampler in counter-draw mode);
+  `stages`        the other BASELINE.json configs at their own sizes (cfg3's postprocessors, cfg4, fits, metrics, the
+                  harness loops);
+  `config.setup.fit_s_host_calls` (the setup fit through the reference's host calls) and, with N > 1,
+                  `gather.ms_per_step_without_gather` (the same steps without their collective).
+The other workloads (--workload) run their CPU legs with --full only.
 The oracle is the checker / baseline only; it is never the thing measured.
 """
 from __future__ import annotations
@@ -198,9 +208,14 @@ def parse_args():
     ap.add_argument("--rows", type=int, default=1_000_000, help="cfg3: rows of the synthetic test set (all ranks together)")
     ap.add_argument("--fit-rows", type=int, default=None,
                     help="cfg3: training rows of the Mahalanobis fit (default: all 50 000 for --workload cfg3, 8 192 in "
-                         "the stages block of the default run; the kNN bank always holds 50 000 rows)")
+                         "the stages block of a --full cfg2 run; the kNN bank always holds 50 000 rows)")
+    ap.add_argument("--full", action="store_true",
+                    help="besides the headline figure, run every other leg the benchmark measures or checks: CPU "
+                         "baselines, parity against the oracle, api_level, the `stages` block, the setup fit through the "
+                         "host calls and, with N > 1, the steps without their gather.  Off (default): set up, warm up, "
+                         "time the steps, write --dump-outputs and print the line, nothing else")
     ap.add_argument("--no-stages", action="store_true",
-                    help="cfg2: leave out the `stages` block (cfg3 postprocessors + cfg4 LaRED leg at BASELINE sizes)")
+                    help="cfg2 with --full: leave out the `stages` block (cfg3 postprocessors + cfg4 LaRED leg at BASELINE sizes)")
     ap.add_argument("--images", type=int, default=10000, help="test images per GPU (workload: 10 000)")
     ap.add_argument("--train-images", type=int, default=4096)
     ap.add_argument("--input-sets", type=int, default=3,
@@ -210,8 +225,8 @@ def parse_args():
                          "path) or made inside the keep-flag kernel by the counter generator")
     ap.add_argument("--ood-corr", type=float, default=0.25, help="spatial correlation of the OOD sample's latent maps")
     ap.add_argument("--cpu-sample", type=int, default=1280, help="images timed on the CPU oracle (1 core)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-api-level", action="store_true")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: leave out the CPU legs")
+    ap.add_argument("--no-api-level", action="store_true", help="cfg2 with --full: leave out `api_level`")
     ap.add_argument("--overlap", action="store_true",
                     help="two HIP streams: K1 of batch i+1 beside K2 of batch i (measured: no gain, 0.324 vs 0.329 ms)")
     ap.add_argument("--chunks", type=int, default=None, help="row blocks pipelined over two streams (default: pipeline's)")
@@ -246,6 +261,10 @@ def parse_args():
         args.steps = {"cfg2": 200, "cfg3": 3, "larex_eval": 1, "baselines_eval": 1}[args.workload]
     if args.warmup is None:
         args.warmup = {"cfg2": 10, "cfg3": 1, "larex_eval": 1, "baselines_eval": 1}[args.workload]
+    # the legs beyond the headline figure: all of them with --full, none without
+    args.cpu_legs = args.full and not args.no_cpu_baseline
+    args.api_level = args.full and not args.no_api_level
+    args.stages = args.full and not args.no_stages
     return args
 
 
@@ -358,7 +377,7 @@ def main_cfg3(args, device, rank, world, dist, saved_stdout):
     gc.disable()
     log = (lambda m: print(m, file=sys.stderr, flush=True)) if rank == 0 else None
     rec = bw.run_cfg3(device, rank, world, dist, args.rows, args.fit_rows or bw.BANK_ROWS, args.steps, args.warmup,
-                      cpu_legs=not args.no_cpu_baseline, log=log)
+                      cpu_legs=args.cpu_legs, log=log)
     gc.enable()
     if rank != 0:
         if dist is not None:
@@ -417,7 +436,7 @@ def main_larex(args, device, rank, world, dist, saved_stdout):
     import bench_workloads as bw
 
     log = (lambda m: print(m, file=sys.stderr, flush=True)) if rank == 0 else None
-    rec = bw.run_larex_eval(device, cpu_legs=(rank == 0 and not args.no_cpu_baseline), log=log)
+    rec = bw.run_larex_eval(device, cpu_legs=(rank == 0 and args.cpu_legs), log=log)
     if dist is not None:
         t = torch.tensor([rec["seconds_device_resident"]], dtype=torch.float64, device=device)
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
@@ -453,7 +472,7 @@ def main_baselines(args, device, rank, world, dist, saved_stdout):
     import bench_workloads as bw
 
     log = (lambda m: print(m, file=sys.stderr, flush=True)) if rank == 0 else None
-    rec = bw.run_baselines_eval(device, cpu_legs=(rank == 0 and not args.no_cpu_baseline), log=log)
+    rec = bw.run_baselines_eval(device, cpu_legs=(rank == 0 and args.cpu_legs), log=log)
     if dist is not None:
         t = torch.tensor([rec["seconds_device_resident"]], dtype=torch.float64, device=device)
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
@@ -552,7 +571,7 @@ def main():
     red, pca, md, setup_s = fit_cfg2()
     setup_rec = {"mode": "device" if rc_config.use_device_fit() else "host", "fit_s": round(setup_s, 3),
                  "what": f"apply_pca_ds_split({h_train.shape[0]} x {h_train.shape[1]} -> {N_PCA}, randomized) + MDLatentSpace.setup"}
-    if rc_config.use_device_fit() and rank == 0 and not args.no_cpu_baseline:
+    if rc_config.use_device_fit() and rank == 0 and args.cpu_legs:
         before = rc_config.device_fit
         rc_config.device_fit = False  # the reference's own host calls beside it (reported, not used)
         try:
@@ -746,6 +765,7 @@ def main():
         elapsed = float(every.max().item())
         gather_info["chosen"] = gather_mode["kind"]
         gather_info["per_rank_ms_per_step"] = [round(1e3 * float(v) / args.steps, 4) for v in every.tolist()]
+    if use_dist and args.full:
         # the same steps without their collective, right after the timed region: what the gather costs on this node
         dist.barrier()
         torch.cuda.synchronize()
@@ -780,7 +800,7 @@ def main():
 
     # ---------------- API level: the public batched entry point, no caller-supplied draws ---------------------------
     api = None
-    if not args.no_api_level and not use_dist:
+    if args.api_level and not use_dist:
         from runia_core_amd import LaRExInference, MCSamplerModule
 
         infer = LaRExInference(torch.nn.Identity(), md, DROP_PROB, BLOCK, N_MC, MCSamplerModule, pca_transform=pca)
@@ -912,7 +932,7 @@ def main():
         out["gather"] = gather_info
     if api is not None:
         out["api_level"] = api
-    if world == 1 and not args.no_cpu_baseline and not counter:
+    if world == 1 and args.cpu_legs and not counter:
         import oracle  # checker / CPU baseline only
 
         m = min(args.cpu_sample, n)
@@ -1004,7 +1024,7 @@ def main():
             }
         except Exception as e:  # the pool leg is a reported baseline; its failure must not lose the measurement
             out["cpu_baseline_all_cores"] = {"value": None, "error": repr(e)[:200]}
-    if world == 1 and not args.no_stages and not use_dist:
+    if world == 1 and args.stages and not use_dist:
         # the other BASELINE.json configs at their own sizes under the driver's clock: cfg3's postprocessors on 1M x 2048
         # rows (tools/bench_workloads.py, the code of --workload cfg3) and cfg4's LaRED leg
         try:
@@ -1014,7 +1034,7 @@ def main():
             del sets, x, rand
             torch.cuda.empty_cache()
             t_s = time.perf_counter()
-            cpu = not args.no_cpu_baseline
+            cpu = args.cpu_legs
             c3 = bw.run_cfg3(device, 0, 1, None, args.rows, args.fit_rows or 8192, 2, 1, cpu_legs=cpu, f4=True)
             stages = dict(c3["stages"])
             stages["f4"] = c3.get("f4")

@@ -214,3 +214,45 @@ def test_steps_and_dump_outputs_arguments(monkeypatch):
         monkeypatch.setattr(sys, "argv", ["bench.py"] + bad)
         with pytest.raises(SystemExit):
             bench.parse_args()
+
+
+def test_plain_run_has_no_extra_legs_and_full_has_them_all(monkeypatch):
+    """A plain run measures the headline figure only; --full adds every other leg, each of which its --no-* option drops."""
+    def args(*extra):
+        monkeypatch.setattr(sys, "argv", ["bench.py", "--gpus", "1", "--steps", "20", "--warmup", "5", *extra])
+        a = bench.parse_args()
+        return a.full, a.cpu_legs, a.api_level, a.stages
+
+    assert args() == (False, False, False, False)
+    assert args("--no-stages", "--no-cpu-baseline") == (False, False, False, False)
+    assert args("--full") == (True, True, True, True)
+    assert args("--full", "--no-stages") == (True, True, True, False)
+    assert args("--full", "--no-cpu-baseline", "--no-api-level") == (True, False, False, True)
+    assert args("--workload", "cfg3")[1] is False and args("--workload", "cfg3", "--full")[1] is True
+
+
+@pytest.mark.gpu
+def test_plain_run_prints_the_headline_and_dumps_the_scores(tmp_path):
+    """`bench.py --gpus 1 --steps K --warmup W` end to end on the GPU: one contract line with the headline keys, the last
+    timed step's scores dumped, and none of the legs that --full adds."""
+    import subprocess
+
+    import numpy as np
+
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "3", "--warmup", "1",
+                        "--dump-outputs", str(tmp_path)], capture_output=True, text=True, timeout=600)
+    assert r.returncode == 0, r.stderr[-3000:]
+    lines = r.stdout.splitlines()
+    assert len(lines) == 1
+    line = json.loads(lines[0])
+    assert line["metric"] == "OOD scores/sec, LaREM 16-MC PCA-256 (ResNet-18 layer4 latent 512x4x4)"
+    assert (line["unit"], line["higher_is_better"], line["dtype"], line["steps"], line["warmup"]) == ("images/s", True, "f64", 3, 1)
+    assert line["value"] > 0 and line["ms_per_step"] > 0
+    assert abs(line["value"] - 10000 / (line["ms_per_step"] * 1e-3)) < 0.01 * line["value"]
+    assert isinstance(line["roofline"], dict) and line["roofline"]["avg_launch_ms"] > 0
+    assert not {"cpu_baseline", "parity", "stages"} & set(line)
+    detail = json.loads(next(l for l in r.stderr.splitlines() if l.startswith("bench detail: "))[len("bench detail: "):])
+    assert not {"cpu_baseline", "cpu_baseline_all_cores", "parity", "api_level", "stages"} & set(detail)
+    assert "fit_s_host_calls" not in detail["config"]["setup"]
+    scores = np.load(tmp_path / "scores.npy")
+    assert scores.shape == (10000,) and scores.dtype == np.float64 and np.isfinite(scores).all()

@@ -602,6 +602,52 @@ int runia_logit_stats(const void* table, int dtype, int64_t n_steps, int64_t B, 
                       int64_t token_stride, int normalize, float* lse, float* log_prob, float* entropy, double* seq,
                       void* workspace, size_t workspace_bytes, runia_stream_t stream);
 
+/* ---- open-set object detection evaluation (evaluation/open_set.py; csrc/open_set.hip) --------------------
+ * quantize: out[i] = float(f"{v:.{decimals}f}") of v = x[i] (+1 in x's own dtype when bit (i % period) of add_one_mask is
+ *   set: process()'s xmin + 1, ymin + 1).  dtype 0 f32, 1 f64, 2 int32, 3 int64.  key_out (nullable): key_max - k with
+ *   k = v * 10^decimals rounded half-to-even, the descending-confidence sort key; a k outside [0, key_max] sets *bad to 1.
+ * bucket_sort: stable ascending counting sort of keys in [0, nb), nb <= 8192: perm[j] = input index of output j,
+ *   bucket_start[nb + 1] (int64) = first output of each bucket.  Workspace: runia_osod_sort_workspace_bytes(n, nb).
+ * overlaps: per detection (f64 quantised boxes [n, 4]) the (ovmax, jmax) of the reference IoU against the ground truth of
+ *   group det_group[d] and of unk_group in image det_img[d] (-1: not annotated -> -inf, -1).  gt_off[n_groups * n_img + 1]:
+ *   ground-truth boxes [.., 4] f64 ordered by (group, image).  ov [n, 2] f64, jpos [n, 2] int32 (global positions).
+ * match: per (method m, sorted position p) with d = perm[p]: class c = K (= n_classes - 1) when relabelled (open_set:
+ *   label == unk_label; else mscore[m, d] < thr[m], both already in the comparison dtype), else label; c = n_classes when
+ *   c is out of range or conf[d] >= min_conf fails (conf nullable).  key[m, p] = m * (n_classes + 1) + c; flags[m, p]:
+ *   1 TP, 2 FP, 0 skipped, | 4 when the unknown overlap exceeds ovthresh.  A candidate (ovmax > ovthresh) is a TP when no
+ *   earlier candidate of the same (m, c, ground-truth slot) exists; slot = cbase[c] + jpos - gstart[group_of_class[c]].
+ *   Workspace: runia_osod_match_workspace_bytes(n_methods, n_slots).
+ * gtu_keys: GTU / UU partition keys from a one-method match: c for rows overlapping unknown ground truth, n_classes + c for
+ *   the others, 2 n_classes for rows not evaluated.
+ * gather_f64: out[i] = src[idx1[idx0[i]]] (idx1 nullable: src[idx0[i]]).
+ * curves: one workgroup per (method, class) segment of bucket_start (from bucket_sort of match's keys; part = its perm):
+ *   summary [n_methods, n_classes, 8] f64 = {ap, rec[-1], prec[-1], tp+fp and fp_os at the first argmin |rec - 0.8|,
+ *   open-set FP count, max(tp+fp), rows}; rec / prec / tpfp / fpos (nullable, all or none) [n_methods * n] at partition
+ *   positions.  use_07: 11-point AP.  Workspace: runia_osod_curves_workspace_bytes(n_methods * n).
+ * No float atomics anywhere: two calls give equal bits. */
+int runia_osod_quantize(const void* x, int dtype, int64_t n, int period, unsigned add_one_mask, int decimals, double* out,
+                        int32_t* key_out, int key_max, int32_t* bad, runia_stream_t stream);
+size_t runia_osod_sort_workspace_bytes(int64_t n, int nb);
+int runia_osod_bucket_sort(const int32_t* keys, int64_t n, int nb, int32_t* perm, int64_t* bucket_start, void* workspace,
+                           size_t workspace_bytes, runia_stream_t stream);
+int runia_osod_overlaps(const double* boxes, const int32_t* det_img, const int32_t* det_group, int64_t n,
+                        const double* gt_boxes, const int32_t* gt_off, int n_img, int n_groups, int unk_group, double* ov,
+                        int32_t* jpos, runia_stream_t stream);
+size_t runia_osod_match_workspace_bytes(int n_methods, int64_t n_slots);
+int runia_osod_match(const int32_t* perm, int64_t n, int n_methods, int n_classes, const int32_t* label,
+                     const int32_t* det_img, const double* ov, const int32_t* jpos, const double* mscore, const double* thr,
+                     int open_set, int unk_label, const double* conf, double min_conf, const int32_t* group_of_class,
+                     const int32_t* gstart, const int64_t* cbase, int64_t n_slots, double ovthresh, int32_t* key,
+                     uint8_t* flags, void* workspace, size_t workspace_bytes, runia_stream_t stream);
+int runia_osod_gtu_keys(const int32_t* key, const uint8_t* flags, int64_t n, int n_classes, int32_t* out,
+                        runia_stream_t stream);
+int runia_osod_gather_f64(const double* src, int64_t n_src, const int32_t* idx0, const int32_t* idx1, int64_t n, double* out,
+                          runia_stream_t stream);
+size_t runia_osod_curves_workspace_bytes(int64_t rows);
+int runia_osod_curves(const int32_t* part, const int64_t* bucket_start, const uint8_t* flags, int64_t n, int n_methods,
+                      int n_classes, const int64_t* npos, int use_07, double* summary, double* rec, double* prec,
+                      double* tpfp, double* fpos, void* workspace, size_t workspace_bytes, runia_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -223,6 +223,26 @@ _SIGNATURES = {
         [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_int64, c_int64,
          c_void_p],
     ),
+    "runia_osod_quantize": (
+        c_int, [c_void_p, c_int, c_int64, c_int, ctypes.c_uint32, c_int, c_void_p, c_void_p, c_int, c_void_p, c_void_p]),
+    "runia_osod_sort_workspace_bytes": (c_size_t, [c_int64, c_int]),
+    "runia_osod_bucket_sort": (c_int, [c_void_p, c_int64, c_int, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]),
+    "runia_osod_overlaps": (
+        c_int, [c_void_p, c_void_p, c_void_p, c_int64, c_void_p, c_void_p, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p]),
+    "runia_osod_match_workspace_bytes": (c_size_t, [c_int, c_int64]),
+    "runia_osod_match": (
+        c_int,
+        [c_void_p, c_int64, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_void_p,
+         c_double, c_void_p, c_void_p, c_void_p, c_int64, c_double, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p],
+    ),
+    "runia_osod_gtu_keys": (c_int, [c_void_p, c_void_p, c_int64, c_int, c_void_p, c_void_p]),
+    "runia_osod_gather_f64": (c_int, [c_void_p, c_int64, c_void_p, c_void_p, c_int64, c_void_p, c_void_p]),
+    "runia_osod_curves_workspace_bytes": (c_size_t, [c_int64]),
+    "runia_osod_curves": (
+        c_int,
+        [c_void_p, c_void_p, c_void_p, c_int64, c_int, c_int, c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_void_p,
+         c_void_p, c_void_p, c_size_t, c_void_p],
+    ),
 }
 
 

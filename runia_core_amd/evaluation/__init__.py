@@ -3,3 +3,18 @@ from .metrics import get_auroc_results  # noqa: F401
 from .metrics import log_evaluate_postprocessors, select_and_log_best_larex  # noqa: F401
 from .latent_space import log_evaluate_larex  # noqa: F401
 from .baselines import baseline_name_dict, calculate_all_baselines, get_labels_from_logits, remove_latent_features  # noqa: F401
+from .open_set import (  # noqa: F401
+    COCOParser,
+    OpenSetEvaluator,
+    convert_xywh_to_xyxy,
+    evaluate_open_set_detection_methods,
+    evaluate_open_set_detection_one_method,
+    get_boxes_from_precalculated,
+    get_boxes_gtu_and_uu_ood_dataset,
+    get_gtu_uu_per_class,
+    get_labels_and_scores_from_logits,
+    get_n_unk_ood_dataset,
+    get_overall_open_set_results,
+    voc_ap,
+    voc_eval,
+)

@@ -602,6 +602,17 @@ int runia_logit_stats(const void* table, int dtype, int64_t n_steps, int64_t B, 
                       int64_t token_stride, int normalize, float* lse, float* log_prob, float* entropy, double* seq,
                       void* workspace, size_t workspace_bytes, runia_stream_t stream);
 
+/* ---- batched eigen_score (llm_uncertainty/scores.py:49-66, utils.py:102-117; csrc/eigen_score.hip) --------
+ * runia_eigen_score_batch: e holds groups * k rows of `hidden` values, dtype 0 f32, 1 f16, 2 bf16, unit column stride,
+ *   row_stride elements between rows (hidden_states[-1][layer] of generate(num_return_sequences=k), read in place).
+ *   out[g] (f64) = [sum over the top min(k, hidden) eigenvalues lambda of the centred Gram matrix Ec Ec^T / (k - 1) of rows
+ *   g*k .. g*k+k-1 of log(max(lambda, 0) + alpha) + (hidden - min(k, hidden)) log(alpha)] / hidden.
+ *   One workgroup per group, one launch, no synchronisation: f64 column means and products, cyclic Jacobi in LDS until a
+ *   sweep applies no rotation (NaN after 30 sweeps).  No atomics: a group's bits do not depend on the other groups.
+ *   2 <= k <= 64, hidden > 0, row_stride >= 0, 1 <= groups < 2^31; RUNIA_E_INVALID otherwise.  No workspace. */
+int runia_eigen_score_batch(const void* e, int dtype_code, int64_t groups, int64_t k, int64_t hidden, int64_t row_stride,
+                            double alpha, double* out, runia_stream_t stream);
+
 /* ---- open-set object detection evaluation (evaluation/open_set.py; csrc/open_set.hip) --------------------
  * quantize: out[i] = float(f"{v:.{decimals}f}") of v = x[i] (+1 in x's own dtype when bit (i % period) of add_one_mask is
  *   set: process()'s xmin + 1, ymin + 1).  dtype 0 f32, 1 f64, 2 int32, 3 int64.  key_out (nullable): key_max - k with

@@ -218,6 +218,7 @@ _SIGNATURES = {
         [c_void_p, c_int, c_int64, c_int64, c_int64, c_void_p, c_int64, c_int, c_void_p, c_void_p, c_void_p, c_void_p,
          c_void_p, c_size_t, c_void_p],
     ),
+    "runia_eigen_score_batch": (c_int, [c_void_p, c_int, c_int64, c_int64, c_int64, c_int64, c_double, c_void_p, c_void_p]),
     "runia_pca_md_score_f64": (
         c_int,
         [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_int64, c_int64,
@@ -1382,6 +1383,40 @@ def centred_gram(e: torch.Tensor, denom: float) -> torch.Tensor:
     g = torch.empty((n, n), dtype=torch.float64, device=e.device)
     _check(lib.runia_centred_gram_f32(e.data_ptr(), g.data_ptr(), n, h, float(denom), _stream()), "runia_centred_gram_f32")
     return g
+
+
+_EIGEN_DTYPES = {torch.float32: 0, torch.float16: 1, torch.bfloat16: 2}
+EIGEN_SCORE_MAX_K = 64
+
+
+@_device_guard()
+def eigen_scores(e: torch.Tensor, k: int, alpha: float = 1e-3) -> torch.Tensor:
+    """e [G * k, H] f32 / f16 / bf16 (host or one GPU, any row stride) -> [G] f64: the eigen_score of every group of k
+    consecutive rows, all groups in ONE launch of ``runia_eigen_score_batch`` (2 <= k <= 64).  Device rows are read in place
+    (a view whose columns are not unit-stride is made contiguous); host rows go up in one copy in their own dtype.  The
+    result lies where ``e`` does."""
+    lib = load_library()
+    if not isinstance(e, torch.Tensor) or e.dim() != 2:
+        raise ValueError("eigen_scores takes a 2-D (G * k, hidden) tensor")
+    if e.dtype not in _EIGEN_DTYPES:
+        raise TypeError(f"eigen_scores takes float32, float16 or bfloat16 rows, not {e.dtype}")
+    n, h = (int(v) for v in e.shape)
+    k = int(k)
+    if not 2 <= k <= EIGEN_SCORE_MAX_K:
+        raise ValueError(f"groups of k = {k} samples: the kernel takes 2 <= k <= {EIGEN_SCORE_MAX_K}")
+    if n == 0 or h == 0 or n % k:
+        raise ValueError(f"{n} rows of width {h} do not form groups of {k} samples")
+    dev = require_gpu()
+    on_host = not e.is_cuda
+    x = e.detach()
+    if on_host:
+        x = x.contiguous().to(dev)
+    elif h > 1 and x.stride(1) != 1:
+        x = x.contiguous()
+    out = torch.empty(n // k, dtype=torch.float64, device=x.device)
+    _check(lib.runia_eigen_score_batch(x.data_ptr(), _EIGEN_DTYPES[x.dtype], n // k, k, h, x.stride(0), float(alpha),
+                                       out.data_ptr(), _stream()), "runia_eigen_score_batch")
+    return out.cpu() if on_host else out
 
 
 @_device_guard("boxes", "batch_idx")

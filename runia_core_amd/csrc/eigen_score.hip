@@ -1,0 +1,259 @@
+// eigen_score of many sample groups in one launch (reference llm_uncertainty/scores.py:49-66, utils.py:102-117; Chen et
+// al. 2024).  e holds groups * k rows of `hidden` values (f32 / f16 / bf16, unit column stride, any row stride): the
+// last-token hidden states hidden_states[-1][layer] of generate(num_return_sequences=k) on a batch of prompts, prompt-major
+// as HF's repeat_interleave leaves them, read in place.  Group g = rows g*k .. g*k+k-1:
+//
+//   out[g] = [ sum_{top min(k, hidden)} log(max(lambda_i, 0) + alpha) + (hidden - min(k, hidden)) log(alpha) ] / hidden,
+//
+// lambda = eigenvalues of the centred Gram matrix Ec Ec^T / (k - 1) - the non-zero spectrum of the reference's
+// torch.cov(E.T) (the Gram form of llm_uncertainty/scores.py, which runs centred_gram_kernel and the Jacobi sweeps of
+// eigh.hip with one host read-back per sweep).
+//
+// One workgroup of 256 threads per group, no atomics, no state shared between workgroups: a group's bits do not depend
+// on the other groups of the launch.  LDS: 64 KB, two 4 096-double halves.
+//   Gram     column chunks of C = 4096 / kpad columns (kpad = k rounded up to 4) are staged in half 0 as f64, centred by
+//            their f64 column mean over the k rows (centred_gram_kernel's arithmetic: widen, mean in row order, product
+//            in f64).  The k(k+1)/2 entries are covered by Q = kb(kb+1)/2 tiles of 4 x 4 entries (kb = kpad / 4, tile
+//            rows <= tile columns): one tile per thread, 16 accumulators, 8 LDS reads per 16 products; R = 256 / Q
+//            threads share a tile and take every R-th column.  The R partials are summed in slot order into G (half 1).
+//   Jacobi   cyclic two-sided Jacobi on G in LDS without eigenvectors: round-robin (circle method) ordering of m/2 disjoint
+//            pairs per step, the rotation rule and threshold of jacobi_angles_kernel (eigh.hip), 2 x 2 block updates of
+//            the upper block triangle mirrored (G stays exactly symmetric).  The "rotated" flag lives in LDS; the loop
+//            stops after the first sweep that applies no rotation, and a group still rotating after 30 sweeps gets NaN.
+//   Score    diag(G) clamped at 0, ranked in descending order, the top min(k, hidden) summed in that order in f64.
+#include <math.h>
+
+#include "common.hpp"
+
+namespace {
+
+enum { kF32 = 0, kF16 = 1, kBF16 = 2 };  // llm_uncertainty/rauq.py _DTYPE_CODES
+
+constexpr int kThreads = 256;
+constexpr int kMaxK = 64;
+constexpr int kHalf = 4096;  // doubles per LDS half: kMaxK x kMaxK, and the staged chunk
+constexpr int kMaxSweeps = 30;
+
+template <int DT>
+__device__ __forceinline__ double load_wide(const void* base, int64_t i) {
+  if constexpr (DT == kF32) {
+    return (double)reinterpret_cast<const float*>(base)[i];
+  } else {
+    const unsigned short h = reinterpret_cast<const unsigned short*>(base)[i];
+    if constexpr (DT == kF16) return (double)(float)__builtin_bit_cast(_Float16, h);
+    else return (double)__uint_as_float((unsigned)h << 16);
+  }
+}
+
+// pair j (0 <= j < m/2) of round t (0 <= t < m-1) of the circle method on m (even) players (eigh.hip tournament_pair)
+__device__ __forceinline__ void tournament_pair(int m, int t, int j, int& p, int& q) {
+  if (j == 0) {
+    p = m - 1;
+    q = t;
+  } else {
+    p = (t + j) % (m - 1);
+    q = (t - j + (m - 1)) % (m - 1);
+  }
+  if (p > q) { const int s = p; p = q; q = s; }
+}
+
+template <int DT>
+__global__ __launch_bounds__(kThreads) void eigen_score_kernel(const void* __restrict__ e, int k, int64_t hidden,
+                                                              int64_t row_stride, double alpha, double* __restrict__ out) {
+  __shared__ double lds[2 * kHalf];
+  double* stage = lds;         // Gram: staged chunk, then the slot partials; Jacobi: rotations, norm, flag, eigenvalues
+  double* G = lds + kHalf;     // [k, k] row-major
+  const int tid = threadIdx.x;
+  const int64_t g = blockIdx.x;
+  const char* rows = reinterpret_cast<const char*>(e) + g * k * row_stride * (DT == kF32 ? 4 : 2);
+
+  // ---- Gram matrix ----------------------------------------------------------------------------------------------------
+  const int kb = (k + 3) / 4, kpad = 4 * kb;
+  const int Q = kb * (kb + 1) / 2;  // <= 136
+  const int R = kThreads / Q;       // >= 1
+  const int C = kHalf / kpad;       // columns per chunk
+  const bool active = tid < Q * R;
+  const int tile = tid % Q, slot = tid / Q;
+  int ti = 0, rem = tile;
+  while (rem >= kb - ti) { rem -= kb - ti; ++ti; }
+  const int tj = ti + rem;  // tile rows 4 ti .. 4 ti + 3, columns 4 tj .. 4 tj + 3
+  double acc[4][4];
+#pragma unroll
+  for (int a = 0; a < 4; ++a)
+#pragma unroll
+    for (int b = 0; b < 4; ++b) acc[a][b] = 0.0;
+
+  for (int64_t h0 = 0; h0 < hidden; h0 += C) {
+    const int w = (int)min((int64_t)C, hidden - h0);
+    for (int idx = tid; idx < k * w; idx += kThreads) {
+      const int r = idx / w, c = idx - r * w;
+      stage[r * C + c] = load_wide<DT>(rows, (int64_t)r * row_stride + h0 + c);
+    }
+    __syncthreads();
+    // centre every column by its mean over the k rows; padding rows (k .. kpad-1) only feed entries that are dropped
+    for (int c = tid; c < w; c += kThreads) {
+      double mean = 0.0;
+      for (int r = 0; r < k; ++r) mean += stage[r * C + c];
+      mean /= (double)k;
+      for (int r = 0; r < k; ++r) stage[r * C + c] -= mean;
+      for (int r = k; r < kpad; ++r) stage[r * C + c] = 0.0;
+    }
+    __syncthreads();
+    if (active) {
+      const double* xa = stage + (4 * ti) * C;
+      const double* xb = stage + (4 * tj) * C;
+      for (int c = slot; c < w; c += R) {
+        double va[4], vb[4];
+#pragma unroll
+        for (int a = 0; a < 4; ++a) { va[a] = xa[a * C + c]; vb[a] = xb[a * C + c]; }
+#pragma unroll
+        for (int a = 0; a < 4; ++a)
+#pragma unroll
+          for (int b = 0; b < 4; ++b) acc[a][b] += va[a] * vb[b];
+      }
+    }
+    __syncthreads();
+  }
+  if (active) {
+#pragma unroll
+    for (int a = 0; a < 4; ++a)
+#pragma unroll
+      for (int b = 0; b < 4; ++b) stage[(slot * Q + tile) * 16 + a * 4 + b] = acc[a][b];
+  }
+  __syncthreads();
+  const double denom = (double)(k - 1);
+  for (int idx = tid; idx < Q * 16; idx += kThreads) {
+    const int t = idx >> 4, a = (idx >> 2) & 3, b = idx & 3;
+    int I = 0, x = t;
+    while (x >= kb - I) { x -= kb - I; ++I; }
+    const int i = 4 * I + a, j = 4 * (I + x) + b;
+    if (i > j || j >= k) continue;
+    double s = 0.0;
+    for (int sl = 0; sl < R; ++sl) s += stage[(sl * Q + t) * 16 + a * 4 + b];
+    G[i * k + j] = s / denom;
+    G[j * k + i] = s / denom;
+  }
+  __syncthreads();
+
+  // ---- cyclic Jacobi on G ---------------------------------------------------------------------------------------------
+  double* rot_c = stage;           // [32]
+  double* rot_s = stage + 32;      // [32]
+  double* part = stage + 64;       // [256]: Frobenius norm partials
+  double* lam = stage + 320;       // [64]: eigenvalues in descending order
+  int* flag = reinterpret_cast<int*>(stage + 384);
+  int* nan_seen = flag + 1;
+  {
+    double s = 0.0;
+    for (int idx = tid; idx < k * k; idx += kThreads) s += G[idx] * G[idx];
+    part[tid] = s;
+    __syncthreads();
+    for (int o = kThreads / 2; o > 0; o >>= 1) {
+      if (tid < o) part[tid] += part[tid + o];
+      __syncthreads();
+    }
+  }
+  const double anorm = sqrt(part[0]);
+  const int m = (k + 1) & ~1, half = m / 2;
+  bool converged = false;
+  for (int sweep = 0; sweep < kMaxSweeps; ++sweep) {
+    if (tid == 0) flag[0] = 0;
+    __syncthreads();
+    for (int t = 0; t < m - 1; ++t) {
+      if (tid < half) {
+        int p, q;
+        tournament_pair(m, t, tid, p, q);
+        double c = 1.0, s = 0.0;
+        if (q < k) {
+          const double app = G[p * k + p], aqq = G[q * k + q], apq = G[p * k + q];
+          const double thr = fmax(1e-19 * anorm, 1e-17 * sqrt(fabs(app * aqq)));
+          if (fabs(apq) > thr) {
+            const double theta = (aqq - app) / (2.0 * apq);
+            const double tt = (theta >= 0.0 ? 1.0 : -1.0) / (fabs(theta) + sqrt(theta * theta + 1.0));
+            c = 1.0 / sqrt(tt * tt + 1.0);
+            s = tt * c;
+            flag[0] = 1;
+          }
+        }
+        rot_c[tid] = c;
+        rot_s[tid] = s;
+      }
+      __syncthreads();
+      // G <- J^T G J on the 2 x 2 blocks {pa, qa} x {pb, qb}, ka <= kb, mirrored (eigh.hip jacobi_apply_kernel)
+      for (int idx = tid; idx < half * half; idx += kThreads) {
+        const int ka = idx / half, kbk = idx - ka * half;
+        if (ka > kbk) continue;
+        const double rac = rot_c[ka], ras = rot_s[ka], rbc = rot_c[kbk], rbs = rot_s[kbk];
+        if (ras == 0.0 && rbs == 0.0) continue;
+        int pa, qa, pb, qb;
+        tournament_pair(m, t, ka, pa, qa);
+        tournament_pair(m, t, kbk, pb, qb);
+        const bool qa_ok = qa < k, qb_ok = qb < k;  // the bye index of odd k leaves its partner untouched
+        const double b00 = G[pa * k + pb];
+        const double b01 = qb_ok ? G[pa * k + qb] : 0.0;
+        const double b10 = qa_ok ? G[qa * k + pb] : 0.0;
+        const double b11 = (qa_ok && qb_ok) ? G[qa * k + qb] : 0.0;
+        const double t00 = rac * b00 - ras * b10, t01 = rac * b01 - ras * b11;
+        const double t10 = ras * b00 + rac * b10, t11 = ras * b01 + rac * b11;
+        double n00 = t00 * rbc - t01 * rbs, n01 = t00 * rbs + t01 * rbc;
+        double n10 = t10 * rbc - t11 * rbs, n11 = t10 * rbs + t11 * rbc;
+        if (ka == kbk) { n01 = 0.0; n10 = 0.0; }  // the rotated pair is annihilated by construction
+        G[pa * k + pb] = n00;
+        G[pb * k + pa] = n00;
+        if (qb_ok) { G[pa * k + qb] = n01; G[qb * k + pa] = n01; }
+        if (qa_ok) { G[qa * k + pb] = n10; G[pb * k + qa] = n10; }
+        if (qa_ok && qb_ok) { G[qa * k + qb] = n11; G[qb * k + qa] = n11; }
+      }
+      __syncthreads();
+    }
+    const int any = flag[0];
+    __syncthreads();  // every thread has read the flag before thread 0 clears it for the next sweep
+    if (!any) { converged = true; break; }
+  }
+
+  // ---- score ----------------------------------------------------------------------------------------------------------
+  if (tid == 0) nan_seen[0] = 0;
+  __syncthreads();
+  if (tid < k) {
+    double v = G[tid * k + tid];
+    v = v < 0.0 ? 0.0 : v;  // NaN stays NaN
+    if (isnan(v)) {
+      nan_seen[0] = 1;
+    } else {
+      int rank = 0;
+      for (int j = 0; j < k; ++j) {
+        double u = G[j * k + j];
+        u = u < 0.0 ? 0.0 : u;
+        rank += (u > v || (u == v && j < tid)) ? 1 : 0;
+      }
+      lam[rank] = v;
+    }
+  }
+  __syncthreads();
+  if (tid == 0) {
+    double res = __builtin_nan("");
+    if (converged && !nan_seen[0]) {
+      const int64_t top = min((int64_t)k, hidden);
+      double total = 0.0;
+      for (int i = 0; i < (int)top; ++i) total += log(lam[i] + alpha);
+      total += (double)(hidden - top) * log(alpha);
+      res = total / (double)hidden;
+    }
+    out[g] = res;
+  }
+}
+
+}  // namespace
+
+extern "C" int runia_eigen_score_batch(const void* e, int dtype_code, int64_t groups, int64_t k, int64_t hidden,
+                                       int64_t row_stride, double alpha, double* out, runia_stream_t stream) {
+  if (!e || !out || groups <= 0 || groups > 0x7fffffffll || k < 2 || k > kMaxK || hidden <= 0 || row_stride < 0)
+    return RUNIA_E_INVALID;
+  hipStream_t s = as_stream(stream);
+  switch (dtype_code) {
+    case kF32: eigen_score_kernel<kF32><<<(unsigned)groups, kThreads, 0, s>>>(e, (int)k, hidden, row_stride, alpha, out); break;
+    case kF16: eigen_score_kernel<kF16><<<(unsigned)groups, kThreads, 0, s>>>(e, (int)k, hidden, row_stride, alpha, out); break;
+    case kBF16: eigen_score_kernel<kBF16><<<(unsigned)groups, kThreads, 0, s>>>(e, (int)k, hidden, row_stride, alpha, out); break;
+    default: return RUNIA_E_INVALID;
+  }
+  return runia_check_launch();
+}

@@ -351,6 +351,18 @@ int runia_roi_mc_entropy_f32(const float* feat_nhwc, const float* boxes, const i
                              int64_t K, int64_t B, int C, int H, int W, int PH, int PW, double spatial_scale,
                              int sampling_ratio, int aligned, int n_mc, double drop_prob, int block_size, int k,
                              double min_dist, runia_stream_t stream);
+/* roi_align(...).mean((2, 3)) as ONE pass from the channels-last map (the per-box reduction of BoxInferenceYolo,
+ * inference/object_level.py; _reduce_features_to_rois, feature_extraction/object_level.py:254-309): feat_nhwc [B, H, W, C]
+ * (runia_nchw_to_nhwc_f32), boxes [K, 4] xyxy, batch_idx [K] or NULL (B == 1), roi_align's PH, PW, spatial_scale,
+ * sampling_ratio, aligned -> out[k * ldo + col_offset + c] f32 for c < C: each hooked layer writes its own column slice of one
+ * (K, C_total) matrix.  The (K, C, PH, PW) tensor is never written: the mean is the separable sum of per-axis bilinear
+ * weights (f64) over the box's pixels.  A batch index outside [0, B) gives a row of zeros.  Limits: H + W <=
+ * RUNIA_ROI_MEANS_MAX_HW, H * W * C * 4 < 2^30 bytes per image (RUNIA_E_INVALID otherwise); any K (K = 0: nothing).  No
+ * workspace, no atomics. */
+#define RUNIA_ROI_MEANS_MAX_HW 2048
+int runia_roi_means_f32(const float* feat_nhwc, const float* boxes, const int* batch_idx, float* out, int64_t ldo,
+                        int64_t col_offset, int64_t K, int64_t B, int C, int H, int W, int PH, int PW, double spatial_scale,
+                        int sampling_ratio, int aligned, runia_stream_t stream);
 
 /* Symmetric eigen-decomposition without a vendor solver: two-sided cyclic Jacobi, f64, parallel ordering.  What
  * scipy.linalg.pinvh (EmpiricalCovariance.fit, inference/postprocessors.py:213-220, inference/funcs.py:52-66), the

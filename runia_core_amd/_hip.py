@@ -168,6 +168,11 @@ _SIGNATURES = {
         [c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_void_p, c_void_p, c_void_p, c_size_t, c_int64, c_int64, c_int, c_int,
          c_int, c_int, c_int, c_double, c_int, c_int, c_int, c_double, c_int, c_int, c_double, c_void_p],
     ),
+    "runia_roi_means_f32": (
+        c_int,
+        [c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_int64, c_int64, c_int64, c_int, c_int, c_int, c_int, c_int,
+         c_double, c_int, c_int, c_void_p],
+    ),
     "runia_linear_f32": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_int64, c_int64, c_float, c_void_p]),
     "runia_ash_s_f32": (c_int, [c_void_p, c_void_p, c_int64, c_int64, c_int, c_void_p]),
     "runia_gen_score_f32": (c_int, [c_void_p, c_void_p, c_int64, c_int64, c_int, c_double, c_void_p]),
@@ -1497,6 +1502,44 @@ def roi_mc_entropy(x_nhwc: torch.Tensor, boxes: torch.Tensor, output_size, spati
             float(spatial_scale), int(sampling_ratio), 1 if aligned else 0, int(n_mc), float(drop_prob), int(block_size), int(k),
             float(min_dist), _stream()), "runia_roi_mc_entropy_f32")
     return (h, z) if return_samples else h
+
+
+ROI_MEANS_MAX_HW = 2048  # RUNIA_ROI_MEANS_MAX_HW: H + W of one feature map (the per-axis weights live in LDS)
+
+
+def roi_means_supported(x_nhwc_shape) -> bool:
+    """Whether :func:`roi_means` takes a map of this ``[B, H, W, C]`` shape (else: ``roi_align`` + ``mean``)."""
+    _, hh, ww, c = x_nhwc_shape
+    return hh + ww <= ROI_MEANS_MAX_HW and hh * ww * c * 4 < ROI_FUSED_MAX_IMAGE_BYTES
+
+
+@_device_guard("boxes", "batch_idx", "out")
+def roi_means(x_nhwc: torch.Tensor, boxes: torch.Tensor, output_size, spatial_scale: float, sampling_ratio: int,
+              aligned: bool, batch_idx: Optional[torch.Tensor] = None, out: Optional[torch.Tensor] = None,
+              col_offset: int = 0) -> torch.Tensor:
+    """``roi_align(x, boxes, output_size, spatial_scale, sampling_ratio, aligned).mean((2, 3))`` in ONE pass from the
+    feature map (NHWC, :func:`nchw_to_nhwc`): x_nhwc [B, H, W, C], boxes [K, 4] xyxy -> [K, C] f32.  The (K, C, PH, PW)
+    tensor is never written.  ``out`` (additive): a ``(K, C_total)`` f32 device matrix with unit column stride whose columns
+    ``col_offset : col_offset + C`` receive the means (one slice per hooked layer, no concatenation); it is returned."""
+    lib = load_library()
+    require_gpu()
+    assert x_nhwc.is_cuda and x_nhwc.dtype == torch.float32 and x_nhwc.dim() == 4 and x_nhwc.is_contiguous()
+    b, hh, ww, c = x_nhwc.shape
+    ph, pw = (output_size, output_size) if isinstance(output_size, int) else tuple(output_size)
+    boxes = boxes.to(device=x_nhwc.device, dtype=torch.float32).contiguous()
+    kk = boxes.shape[0]
+    if batch_idx is not None:
+        batch_idx = batch_idx.to(device=x_nhwc.device, dtype=torch.int32).contiguous()
+    if out is None:
+        out = torch.empty((kk, c), dtype=torch.float32, device=x_nhwc.device)
+        col_offset = 0
+    assert out.dtype == torch.float32 and out.device == x_nhwc.device and out.dim() == 2 and out.shape[0] == kk
+    assert out.stride(1) == 1 and 0 <= col_offset and col_offset + c <= out.shape[1]
+    _check(lib.runia_roi_means_f32(x_nhwc.data_ptr(), boxes.data_ptr(), _ptr(batch_idx), out.data_ptr(),
+                                   out.stride(0) if kk > 1 else out.shape[1], int(col_offset), kk, b, c, hh, ww, int(ph),
+                                   int(pw), float(spatial_scale), int(sampling_ratio), 1 if aligned else 0, _stream()),
+           "runia_roi_means_f32")
+    return out
 
 
 KDE_KERNELS = ("gaussian", "tophat", "epanechnikov", "exponential", "linear", "cosine")

@@ -18,7 +18,7 @@ from .. import _hip
 from ..evaluation.entropy import MIN_DIST, neighbors_for
 from .abstract_classes import MCSamplerModule
 
-__all__ = ["roi_align", "_reduce_features_to_rois", "_dropblock_rois_get_entropy"]
+__all__ = ["roi_align", "roi_means", "_reduce_features_to_rois", "_dropblock_rois_get_entropy"]
 
 
 def roi_align(input: Tensor, boxes, output_size, spatial_scale: float = 1.0, sampling_ratio: int = -1,
@@ -44,6 +44,39 @@ def _rois(latent_mcd_sample, output_sizes, boxes, img_shape, sampling_ratio, n_h
                   spatial_scale=latent_mcd_sample[i].shape[3] / img_shape[1], sampling_ratio=sampling_ratio, aligned=True)
         for i in range(n_hooked_reps)
     ]
+
+
+def roi_means(latent_maps: List[Tensor], output_sizes: Tuple[int], boxes, img_shape: Tuple[int, ...], sampling_ratio: int,
+              batch_idx: Tensor = None) -> Tensor:
+    """Additive device entry point of the per-box path: the ``(K, C_total)`` f32 device matrix of ROI means that
+    ``_reduce_features_to_rois`` builds (``roi_align`` of every hooked layer with its own output size, ``spatial_scale =
+    W_feat / W_img``, ``aligned=True``, mean over the bins, concatenated along channels), without the ``(K, C, PH, PW)``
+    tensors: every layer writes its column slice straight from its channels-last map (``runia_roi_means_f32``).
+    ``boxes`` ``[K, 4]`` xyxy in image pixels; ``batch_idx`` ``[K]`` the image of every box when the maps hold several
+    images (an index outside the batch gives zeros).  A map beyond the kernel's limits (``_hip.roi_means_supported``) takes
+    ``roi_align`` + ``mean`` for its slice."""
+    maps = [m.detach().to(torch.float32) if isinstance(m, Tensor) and m.is_cuda else _hip.to_device(m, torch.float32)
+            for m in latent_maps[: len(output_sizes)]]  # (device tensors stay on their GPU)
+    dev = maps[0].device
+    boxes = torch.as_tensor(boxes).to(device=dev, dtype=torch.float32).reshape(-1, 4)
+    k = boxes.shape[0]
+    if batch_idx is not None:
+        batch_idx = torch.as_tensor(batch_idx).to(device=dev, dtype=torch.int32)
+    elif any(m.shape[0] != 1 for m in maps):
+        raise ValueError("roi_means: batch_idx is required when the maps hold more than one image")
+    out = torch.empty((k, sum(m.shape[1] for m in maps)), dtype=torch.float32, device=dev)
+    col = 0
+    for m, osz in zip(maps, output_sizes):
+        c = m.shape[1]
+        scale = m.shape[3] / img_shape[1]
+        if k > 0:
+            nhwc_shape = (m.shape[0], m.shape[2], m.shape[3], c)
+            if _hip.roi_means_supported(nhwc_shape):
+                _hip.roi_means(_hip.nchw_to_nhwc(m.contiguous()), boxes, osz, scale, sampling_ratio, True, batch_idx, out, col)
+            else:
+                out[:, col : col + c] = _hip.roi_align(m, boxes, osz, scale, sampling_ratio, True, batch_idx).mean(dim=(2, 3))
+        col += c
+    return out
 
 
 def _reduce_features_to_rois(latent_mcd_sample: List[Tensor], output_sizes: Tuple[int], boxes: Tensor,

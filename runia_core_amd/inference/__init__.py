@@ -22,6 +22,7 @@ from .funcs import (  # noqa: F401
     normalizer,
 )
 from .image_level import LaRDInference, LaRExInference  # noqa: F401
+from .object_level import BoxInferenceYolo, ObjectLevelInference  # noqa: F401
 from .pipeline import LaREMPipeline  # noqa: F401
 from .postprocessors import (  # noqa: F401
     ASH,

@@ -671,6 +671,38 @@ int runia_osod_curves(const int32_t* part, const int64_t* bucket_start, const ui
                       int n_classes, const int64_t* npos, int use_07, double* summary, double* rec, double* prec,
                       double* tpfp, double* fpos, void* workspace, size_t workspace_bytes, runia_stream_t stream);
 
+/* ---- greedy NMS and the YOLOv8 candidate filter (nms.hip) ------------------------------------------------------------ *
+ * torchvision.ops.nms, which ObjectDetectionExtractor.yolo_get_logits calls (feature_extraction/abstract_classes.py:606-715).
+ *
+ * runia_yolo_candidates_f32: one image's head pred [4 + nc + nm, A] f32, channel-major (row r of anchor a at r * A + a).
+ *   Per anchor: best = max of the nc class rows, j = the first class index reaching it; candidate when no class score is
+ *   NaN, best > conf_thres (strict) and, when n_classes > 0, (float)j equals one of classes[n_classes] (f32).  The
+ *   candidates are compacted in anchor order (deterministic: no atomics) into cand_boxes [A, 4] = rows 0-3 + j * max_wh
+ *   (f32; max_wh = 0 for class-agnostic NMS), cand_scores [A] = best, cand_anchor [A], cand_cls [A]; *count (int64) = their
+ *   number.  Rows 0-3 are taken as they are (xyxy in the reference's reading).  A <= RUNIA_YOLO_MAX_ANCHORS.
+ *   Workspace: runia_yolo_candidates_workspace_bytes(A) = 8 * A + 4 * ceil(A / 256).
+ * runia_nms_keys_f32: keys[i] = (desc(scores[i]) << 31) | i, int64, desc = the order-reversing uint32 image of the f32 score
+ *   (-0 folded onto +0, NaN before +inf).  Ascending keys = descending score, ties by ascending index (stable).
+ * runia_nms_sort_keys: sorts n <= RUNIA_NMS_SORT_MAX keys in place (one workgroup, LDS bitonic sort).  Longer lists may be
+ *   sorted by any device sort of the same keys: they are distinct, so the order is the same.
+ * runia_nms_sorted_f32: boxes [*, 4] xyxy f32 indexed by key & 0x7fffffff; the first m sorted keys (m <=
+ *   RUNIA_NMS_MAX_BOXES) are walked greedily: a box is kept unless a kept box before it has IoU > iou_threshold with it
+ *   (torchvision's f32 expression and order; a 0/0 IoU suppresses nothing).  keep[0 : *count] (int64) = the kept boxes'
+ *   indices in sorted order, at most max_det of them.  Workspace: runia_nms_workspace_bytes(m) = m * ceil(m / 64) * 8 (the
+ *   IoU bitmask). */
+#define RUNIA_YOLO_MAX_ANCHORS (1 << 22)
+#define RUNIA_NMS_SORT_MAX 4096
+#define RUNIA_NMS_MAX_BOXES 65536
+size_t runia_yolo_candidates_workspace_bytes(int64_t A);
+int runia_yolo_candidates_f32(const float* pred, int64_t A, int nc, int nm, float conf_thres, const float* classes,
+                              int n_classes, float max_wh, float* cand_boxes, float* cand_scores, int* cand_anchor,
+                              int* cand_cls, int64_t* count, void* workspace, size_t workspace_bytes, runia_stream_t stream);
+int runia_nms_keys_f32(const float* scores, int64_t n, int64_t* keys, runia_stream_t stream);
+int runia_nms_sort_keys(int64_t* keys, int64_t n, runia_stream_t stream);
+size_t runia_nms_workspace_bytes(int64_t m);
+int runia_nms_sorted_f32(const float* boxes, const int64_t* sorted_keys, int64_t m, float iou_threshold, int64_t max_det,
+                         int64_t* keep, int64_t* count, void* workspace, size_t workspace_bytes, runia_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -249,6 +249,17 @@ _SIGNATURES = {
         [c_void_p, c_void_p, c_void_p, c_int64, c_int, c_int, c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_void_p,
          c_void_p, c_void_p, c_size_t, c_void_p],
     ),
+    "runia_yolo_candidates_workspace_bytes": (c_size_t, [c_int64]),
+    "runia_yolo_candidates_f32": (
+        c_int,
+        [c_void_p, c_int64, c_int, c_int, c_float, c_void_p, c_int, c_float, c_void_p, c_void_p, c_void_p, c_void_p,
+         c_void_p, c_void_p, c_size_t, c_void_p],
+    ),
+    "runia_nms_keys_f32": (c_int, [c_void_p, c_int64, c_void_p, c_void_p]),
+    "runia_nms_sort_keys": (c_int, [c_void_p, c_int64, c_void_p]),
+    "runia_nms_workspace_bytes": (c_size_t, [c_int64]),
+    "runia_nms_sorted_f32": (
+        c_int, [c_void_p, c_void_p, c_int64, c_float, c_int64, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]),
 }
 
 
@@ -1666,3 +1677,92 @@ def cholesky(a: torch.Tensor, jitter: float = 0.0):
     fn = lib.runia_cholesky_f32 if a.dtype == torch.float32 else lib.runia_cholesky_f64
     _check(fn(m.data_ptr(), info.data_ptr(), m.shape[0], m.shape[1], float(jitter), _stream()), "runia_cholesky")
     return m.reshape(a.shape), info
+
+
+NMS_SORT_MAX = 4096  # RUNIA_NMS_SORT_MAX: keys one workgroup sorts in LDS (longer lists: torch.sort of the same keys)
+NMS_MAX_BOXES = 65536  # RUNIA_NMS_MAX_BOXES: boxes one greedy walk takes (its removed bitmap lives in LDS)
+YOLO_MAX_ANCHORS = 1 << 22  # RUNIA_YOLO_MAX_ANCHORS
+
+
+def nms_workspace_bytes(m: int) -> int:
+    """Bytes of the IoU bitmask of ``m`` sorted boxes: ``m * ceil(m / 64) * 8``."""
+    return int(load_library().runia_nms_workspace_bytes(int(m)))
+
+
+@_device_guard()
+def nms_sorted_keys(scores: torch.Tensor) -> torch.Tensor:
+    """scores [n] f32 (device) -> the int64 keys ``(desc(score) << 31) | i`` in ascending order = descending score, ties by
+    ascending index (``runia_nms_keys_f32``, then ``runia_nms_sort_keys`` up to :data:`NMS_SORT_MAX` keys, a device
+    ``torch.sort`` of the same distinct keys above: one order either way)."""
+    lib = load_library()
+    require_gpu()
+    assert scores.is_cuda and scores.dtype == torch.float32 and scores.dim() == 1
+    n = scores.shape[0]
+    assert n <= 0x7FFFFFFF
+    keys = torch.empty((n,), dtype=torch.int64, device=scores.device)
+    if n == 0:
+        return keys
+    scores = scores.contiguous()
+    _check(lib.runia_nms_keys_f32(scores.data_ptr(), n, keys.data_ptr(), _stream()), "runia_nms_keys_f32")
+    if n <= NMS_SORT_MAX:
+        _check(lib.runia_nms_sort_keys(keys.data_ptr(), n, _stream()), "runia_nms_sort_keys")
+        return keys
+    return torch.sort(keys, stable=True).values
+
+
+@_device_guard()
+def nms_sorted(boxes: torch.Tensor, sorted_keys: torch.Tensor, iou_threshold: float, max_det: Optional[int] = None):
+    """Greedy NMS of the boxes [*, 4] xyxy f32 (device) in the order of ``sorted_keys`` (:func:`nms_sorted_keys`, possibly
+    truncated) -> ``(keep, count)``: int64 device tensors, ``keep[:count]`` the kept boxes' indices (at most ``max_det``),
+    in sorted order (``runia_nms_sorted_f32``).  Nothing is read back here."""
+    lib = load_library()
+    require_gpu()
+    assert boxes.is_cuda and boxes.dtype == torch.float32 and boxes.dim() == 2 and boxes.shape[1] == 4
+    assert sorted_keys.dtype == torch.int64 and sorted_keys.dim() == 1 and sorted_keys.device == boxes.device
+    m = sorted_keys.shape[0]
+    if m > NMS_MAX_BOXES:
+        raise RuniaHipError(f"nms: {m} boxes, at most {NMS_MAX_BOXES} per call")
+    max_det = m if max_det is None else max(0, min(int(max_det), m))
+    boxes, sorted_keys = boxes.contiguous(), sorted_keys.contiguous()
+    keep = torch.empty((max(max_det, 1),), dtype=torch.int64, device=boxes.device)
+    count = torch.zeros((1,), dtype=torch.int64, device=boxes.device)
+    ws_bytes = nms_workspace_bytes(m)
+    ws = torch.empty(((ws_bytes + 7) // 8,), dtype=torch.int64, device=boxes.device) if ws_bytes else None
+    _check(lib.runia_nms_sorted_f32(boxes.data_ptr(), sorted_keys.data_ptr(), m, float(iou_threshold), max_det,
+                                    keep.data_ptr(), count.data_ptr(), _ptr(ws), ws_bytes, _stream()), "runia_nms_sorted_f32")
+    return keep, count
+
+
+@_device_guard("classes")
+def yolo_candidates(pred: torch.Tensor, nc: int, conf_thres: float, classes=None, max_wh: float = 0.0):
+    """One image's YOLOv8 head ``pred`` [4 + nc + nm, A] f32 (device, channel-major) -> its candidates in anchor order
+    (``runia_yolo_candidates_f32``): ``(boxes [A, 4] = rows 0-3 + best class * max_wh, scores [A], anchor [A] int32,
+    cls [A] int32, count)`` with ``count`` an int64 device tensor [1]; the first ``count`` rows are valid."""
+    lib = load_library()
+    require_gpu()
+    assert pred.is_cuda and pred.dtype == torch.float32 and pred.dim() == 2
+    c, a = pred.shape
+    nm = c - 4 - int(nc)
+    assert nc >= 1 and nm >= 0, "head rows must be 4 + nc + nm"
+    if a > YOLO_MAX_ANCHORS:
+        raise RuniaHipError(f"yolo_candidates: {a} anchors, at most {YOLO_MAX_ANCHORS}")
+    dev = pred.device
+    pred = pred.contiguous()
+    cls_list = None
+    if classes is not None:
+        cls_list = torch.as_tensor(classes).reshape(-1).to(device=dev, dtype=torch.float32).contiguous()
+    boxes = torch.empty((a, 4), dtype=torch.float32, device=dev)
+    scores = torch.empty((a,), dtype=torch.float32, device=dev)
+    anchor = torch.empty((a,), dtype=torch.int32, device=dev)
+    cls = torch.empty((a,), dtype=torch.int32, device=dev)
+    count = torch.zeros((1,), dtype=torch.int64, device=dev)
+    if a == 0:
+        return boxes, scores, anchor, cls, count
+    ws_bytes = int(lib.runia_yolo_candidates_workspace_bytes(a))
+    ws = torch.empty(((ws_bytes + 7) // 8,), dtype=torch.int64, device=dev)
+    n_cls = 0 if cls_list is None else int(cls_list.numel())
+    _check(lib.runia_yolo_candidates_f32(pred.data_ptr(), a, int(nc), nm, float(conf_thres),
+                                         _ptr(cls_list) if n_cls else None, n_cls, float(max_wh), boxes.data_ptr(),
+                                         scores.data_ptr(), anchor.data_ptr(), cls.data_ptr(), count.data_ptr(), ws.data_ptr(),
+                                         ws_bytes, _stream()), "runia_yolo_candidates_f32")
+    return boxes, scores, anchor, cls, count

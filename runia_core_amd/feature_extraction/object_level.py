@@ -1,7 +1,7 @@
 """Per-ROI sampling for object-level inference (BASELINE config 4), device-resident: the tail of the reference's
 ``BoxFeaturesExtractor`` that IS the scoring hot path (``runia_core/feature_extraction/object_level.py``:
 ``_reduce_features_to_rois`` :254-309, ``_dropblock_rois_get_entropy`` :312-367) with the same signatures.  The detector
-glue around it (``BoxFeaturesExtractor`` itself: hooks, NMS, architecture switches) is out of scope.
+glue around it (``BoxFeaturesExtractor`` itself: hooks, NMS, architecture switches) is ``feature_extraction.detectors``.
 
 ``roi_align`` -> per-detection ``MCSamplerModule`` -> ``get_dl_h_z(.)[1]`` run as HIP kernels on the hooked feature maps
 (``runia_roi_align_f32`` -> ``runia_mc_entropy_f32`` / ``runia_mc_stack_f32`` + ``runia_kl_entropy_per_dim_f32``): nothing

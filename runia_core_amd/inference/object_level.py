@@ -216,9 +216,9 @@ class BoxInferenceYolo(InferenceModule):
 class ObjectLevelInference(ObjectDetectionInference):
     """Object-level inference around a detector's feature extractor: scores of the detections' latent rows.
 
-    The reference builds a ``BoxFeaturesExtractor`` (detector glue, out of this package's scope) in its constructor; here
-    it is passed in as ``features_extractor=``: any object with ``_get_samples_one_image(image, conf, **kw) ->
-    (results, found_flag)``.  When ``results["latent_space_means"]`` is a device tensor it is scored on the device."""
+    The reference builds a ``BoxFeaturesExtractor`` in its constructor; here it is passed in as ``features_extractor=``:
+    ``runia_core_amd.feature_extraction.BoxFeaturesExtractor``, or any object with ``_get_samples_one_image(image, conf,
+    **kw) -> (results, found_flag)``.  When ``results["latent_space_means"]`` is a device tensor it is scored on the device."""
 
     def __init__(self, model, postprocessor, architecture: str, latent_space_method: bool, hooked_layers: List[Hook],
                  postprocessor_input: List[str], roi_output_sizes: Tuple[int], roi_sampling_ratio: int = -1,
@@ -232,8 +232,7 @@ class ObjectLevelInference(ObjectDetectionInference):
         if features_extractor is None or not hasattr(features_extractor, "_get_samples_one_image"):
             raise ValueError(
                 "ObjectLevelInference needs features_extractor=: an object with _get_samples_one_image(image, conf, **kw) "
-                "-> (results, found_flag), such as the reference's BoxFeaturesExtractor (detector glue, not part of "
-                "runia_core_amd)")
+                "-> (results, found_flag), such as runia_core_amd.feature_extraction.BoxFeaturesExtractor")
         self.features_extractor = features_extractor
 
     def get_score(self, input_image, predict_conf, **kwargs):

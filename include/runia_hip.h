@@ -703,6 +703,55 @@ size_t runia_nms_workspace_bytes(int64_t m);
 int runia_nms_sorted_f32(const float* boxes, const int64_t* sorted_keys, int64_t m, float iou_threshold, int64_t max_det,
                          int64_t* keep, int64_t* count, void* workspace, size_t workspace_bytes, runia_stream_t stream);
 
+/* ---- PaCMAP embedding (pacmap.hip) ---------------------------------------------------------------------------------- *
+ * The device half of runia_core_amd.embedding.PaCMAP (the reference's fit_pacmap / apply_pacmap_transform /
+ * plot_samples_pacmap on pacmap==0.7.0, dimensionality_reduction.py:88-177).
+ *
+ * runia_pacmap_knn_f32: exact kNN of q [Q, D] among bank [N, D] (f32, row-major).  Squared distance = the f32 sum over the
+ *   columns in order of (q - b)^2 (fma); lists sorted by (squared distance, bank index) ascending.  exclude_self: bank row i
+ *   is left out of query row i's list by index (the fit, q == bank; duplicates of the row stay, at distance 0).
+ *   idx [Q, K] int32, dist [Q, K] f32 = sqrt of the squared distance.  1 <= K <= RUNIA_PACMAP_MAX_K, K <= N - exclude_self,
+ *   N < 2^31; RUNIA_E_INVALID otherwise.  No workspace.
+ * runia_pacmap_pairs: the pair lists of R rows x [R, D] against bank [Nb, D] from their kNN table knn_idx / knn_dist [R, K]
+ *   (runia_pacmap_knn_f32).  Fit (transform = 0; x = bank, R = Nb): sig_i = max(mean(dist_i[3 : min(6, K)]), 1e-10)
+ *   (1e-10 when K <= 3); the n_nb candidates with the smallest (dist^2 / sig_i) / sig_j (f32; ties: earlier candidate) ->
+ *   pair_nb [R * n_nb, 2] = (i, j) in that order; n_mn MN pairs per row -> pair_mn [R * n_mn, 2]: the second closest
+ *   (squared distance as in the kNN, ties: earlier draw) of 6 uniform draws among the other rows; n_fp FP pairs -> pair_fp
+ *   [R * n_fp, 2]: distinct uniform rows that are neither the row nor an NB partner.  Transform (transform = 1, n_mn = 0): NB
+ *   = the first n_nb candidates, FP rows are not NB partners (the row itself is a bank row like any other).  Draws:
+ *   Philox4x32-10, counter (row, (kind << 16) | slot, candidate, attempt), key (seed.lo, seed.hi), word 0; kind 0 = MN,
+ *   1 = FP; index = floor(u32 * M / 2^32) with M = Nb - 1 for MN (j' -> j' + (j' >= row)) and M = Nb for FP (a rejected
+ *   draw takes the next attempt).  Limits: n_nb <= K <= RUNIA_PACMAP_MAX_K, n_mn <= RUNIA_PACMAP_MAX_MN, n_fp <=
+ *   RUNIA_PACMAP_MAX_FP and <= Nb - n_nb - (1 for the fit), rows <= RUNIA_PACMAP_MAX_ROWS.  Workspace (fit only):
+ *   runia_pacmap_pairs_workspace_bytes(R) = 4 * R.
+ * runia_pacmap_phase_weights: w[3] = (w_NB, w_MN, w_FP) of iteration t (t < 100: 2, (1 - t/100) 1000 + (t/100) 3, 1;
+ *   t < 200: 3, 3, 1; then 1, 0, 1), f32.  Host only.
+ * runia_pacmap_step_f32: one Adam iteration t (beta1 0.9, beta2 0.999, eps 1e-7, lr_t = lr sqrt(1 - beta2^(t+1)) /
+ *   (1 - beta1^(t+1))) of the R rows y_in [R, C] -> y_out [R, C] (a different buffer), m / v [R, C] updated in place.  Row
+ *   r's pairs are entries[offsets[r] : offsets[r+1]] (offsets [R + 1] int64), each (kind << 30) | partner with kind
+ *   RUNIA_PACMAP_KIND_*; the partner's coordinates are y_part[partner] (= y_in for a fit, the frozen fitted rows for a
+ *   transform).  With d = 1 + |y_r - y_p|^2 the gradient is w (y_r - y_p) summed over the entries: NB w = w_NB 20 /
+ *   (10 + d)^2, MN w = w_MN 2e4 / (1e4 + d)^2, FP w = -w_FP 2 / (1 + d)^2 (the kind fixes the sign).  Fixed summation order
+ *   (no atomics): the same inputs give the same bits.  1 <= C <= RUNIA_PACMAP_MAX_COMPONENTS.  No workspace. */
+#define RUNIA_PACMAP_MAX_K 192
+#define RUNIA_PACMAP_MAX_MN 128
+#define RUNIA_PACMAP_MAX_FP 256
+#define RUNIA_PACMAP_MAX_COMPONENTS 16
+#define RUNIA_PACMAP_MAX_ROWS (1 << 30)
+#define RUNIA_PACMAP_KIND_NB 0
+#define RUNIA_PACMAP_KIND_MN 1
+#define RUNIA_PACMAP_KIND_FP 2
+int runia_pacmap_knn_f32(const float* q, int64_t Q, const float* bank, int64_t N, int64_t D, int K, int exclude_self,
+                         int32_t* idx, float* dist, runia_stream_t stream);
+size_t runia_pacmap_pairs_workspace_bytes(int64_t R);
+int runia_pacmap_pairs(const float* x, int64_t R, const float* bank, int64_t Nb, int64_t D, const int32_t* knn_idx,
+                       const float* knn_dist, int K, int n_nb, int n_mn, int n_fp, uint64_t seed, int transform,
+                       int32_t* pair_nb, int32_t* pair_mn, int32_t* pair_fp, void* workspace, size_t workspace_bytes,
+                       runia_stream_t stream);
+int runia_pacmap_phase_weights(int t, float* w);
+int runia_pacmap_step_f32(const float* y_in, const float* y_part, float* y_out, float* m, float* v, const int64_t* offsets,
+                          const int32_t* entries, int64_t R, int n_components, int t, float lr, runia_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

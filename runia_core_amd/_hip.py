@@ -260,6 +260,16 @@ _SIGNATURES = {
     "runia_nms_workspace_bytes": (c_size_t, [c_int64]),
     "runia_nms_sorted_f32": (
         c_int, [c_void_p, c_void_p, c_int64, c_float, c_int64, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]),
+    "runia_pacmap_knn_f32": (c_int, [c_void_p, c_int64, c_void_p, c_int64, c_int64, c_int, c_int, c_void_p, c_void_p, c_void_p]),
+    "runia_pacmap_pairs_workspace_bytes": (c_size_t, [c_int64]),
+    "runia_pacmap_pairs": (
+        c_int,
+        [c_void_p, c_int64, c_void_p, c_int64, c_int64, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_uint64, c_int,
+         c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p],
+    ),
+    "runia_pacmap_phase_weights": (c_int, [c_int, c_void_p]),
+    "runia_pacmap_step_f32": (
+        c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_int, c_int, c_float, c_void_p]),
 }
 
 
@@ -1766,3 +1776,76 @@ def yolo_candidates(pred: torch.Tensor, nc: int, conf_thres: float, classes=None
                                          scores.data_ptr(), anchor.data_ptr(), cls.data_ptr(), count.data_ptr(), ws.data_ptr(),
                                          ws_bytes, _stream()), "runia_yolo_candidates_f32")
     return boxes, scores, anchor, cls, count
+
+
+PACMAP_MAX_K = 192  # RUNIA_PACMAP_MAX_K: neighbour candidates per row of the kNN graph
+PACMAP_MAX_MN = 128  # RUNIA_PACMAP_MAX_MN
+PACMAP_MAX_FP = 256  # RUNIA_PACMAP_MAX_FP
+PACMAP_MAX_COMPONENTS = 16  # RUNIA_PACMAP_MAX_COMPONENTS
+PACMAP_KIND_NB, PACMAP_KIND_MN, PACMAP_KIND_FP = 0, 1, 2  # RUNIA_PACMAP_KIND_*: bits 30-31 of a grouped pair entry
+
+
+@_device_guard()
+def pacmap_knn(q: torch.Tensor, bank: torch.Tensor, k: int, exclude_self: bool):
+    """Exact kNN of the rows of ``q`` [Q, D] among ``bank`` [N, D] (f32, device) -> ``(idx [Q, k] int32, dist [Q, k] f32)``,
+    sorted by (distance, index); ``exclude_self`` leaves bank row i out of query row i's list (``runia_pacmap_knn_f32``)."""
+    lib = load_library()
+    require_gpu()
+    assert q.is_cuda and bank.is_cuda and q.dtype == torch.float32 and bank.dtype == torch.float32
+    assert q.dim() == 2 and bank.dim() == 2 and q.shape[1] == bank.shape[1]
+    q, bank = q.contiguous(), bank.contiguous()
+    idx = torch.empty((q.shape[0], k), dtype=torch.int32, device=q.device)
+    dist = torch.empty((q.shape[0], k), dtype=torch.float32, device=q.device)
+    _check(lib.runia_pacmap_knn_f32(q.data_ptr(), q.shape[0], bank.data_ptr(), bank.shape[0], bank.shape[1], int(k),
+                                    int(bool(exclude_self)), idx.data_ptr(), dist.data_ptr(), _stream()), "runia_pacmap_knn_f32")
+    return idx, dist
+
+
+@_device_guard()
+def pacmap_pairs(x: torch.Tensor, bank: torch.Tensor, knn_idx: torch.Tensor, knn_dist: torch.Tensor, n_nb: int, n_mn: int,
+                 n_fp: int, seed: int, transform: bool):
+    """NB / MN / FP pair lists ``(pair_nb [R * n_nb, 2], pair_mn [R * n_mn, 2], pair_fp [R * n_fp, 2])`` int32 (device) of the
+    rows ``x`` [R, D] against ``bank`` [Nb, D] from their kNN table (``runia_pacmap_pairs``; the fit passes ``x is bank``)."""
+    lib = load_library()
+    require_gpu()
+    assert x.dtype == torch.float32 and bank.dtype == torch.float32 and knn_idx.dtype == torch.int32
+    assert knn_dist.dtype == torch.float32 and knn_idx.shape == knn_dist.shape and knn_idx.shape[0] == x.shape[0]
+    x, bank, knn_idx, knn_dist = x.contiguous(), bank.contiguous(), knn_idx.contiguous(), knn_dist.contiguous()
+    r, d = x.shape
+    dev = x.device
+    nb = torch.empty((r * n_nb, 2), dtype=torch.int32, device=dev)
+    mn = torch.empty((r * n_mn, 2), dtype=torch.int32, device=dev)
+    fp = torch.empty((r * n_fp, 2), dtype=torch.int32, device=dev)
+    ws_bytes = 0 if transform else int(lib.runia_pacmap_pairs_workspace_bytes(r))
+    ws = torch.empty(((ws_bytes + 7) // 8,), dtype=torch.int64, device=dev) if ws_bytes else None
+    _check(lib.runia_pacmap_pairs(x.data_ptr(), r, bank.data_ptr(), bank.shape[0], d, knn_idx.data_ptr(), knn_dist.data_ptr(),
+                                  knn_idx.shape[1], int(n_nb), int(n_mn), int(n_fp), int(seed) & 0xFFFFFFFFFFFFFFFF,
+                                  int(bool(transform)), nb.data_ptr(), mn.data_ptr() if n_mn else None,
+                                  fp.data_ptr() if n_fp else None, _ptr(ws), ws_bytes, _stream()), "runia_pacmap_pairs")
+    return nb, mn, fp
+
+
+def pacmap_phase_weights(t: int):
+    """``(w_NB, w_MN, w_FP)`` of iteration ``t`` as the step kernel uses them (``runia_pacmap_phase_weights``, host only)."""
+    w = (c_float * 3)()
+    _check(load_library().runia_pacmap_phase_weights(int(t), ctypes.addressof(w)), "runia_pacmap_phase_weights")
+    return tuple(float(v) for v in w)
+
+
+@_device_guard()
+def pacmap_step(y_in: torch.Tensor, y_part: torch.Tensor, y_out: torch.Tensor, m: torch.Tensor, v: torch.Tensor,
+                offsets: torch.Tensor, entries: torch.Tensor, t: int, lr: float) -> torch.Tensor:
+    """One Adam iteration ``t`` of the rows ``y_in`` [R, C] into ``y_out`` (``runia_pacmap_step_f32``); ``m`` / ``v`` are
+    updated in place.  Row r's pairs: ``entries[offsets[r]:offsets[r + 1]]`` = ``(kind << 30) | partner``, partners read
+    from ``y_part``.  All operands contiguous f32 / int64 / int32 on one device."""
+    lib = load_library()
+    require_gpu()
+    r, c = y_in.shape
+    for a, dt in ((y_in, torch.float32), (y_part, torch.float32), (y_out, torch.float32), (m, torch.float32),
+                  (v, torch.float32), (offsets, torch.int64), (entries, torch.int32)):
+        assert a.is_cuda and a.dtype == dt and a.is_contiguous()
+    assert y_out.shape == y_in.shape == m.shape == v.shape and y_part.shape[1] == c and offsets.shape[0] == r + 1
+    _check(lib.runia_pacmap_step_f32(y_in.data_ptr(), y_part.data_ptr(), y_out.data_ptr(), m.data_ptr(), v.data_ptr(),
+                                     offsets.data_ptr(), entries.data_ptr(), r, c, int(t), float(lr), _stream()),
+           "runia_pacmap_step_f32")
+    return y_out

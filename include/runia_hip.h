@@ -77,6 +77,30 @@ int runia_mc_drop_flat_f32(const float* x, const float* rand, int64_t rand_image
  *   mode 1: return_stds = torch.std(torch.std(., dim=3), dim=2)    -> out [maps]  (unbiased; NaN when H or W is 1) */
 int runia_map_reduce_f32(const float* x, float* out, int64_t maps, int H, int W, int mode, runia_stream_t stream);
 
+/* The reduction MCDSamplesExtractor applies to the hooked activation after EACH of its mcd_nro_samples stochastic forward
+ * passes (feature_extraction/image_level.py:366-410: get_mean_or_fullmean_ls_sample / avg_pool2d / squeeze, reshape(1, -1),
+ * two levels of torch.cat), for a whole batch, written into the pass's rows of an existing sample table.
+ *   x      the hooked activation seen as (B, C, H, W): element strides sb, sc, sh, sw (>= 0; NCHW, channels_last and sliced
+ *          views are read in place; a (B, F) activation is H = W = 1).  dtype 0 f32, 1 f16, 2 bf16.
+ *   mode   RUNIA_MCD_FULLMEAN: mean over H and W -> D = C values per image;  RUNIA_MCD_MEAN: mean over W -> D = C * H
+ *          values, channel-major;  RUNIA_MCD_AVGPOOL: torch.nn.functional.avg_pool2d(kernel, stride, padding) with its
+ *          defaults (floor, padding counted, divisor kernel^2; 2 * padding <= kernel) -> D = C * Ho * Wo values in
+ *          (C, Ho, Wo) order;  RUNIA_MCD_COPY: the flattened activation, D = C * H * W.  kernel / stride / padding are read
+ *          by RUNIA_MCD_AVGPOOL only.
+ *   table  [table_rows, ld] f32, ld >= D: the D values of image b go to row row0 + b * row_step; other rows and the columns
+ *          from D on are not touched.  row0 = s, row_step = mcd: pass s of a batch fills its slot of an image-major
+ *          (B * mcd, D) block.
+ * f32 accumulation (f16 / bf16 widened exactly).  One launch; a channels_last fullmean of fewer images than fill the device (or of
+ * maps with more than 512 pixels per pixel slot of a workgroup) splits the pixels of an image over several workgroups, which add their partial means with float atomics into rows zeroed by
+ * a small launch in front (the only case whose last bits depend on the order of arrival). */
+#define RUNIA_MCD_FULLMEAN 0
+#define RUNIA_MCD_MEAN 1
+#define RUNIA_MCD_AVGPOOL 2
+#define RUNIA_MCD_COPY 3
+int runia_mcd_reduce_rows(const void* x, int dtype, int64_t B, int64_t C, int64_t H, int64_t W, int64_t sb, int64_t sc,
+                          int64_t sh, int64_t sw, int mode, int kernel, int stride, int padding, float* table,
+                          int64_t table_rows, int64_t ld, int64_t row0, int64_t row_step, runia_stream_t stream);
+
 /* ---- a2  Kozachenko-Leonenko kNN entropy --------------------------------- *
  * Replaces the loops of get_dl_h_z / single_image_entropy_calculation
  * (evaluation/entropy.py:20-93) over entropy_estimators.continuous.get_h(col, k,

@@ -37,6 +37,11 @@ _SIGNATURES = {
         [c_void_p, c_void_p, c_int64, c_void_p, c_int64, c_int, c_int, c_int, c_int, c_double, c_int, c_void_p],
     ),
     "runia_map_reduce_f32": (c_int, [c_void_p, c_void_p, c_int64, c_int, c_int, c_int, c_void_p]),
+    "runia_mcd_reduce_rows": (
+        c_int,
+        [c_void_p, c_int, c_int64, c_int64, c_int64, c_int64, c_int64, c_int64, c_int64, c_int64, c_int, c_int, c_int,
+         c_int, c_void_p, c_int64, c_int64, c_int64, c_int64, c_void_p],
+    ),
     "runia_kl_entropy_per_dim_f32": (c_int, [c_void_p, c_void_p, c_int64, c_int, c_int64, c_int, c_double, c_void_p]),
     "runia_kl_entropy_joint_f32": (c_int, [c_void_p, c_void_p, c_int64, c_int, c_int64, c_int, c_double, c_void_p]),
     "runia_kl_entropy_both_fused": (c_int, [c_int, c_int64, c_int]),
@@ -633,6 +638,65 @@ def map_reduce(x: torch.Tensor, h: int, w: int, mode: str) -> torch.Tensor:
     _check(lib.runia_map_reduce_f32(x.data_ptr(), out.data_ptr(), maps, h, w, 0 if mode == "mean" else 1, _stream()),
            "runia_map_reduce_f32")
     return out
+
+
+_MCD_MODES = {"fullmean": 0, "mean": 1, "avgpool": 2, "copy": 3}
+_MCD_DTYPES = {torch.float32: 0, torch.float16: 1, torch.bfloat16: 2}
+
+
+def mcd_row_width(shape, mode: str, avg_pooling_parameters=None) -> int:
+    """Width D of the row ``mcd_reduce_rows`` writes per image for an activation of ``shape`` (2-D or 4-D)."""
+    assert mode in _MCD_MODES, f"mode must be one of {sorted(_MCD_MODES)}"
+    assert len(shape) in (2, 4), "the activation must be (B, F) or (B, C, H, W)"
+    c, h, w = (int(shape[1]), 1, 1) if len(shape) == 2 else (int(shape[1]), int(shape[2]), int(shape[3]))
+    if mode == "fullmean":
+        return c
+    if mode == "mean":
+        return c * h
+    if mode == "copy":
+        return c * h * w
+    assert avg_pooling_parameters is not None and len(avg_pooling_parameters) == 3, \
+        "Three parameters are needed for average pooling"
+    k, st, p = (int(v) for v in avg_pooling_parameters)
+    assert k > 0 and st > 0 and 0 <= 2 * p <= k, "pad should be at most half of the kernel size"
+    assert h + 2 * p >= k and w + 2 * p >= k, "the pooling window is larger than the padded map"
+    return c * ((h + 2 * p - k) // st + 1) * ((w + 2 * p - k) // st + 1)
+
+
+@_device_guard()
+def mcd_reduce_rows(x: torch.Tensor, table: torch.Tensor, mode: str, row0: int = 0, row_step: int = 1,
+                    avg_pooling_parameters=None) -> torch.Tensor:
+    """Reduce the hooked activation ``x`` ((B, C, H, W) or (B, F); f32 / f16 / bf16; any strides, read in place) and write
+    the row of image ``b`` into ``table[row0 + b * row_step, :D]`` (``table`` f32, row-major, ``table.shape[1] >= D``).
+    ``mode``: ``"fullmean"`` (D = C), ``"mean"`` (over W, D = C*H), ``"avgpool"`` with ``avg_pooling_parameters =
+    (kernel, stride, padding)`` (``avg_pool2d`` defaults, D = C*Ho*Wo), ``"copy"`` (the flattened activation).  One
+    launch on the current stream; the other rows and the columns from D on keep their contents.  Returns ``table``."""
+    # shapes and dtypes first, then the devices: every refusal comes before the library is touched
+    assert isinstance(x, torch.Tensor) and isinstance(table, torch.Tensor)
+    assert x.dtype in _MCD_DTYPES, f"unsupported activation dtype {x.dtype} (float32, float16, bfloat16)"
+    assert table.dtype == torch.float32 and table.dim() == 2 and (table.shape[0] <= 1 or table.stride(0) >= table.shape[1]) \
+        and (table.shape[1] <= 1 or table.stride(1) == 1), "the table must be a row-major float32 matrix"
+    d = mcd_row_width(x.shape, mode, avg_pooling_parameters)
+    assert table.shape[1] >= d, f"the table is too narrow: {table.shape[1]} columns for rows of {d} values"
+    b = int(x.shape[0])
+    row0, row_step = int(row0), int(row_step)
+    assert row0 >= 0 and row_step >= 1 and (b == 0 or row0 + (b - 1) * row_step < table.shape[0]), \
+        f"rows {row0} + b * {row_step}, b < {b}, leave the table of {table.shape[0]} rows"
+    assert x.is_cuda, "the activation must be a device tensor"
+    assert table.is_cuda and table.device == x.device, "the table must be on the activation's device"
+    lib = load_library()
+    require_gpu()
+    if b == 0:
+        return table
+    if x.dim() == 2:
+        x = x[:, :, None, None]
+    k, st, p = (int(v) for v in avg_pooling_parameters) if mode == "avgpool" else (0, 0, 0)
+    ld = int(table.stride(0)) if table.shape[0] > 1 else max(int(table.stride(0)), int(table.shape[1]))
+    _check(lib.runia_mcd_reduce_rows(x.data_ptr(), _MCD_DTYPES[x.dtype], b, x.shape[1], x.shape[2], x.shape[3],
+                                     x.stride(0), x.stride(1), x.stride(2), x.stride(3), _MCD_MODES[mode], k, st, p,
+                                     table.data_ptr(), table.shape[0], ld, row0, row_step, _stream()),
+           "runia_mcd_reduce_rows")
+    return table
 
 
 @_device_guard()

@@ -18,10 +18,14 @@
 // Numerics.  With S = 1 + s' the softmax denominator relative to the max,
 //   lse = m + log1p(s'),   H = -sum p log p = log1p(s') + u / (1 + s'),
 // both terms >= 0, so there is no cancellation and peaked rows keep their accuracy.  A -inf logit contributes nothing
-// (its e^(x-m) (m-x) = 0 * inf term is skipped explicitly).  The reference clamps p at 1e-12 before the log; that moves H
-// by at most V e^-1 1e-12 (4.7e-8 nats, 4e-9 after the division by log V at V = 128 256) and is dropped here.  A row
-// that holds NaN or +inf, or only -inf, gives NaN in all three outputs, as torch's softmax does; a token whose logit is
-// -inf gets log_prob = -inf exactly.
+// (its e^(x-m) (m-x) = 0 * inf term is skipped explicitly), and neither does a finite one so far below the max that
+// m - x, or (m - x) (1 + s') in the f32 lane merges, leaves the f32 range (bf16 / f32 rows holding both signs of
+// ~3e38, or torch.finfo(dtype).min as a logits processor's mask value): its weight e^(x-m) is 0 and the same
+// 0 * inf is skipped.  log_prob is (x[tok] - m) - log1p(s') in f64, so it keeps the log term whatever the size of m;
+// the lse output is m + log1p(s') rounded to f32 and equals m once |m| >= 2^24 log1p(s') (no f32 holds more).
+// The reference clamps p at 1e-12 before the log; that moves H by at most V e^-1 1e-12 (4.7e-8 nats, 4e-9 after the
+// division by log V at V = 128 256) and is dropped here.  A row that holds NaN or +inf, or only -inf, gives NaN in
+// all three outputs, as torch's softmax does; a token whose logit is -inf gets log_prob = -inf exactly.
 #include "common.hpp"
 
 namespace {
@@ -96,7 +100,8 @@ __device__ __forceinline__ void merge(T& m, T& s, T& u, int& bad, const P& q) {
   const T l1 = (T)1 + ls;
   m = hm;
   s = hs + r * l1;
-  u = hu + r * (lu + d * l1);
+  // r = 0 (d past ~104 in f32): the lower partial has no weight left; d, or d * l1 in f32, may be inf there (0 * inf)
+  u = hu + (r > (T)0 ? r * (lu + d * l1) : (T)0);
 }
 
 __device__ __forceinline__ Partial shfl_xor_partial(const Partial& p, int o) {
@@ -137,8 +142,10 @@ __global__ __launch_bounds__(kThreads) void partial_kernel(const StepDesc* __res
     for (int e = 0; e < kPerLane; ++e) {
       const bool own = !skipped && x[e] == m;
       skipped |= own;
-      const bool live = !own && x[e] > -__builtin_inff();  // -inf: e^(x-m) = 0 and (m - x) = inf, no 0 * inf
-      const float d = live ? m - x[e] : 0.f;
+      const float gap = m - x[e];
+      // x = -inf, or finite and more than FLT_MAX below the max: e^(x-m) = 0 and (m - x) = inf, no 0 * inf
+      const bool live = !own && gap < __builtin_inff();
+      const float d = live ? gap : 0.f;
       // v_exp_f32 of -d log2(e): the rounded product moves e^-d by at most d 2^-24 relative, so s' and u move by at
       // most 6e-8 H relative (H the entropy, <= log V) - 1e-6 of lse at V = 128 256; the accurate expf made the kernel
       // ALU-bound (bf16 as slow as f32)
@@ -188,8 +195,9 @@ __global__ __launch_bounds__(256) void finish_kernel(const StepDesc* __restrict_
     const StepDesc sd = tab[t];
     const char* row = reinterpret_cast<const char*>(sd.ptr) + b * sd.row_stride * Elem<DT>::kSize;
     const float xt = load_one<DT>(row, tokens[b * token_stride + t]);
-    // x - lse with x = -inf stays -inf exactly; a NaN row gives NaN whatever the token
-    log_prob[o] = normalize ? (float)((double)xt - row_lse) : xt;
+    // (x - m) - log1p(s'), not x - lse: m + log1p(s') drops the log term in f64 once |m| passes 2^53 (bf16 1e30)
+    // x = -inf stays -inf exactly; a NaN row gives NaN whatever the token
+    log_prob[o] = !normalize ? xt : nan_row ? __builtin_nanf("") : (float)(((double)xt - m) - l1p);
   }
 }
 

@@ -32,11 +32,11 @@ def restate(x, tokens):
         m = np.where(bad, 0.0, np.max(np.where(np.isnan(x), -np.inf, x), axis=-1))
         e = np.exp(x - m[..., None])
         s = e.sum(-1)
-        lse = m + np.log(s)
         p = e / s[..., None]
         h = -(p * np.log(np.maximum(p, 1e-12))).sum(-1) / np.log(V)
         xt = np.take_along_axis(x, tok[..., None], -1)[..., 0]
-        lp = np.where(np.isneginf(xt), -np.inf, xt - lse)
+        # (x - m) - log s, as log_softmax: m + log s loses log s in f64 once |m| passes 2^53 (bf16 logits of 1e30)
+        lp = np.where(np.isneginf(xt), -np.inf, (xt - m) - np.log(s))
     lp = np.where(bad, np.nan, lp).T
     h = np.where(bad, np.nan, h).T
     with np.errstate(invalid="ignore"):
@@ -223,3 +223,193 @@ def test_restatement_reproduces_every_fixture_number(case):
         assert_close(got[k], case[k], ref_tol(V, 1e-6), True, f"{name} {k}")
     if "hf_log_probs" in case:  # HF's call on the generation's own scores
         assert_log_probs(got["log_probs"], case["hf_log_probs"], f"{name} HF", ref_tol(V, 2e-6))
+
+
+# ---- the edge-case generators of test_logit_scores_edges_gpu.py (logit_edge_cases.py), checked without a device ------
+import logit_edge_cases as ec  # noqa: E402
+
+
+def edge_cases():
+    """Every case the GPU edge tests score, by name."""
+    cases = [ec.v_sweep_case(V, d) for V in ec.V_SWEEP for d in ec.DTYPE_NAMES]
+    cases += [ec.masked_case(V, d, m) for V in ec.MASK_VOCABS for d in ec.DTYPE_NAMES for m in (False, True)]
+    cases += [ec.equal_rows_case(V, d) for V in ec.EQUAL_VOCABS for d in ec.DTYPE_NAMES]
+    cases += [ec.maxima_case(d) for d in ec.DTYPE_NAMES]
+    cases += [ec.peaked_case(lead, d) for lead in ec.PEAK_LEADS for d in ("float32", "bfloat16")]
+    cases += [ec.extreme_case(d, mag) for d, mag in ec.EXTREMES]
+    cases += [ec.batch_case(B, T) for B in ec.BATCH_SIZES for T in ec.BATCH_STEPS]
+    return cases
+
+
+def _torch_f64(case):
+    """log_probs and token_entropy (B, T) of torch.log_softmax / torch.softmax in f64."""
+    x = torch.from_numpy(case["x"]).double()
+    tok = torch.from_numpy(case["tokens"]).t()[..., None]  # (T, B, 1)
+    lp = torch.log_softmax(x, -1).gather(-1, tok)[..., 0].t()
+    p = torch.softmax(x, -1)
+    h = (-(p * p.clamp_min(1e-12).log()).sum(-1) / np.log(x.shape[-1])).t()
+    return lp.numpy(), h.numpy()
+
+
+@pytest.mark.parametrize("case", edge_cases(), ids=lambda c: c["name"])
+def test_restatement_agrees_with_torch_f64_on_the_edge_cases(case):
+    """restate() is the judge of the GPU edge tests: on every input they use it agrees with torch's own f64 log_softmax /
+    softmax to 1e-12, with -inf and NaN at torch's places (no case here holds an all -inf row, the one place where
+    restate's NaN convention is its own), and the case's values are exact in its dtype."""
+    assert case["x"].dtype == np.float32 and case["tokens"].dtype == np.int64
+    T, B, V = case["x"].shape
+    assert case["tokens"].shape == (B, T) and case["tokens"].min() >= 0 and case["tokens"].max() < V
+    np.testing.assert_array_equal(ec.representable(case["x"], case["dtype"]), case["x"])
+    assert not np.isneginf(case["x"]).all(-1).any()
+    got = restate(ec.values64(case), case["tokens"])
+    lp, h = _torch_f64(case)
+    assert_log_probs(got["log_probs"], lp, case["name"], 1e-12)
+    assert_close(got["token_entropy"], h, 1e-12, False, f"{case['name']} token entropy")
+    with np.errstate(invalid="ignore"):
+        finite = ~np.isneginf(lp)
+        means = np.where(finite, lp, 0.0).sum(1) / finite.sum(1)
+    assert_close(got["generation_entropy"], h.mean(1), 1e-12, True, f"{case['name']} generation entropy")
+    assert_close(got["perplexity"], -lp.mean(1), 1e-12, True, f"{case['name']} perplexity")
+    assert_close(got["normalized_entropy"], -means.sum() / B, 1e-12, True, f"{case['name']} normalized entropy")
+
+
+@pytest.mark.parametrize("V", ec.MASK_VOCABS)
+@pytest.mark.parametrize("dtype", ec.DTYPE_NAMES)
+@pytest.mark.parametrize("finfo_min", [False, True], ids=["inf", "min"])
+def test_masked_cases_have_the_empty_chunks_and_lanes_they_are_named_for(V, dtype, finfo_min):
+    case = ec.masked_case(V, dtype, finfo_min)
+    nc = ec.n_chunks(V)
+    assert nc == {128256: 32, 32001: 8}[V] and V % ec.K_CHUNK != 0 and ec.LANES * ec.PER_LANE == ec.K_CHUNK
+    assert case["fill"] == (float(torch.finfo(DTYPES[dtype]).min) if finfo_min else -np.inf)
+    assert [(r["placement"], r["k"]) for r in case["rows"]] == [(p, k) for p in ec.MASK_PLACEMENTS for k in ec.MASK_KEEP]
+    seen = set()
+    for b, row in enumerate(case["rows"]):
+        k, placement, pos = row["k"], row["placement"], row["positions"]
+        for t in range(case["x"].shape[0]):
+            x = case["x"][t, b]
+            np.testing.assert_array_equal(np.flatnonzero(x != case["fill"]), pos)
+            assert np.isfinite(x[pos]).all() and np.abs(x[pos]).max() < 20
+            chunks, lanes = ec.live_chunks_and_lanes(x, dtype, case["fill"])
+            want_chunks, want_lanes = ec.mask_expected_live(V, k, placement)
+            assert chunks == want_chunks, (placement, k)
+            assert want_lanes is None or lanes == want_lanes, (placement, k)
+            # the row's empty chunks and (chunk, lane) pairs: all but those few
+            if placement in ("first_chunk", "last_chunk", "row_end"):
+                assert nc - chunks == nc - 1
+            if k == 1:
+                assert nc * ec.LANES - lanes == nc * ec.LANES - 1
+        live = {int(p) // ec.K_CHUNK for p in pos}
+        if placement == "first_chunk":
+            assert live == {0}
+        elif placement in ("last_chunk", "row_end"):
+            assert live == {nc - 1} and (placement == "last_chunk" or pos[-1] == V - 1)
+        elif placement == "spread":
+            assert live == (set(range(nc)) if k > nc else {nc // 2} if k == 1 else live) and len(live) == min(k, nc)
+            if k == 2:
+                assert live == {0, nc - 1}
+        elif placement == "one_lane":
+            assert {ec.lane_of(int(p), dtype)[1] for p in pos} == {3} and 0 not in live and nc - 1 not in live
+        seen |= live
+        # step 0 scores a survivor, step 1 a masked position
+        assert case["tokens"][b, 0] in pos and case["tokens"][b, 1] not in pos
+    assert {0, nc // 2, nc - 1} <= seen  # the finite chunk is first, in the middle and last
+    b = case["all_tokens_masked_row"]
+    ref = restate(ec.values64(case), case["tokens"])
+    if finfo_min:
+        assert np.isfinite(ref["log_probs"]).all() and np.isfinite(ref["token_entropy"]).all()
+        assert np.isfinite(ref["normalized_entropy"])
+    else:
+        assert np.isneginf(ref["log_probs"][b]).all() and np.isnan(ref["normalized_entropy"])
+        assert np.isneginf(ref["log_probs"][:b, 1]).all() and np.isfinite(ref["log_probs"][:b, 0]).all()
+        assert np.isfinite(restate(ec.values64(case)[:, :b], case["tokens"][:b])["normalized_entropy"])
+
+
+def test_repeated_maxima_sit_where_their_names_say():
+    for dtype in ec.DTYPE_NAMES:
+        case = ec.maxima_case(dtype)
+        assert ec.n_chunks(ec.MAXIMA_V) == 4 and ec.MAXIMA_V % ec.K_CHUNK == 1
+        for b, row in enumerate(case["rows"]):
+            x, pos = case["x"][0, b], row["positions"]
+            assert len(pos) == row["n"] == len(set(pos))
+            np.testing.assert_array_equal(np.flatnonzero(x == x.max()), sorted(pos))
+            where = [ec.lane_of(p, dtype) for p in pos]
+            chunks, lanes = {c for c, _ in where}, {l for _, l in where}
+            if row["placement"] == "same_lane":
+                assert len(chunks) == 1 and len(lanes) == 1
+            elif row["placement"] == "neighbour_lanes":
+                assert len(chunks) == 1 and sorted(lanes) == list(range(min(lanes), min(lanes) + row["n"]))
+                assert len({l // 64 for l in lanes}) == 1
+            elif row["placement"] == "other_wave":
+                assert len(chunks) == 1 and len({l // 64 for l in lanes}) == row["n"]
+            elif row["placement"] == "other_chunk":
+                assert len(chunks) == row["n"]
+            else:
+                assert pos[0] == ec.MAXIMA_V - 1 and len(chunks) == row["n"]
+    for V in ec.EQUAL_VOCABS:
+        case = ec.equal_rows_case(V, "bfloat16")
+        assert (case["x"] == case["x"][..., :1]).all()
+        ref = restate(ec.values64(case), case["tokens"])
+        np.testing.assert_allclose(ref["log_probs"], -np.log(V), rtol=0, atol=1e-12)
+        if V > 1:
+            np.testing.assert_allclose(ref["token_entropy"], 1.0, rtol=0, atol=1e-12)
+        else:
+            assert np.isnan(ref["token_entropy"]).all()  # 0 / log 1
+
+
+@pytest.mark.parametrize("dtype", ["float32", "bfloat16"])
+@pytest.mark.parametrize("lead", ec.PEAK_LEADS)
+def test_peaked_rows_are_peaked(lead, dtype):
+    case = ec.peaked_case(lead, dtype)
+    ref = restate(ec.values64(case), case["tokens"])
+    # a lead of 10 over 50 256 Gaussian logits leaves them e^-10 * 50 256 * e^(1/2 - max) ~ 0.06 of the mass: peaked, but not
+    # below 1e-3; from 30 on the entropy is below 1e-3 (1e-9 and smaller)
+    bound = 1e-3 if lead >= 30 else 0.1
+    assert (ref["token_entropy"] < bound).all() and (ref["token_entropy"] > 0).all()
+    assert (ref["log_probs"][:, 0] > -bound).all() and (ref["log_probs"][:, 1] < -lead + bound).all()
+    chunks = [w // ec.K_CHUNK for w in case["winners"]]
+    assert chunks[0] == 0 and chunks[2] == ec.n_chunks(ec.PEAK_V) - 1 and 0 < chunks[1] < chunks[2]
+    if lead == 120:
+        assert ref["token_entropy"].max() < 1e-30 * 1e-10
+
+
+def test_extreme_rows_are_finite_and_far_apart():
+    for dtype, mag in ec.EXTREMES:
+        case = ec.extreme_case(dtype, mag)
+        assert np.isfinite(case["x"]).all() and case["x"].max() == case["mag"] and case["x"].min() == -case["mag"]
+        assert abs(case["mag"] / mag - 1) < 2 ** -8
+        ref = restate(ec.values64(case), case["tokens"])
+        assert all(np.isfinite(np.asarray(v)).all() for v in ref.values())
+        assert np.abs(ref["log_probs"]).max() < 10
+        b, tok = case["overflow_token"]
+        assert case["x"][0, b, tok] == -case["mag"]
+    assert 2 * ec.extreme_case("bfloat16", 3e38)["mag"] > float(np.finfo(np.float32).max)
+
+
+@pytest.mark.parametrize("which", ec.BAD_TOKEN_IDS)
+@pytest.mark.parametrize("column", [0, 2], ids=["first", "last"])
+def test_token_ids_out_of_range_raise_before_any_launch(which, column, monkeypatch):
+    """finish_kernel loads row[token] unchecked: the wrapper's [0, V) check is the only guard.  No device exists here,
+    so a missing check would surface as RuniaHipError, not as the ValueError asserted."""
+    from runia_core_amd.llm_uncertainty import generation_scores, transition_scores
+    from runia_core_amd.llm_uncertainty.logits import _token_ids
+
+    monkeypatch.setattr(torch.cuda, "is_available", lambda: False)
+    V, B, T = 7, 2, 3
+    scores = tuple(torch.zeros(B, V) for _ in range(T))
+    bad = torch.from_numpy(ec.bad_token_sequences(which, column, V, B, T))
+    assert not (0 <= int(bad[1, 5 + column]) < V) and bad.shape == (B, 5 + T)
+    with pytest.raises(ValueError, match=r"\[0, 7\)"):
+        _token_ids(bad, B, T, V)
+    for call in (lambda: generation_scores(bad, scores), lambda: transition_scores(bad, scores, normalize_logits=True),
+                 lambda: transition_scores(bad, scores), lambda: generation_scores(bad.numpy(), scores)):
+        with pytest.raises(ValueError, match=r"\[0, 7\)"):
+            call()
+    # the largest and smallest valid ids pass the check, and a bad id in a prompt column (not scored) is accepted
+    ok = bad.clone()
+    ok[1, 5 + column] = V - 1
+    ok[0, 5] = 0
+    assert torch.equal(_token_ids(ok, B, T, V), ok[:, 5:])
+    ok[0, 4] = {"-1": -1, "V": V, "2**40": 2 ** 40}[which]
+    assert torch.equal(_token_ids(ok, B, T, V), ok[:, 5:])
+    with pytest.raises(_hip.RuniaHipError):  # past the checks: no device here
+        generation_scores(ok, scores)

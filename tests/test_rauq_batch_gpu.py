@@ -228,3 +228,40 @@ def test_rauq_batch_llama_8b_shape_bf16():
         del att
         gc.collect()
         torch.cuda.empty_cache()
+
+
+# ---- the summation-order switch of gather_value at k = 512 (inputs: rauq_switch_cases.py) --------------------------------
+import rauq_switch_cases as sw  # noqa: E402
+
+
+@pytest.mark.parametrize("dtype", list(sw.DTYPES))
+@pytest.mark.parametrize("tie", [False, True], ids=["margin", "tie"])
+def test_rauq_batch_rows_on_both_sides_of_the_summation_switch(dtype, tie):
+    """B = 3 left-padded rows whose k at step g is 513 + g, 510 + g and 507 + g: row 0 is always over 512 columns, row 1
+    crosses 512 at its third step, row 2 (five steps) stays under it, so at each of row 2's steps a row under 512 sits next to one
+    at or over it.  Every row's bits are the one-row call's on its slices, its scores meet the restatement
+    of its own maps, and its chosen heads are the restatement's."""
+    inp, pads = sw.BATCH["input_length"], list(sw.BATCH["pads"])
+    lengths = torch.tensor(sw.BATCH["lengths"])
+    steps = sw.batch_steps(dtype, 300, tie)
+    att = sw.batch_tensors(steps, dtype, "cuda")
+    lp = torch.from_numpy(sw.log_probs(sw.BATCH["n_gen"], 31, rows=len(pads)))
+    mask = _mask(pads, inp)
+    for h in HEADS:
+        got = rauq_batch(lp, att, inp, "mean_all_tokens", h, sw.ALPHAS, mask, lengths)
+        exp = _one_row(att, lp, mask, lengths, inp, h, "mean_all_tokens", sw.ALPHAS)
+        assert _bits_equal(got, exp), (dtype, h, got, exp)
+        for b, pad in enumerate(pads):
+            n = int(lengths[b])
+            lpb = lp[b, :n].numpy()
+            r, heads = restate(row_steps(steps, pad, n, b), dtype, lpb.reshape(1, -1) if h == "rollout" else lpb, inp - pad,
+                               sw.ALPHAS, h, "mean_all_tokens")
+            print(f"batch row {b} {dtype} {h}: rel {_rel(got[b].cpu().numpy(), r):.2e}")
+            assert _rel(got[b].cpu().numpy(), r) <= (1e-5 if h == "rollout" else 1e-6), (dtype, h, b)
+            if h == "original":
+                sl = tuple(tuple(t[b:b + 1, :, pad:, pad:] if g == 0 else t[b:b + 1, :, :, pad:] for t in att[g])
+                           for g in range(n))
+                _, got_heads = rq._gather_scores(lp[b, :n], sl, "mean_all_tokens", sw.ALPHAS, rq._HEAD_ARGMAX)
+                np.testing.assert_array_equal(got_heads, heads, err_msg=f"heads of row {b}, {dtype}")
+                if tie:
+                    assert (np.asarray(got_heads) == sw.TIE_HEADS[0]).all()

@@ -230,3 +230,87 @@ def test_rauq_real_hf_generation():
                 got = _call(h, t, lp[0], att, inp, alphas)
             exp, _ = restate(steps, "float32", lp.cpu().numpy(), inp, alphas, h, t)
             assert _rel(got, exp) <= (1e-5 if h == "rollout" else 1e-6), (h, t, got, exp)
+
+
+# ---- the summation-order switch of gather_value at k = 512 (inputs: rauq_switch_cases.py) --------------------------------
+import rauq_switch_cases as sw  # noqa: E402
+
+
+def _switch_check(steps, dtype, inp, seed):
+    """"mean_all_tokens" in the three head modes against the restatement, the chosen heads included."""
+    n_gen = len(steps)
+    att = sw.one_row_tensors(steps, dtype, "cuda")
+    lp = torch.from_numpy(sw.log_probs(n_gen, seed))
+    steps64 = [s.astype(np.float64) for s in steps]
+    out = {}
+    for h in HEADS:
+        got = _call(h, "mean_all_tokens", lp if h == "rollout" else lp[0], att, inp, sw.ALPHAS)
+        exp, heads = restate(steps64, dtype, lp.numpy() if h == "rollout" else lp[0].numpy(), inp, sw.ALPHAS, h,
+                             "mean_all_tokens")
+        print(f"k {inp}..{inp + n_gen - 1} {dtype} {h}: rel {_rel(got, exp):.2e}")
+        assert _rel(got, exp) <= (1e-5 if h == "rollout" else 1e-6), (h, dtype, inp, got, exp)
+        if h == "original":
+            _, got_heads = rq._gather_scores(lp[0], att, "mean_all_tokens", sw.ALPHAS, rq._HEAD_ARGMAX)
+            np.testing.assert_array_equal(got_heads, heads, err_msg=f"heads, k from {inp}, {dtype}")
+            out["heads"] = np.asarray(got_heads)
+        out[h] = got
+    return out
+
+
+@pytest.mark.parametrize("dtype", list(sw.DTYPES))
+@pytest.mark.parametrize("k", sw.SWITCH_KS)
+def test_rauq_row_means_at_the_summation_switch(k, dtype):
+    """Prompt lengths that put the row means' k at 510, 511, 512 and 513: both sides of the switch from torch's cascade
+    order to the wave sum.  The heads' gains keep the head choice off a near-tie (asserted in test_rauq_host.py)."""
+    _switch_check(sw.one_row_steps(k, 3, dtype, 100 + k), dtype, k, k)
+
+
+@pytest.mark.parametrize("dtype", list(sw.DTYPES))
+@pytest.mark.parametrize("tie", [False, True], ids=["margin", "tie"])
+def test_rauq_generation_crossing_the_summation_switch(dtype, tie):
+    """Six steps from k = 509: the means of one series come from both summation orders.  With head 3 a copy of head 1
+    and both largest, the first index wins, as the reference's argmax."""
+    inp, n_gen = sw.GENERATION["input_length"], sw.GENERATION["n_gen"]
+    out = _switch_check(sw.one_row_steps(inp, n_gen, dtype, 200, tie), dtype, inp, 7)
+    if tie:
+        assert (out["heads"] == sw.TIE_HEADS[0]).all()
+
+
+def _gathered_means(ks):
+    """w (L, H, len(ks)) f32 of runia_rauq_gather in "mean_all_tokens" on one step per k (rauq._gather_scores' own call)."""
+    from runia_core_amd import _hip
+
+    att = sw.mean_steps(ks, "cuda")
+    lib = _hip.load_library()
+    table, keep = rq._map_table(att, torch.device("cuda"), first_row_only=True)
+    w = torch.full((sw.MEAN_L, sw.MEAN_H, len(ks)), float("nan"), dtype=torch.float32, device="cuda")
+    _hip._check(lib.runia_rauq_gather(table.data_ptr(), rq._DTYPE_CODES[torch.float32], len(ks), sw.MEAN_L, sw.MEAN_H, 1,
+                                      w.data_ptr(), _hip._stream()), "runia_rauq_gather")
+    torch.cuda.synchronize()
+    del keep
+    return w.cpu().numpy()
+
+
+def _bits(a):
+    return np.ascontiguousarray(a, dtype=np.float32).view(np.uint32)
+
+
+def test_rauq_gathered_row_means_are_bitwise_torchs_below_512():
+    """The kernel header's promise for rows of k < 512 columns, up to 510 and 511: the gathered f32 means are torch's own
+    CPU mean(-1) of the same rows, bit for bit (and the oracle's restatement of that order).  These rows' bits differ
+    under the wave order (test_rauq_host.py), so a switch one column early is seen."""
+    from test_rauq_host import f32_mean_lastdim
+
+    w = _gathered_means(sw.MEAN_KS_CASCADE)
+    for i, k in enumerate(sw.MEAN_KS_CASCADE):
+        a = sw.mean_rows(k)
+        np.testing.assert_array_equal(_bits(w[:, :, i]), _bits(torch.from_numpy(a).mean(-1).numpy()[..., 0]), err_msg=f"torch, k = {k}")
+        np.testing.assert_array_equal(_bits(w[:, :, i]), _bits(f32_mean_lastdim(a)[..., 0]), err_msg=f"oracle, k = {k}")
+
+
+def test_rauq_gathered_row_means_are_bitwise_the_wave_sum_from_512():
+    """From 512 columns on the documented order: lane j adds the elements j, j + 64, ... in index order, then the xor
+    butterfly 32 .. 1.  These rows' bits differ under torch's cascade order, so a switch one column late is seen."""
+    w = _gathered_means(sw.MEAN_KS_WAVE)
+    for i, k in enumerate(sw.MEAN_KS_WAVE):
+        np.testing.assert_array_equal(_bits(w[:, :, i]), _bits(sw.wave_order_mean(sw.mean_rows(k))[..., 0]), err_msg=f"k = {k}")

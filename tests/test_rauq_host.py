@@ -230,3 +230,84 @@ def test_rauq_python_contract_without_a_device(monkeypatch):
                  lambda: RAUQ(lp, att, 6, "original", "rollout", [0.4], True)):
         with pytest.raises(_hip.RuniaHipError):
             call()
+
+
+# ---- the inputs of the GPU tests at the summation-order switch (rauq_switch_cases.py) --------------------------------
+import rauq_switch_cases as sw  # noqa: E402
+
+
+def switch_rows():
+    """(name, input_length, n_gen, seed, steps maker) of every one-row input the GPU switch tests score: the prompt
+    lengths that put k at 510 .. 513, the generation crossing 512, and the batch's rows on their own."""
+    rows = [(f"k{k}", k, 3, 100 + k) for k in sw.SWITCH_KS]
+    rows.append(("generation", sw.GENERATION["input_length"], sw.GENERATION["n_gen"], 200))
+    rows += [(f"batch_row{b}", sw.BATCH["input_length"] - pad, n, 300 + 10 * b)
+             for b, (pad, n) in enumerate(zip(sw.BATCH["pads"], sw.BATCH["lengths"]))]
+    return rows
+
+
+@pytest.mark.parametrize("dtype", list(sw.DTYPES))
+@pytest.mark.parametrize("tie", [False, True], ids=["margin", "tie"])
+def test_switch_inputs_cross_512_with_a_clear_head_margin(dtype, tie):
+    """The per-head mode picks a head by argmax over means that differ in their last bits for plain softmax rows.  On
+    these inputs the oracle's two largest head means differ by at least 1e-3 relative in every layer, so the choice does
+    not hang on a summation order; in the tie inputs heads 1 and 3 are bitwise equal and largest, the next is 1e-3 lower,
+    and the reference's argmax takes head 1."""
+    ks = set()
+    for name, inp, n_gen, seed in switch_rows():
+        steps = sw.one_row_steps(inp, n_gen, dtype, seed, tie)[:n_gen]
+        assert [s.shape for s in steps] == [(sw.L, sw.H, inp, inp)] + [(sw.L, sw.H, 1, inp + g) for g in range(1, n_gen)]
+        for s in steps:
+            np.testing.assert_array_equal(sw._representable(s, dtype), s)
+        assert not np.triu(steps[0], 1).any()  # causal
+        ks |= {s.shape[-1] for s in steps}
+        w = gather_values([s.astype(np.float64) for s in steps], "mean_all_tokens", dtype)
+        means = f32_mean_lastdim(w[:, :, 1:]).astype(np.float64)
+        heads = argmax_heads(w)
+        for l in range(sw.L):
+            order = np.argsort(-means[l], kind="stable")
+            if tie:
+                assert sorted(order[:2]) == list(sw.TIE_HEADS) and means[l, order[0]] == means[l, order[1]], (name, l)
+                assert np.array_equal(w[l, sw.TIE_HEADS[0]], w[l, sw.TIE_HEADS[1]])
+                assert heads[l] == sw.TIE_HEADS[0]
+                order = order[1:]
+            assert means[l, order[0]] - means[l, order[1]] >= 1e-3 * means[l, order[0]], (name, l, means[l])
+    assert {509, 510, 511, 512, 513, 514} <= ks and sw.SWITCH == 512
+    # the batch: at one step some row is under 512 columns and another at or over it
+    inp, pads = sw.BATCH["input_length"], sw.BATCH["pads"]
+    assert any(min(inp - p + g for p in pads) < 512 <= max(inp - p + g for p in pads) for g in range(sw.BATCH["n_gen"]))
+    b_steps = sw.batch_steps(dtype, 300, tie)
+    for b, pad in enumerate(pads):
+        own = sw.one_row_steps(inp - pad, sw.BATCH["n_gen"], dtype, 300 + 10 * b, tie)
+        for g, s in enumerate(b_steps):
+            got = s[b, :, :, pad:, pad:] if g == 0 else s[b, :, :, :, pad:]
+            np.testing.assert_array_equal(got, own[g])
+            assert not s[b, ..., :pad].any()
+
+
+def _bits(a):
+    return np.ascontiguousarray(a, dtype=np.float32).view(np.uint32)
+
+
+def test_row_mean_orders_are_torchs_below_512_and_differ_from_the_wave_order():
+    """The expected values of test_rauq_gathered_row_means_are_bitwise_* (test_rauq_gpu.py).  Below 512 columns torch's own
+    CPU f32 mean(-1) of the rows equals the oracle's restatement of its cascade order bit for bit (the oracle was verified
+    up to n = 69 only).  At every tested k, on both sides of 512, the cascade order and the wave order give different bits
+    on some of the rows: a kernel that used the other order there, or switched one column early or late, is seen."""
+    assert sw.SWITCH == 512 and max(sw.MEAN_KS_CASCADE) == 511 and min(sw.MEAN_KS_WAVE) == 512
+    assert {510, 511} <= set(sw.MEAN_KS_CASCADE) and {512, 513} <= set(sw.MEAN_KS_WAVE)
+    for k in sw.MEAN_KS_CASCADE + sw.MEAN_KS_WAVE:
+        a = sw.mean_rows(k)
+        assert a.shape == (sw.MEAN_L, sw.MEAN_H, 1, k) and a.dtype == np.float32 and (a > 0).all()
+        cascade, wave = f32_mean_lastdim(a), sw.wave_order_mean(a)
+        np.testing.assert_allclose(wave, a.astype(np.float64).mean(-1), rtol=1e-6)
+        np.testing.assert_allclose(cascade, a.astype(np.float64).mean(-1), rtol=1e-6)
+        assert (_bits(cascade) != _bits(wave)).sum() >= 8, k
+        if k < sw.SWITCH:
+            np.testing.assert_array_equal(_bits(torch.from_numpy(a).mean(-1).numpy()), _bits(cascade), err_msg=f"k = {k}")
+    # the wave order by hand on a row whose sum depends on it: lanes 0 and 1 of two trips, then the butterfly
+    row = np.zeros(128, dtype=np.float32)
+    row[[0, 64, 1]] = [1.0, 2.0 ** -24, 2.0 ** -24]
+    # lane 0: 1 + 2^-24 -> 1 (ties to even), then + lane 1's 2^-24 -> 1; index order would give 1 + 2^-23
+    assert sw.wave_order_mean(row[None])[0] == np.float32(1.0) / np.float32(128)
+    assert np.float32(np.float32(row[1] + row[64]) + row[0]) / np.float32(128) != np.float32(1.0) / np.float32(128)

@@ -1,15 +1,22 @@
-"""Randomised differential check of the stand-alone stages against the CPU oracle (one MI355X, a few minutes):
-joint / per-dimension entropy, Energy / MSP, normaliser, PCA transform + MD at sizes around the tile switches, kNN
-(k-th distance) and LaRED on both kernel forms.  Shapes are drawn around the places where a kernel changes its launch
-shape or code path (vector widths, register-resident row limits, 16- / 32-row tiles, column halves, chunk limits).
+"""Randomised differential check of the stand-alone stages against the CPU oracle (one MI355X, a few minutes): joint /
+per-dimension entropy, Energy / MSP, normaliser, PCA transform + MD at sizes around the tile switches, kNN (k-th
+distance) and LaRED on both kernel forms, the LLM logit scores and RAUQ's row means.  Shapes are drawn around the places
+where a kernel changes its launch shape or code path (vector widths, register-resident row limits, 16- / 32-row tiles,
+column halves, chunk limits).
 
     gpurun -- python tools/fuzz_kernels.py [--seed S] [--rounds R]
 """
 import argparse, os, sys
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+sys.path.insert(1, os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "tests"))
 import numpy as np, torch
 import oracle
 from runia_core_amd import _hip
+from runia_core_amd.llm_uncertainty import RAUQ, generation_scores, rauq_batch
+from runia_core_amd.llm_uncertainty import rauq as rq
+# the RAUQ block's inputs and f64 restatement are the test suite's (tests/rauq_switch_cases.py, tests/test_rauq_host.py)
+import rauq_switch_cases as sw
+from test_rauq_host import f32_mean_lastdim, restate as rauq_restate
 
 ap = argparse.ArgumentParser()
 ap.add_argument("--seed", type=int, default=2024)
@@ -446,6 +453,87 @@ for t in range(a.rounds):
             big_ = np.maximum(rng.standard_normal(int(rng.choice([1 << 22, (1 << 22) + 12345]))).astype(np.float32), 0 if rng.random() < 0.5 else -9)
             qq_ = float(rng.choice([90, 65, 99.5, 12.5]))
             check("percentile_flat", (big_.size, qq_), 0.0 if np.array_equal(percentile_flat(big_, qq_), np.percentile(big_, qq_)) else 1.0, 0.5)
+
+
+    # ---- LLM logit scores (logits.hip): V around the 4 096-logit chunk and the 16-byte load, B past the sequence kernel's
+    # 16 waves, top-k style masks; against torch's f64 log_softmax / softmax (2e-6 max(1, |ref|) for the log-probs, 1e-6
+    # absolute for the token entropy, 1e-6 relative for the sequence scores) ----
+    vl = int(rng.choice([1, 2, 7, 8, 9, 4095, 4096, 4097, 4103, 8192, 8193, 12289, 32001, 50257]) + (rng.integers(0, 9) if rng.random() < 0.3 else 0))
+    bl, tl = int(rng.choice([1, 3, 16, 17, 33, 70])), int(rng.choice([1, 2, 63, 64, 65]))
+    if vl > 10_000:
+        bl, tl = min(bl, 17), min(tl, 2)
+    dtl = [torch.float32, torch.float16, torch.bfloat16][int(rng.integers(0, 3))]
+    keep = float(rng.choice([1.0, 1.0, 0.5, 0.01]))  # share of the logits a mask leaves finite
+    fill = float(rng.choice([-np.inf, float(torch.finfo(dtl).min)]))
+    xl = torch.from_numpy(rng.standard_normal((tl, bl, vl), dtype=np.float32) * np.float32(rng.choice([0.5, 3.0, 12.0]))).to(dtl)
+    tokl = torch.from_numpy(rng.integers(0, vl, (bl, tl)))
+    if keep < 1.0:
+        drop = torch.from_numpy(rng.random((tl, bl, vl)) >= keep)
+        drop.scatter_(2, tokl.t()[..., None] if rng.random() < 0.5 else torch.from_numpy(rng.integers(0, vl, (tl, bl, 1))), False)  # a survivor per row
+        xl = xl.masked_fill(drop, fill)
+    res = generation_scores(tokl.cuda(), tuple(xl[i].cuda() for i in range(tl)))
+    x64 = xl.double()
+    lp64 = torch.log_softmax(x64, -1).gather(2, tokl.t()[..., None])[..., 0].t().numpy()
+    p64 = torch.softmax(x64, -1)
+    h64 = (-(p64 * p64.clamp_min(1e-12).log()).sum(-1) / np.log(vl)).t().numpy()
+    with np.errstate(invalid="ignore", divide="ignore"):
+        fin = ~np.isneginf(lp64)
+        ne64 = -(np.where(fin, lp64, 0.0).sum(1) / fin.sum(1)).sum() / bl
+    argl = (vl, bl, tl, str(dtl), keep, fill)
+    gl = res.log_probs.cpu().numpy()
+    same_inf = np.array_equal(np.isneginf(gl), np.isneginf(lp64)) and np.array_equal(np.isnan(gl), np.isnan(lp64))
+    check("logit log_probs", argl, rel(gl, lp64) if same_inf else 1.0, 2e-6)
+    ge = res.token_entropy.cpu().numpy().astype(np.float64)
+    check("logit token entropy", argl, float(np.nanmax(np.abs(ge - h64), initial=0.0)) if np.array_equal(np.isnan(ge), np.isnan(h64)) else 1.0, 1e-6)
+    check("logit generation entropy", argl, rel(res.generation_entropy.cpu().numpy(), h64.mean(1)), 1e-6)
+    check("logit perplexity", argl, rel(res.perplexity.cpu().numpy(), -lp64.mean(1)), 1e-6)
+    check("logit normalized entropy", argl, rel(np.array([res.normalized_entropy]), np.array([ne64])), 1e-6)
+
+    # ---- RAUQ (rauq.hip): row means of k around 512 columns, where gather_value changes its summation order; the three
+    # head modes against the f64 restatement of tests/test_rauq_host.py (1e-6, rollout 1e-5) with the chosen heads, and
+    # the batched call bitwise against the one-row calls ----
+    if t % 4 == 1:
+        inr, ngr = int(rng.integers(505, 514)), int(rng.integers(2, 7))
+        dtr = str(rng.choice(list(sw.DTYPES)))
+        tier = bool(rng.random() < 0.3)
+        stp = sw.one_row_steps(inr, ngr, dtr, int(rng.integers(0, 1 << 30)), tier)
+        attr = sw.one_row_tensors(stp, dtr, "cuda")
+        lpr = torch.from_numpy(sw.log_probs(ngr, int(rng.integers(0, 1 << 30))))
+        for hm in ("original", "mean_heads", "rollout"):
+            lph = lpr if hm == "rollout" else lpr[0]
+            got_r = np.array(RAUQ(lph, attr, inr, "mean_all_tokens", hm, sw.ALPHAS, True))
+            exp_r, heads_r = rauq_restate([s_.astype(np.float64) for s_ in stp], dtr, lph.numpy(), inr, sw.ALPHAS, hm, "mean_all_tokens")
+            check(f"rauq {hm}", (inr, ngr, dtr, tier), float(np.max(np.abs(got_r - exp_r) / np.abs(exp_r))), 1e-5 if hm == "rollout" else 1e-6)
+            if hm == "original":
+                got_h = rq._gather_scores(lph, attr, "mean_all_tokens", sw.ALPHAS, rq._HEAD_ARGMAX)[1]
+                check("rauq heads", (inr, ngr, dtr, tier), 0.0 if np.array_equal(got_h, heads_r) else 1.0, 0.5)
+            # the same row behind 3 zero pad keys, as a batch of one: the batched kernels give the one-row call's bits
+            padr = 3
+            batt = []
+            for g_, step_ in enumerate(attr):
+                per_ = []
+                for m_ in step_:
+                    bm = torch.zeros((1, m_.shape[1], m_.shape[2] + (padr if g_ == 0 else 0), m_.shape[3] + padr), dtype=m_.dtype, device="cuda")
+                    bm[0, :, (padr if g_ == 0 else 0):, padr:] = m_[0]
+                    per_.append(bm)
+                batt.append(tuple(per_))
+            maskr = torch.cat([torch.zeros(1, padr, dtype=torch.int64), torch.ones(1, inr, dtype=torch.int64)], 1)
+            got_b = rauq_batch(lpr, tuple(batt), inr + padr, "mean_all_tokens", hm, sw.ALPHAS, maskr, torch.tensor([ngr]))
+            check(f"rauq_batch {hm} bits", (inr, ngr, dtr, tier), 0.0 if np.array_equal(got_b[0].cpu().numpy(), got_r.astype(np.float32)) else 1.0, 0.5)
+            del batt
+        del attr
+        # the gathered f32 row means bit for bit: torch's cascade order below 512 columns, the wave order from 512 on
+        km = int(rng.integers(480, 560))
+        am = rng.standard_normal((2, 8, 1, km)) * 2
+        am = np.exp(am - am.max(-1, keepdims=True))
+        am = (am / am.sum(-1, keepdims=True) * rng.uniform(0.5, 1.0, (2, 8, 1, 1))).astype(np.float32)
+        attm = ((dev(am[0])[None], dev(am[1])[None]),)
+        tabm, keepm = rq._map_table(attm, torch.device("cuda"), first_row_only=True)
+        wm = torch.empty((2, 8, 1), dtype=torch.float32, device="cuda")
+        _hip._check(_hip.load_library().runia_rauq_gather(tabm.data_ptr(), 0, 1, 2, 8, 1, wm.data_ptr(), _hip._stream()), "runia_rauq_gather")
+        exp_m = (f32_mean_lastdim(am) if km < 512 else sw.wave_order_mean(am))
+        check("rauq row means bits", (km,), 0.0 if np.array_equal(wm.cpu().numpy().view(np.uint32), exp_m.view(np.uint32)) else 1.0, 0.5)
+        del attm, keepm
 
     if (t + 1) % 10 == 0:
         print(f"round {t + 1}/{a.rounds}, mismatches so far: {bad}", flush=True)

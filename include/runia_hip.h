@@ -101,6 +101,27 @@ int runia_mcd_reduce_rows(const void* x, int dtype, int64_t B, int64_t C, int64_
                           int64_t sh, int64_t sw, int mode, int kernel, int stride, int padding, float* table,
                           int64_t table_rows, int64_t ld, int64_t row0, int64_t row_step, runia_stream_t stream);
 
+/* The row tables of get_aggregated_data_dict (feature_extraction/utils.py:160-191: per field one torch.cat over the images
+ * that have rows, with torch.log(logits + 1e-10) per image when probs_as_logits) from the caller's per-image tensors.
+ *   table      device array of n_seg segment descriptors, 4 int64 each: {pointer to the segment's (rows, D) tensor, rows,
+ *              row stride, column stride (elements)}.  Every tensor is read in place through its own strides.  The caller
+ *              checks the shapes (the kernel trusts the table); segments of 0 rows are legal.
+ *   row_start  device array of n_seg + 1 int64: exclusive prefix sum of the rows (row_start[n_seg] == total).
+ *   dtype      0 f32, 1 f16, 2 bf16 (all segments and out of one call).
+ *   mode       RUNIA_RAGGED_COPY: the rows as they are (bit copies);  RUNIA_RAGGED_LOG_EPS: log(x + 1e-10) as torch forms
+ *              it on a tensor of that dtype: the sum in f32 rounded to dtype, the logarithm in f32 rounded to dtype (an f16
+ *              zero gives -inf, an f32 zero log(1e-10f)).
+ *   out        [total, ld] of dtype, ld >= D: segment s fills rows row_start[s] .. row_start[s + 1] - 1; the columns from D
+ *              on are not touched.
+ *   seg_of_row [total] int32 or NULL: the segment every output row came from.
+ * One launch whatever n_seg is (none when total or n_seg is 0).  Segments whose columns are contiguous, whose pointer is
+ * 16-byte aligned and whose rows lie a whole number of 16-byte vectors apart move 16 bytes per lane (out 16-byte aligned,
+ * ld a multiple of the vector as well); every other segment moves element by element. */
+#define RUNIA_RAGGED_COPY 0
+#define RUNIA_RAGGED_LOG_EPS 1
+int runia_ragged_rows(const int64_t* table, const int64_t* row_start, int64_t n_seg, int64_t total, int64_t D, int dtype,
+                      int mode, void* out, int64_t ld, int32_t* seg_of_row, runia_stream_t stream);
+
 /* ---- a2  Kozachenko-Leonenko kNN entropy --------------------------------- *
  * Replaces the loops of get_dl_h_z / single_image_entropy_calculation
  * (evaluation/entropy.py:20-93) over entropy_estimators.continuous.get_h(col, k,

@@ -42,6 +42,8 @@ _SIGNATURES = {
         [c_void_p, c_int, c_int64, c_int64, c_int64, c_int64, c_int64, c_int64, c_int64, c_int64, c_int, c_int, c_int,
          c_int, c_void_p, c_int64, c_int64, c_int64, c_int64, c_void_p],
     ),
+    "runia_ragged_rows": (
+        c_int, [c_void_p, c_void_p, c_int64, c_int64, c_int64, c_int, c_int, c_void_p, c_int64, c_void_p, c_void_p]),
     "runia_kl_entropy_per_dim_f32": (c_int, [c_void_p, c_void_p, c_int64, c_int, c_int64, c_int, c_double, c_void_p]),
     "runia_kl_entropy_joint_f32": (c_int, [c_void_p, c_void_p, c_int64, c_int, c_int64, c_int, c_double, c_void_p]),
     "runia_kl_entropy_both_fused": (c_int, [c_int, c_int64, c_int]),
@@ -697,6 +699,53 @@ def mcd_reduce_rows(x: torch.Tensor, table: torch.Tensor, mode: str, row0: int =
                                      table.data_ptr(), table.shape[0], ld, row0, row_step, _stream()),
            "runia_mcd_reduce_rows")
     return table
+
+
+_RAGGED_MODES = {"copy": 0, "log_eps": 1}
+
+
+@_device_guard()
+def ragged_rows(tensors, mode: str = "copy", out: Optional[torch.Tensor] = None, return_segments: bool = False):
+    """``torch.cat(tensors, dim=0)`` of 2-D device tensors of one width and dtype (f32 / f16 / bf16; any strides, read in place;
+    tensors of 0 rows allowed) in ONE launch: the descriptors and the prefix sum of the row counts go up as one copy.
+    ``mode="log_eps"`` writes ``torch.log(t + 1e-10)`` of every tensor instead.  ``out``: an existing row-major table of that
+    dtype with ``sum(rows)`` rows and at least D columns (the columns from D on keep their contents).  Returns the table, and
+    with ``return_segments`` also the int32 index of the tensor every row came from.  No host synchronisation."""
+    assert mode in _RAGGED_MODES, f"mode must be one of {sorted(_RAGGED_MODES)}"
+    tensors = list(tensors)
+    assert len(tensors) > 0 or out is not None, "an empty list needs an output table to tell width, dtype and device"
+    first = tensors[0] if tensors else out
+    dtype, dev = first.dtype, first.device
+    assert dtype in _MCD_DTYPES, f"unsupported dtype {dtype} (float32, float16, bfloat16)"
+    d = int(first.shape[1]) if tensors else int(out.shape[1])
+    # shapes and dtypes first, then the devices: every refusal comes before the library is touched
+    for i, t in enumerate(tensors):
+        assert isinstance(t, torch.Tensor) and t.dim() == 2 and t.shape[1] == d and t.dtype == dtype, \
+            f"tensor {i}: every tensor must be (rows, {d}) of {dtype}"
+    desc = np.empty((len(tensors) + 1, 5), np.int64)  # rows 0 .. n-1: pointer, rows, strides, start; row n: the total
+    total = 0
+    for i, t in enumerate(tensors):
+        assert t.is_cuda and t.device == dev, f"tensor {i}: every tensor must be on one GPU"
+        desc[i] = (t.data_ptr(), t.shape[0], t.stride(0), t.stride(1), total)
+        total += int(t.shape[0])
+    desc[len(tensors)] = (0, 0, 0, 0, total)
+    if out is None:
+        out = torch.empty((total, d), dtype=dtype, device=dev)
+    assert out.is_cuda and out.device == dev and out.dtype == dtype and out.dim() == 2 and out.shape[0] == total and \
+        out.shape[1] >= d and (out.shape[1] <= 1 or out.stride(1) == 1) and (total <= 1 or out.stride(0) >= out.shape[1]), \
+        f"the output must be a row-major ({total}, >= {d}) table of {dtype} on the tensors' device"
+    lib = load_library()
+    require_gpu()
+    seg = torch.empty(total, dtype=torch.int32, device=dev) if return_segments else None
+    if total > 0 and d > 0:
+        n = len(tensors)
+        # one upload: [n, 4] descriptors followed by the n + 1 prefix sums
+        packed = np.concatenate([desc[:n, :4].reshape(-1), desc[:, 4]])
+        up = torch.from_numpy(packed).to(dev, non_blocking=False)
+        ld = int(out.stride(0)) if total > 1 else max(int(out.stride(0)), int(out.shape[1]))
+        _check(lib.runia_ragged_rows(up.data_ptr(), up.data_ptr() + 32 * n, n, total, d, _MCD_DTYPES[dtype],
+                                     _RAGGED_MODES[mode], out.data_ptr(), ld, _ptr(seg), _stream()), "runia_ragged_rows")
+    return (out, seg) if return_segments else out
 
 
 @_device_guard()

@@ -18,3 +18,4 @@ from .open_set import (  # noqa: F401
     voc_ap,
     voc_eval,
 )
+from .box_subsets import get_gtu_uu_metrics, subset_boxes  # noqa: F401

@@ -149,6 +149,8 @@ def _log_evaluate_larex(cfg, baselines_names, ood_baselines_scores, ind_data_dic
                                   frames[0], mlflow_logging)
 
     def on_device(a):
+        if isinstance(a, torch.Tensor):  # rows that are on the device already (get_aggregated_data_dict(device_resident=True))
+            return _hip.to_device(a, torch.float32 if a.dtype == torch.float32 else torch.float64)
         a = np.asarray(a)
         return _hip.to_device(a, torch.float32 if a.dtype == np.float32 else torch.float64)
 

@@ -10,3 +10,4 @@ from .detectors import (  # noqa: F401
     ImageLvlFeatureExtractor,
     ObjectDetectionExtractor,
 )
+from .aggregation import associate_precalculated_baselines_with_raw_predictions, get_aggregated_data_dict  # noqa: F401

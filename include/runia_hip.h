@@ -520,6 +520,47 @@ int runia_mcd_uncertainty_f32(const float* logits, float* probs, float* pred_h, 
                               runia_stream_t stream);
 int runia_ash_s_rows_f32(const float* x, float* y, float* pruned, int64_t N, int64_t D, int percentile,
                          int keep_all_when_k_is_zero, runia_stream_t stream);
+
+/* ---- per-pixel uncertainty maps of a segmentation head ---------------------- *
+ * get_predictive_uncertainty_score (inference/funcs.py:430-465), Energy.postprocess and MSP.postprocess
+ * (inference/postprocessors.py:529-551, 586-608) for every pixel of G images from the logits of n_mc stochastic forward
+ * passes, read where they lie.  (On a 4-D tensor the reference's function sums its expected-entropy term over W instead of
+ * the classes; the definition taken is that function on one row per (image, pixel, sample).)
+ *   table      DEVICE array of base pointers.  single == 0: n_mc pointers, pass s is a (G, C, H, W) block at table[s].
+ *              single == 1: one pointer to a (G * n_mc, C, H, W) block whose rows g * n_mc + s are the samples of image g
+ *              (torch.split(x, n_mc) order).  dtype 0 f32, 1 f16, 2 bf16 (the codes of runia_mcd_reduce_rows), widened
+ *              exactly; all arithmetic in f32.
+ *   sn sc sh sw element strides (>= 0) of the row, class, h and w dimensions, shared by all blocks: NCHW, channels_last
+ *              (sc == 1) and sliced views are read in place.
+ *   outputs    f32 (G, H, W) contiguous, each may be NULL, at least one set:
+ *                pred_h    -sum_c pbar_c log pbar_c,  pbar = mean_s softmax_c(x_s)
+ *                mi        pred_h - mean_s(-sum_c p_sc log p_sc)        (n_mc == 1: exactly 0, or NaN)
+ *                msp       max_c pbar_c
+ *                energy    mean_s logsumexp_c x_sc                       (unflipped)
+ *                max_logit max_c mean_s x_sc
+ *                label     int32 argmax_c pbar_c, lowest index on ties
+ *                mean_probs  f32 (G, C, H, W) contiguous: pbar
+ *              The arithmetic is runia_mcd_uncertainty_f32's: 0 * log 0 is NaN as in the reference's torch expression (a
+ *              class more than ~104 below the maximum of a sample makes pred_h and mi of that pixel NaN); sums over classes
+ *              in ascending class order inside one lane: run-to-run bit identical, no atomics.
+ * One launch.  C <= 24 and no max_logit: logits and means in registers, every logit read once.  Otherwise two passes in the
+ * launch (row statistics, then the classes; the logits are re-read from the caches); the statistics live in LDS up to
+ * n_mc = 21 and beyond that in `workspace` (runia_pixel_maps_workspace_bytes, 0 when none is needed; 4-byte aligned;
+ * RUNIA_E_WORKSPACE if missing or short).  Four pixels per lane and load (16 bytes f32, 8 bytes f16 / bf16) when w has unit
+ * stride and the other strides and bases are multiples of four elements; element loads through the strides otherwise.
+ * G, C, H, W < 2^31, G * H * W < 2^39, n_mc <= 2^20; RUNIA_E_INVALID otherwise.  G == 0 or H * W == 0: 0, nothing launched.
+ *
+ * runia_pixel_map_reduce_f32: per image the mean, max and count of the pixels of map (G, HW) f32 whose `valid` byte is
+ *   non-zero (valid NULL: all) -> mean [G] f32, max [G] f32, count [G] int64 (each may be NULL, one set).  One workgroup
+ *   per image, f64 partial sums in a fixed order: deterministic.  No valid pixel: NaN, -inf, 0.  A NaN pixel makes the mean
+ *   NaN and is skipped by the max. */
+size_t runia_pixel_maps_workspace_bytes(int64_t G, int64_t C, int64_t H, int64_t W, int n_mc, int want_max_logit);
+int runia_pixel_uncertainty_maps(const void* const* table, int single, int dtype, int64_t G, int n_mc, int64_t C, int64_t H,
+                                 int64_t W, int64_t sn, int64_t sc, int64_t sh, int64_t sw, float* pred_h, float* mi,
+                                 float* msp, float* energy, float* max_logit, int32_t* label, float* mean_probs,
+                                 void* workspace, size_t workspace_bytes, runia_stream_t stream);
+int runia_pixel_map_reduce_f32(const float* map, const uint8_t* valid, int64_t G, int64_t HW, float* mean, float* max,
+                               int64_t* count, runia_stream_t stream);
 /* runia_tril_inverse_f64: inv [batch, D, D] = inverse of the lower-triangular factors tril [batch, D, D] (row-major f64; the strict
  *   upper triangle of inv is zero).  Setup of the class-wise Gaussians of GMMLatentSpace / DDU (inference/postprocessors.py:
  *   426-492, 694-786; torch.distributions.MultivariateNormal keeps scale_tril): the precision of a class is inv^T inv. */

@@ -274,6 +274,13 @@ _SIGNATURES = {
         [c_void_p, c_int64, c_void_p, c_int64, c_int64, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_uint64, c_int,
          c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p],
     ),
+    "runia_pixel_maps_workspace_bytes": (c_size_t, [c_int64, c_int64, c_int64, c_int64, c_int, c_int]),
+    "runia_pixel_uncertainty_maps": (
+        c_int,
+        [c_void_p, c_int, c_int, c_int64, c_int, c_int64, c_int64, c_int64, c_int64, c_int64, c_int64, c_int64, c_void_p,
+         c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p],
+    ),
+    "runia_pixel_map_reduce_f32": (c_int, [c_void_p, c_void_p, c_int64, c_int64, c_void_p, c_void_p, c_void_p, c_void_p]),
     "runia_pacmap_phase_weights": (c_int, [c_int, c_void_p]),
     "runia_pacmap_step_f32": (
         c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_int, c_int, c_float, c_void_p]),
@@ -1358,6 +1365,75 @@ def mcd_uncertainty(logits: torch.Tensor, n_mc: int, want_probs: bool = False):
     _check(lib.runia_mcd_uncertainty_f32(logits.data_ptr(), _ptr(probs), ph.data_ptr(), mi.data_ptr(), n, int(n_mc), c, _stream()),
            "runia_mcd_uncertainty_f32")
     return ph, mi, probs
+
+
+PIXEL_MAP_SCORES = ("pred_h", "mi", "msp", "energy", "max_logit")
+
+
+@_device_guard()
+def pixel_uncertainty_maps(passes, n_mc: int, scores=("pred_h", "mi"), want_label: bool = False,
+                           want_mean_probs: bool = False):
+    """Per-pixel maps of a segmentation head, one launch (``runia_pixel_uncertainty_maps``).  ``passes``: ONE device tensor
+    (G * n_mc, C, H, W) whose rows g * n_mc + s are the samples of image g, or a list / tuple of ``n_mc`` device tensors
+    (G, C, H, W) of one shape, dtype (f32 / f16 / bf16) and stride tuple; any strides, read in place.  Returns a dict with
+    the requested ``scores`` (f32 (G, H, W)) and, when asked for, ``"label"`` (int32 (G, H, W)) and ``"mean_probs"`` (f32
+    (G, C, H, W)).  ``0 * log 0`` is NaN as in ``mcd_uncertainty``."""
+    single = isinstance(passes, torch.Tensor)
+    first = passes if single else passes[0]
+    n_mc = int(n_mc)
+    assert all(s in PIXEL_MAP_SCORES for s in scores), f"scores must be among {PIXEL_MAP_SCORES}"
+    assert first.dim() == 4 and first.dtype in _MCD_DTYPES and first.is_cuda
+    if single:
+        assert first.shape[0] % n_mc == 0
+        g = first.shape[0] // n_mc
+    else:
+        assert len(passes) == n_mc and all(
+            t.is_cuda and t.device == first.device and t.shape == first.shape and t.dtype == first.dtype
+            and t.stride() == first.stride() for t in passes)
+        g = first.shape[0]
+    lib = load_library()
+    require_gpu()
+    _, c, h, w = (int(v) for v in first.shape)
+    dev = first.device
+    out = {s: torch.empty((g, h, w), dtype=torch.float32, device=dev) for s in scores}
+    if want_label:
+        out["label"] = torch.empty((g, h, w), dtype=torch.int32, device=dev)
+    if want_mean_probs:
+        out["mean_probs"] = torch.empty((g, c, h, w), dtype=torch.float32, device=dev)
+    if g == 0 or h * w == 0:
+        return out
+    assert out, "at least one map must be requested"
+    table = torch.tensor([first.data_ptr()] if single else [t.data_ptr() for t in passes], dtype=torch.int64).to(dev)
+    need = lib.runia_pixel_maps_workspace_bytes(g, c, h, w, n_mc, int("max_logit" in out))
+    ws = torch.empty((need // 4,), dtype=torch.float32, device=dev) if need else None
+    sn, sc, sh, sw = (int(v) for v in first.stride())
+    _check(lib.runia_pixel_uncertainty_maps(
+        table.data_ptr(), int(single), _MCD_DTYPES[first.dtype], g, n_mc, c, h, w, sn, sc, sh, sw,
+        _ptr(out.get("pred_h")), _ptr(out.get("mi")), _ptr(out.get("msp")), _ptr(out.get("energy")),
+        _ptr(out.get("max_logit")), _ptr(out.get("label")), _ptr(out.get("mean_probs")), _ptr(ws), need, _stream()),
+        "runia_pixel_uncertainty_maps")
+    return out
+
+
+@_device_guard()
+def pixel_map_reduce(score_map: torch.Tensor, valid: Optional[torch.Tensor] = None):
+    """Per-image (mean, max, count) of a (G, H, W) f32 device map under an optional (G, H, W) bool / uint8 validity mask ->
+    (f32 (G,), f32 (G,), int64 (G,)); deterministic.  An image without a valid pixel gives (NaN, -inf, 0)."""
+    assert score_map.is_cuda and score_map.dtype == torch.float32 and score_map.dim() == 3
+    lib = load_library()
+    require_gpu()
+    m = score_map.contiguous()
+    g, hw = int(m.shape[0]), int(m.shape[1] * m.shape[2])
+    v = None
+    if valid is not None:
+        assert tuple(valid.shape) == tuple(m.shape) and valid.dtype in (torch.bool, torch.uint8)
+        v = valid.to(m.device).contiguous().view(torch.uint8)
+    mean = torch.empty((g,), dtype=torch.float32, device=m.device)
+    mx = torch.empty((g,), dtype=torch.float32, device=m.device)
+    cnt = torch.empty((g,), dtype=torch.int64, device=m.device)
+    _check(lib.runia_pixel_map_reduce_f32(m.data_ptr(), _ptr(v), g, hw, mean.data_ptr(), mx.data_ptr(), cnt.data_ptr(),
+                                          _stream()), "runia_pixel_map_reduce_f32")
+    return mean, mx, cnt
 
 
 @_device_guard()

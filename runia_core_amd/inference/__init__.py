@@ -24,6 +24,12 @@ from .funcs import (  # noqa: F401
 from .image_level import LaRDInference, LaRExInference  # noqa: F401
 from .object_level import BoxInferenceYolo, ObjectLevelInference  # noqa: F401
 from .pipeline import LaREMPipeline  # noqa: F401
+from .pixel_level import (  # noqa: F401
+    get_pixel_mcd_uncertainty_maps,
+    image_scores_from_maps,
+    pixel_ood_metrics,
+    pixel_uncertainty_maps,
+)
 from .postprocessors import (  # noqa: F401
     ASH,
     DDU,

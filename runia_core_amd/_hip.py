@@ -449,6 +449,10 @@ def _stream() -> int:
     return torch.cuda.current_stream().cuda_stream
 
 
+# element dtype of a tensor read in place -> the `dtype` code of the C ABI (csrc/elem.hpp)
+ELEM_DTYPE_CODES = {torch.float32: 0, torch.float16: 1, torch.bfloat16: 2}
+
+
 def _ptr(t: Optional[torch.Tensor]) -> Optional[int]:
     return None if t is None else t.data_ptr()
 
@@ -650,7 +654,6 @@ def map_reduce(x: torch.Tensor, h: int, w: int, mode: str) -> torch.Tensor:
 
 
 _MCD_MODES = {"fullmean": 0, "mean": 1, "avgpool": 2, "copy": 3}
-_MCD_DTYPES = {torch.float32: 0, torch.float16: 1, torch.bfloat16: 2}
 
 
 def mcd_row_width(shape, mode: str, avg_pooling_parameters=None) -> int:
@@ -682,7 +685,7 @@ def mcd_reduce_rows(x: torch.Tensor, table: torch.Tensor, mode: str, row0: int =
     launch on the current stream; the other rows and the columns from D on keep their contents.  Returns ``table``."""
     # shapes and dtypes first, then the devices: every refusal comes before the library is touched
     assert isinstance(x, torch.Tensor) and isinstance(table, torch.Tensor)
-    assert x.dtype in _MCD_DTYPES, f"unsupported activation dtype {x.dtype} (float32, float16, bfloat16)"
+    assert x.dtype in ELEM_DTYPE_CODES, f"unsupported activation dtype {x.dtype} (float32, float16, bfloat16)"
     assert table.dtype == torch.float32 and table.dim() == 2 and (table.shape[0] <= 1 or table.stride(0) >= table.shape[1]) \
         and (table.shape[1] <= 1 or table.stride(1) == 1), "the table must be a row-major float32 matrix"
     d = mcd_row_width(x.shape, mode, avg_pooling_parameters)
@@ -701,7 +704,7 @@ def mcd_reduce_rows(x: torch.Tensor, table: torch.Tensor, mode: str, row0: int =
         x = x[:, :, None, None]
     k, st, p = (int(v) for v in avg_pooling_parameters) if mode == "avgpool" else (0, 0, 0)
     ld = int(table.stride(0)) if table.shape[0] > 1 else max(int(table.stride(0)), int(table.shape[1]))
-    _check(lib.runia_mcd_reduce_rows(x.data_ptr(), _MCD_DTYPES[x.dtype], b, x.shape[1], x.shape[2], x.shape[3],
+    _check(lib.runia_mcd_reduce_rows(x.data_ptr(), ELEM_DTYPE_CODES[x.dtype], b, x.shape[1], x.shape[2], x.shape[3],
                                      x.stride(0), x.stride(1), x.stride(2), x.stride(3), _MCD_MODES[mode], k, st, p,
                                      table.data_ptr(), table.shape[0], ld, row0, row_step, _stream()),
            "runia_mcd_reduce_rows")
@@ -723,7 +726,7 @@ def ragged_rows(tensors, mode: str = "copy", out: Optional[torch.Tensor] = None,
     assert len(tensors) > 0 or out is not None, "an empty list needs an output table to tell width, dtype and device"
     first = tensors[0] if tensors else out
     dtype, dev = first.dtype, first.device
-    assert dtype in _MCD_DTYPES, f"unsupported dtype {dtype} (float32, float16, bfloat16)"
+    assert dtype in ELEM_DTYPE_CODES, f"unsupported dtype {dtype} (float32, float16, bfloat16)"
     d = int(first.shape[1]) if tensors else int(out.shape[1])
     # shapes and dtypes first, then the devices: every refusal comes before the library is touched
     for i, t in enumerate(tensors):
@@ -750,7 +753,7 @@ def ragged_rows(tensors, mode: str = "copy", out: Optional[torch.Tensor] = None,
         packed = np.concatenate([desc[:n, :4].reshape(-1), desc[:, 4]])
         up = torch.from_numpy(packed).to(dev, non_blocking=False)
         ld = int(out.stride(0)) if total > 1 else max(int(out.stride(0)), int(out.shape[1]))
-        _check(lib.runia_ragged_rows(up.data_ptr(), up.data_ptr() + 32 * n, n, total, d, _MCD_DTYPES[dtype],
+        _check(lib.runia_ragged_rows(up.data_ptr(), up.data_ptr() + 32 * n, n, total, d, ELEM_DTYPE_CODES[dtype],
                                      _RAGGED_MODES[mode], out.data_ptr(), ld, _ptr(seg), _stream()), "runia_ragged_rows")
     return (out, seg) if return_segments else out
 
@@ -1382,7 +1385,7 @@ def pixel_uncertainty_maps(passes, n_mc: int, scores=("pred_h", "mi"), want_labe
     first = passes if single else passes[0]
     n_mc = int(n_mc)
     assert all(s in PIXEL_MAP_SCORES for s in scores), f"scores must be among {PIXEL_MAP_SCORES}"
-    assert first.dim() == 4 and first.dtype in _MCD_DTYPES and first.is_cuda
+    assert first.dim() == 4 and first.dtype in ELEM_DTYPE_CODES and first.is_cuda
     if single:
         assert first.shape[0] % n_mc == 0
         g = first.shape[0] // n_mc
@@ -1408,7 +1411,7 @@ def pixel_uncertainty_maps(passes, n_mc: int, scores=("pred_h", "mi"), want_labe
     ws = torch.empty((need // 4,), dtype=torch.float32, device=dev) if need else None
     sn, sc, sh, sw = (int(v) for v in first.stride())
     _check(lib.runia_pixel_uncertainty_maps(
-        table.data_ptr(), int(single), _MCD_DTYPES[first.dtype], g, n_mc, c, h, w, sn, sc, sh, sw,
+        table.data_ptr(), int(single), ELEM_DTYPE_CODES[first.dtype], g, n_mc, c, h, w, sn, sc, sh, sw,
         _ptr(out.get("pred_h")), _ptr(out.get("mi")), _ptr(out.get("msp")), _ptr(out.get("energy")),
         _ptr(out.get("max_logit")), _ptr(out.get("label")), _ptr(out.get("mean_probs")), _ptr(ws), need, _stream()),
         "runia_pixel_uncertainty_maps")
@@ -1600,7 +1603,6 @@ def centred_gram(e: torch.Tensor, denom: float) -> torch.Tensor:
     return g
 
 
-_EIGEN_DTYPES = {torch.float32: 0, torch.float16: 1, torch.bfloat16: 2}
 EIGEN_SCORE_MAX_K = 64
 
 
@@ -1613,7 +1615,7 @@ def eigen_scores(e: torch.Tensor, k: int, alpha: float = 1e-3) -> torch.Tensor:
     lib = load_library()
     if not isinstance(e, torch.Tensor) or e.dim() != 2:
         raise ValueError("eigen_scores takes a 2-D (G * k, hidden) tensor")
-    if e.dtype not in _EIGEN_DTYPES:
+    if e.dtype not in ELEM_DTYPE_CODES:
         raise TypeError(f"eigen_scores takes float32, float16 or bfloat16 rows, not {e.dtype}")
     n, h = (int(v) for v in e.shape)
     k = int(k)
@@ -1629,7 +1631,7 @@ def eigen_scores(e: torch.Tensor, k: int, alpha: float = 1e-3) -> torch.Tensor:
     elif h > 1 and x.stride(1) != 1:
         x = x.contiguous()
     out = torch.empty(n // k, dtype=torch.float64, device=x.device)
-    _check(lib.runia_eigen_score_batch(x.data_ptr(), _EIGEN_DTYPES[x.dtype], n // k, k, h, x.stride(0), float(alpha),
+    _check(lib.runia_eigen_score_batch(x.data_ptr(), ELEM_DTYPE_CODES[x.dtype], n // k, k, h, x.stride(0), float(alpha),
                                        out.data_ptr(), _stream()), "runia_eigen_score_batch")
     return out.cpu() if on_host else out
 

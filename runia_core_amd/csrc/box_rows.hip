@@ -11,33 +11,9 @@
 // segment (transposed or sliced views, an odd leading dimension), and the last partial vector of a row, moves element
 // by element through the tensor's own strides.  Plain vector stores only.
 #include "common.hpp"
+#include "elem.hpp"
 
 namespace {
-
-struct F32 { typedef float elem; static constexpr int V = 4; };
-struct F16 { typedef uint16_t elem; static constexpr int V = 8; };
-struct BF16 { typedef uint16_t elem; static constexpr int V = 8; };
-
-__device__ __forceinline__ float widen(F32, float v) { return v; }
-__device__ __forceinline__ float widen(F16, uint16_t v) {
-  _Float16 h;
-  __builtin_memcpy(&h, &v, 2);
-  return (float)h;
-}
-__device__ __forceinline__ float widen(BF16, uint16_t v) { return __uint_as_float((uint32_t)v << 16); }
-
-__device__ __forceinline__ float narrow(F32, float f) { return f; }
-__device__ __forceinline__ uint16_t narrow(F16, float f) {  // round to nearest even (v_cvt_f16_f32)
-  const _Float16 h = (_Float16)f;
-  uint16_t v;
-  __builtin_memcpy(&v, &h, 2);
-  return v;
-}
-__device__ __forceinline__ uint16_t narrow(BF16, float f) {  // round to nearest even; NaN -> the quiet NaN torch writes
-  const uint32_t u = __float_as_uint(f);
-  if (f != f) return 0x7fc0;
-  return (uint16_t)((u + 0x7fffu + ((u >> 16) & 1u)) >> 16);
-}
 
 // torch.log(x + 1e-10) on a tensor of T: the sum is formed in f32 and rounded to T, the logarithm is taken in f32 and
 // rounded to T (an f16 zero stays zero: 1e-10 is below half of the smallest f16 denormal -> -inf, as torch gives)
@@ -131,13 +107,12 @@ int launch(const int64_t* table, const int64_t* start, int64_t n_seg, int64_t to
 
 extern "C" int runia_ragged_rows(const int64_t* table, const int64_t* row_start, int64_t n_seg, int64_t total, int64_t D,
                                  int dtype, int mode, void* out, int64_t ld, int32_t* seg_of_row, runia_stream_t stream) {
-  if (n_seg < 0 || total < 0 || D <= 0 || dtype < 0 || dtype > 2 || (mode != RUNIA_RAGGED_COPY && mode != RUNIA_RAGGED_LOG_EPS) ||
-      ld < D || n_seg > 0x7fffffffll)
+  if (n_seg < 0 || total < 0 || D <= 0 || !elem_dtype_ok(dtype) ||
+      (mode != RUNIA_RAGGED_COPY && mode != RUNIA_RAGGED_LOG_EPS) || ld < D || n_seg > 0x7fffffffll)
     return RUNIA_E_INVALID;
   if (total == 0 || n_seg == 0) return RUNIA_OK;
   if (!table || !row_start || !out) return RUNIA_E_INVALID;
-  hipStream_t s = as_stream(stream);
-  if (dtype == 0) return launch<F32>(table, row_start, n_seg, total, D, mode, out, ld, seg_of_row, s);
-  if (dtype == 1) return launch<F16>(table, row_start, n_seg, total, D, mode, out, ld, seg_of_row, s);
-  return launch<BF16>(table, row_start, n_seg, total, D, mode, out, ld, seg_of_row, s);
+  return dispatch_elem(dtype, [&](auto t) {
+    return launch<decltype(t)>(table, row_start, n_seg, total, D, mode, out, ld, seg_of_row, as_stream(stream));
+  });
 }

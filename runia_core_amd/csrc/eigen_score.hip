@@ -24,26 +24,14 @@
 #include <math.h>
 
 #include "common.hpp"
+#include "elem.hpp"
 
 namespace {
-
-enum { kF32 = 0, kF16 = 1, kBF16 = 2 };  // llm_uncertainty/rauq.py _DTYPE_CODES
 
 constexpr int kThreads = 256;
 constexpr int kMaxK = 64;
 constexpr int kHalf = 4096;  // doubles per LDS half: kMaxK x kMaxK, and the staged chunk
 constexpr int kMaxSweeps = 30;
-
-template <int DT>
-__device__ __forceinline__ double load_wide(const void* base, int64_t i) {
-  if constexpr (DT == kF32) {
-    return (double)reinterpret_cast<const float*>(base)[i];
-  } else {
-    const unsigned short h = reinterpret_cast<const unsigned short*>(base)[i];
-    if constexpr (DT == kF16) return (double)(float)__builtin_bit_cast(_Float16, h);
-    else return (double)__uint_as_float((unsigned)h << 16);
-  }
-}
 
 // pair j (0 <= j < m/2) of round t (0 <= t < m-1) of the circle method on m (even) players (eigh.hip tournament_pair)
 __device__ __forceinline__ void tournament_pair(int m, int t, int j, int& p, int& q) {
@@ -57,7 +45,7 @@ __device__ __forceinline__ void tournament_pair(int m, int t, int j, int& p, int
   if (p > q) { const int s = p; p = q; q = s; }
 }
 
-template <int DT>
+template <class T>
 __global__ __launch_bounds__(kThreads) void eigen_score_kernel(const void* __restrict__ e, int k, int64_t hidden,
                                                               int64_t row_stride, double alpha, double* __restrict__ out) {
   __shared__ double lds[2 * kHalf];
@@ -65,7 +53,8 @@ __global__ __launch_bounds__(kThreads) void eigen_score_kernel(const void* __res
   double* G = lds + kHalf;     // [k, k] row-major
   const int tid = threadIdx.x;
   const int64_t g = blockIdx.x;
-  const char* rows = reinterpret_cast<const char*>(e) + g * k * row_stride * (DT == kF32 ? 4 : 2);
+  const char* group = reinterpret_cast<const char*>(e) + g * k * row_stride * T::kBytes;
+  const typename T::elem* rows = reinterpret_cast<const typename T::elem*>(group);
 
   // ---- Gram matrix ----------------------------------------------------------------------------------------------------
   const int kb = (k + 3) / 4, kpad = 4 * kb;
@@ -87,7 +76,7 @@ __global__ __launch_bounds__(kThreads) void eigen_score_kernel(const void* __res
     const int w = (int)min((int64_t)C, hidden - h0);
     for (int idx = tid; idx < k * w; idx += kThreads) {
       const int r = idx / w, c = idx - r * w;
-      stage[r * C + c] = load_wide<DT>(rows, (int64_t)r * row_stride + h0 + c);
+      stage[r * C + c] = (double)ld1<T>(rows + (int64_t)r * row_stride + h0 + c);
     }
     __syncthreads();
     // centre every column by its mean over the k rows; padding rows (k .. kpad-1) only feed entries that are dropped
@@ -246,14 +235,12 @@ __global__ __launch_bounds__(kThreads) void eigen_score_kernel(const void* __res
 
 extern "C" int runia_eigen_score_batch(const void* e, int dtype_code, int64_t groups, int64_t k, int64_t hidden,
                                        int64_t row_stride, double alpha, double* out, runia_stream_t stream) {
-  if (!e || !out || groups <= 0 || groups > 0x7fffffffll || k < 2 || k > kMaxK || hidden <= 0 || row_stride < 0)
+  if (!e || !out || groups <= 0 || groups > 0x7fffffffll || k < 2 || k > kMaxK || hidden <= 0 || row_stride < 0 ||
+      !elem_dtype_ok(dtype_code))
     return RUNIA_E_INVALID;
   hipStream_t s = as_stream(stream);
-  switch (dtype_code) {
-    case kF32: eigen_score_kernel<kF32><<<(unsigned)groups, kThreads, 0, s>>>(e, (int)k, hidden, row_stride, alpha, out); break;
-    case kF16: eigen_score_kernel<kF16><<<(unsigned)groups, kThreads, 0, s>>>(e, (int)k, hidden, row_stride, alpha, out); break;
-    case kBF16: eigen_score_kernel<kBF16><<<(unsigned)groups, kThreads, 0, s>>>(e, (int)k, hidden, row_stride, alpha, out); break;
-    default: return RUNIA_E_INVALID;
-  }
+  dispatch_elem(dtype_code, [&](auto t) {
+    eigen_score_kernel<decltype(t)><<<(unsigned)groups, kThreads, 0, s>>>(e, (int)k, hidden, row_stride, alpha, out);
+  });
   return runia_check_launch();
 }

@@ -27,10 +27,9 @@
 // division by log V at V = 128 256) and is dropped here.  A row that holds NaN or +inf, or only -inf, gives NaN in
 // all three outputs, as torch's softmax does; a token whose logit is -inf gets log_prob = -inf exactly.
 #include "common.hpp"
+#include "elem.hpp"
 
 namespace {
-
-enum { kF32 = 0, kF16 = 1, kBF16 = 2 };  // llm_uncertainty/rauq.py _DTYPE_CODES
 
 constexpr int kChunk = 4096;  // logits per partial: 256 lanes x 16
 constexpr int kThreads = 256;
@@ -45,43 +44,25 @@ struct Partial {  // 16 bytes, one per (row, chunk) in the workspace
   int bad;
 };
 
-template <int DT> struct Elem;
-template <> struct Elem<kF32> { static constexpr int kSize = 4; };
-template <> struct Elem<kF16> { static constexpr int kSize = 2; };
-template <> struct Elem<kBF16> { static constexpr int kSize = 2; };
-
-template <int DT>
-__device__ __forceinline__ float widen(unsigned short h) {
-  if constexpr (DT == kF16) return (float)__builtin_bit_cast(_Float16, h);
-  else return __uint_as_float((unsigned)h << 16);
+// row b of a step (rows are addressed in bytes: `aligned` below is a property of the address), and element j of a row
+template <class T>
+__device__ __forceinline__ const char* step_row(const StepDesc& sd, int64_t b) {
+  return reinterpret_cast<const char*>(sd.ptr) + b * sd.row_stride * T::kBytes;
+}
+template <class T>
+__device__ __forceinline__ const typename T::elem* elem_at(const char* row, int64_t j) {
+  return reinterpret_cast<const typename T::elem*>(row) + j;
 }
 
-template <int DT>
-__device__ __forceinline__ float load_one(const char* row, int64_t j) {
-  if constexpr (DT == kF32) return reinterpret_cast<const float*>(row)[j];
-  else return widen<DT>(reinterpret_cast<const unsigned short*>(row)[j]);
-}
-
-// W = 16 / element size consecutive logits from element j: one 16-byte load when the row is 16-byte aligned and all W lie
-// inside the row, element loads otherwise (-inf past V)
-template <int DT>
+// T::V consecutive logits from element j: one 16-byte load when the row is 16-byte aligned and all of them lie inside the
+// row, element loads otherwise (-inf past V)
+template <class T>
 __device__ __forceinline__ void load_vec(const char* row, int64_t j, int64_t V, bool aligned, float* out) {
-  constexpr int W = 16 / Elem<DT>::kSize;
-  if (aligned && j + W <= V) {
-    const uint4 q = *reinterpret_cast<const uint4*>(row + j * Elem<DT>::kSize);
-    if constexpr (DT == kF32) {
-      out[0] = __uint_as_float(q.x); out[1] = __uint_as_float(q.y); out[2] = __uint_as_float(q.z); out[3] = __uint_as_float(q.w);
-    } else {
-      const unsigned w[4] = {q.x, q.y, q.z, q.w};
-#pragma unroll
-      for (int k = 0; k < 4; ++k) {
-        out[2 * k] = widen<DT>((unsigned short)(w[k] & 0xffffu));
-        out[2 * k + 1] = widen<DT>((unsigned short)(w[k] >> 16));
-      }
-    }
+  if (aligned && j + T::V <= V) {
+    ld16<T>(elem_at<T>(row, j), out);
   } else {
 #pragma unroll
-    for (int e = 0; e < W; ++e) out[e] = j + e < V ? load_one<DT>(row, j + e) : -__builtin_inff();
+    for (int e = 0; e < T::V; ++e) out[e] = j + e < V ? ld1<T>(elem_at<T>(row, j + e)) : -__builtin_inff();
   }
 }
 
@@ -110,23 +91,23 @@ __device__ __forceinline__ Partial shfl_xor_partial(const Partial& p, int o) {
 
 // ---- partial -----------------------------------------------------------------------------------------------------------
 // block = (row r = t * B + b, chunk c); lane i holds elements c*kChunk + (k*256 + i)*W + e of the row, k < kPerLane / W
-template <int DT>
+template <class T>
 __global__ __launch_bounds__(kThreads) void partial_kernel(const StepDesc* __restrict__ tab, int64_t B, int64_t V, int nc,
                                                            Partial* __restrict__ part) {
-  constexpr int W = 16 / Elem<DT>::kSize;
+  constexpr int W = T::V;
   const int64_t blk = blockIdx.x;
   const int64_t r = blk / nc;
   const int c = (int)(blk - r * nc);
   const int64_t t = r / B, b = r - t * B;
   const StepDesc sd = tab[t];
-  const char* row = reinterpret_cast<const char*>(sd.ptr) + b * sd.row_stride * Elem<DT>::kSize;
+  const char* row = step_row<T>(sd, b);
   const bool aligned = (reinterpret_cast<uintptr_t>(row) & 15) == 0;
   const int lane = threadIdx.x;
   const int64_t c0 = (int64_t)c * kChunk;
 
   float x[kPerLane];
 #pragma unroll
-  for (int k = 0; k < kPerLane / W; ++k) load_vec<DT>(row, c0 + ((int64_t)k * kThreads + lane) * W, V, aligned, x + k * W);
+  for (int k = 0; k < kPerLane / W; ++k) load_vec<T>(row, c0 + ((int64_t)k * kThreads + lane) * W, V, aligned, x + k * W);
 
   float m = -__builtin_inff();
   int bad = 0;
@@ -173,13 +154,14 @@ __global__ __launch_bounds__(kThreads) void partial_kernel(const StepDesc* __res
 }
 
 // ---- finish ------------------------------------------------------------------------------------------------------------
-template <int DT>
-__global__ __launch_bounds__(256) void finish_kernel(const StepDesc* __restrict__ tab, int64_t B, int64_t T, int64_t V, int nc,
-                                                     const Partial* __restrict__ part, const int64_t* __restrict__ tokens,
-                                                     int64_t token_stride, int normalize, float* __restrict__ lse,
-                                                     float* __restrict__ log_prob, float* __restrict__ entropy) {
+template <class T>
+__global__ __launch_bounds__(256) void finish_kernel(const StepDesc* __restrict__ tab, int64_t B, int64_t n_steps, int64_t V,
+                                                     int nc, const Partial* __restrict__ part,
+                                                     const int64_t* __restrict__ tokens, int64_t token_stride, int normalize,
+                                                     float* __restrict__ lse, float* __restrict__ log_prob,
+                                                     float* __restrict__ entropy) {
   const int64_t r = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;  // t * B + b
-  if (r >= B * T) return;
+  if (r >= B * n_steps) return;
   const int64_t t = r / B, b = r - t * B;
   double m = -__builtin_inf(), s = 0.0, u = 0.0;
   int bad = 0;
@@ -188,13 +170,11 @@ __global__ __launch_bounds__(256) void finish_kernel(const StepDesc* __restrict_
   const bool nan_row = bad || !(m > -__builtin_inf());
   const double l1p = log1p(s);
   const double row_lse = nan_row ? __builtin_nan("") : m + l1p;
-  const int64_t o = b * T + t;
+  const int64_t o = b * n_steps + t;
   if (lse) lse[o] = (float)row_lse;
   if (entropy) entropy[o] = nan_row ? __builtin_nanf("") : (float)((l1p + u / (1.0 + s)) / log((double)V));
   if (log_prob) {
-    const StepDesc sd = tab[t];
-    const char* row = reinterpret_cast<const char*>(sd.ptr) + b * sd.row_stride * Elem<DT>::kSize;
-    const float xt = load_one<DT>(row, tokens[b * token_stride + t]);
+    const float xt = ld1<T>(elem_at<T>(step_row<T>(tab[t], b), tokens[b * token_stride + t]));
     // (x - m) - log1p(s'), not x - lse: m + log1p(s') drops the log term in f64 once |m| passes 2^53 (bf16 1e30)
     // x = -inf stays -inf exactly; a NaN row gives NaN whatever the token
     log_prob[o] = !normalize ? xt : nan_row ? __builtin_nanf("") : (float)(((double)xt - m) - l1p);
@@ -238,16 +218,6 @@ __global__ __launch_bounds__(1024) void sequence_kernel(const float* __restrict_
 
 int64_t n_chunks(int64_t V) { return (V + kChunk - 1) / kChunk; }
 
-template <class F>
-int dispatch_dtype(int dtype, F f) {
-  switch (dtype) {
-    case kF32: f(std::integral_constant<int, kF32>{}); break;
-    case kF16: f(std::integral_constant<int, kF16>{}); break;
-    default: f(std::integral_constant<int, kBF16>{}); break;
-  }
-  return runia_check_launch();
-}
-
 constexpr int64_t kMaxRows = 1ll << 26;  // B * n_steps
 constexpr int64_t kMaxV = 1ll << 28;
 
@@ -266,7 +236,7 @@ extern "C" size_t runia_logit_stats_workspace_bytes(int64_t n_steps, int64_t B, 
 extern "C" int runia_logit_stats(const void* table, int dtype, int64_t n_steps, int64_t B, int64_t V, const int64_t* tokens,
                                  int64_t token_stride, int normalize, float* lse, float* log_prob, float* entropy,
                                  double* seq, void* workspace, size_t workspace_bytes, runia_stream_t stream) {
-  if (!table || dtype < kF32 || dtype > kBF16 || !dims_ok(n_steps, B, V)) return RUNIA_E_INVALID;
+  if (!table || !elem_dtype_ok(dtype) || !dims_ok(n_steps, B, V)) return RUNIA_E_INVALID;
   if (!lse && !log_prob && !entropy && !seq) return RUNIA_E_INVALID;
   if (log_prob && (!tokens || (B > 1 && token_stride < n_steps))) return RUNIA_E_INVALID;
   if (seq && (!log_prob || !entropy)) return RUNIA_E_INVALID;
@@ -277,12 +247,13 @@ extern "C" int runia_logit_stats(const void* table, int dtype, int64_t n_steps, 
   const StepDesc* tab = reinterpret_cast<const StepDesc*>(table);
   Partial* part = reinterpret_cast<Partial*>(workspace);
   const hipStream_t s = as_stream(stream);
-  const int rc = dispatch_dtype(dtype, [&](auto dt) {
-    constexpr int DT = decltype(dt)::value;
-    partial_kernel<DT><<<(unsigned)(rows * nc), kThreads, 0, s>>>(tab, B, V, nc, part);
-    finish_kernel<DT><<<(unsigned)((rows + 255) / 256), 256, 0, s>>>(tab, B, n_steps, V, nc, part, tokens, token_stride,
+  dispatch_elem(dtype, [&](auto t) {
+    typedef decltype(t) T;
+    partial_kernel<T><<<(unsigned)(rows * nc), kThreads, 0, s>>>(tab, B, V, nc, part);
+    finish_kernel<T><<<(unsigned)((rows + 255) / 256), 256, 0, s>>>(tab, B, n_steps, V, nc, part, tokens, token_stride,
                                                                      normalize, lse, log_prob, entropy);
   });
+  const int rc = runia_check_launch();
   if (rc != RUNIA_OK || !seq) return rc;
   sequence_kernel<<<1, 1024, 0, s>>>(log_prob, entropy, B, n_steps, seq);
   return runia_check_launch();

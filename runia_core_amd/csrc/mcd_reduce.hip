@@ -18,6 +18,7 @@
 //   anything else:  mcd_elem_kernel, one thread per output value, scalar loads, any strides.
 // f32 accumulation; f16 / bf16 are widened exactly.  Plain stores (and float atomics in the split case) only.
 #include "common.hpp"
+#include "elem.hpp"
 
 namespace {
 
@@ -30,38 +31,6 @@ struct McdArgs {
   int kh, kw, sth, stw, ph, pw, OH, OW;
   float div;  // kh * kw
 };
-
-struct F32 { typedef float elem; static constexpr int V = 4; };
-struct F16 { typedef uint16_t elem; static constexpr int V = 8; };
-struct BF16 { typedef uint16_t elem; static constexpr int V = 8; };
-
-__device__ __forceinline__ float widen(F32, float v) { return v; }
-__device__ __forceinline__ float widen(F16, uint16_t v) {
-  _Float16 h;
-  __builtin_memcpy(&h, &v, 2);
-  return (float)h;
-}
-__device__ __forceinline__ float widen(BF16, uint16_t v) { return __uint_as_float((uint32_t)v << 16); }
-
-template <class T>
-__device__ __forceinline__ float ld1(const typename T::elem* p) { return widen(T{}, *p); }
-
-// 16 aligned bytes -> T::V floats
-template <class T>
-__device__ __forceinline__ void ld16(const typename T::elem* p, float (&v)[T::V]) {
-  const uint4 r = *reinterpret_cast<const uint4*>(p);
-  const uint32_t w[4] = {r.x, r.y, r.z, r.w};
-  if constexpr (T::V == 4) {
-#pragma unroll
-    for (int j = 0; j < 4; ++j) v[j] = __uint_as_float(w[j]);
-  } else {
-#pragma unroll
-    for (int j = 0; j < 4; ++j) {
-      v[2 * j] = widen(T{}, (uint16_t)(w[j] & 0xffffu));
-      v[2 * j + 1] = widen(T{}, (uint16_t)(w[j] >> 16));
-    }
-  }
-}
 
 template <class T>
 __device__ __forceinline__ float sum16(const typename T::elem* p) {
@@ -367,7 +336,7 @@ extern "C" int runia_mcd_reduce_rows(const void* x, int dtype, int64_t B, int64_
                                      float* table, int64_t table_rows, int64_t ld, int64_t row0, int64_t row_step,
                                      runia_stream_t stream) {
   const int64_t lim = 0x7fffffffll;
-  if (B < 0 || C <= 0 || H <= 0 || W <= 0 || B > lim || C > lim || H > lim || W > lim || dtype < 0 || dtype > 2 ||
+  if (B < 0 || C <= 0 || H <= 0 || W <= 0 || B > lim || C > lim || H > lim || W > lim || !elem_dtype_ok(dtype) ||
       sb < 0 || sc < 0 || sh < 0 || sw < 0 || table_rows < 0 || ld < 0 || row0 < 0 || row_step < 0)
     return RUNIA_E_INVALID;
   McdArgs a;
@@ -395,8 +364,5 @@ extern "C" int runia_mcd_reduce_rows(const void* x, int dtype, int64_t B, int64_
   if (D > lim * 64) return RUNIA_E_INVALID;
   if (B == 0) return RUNIA_OK;
   if (!x || !table || ld < D || (B > 1 && row_step < 1) || row0 + (B - 1) * row_step >= table_rows) return RUNIA_E_INVALID;
-  hipStream_t s = as_stream(stream);
-  if (dtype == 0) return launch<F32>(a, s);
-  if (dtype == 1) return launch<F16>(a, s);
-  return launch<BF16>(a, s);
+  return dispatch_elem(dtype, [&](auto t) { return launch<decltype(t)>(a, as_stream(stream)); });
 }

@@ -27,24 +27,13 @@
 // by the end of a row, an odd base or any other stride pattern (channels_last: sc == 1; crops) is read element by element
 // through the strides, in place.  Rows that follow one another in memory (sh == W * sw) are treated as one long row.
 #include "common.hpp"
+#include "elem.hpp"
 
 namespace {
 
 constexpr int kPix = 4;        // pixels per lane of the vector variants
 constexpr int kRegC = 24;      // widest head of the register kernel
 constexpr int kLdsBytes = 64 * 1024;
-
-struct F32 { typedef float elem; };
-struct F16 { typedef uint16_t elem; };
-struct BF16 { typedef uint16_t elem; };
-
-__device__ __forceinline__ float widen(F32, float v) { return v; }
-__device__ __forceinline__ float widen(F16, uint16_t v) {
-  _Float16 h;
-  __builtin_memcpy(&h, &v, 2);
-  return (float)h;
-}
-__device__ __forceinline__ float widen(BF16, uint16_t v) { return __uint_as_float((uint32_t)v << 16); }
 
 struct PixArgs {
   const void* const* ptrs;  // n_mc bases of (G, C, H, W) blocks, or one base of (G * n_mc, C, H, W) when `single`
@@ -80,16 +69,8 @@ template <class T, int PPL, bool VEC>
 __device__ __forceinline__ void load_px(const typename T::elem* p, int64_t sw, int nv, float (&v)[PPL]) {
   if constexpr (VEC) {
     static_assert(PPL == 4, "vector loads are four pixels wide");
-    if constexpr (sizeof(typename T::elem) == 4) {
-      const float4 r = *reinterpret_cast<const float4*>(p);
-      v[0] = r.x; v[1] = r.y; v[2] = r.z; v[3] = r.w;
-    } else {
-      const uint2 r = *reinterpret_cast<const uint2*>(p);
-      v[0] = widen(T{}, (uint16_t)(r.x & 0xffffu));
-      v[1] = widen(T{}, (uint16_t)(r.x >> 16));
-      v[2] = widen(T{}, (uint16_t)(r.y & 0xffffu));
-      v[3] = widen(T{}, (uint16_t)(r.y >> 16));
-    }
+    if constexpr (T::kBytes == 4) ld16<T>(p, v);
+    else ld8<T>(p, v);
   } else {
 #pragma unroll
     for (int j = 0; j < PPL; ++j) {
@@ -431,7 +412,7 @@ extern "C" int runia_pixel_uncertainty_maps(const void* const* table, int single
                                             float* mean_probs, void* workspace, size_t workspace_bytes,
                                             runia_stream_t stream) {
   const int64_t lim = 0x7fffffffll;
-  if (G < 0 || C < 1 || H < 0 || W < 0 || n_mc < 1 || G > lim || C > lim || H > lim || W > lim || dtype < 0 || dtype > 2 ||
+  if (G < 0 || C < 1 || H < 0 || W < 0 || n_mc < 1 || G > lim || C > lim || H > lim || W > lim || !elem_dtype_ok(dtype) ||
       sn < 0 || sc < 0 || sh < 0 || sw < 0 || (single != 0 && single != 1))
     return RUNIA_E_INVALID;
   if (G == 0 || H * W == 0) return RUNIA_OK;
@@ -458,11 +439,10 @@ extern "C" int runia_pixel_uncertainty_maps(const void* const* table, int single
   a.items = G * a.Hr * a.GW;
   const bool two_pass = two_pass_needed(C, max_logit != nullptr);
   hipStream_t s = as_stream(stream);
-#define RUNIA_PIX_DISPATCH(T) (a.vec ? launch_ppl<T, kPix>(a, two_pass, s) : launch_ppl<T, 1>(a, two_pass, s))
-  if (dtype == 0) return RUNIA_PIX_DISPATCH(F32);
-  if (dtype == 1) return RUNIA_PIX_DISPATCH(F16);
-  return RUNIA_PIX_DISPATCH(BF16);
-#undef RUNIA_PIX_DISPATCH
+  return dispatch_elem(dtype, [&](auto t) {
+    typedef decltype(t) T;
+    return a.vec ? launch_ppl<T, kPix>(a, two_pass, s) : launch_ppl<T, 1>(a, two_pass, s);
+  });
 }
 
 extern "C" int runia_pixel_map_reduce_f32(const float* map, const uint8_t* valid, int64_t G, int64_t HW, float* mean,

@@ -23,14 +23,13 @@
 #include <algorithm>
 
 #include "common.hpp"
+#include "elem.hpp"
 
 namespace {
 
 struct MapDesc {  // one (step, layer) map, batch 0; strides and sizes in elements
   int64_t ptr, head_stride, row_stride, col_stride, k, q;
 };
-
-enum { kF32 = 0, kF16 = 1, kBF16 = 2 };
 
 // one (step, layer) map of a batched call: batch 0 plus the batch stride; strides and sizes in elements
 struct BMapDesc {
@@ -41,14 +40,14 @@ struct RowInfo {  // one batch row: its prompt's left-pad count and the generate
   int64_t pad, n;
 };
 
+// ET below: the element tag of the maps (elem.hpp); T is taken in this file, it is the side of the T x T rollout map.
 // Row b's own map, as the one-row path sees the slice [b, :, pad:, pad:] of step 0 or [b, :, :, pad:] of a later step.
 // A step 0 of one query row is not sliced by rows (the caller allows it only without padding).
-template <int DT>
+template <class ET>
 __device__ __forceinline__ MapDesc row_view(const BMapDesc& d, int64_t b, int64_t pad, bool step0) {
   const bool by_rows = step0 && d.q > 1;
   const int64_t off = b * d.batch_stride + pad * d.col_stride + (by_rows ? pad * d.row_stride : 0);
-  return MapDesc{d.ptr + off * (DT == kF32 ? 4 : 2), d.head_stride, d.row_stride, d.col_stride, d.k - pad,
-                 by_rows ? d.q - pad : d.q};
+  return MapDesc{d.ptr + off * ET::kBytes, d.head_stride, d.row_stride, d.col_stride, d.k - pad, by_rows ? d.q - pad : d.q};
 }
 
 // map (step s, layer l) at index s * L + l: the one-row table as it is, or row b's views of a batched table
@@ -56,51 +55,49 @@ struct OneTab {
   const MapDesc* t;
   __device__ __forceinline__ MapDesc operator()(int64_t idx, bool) const { return t[idx]; }
 };
-template <int DT>
+template <class ET>
 struct RowTab {
   const BMapDesc* t;
   int64_t b, pad;
-  __device__ __forceinline__ MapDesc operator()(int64_t idx, bool step0) const { return row_view<DT>(t[idx], b, pad, step0); }
+  __device__ __forceinline__ MapDesc operator()(int64_t idx, bool step0) const { return row_view<ET>(t[idx], b, pad, step0); }
 };
 
-template <int DT>
+template <class ET>
 __device__ __forceinline__ float ld(const MapDesc& m, int64_t off) {
-  if constexpr (DT == kF32) return reinterpret_cast<const float*>(m.ptr)[off];
-  else if constexpr (DT == kF16) return (float)reinterpret_cast<const _Float16*>(m.ptr)[off];
-  else return __uint_as_float((unsigned)reinterpret_cast<const unsigned short*>(m.ptr)[off] << 16);
+  return ld1<ET>(reinterpret_cast<const typename ET::elem*>(m.ptr) + off);
 }
 
 // an f32 value rounded to the map dtype (round to nearest even, as torch's casts) and widened back
-template <int DT>
+template <class ET>
 __device__ __forceinline__ float round_to(float x) {
-  if constexpr (DT == kF32) return x;
-  else if constexpr (DT == kF16) return (float)(_Float16)x;
-  else {
-    unsigned u = __float_as_uint(x);
-    if ((u & 0x7fffffffu) > 0x7f800000u) return x;  // NaN
-    u += 0x7fffu + ((u >> 16) & 1u);
-    return __uint_as_float(u & 0xffff0000u);
-  }
+  return widen(ET{}, narrow(ET{}, x));
+}
+// bf16 hands a NaN back as it came, payload and all (narrow would write torch's quiet NaN)
+template <>
+__device__ __forceinline__ float round_to<BF16>(float x) {
+  const uint32_t u = __float_as_uint(x);
+  if ((u & 0x7fffffffu) > 0x7f800000u) return x;
+  return __uint_as_float(bf16_round_bits(u) & 0xffff0000u);
 }
 
 // ---- gather ------------------------------------------------------------------------------------------------------------
 // the token-aggregation value of query row 0 of map m (every lane returns it)
-template <int DT>
+template <class ET>
 __device__ __forceinline__ float gather_value(const MapDesc& m, int h, int lane, int mean_all) {
   const int64_t base = (int64_t)h * m.head_stride;  // query row 0
-  if (!mean_all) return ld<DT>(m, base + (m.k - 2) * m.col_stride);
+  if (!mean_all) return ld<ET>(m, base + (m.k - 2) * m.col_stride);
   if (m.k < 512) {
     // torch's own summation order (ATen cascade_sum): the head choice of the per-head mode compares row means that all
     // sit near 1/k for softmax rows, and is decided in their last bits
-    return round_to<DT>(torch_row_sum([&](int j) { return ld<DT>(m, base + (int64_t)j * m.col_stride); }, (int)m.k) / (float)m.k);
+    return round_to<ET>(torch_row_sum([&](int j) { return ld<ET>(m, base + (int64_t)j * m.col_stride); }, (int)m.k) / (float)m.k);
   }
   float s = 0.f;
-  for (int64_t j = lane; j < m.k; j += 64) s += ld<DT>(m, base + j * m.col_stride);
+  for (int64_t j = lane; j < m.k; j += 64) s += ld<ET>(m, base + j * m.col_stride);
   s = wave_sum_f32(s);
-  return round_to<DT>(s / (float)m.k);
+  return round_to<ET>(s / (float)m.k);
 }
 
-template <int DT>
+template <class ET>
 __global__ __launch_bounds__(256) void gather_kernel(const MapDesc* __restrict__ tab, int L, int H, int N, int mean_all,
                                                      float* __restrict__ w) {
   const int64_t row = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
@@ -108,12 +105,12 @@ __global__ __launch_bounds__(256) void gather_kernel(const MapDesc* __restrict__
   if (row >= (int64_t)N * L * H) return;
   const int i = (int)(row / ((int64_t)L * H)), l = (int)((row / H) % L), h = (int)(row % H);
   const int g = mean_all ? i : i + 1;  // "original" reads steps 1 .. n_gen-1
-  const float v = gather_value<DT>(tab[(int64_t)g * L + l], h, lane, mean_all);
+  const float v = gather_value<ET>(tab[(int64_t)g * L + l], h, lane, mean_all);
   if (lane == 0) w[((int64_t)l * H + h) * N + i] = v;
 }
 
 // batched: one wave per (row b, token i < N_b, layer, head) into w[b][l][h][N] (N = the largest N_b)
-template <int DT>
+template <class ET>
 __global__ __launch_bounds__(256) void gather_batch_kernel(const BMapDesc* __restrict__ tab, const RowInfo* __restrict__ rows,
                                                            int B, int L, int H, int N, int mean_all, float* __restrict__ w) {
   const int64_t row = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
@@ -126,7 +123,7 @@ __global__ __launch_bounds__(256) void gather_batch_kernel(const BMapDesc* __res
   const RowInfo ri = rows[b];
   if (i >= (mean_all ? ri.n : ri.n - 1)) return;
   const int g = mean_all ? i : i + 1;
-  const float v = gather_value<DT>(row_view<DT>(tab[(int64_t)g * L + l], b, ri.pad, g == 0), h, lane, mean_all);
+  const float v = gather_value<ET>(row_view<ET>(tab[(int64_t)g * L + l], b, ri.pad, g == 0), h, lane, mean_all);
   if (lane == 0) w[(((int64_t)b * L + l) * H + h) * N + i] = v;
 }
 
@@ -249,7 +246,7 @@ __device__ __forceinline__ RowRef row_ref(const Tab& tab, int L, int l, int in, 
 }
 
 // sum over heads of column j (head order 0 .. H-1, as torch's mean over dim 0 of (H, T, T)); nz: a non-zero entry
-template <int DT>
+template <class ET>
 __device__ __forceinline__ float head_sum(const RowRef& r, int H, int64_t j, bool& nz) {
   const int64_t off = r.off + j * r.m.col_stride;
   float acc = 0.f;
@@ -257,7 +254,7 @@ __device__ __forceinline__ float head_sum(const RowRef& r, int H, int64_t j, boo
   for (; h0 + 8 <= H; h0 += 8) {
     float v[8];
 #pragma unroll
-    for (int u = 0; u < 8; ++u) v[u] = ld<DT>(r.m, off + (int64_t)(h0 + u) * r.m.head_stride);
+    for (int u = 0; u < 8; ++u) v[u] = ld<ET>(r.m, off + (int64_t)(h0 + u) * r.m.head_stride);
 #pragma unroll
     for (int u = 0; u < 8; ++u) {
       acc += v[u];
@@ -265,7 +262,7 @@ __device__ __forceinline__ float head_sum(const RowRef& r, int H, int64_t j, boo
     }
   }
   for (; h0 < H; ++h0) {
-    const float v = ld<DT>(r.m, off + (int64_t)h0 * r.m.head_stride);
+    const float v = ld<ET>(r.m, off + (int64_t)h0 * r.m.head_stride);
     acc += v;
     nz |= v != 0.f;
   }
@@ -273,7 +270,7 @@ __device__ __forceinline__ float head_sum(const RowRef& r, int H, int64_t j, boo
 }
 
 // row i of layer l: rsum / diag / sub at element e
-template <int DT, class Tab>
+template <class ET, class Tab>
 __device__ __forceinline__ void rows_body(const Tab& tab, int L, int H, int in, int i, int l, int64_t e,
                                           float* __restrict__ rsum, float* __restrict__ diag, float* __restrict__ sub,
                                           int* __restrict__ upper_flag) {
@@ -288,7 +285,7 @@ __device__ __forceinline__ void rows_body(const Tab& tab, int L, int H, int in, 
   const float inv_h_div = (float)H;
   for (int64_t j = t; j < r.k; j += 256) {
     bool nz = false;
-    const float m = head_sum<DT>(r, H, j, nz) / inv_h_div;
+    const float m = head_sum<ET>(r, H, j, nz) / inv_h_div;
     s += m;
     if (j > i) upper |= nz;
     if (j == i) m_diag = m;
@@ -306,17 +303,17 @@ __device__ __forceinline__ void rows_body(const Tab& tab, int L, int H, int in, 
   }
 }
 
-template <int DT>
+template <class ET>
 __global__ __launch_bounds__(256) void rows_kernel(const MapDesc* __restrict__ tab, int L, int H, int in, int T,
                                                    float* __restrict__ rsum, float* __restrict__ diag,
                                                    float* __restrict__ sub, int* __restrict__ upper_flag) {
   const int i = blockIdx.x, l = blockIdx.y;
-  rows_body<DT>(OneTab{tab}, L, H, in, i, l, (int64_t)l * T + i, rsum, diag, sub, upper_flag);
+  rows_body<ET>(OneTab{tab}, L, H, in, i, l, (int64_t)l * T + i, rsum, diag, sub, upper_flag);
 }
 
 // batched: grid (T, L, B) with T = in + n_gen; row b's map has T_b = in - pad_b + n_b rows (in[b][l][T] layout), rows
 // with n_b < 2 are skipped (their one-row call raises)
-template <int DT>
+template <class ET>
 __global__ __launch_bounds__(256) void rows_batch_kernel(const BMapDesc* __restrict__ tab, const RowInfo* __restrict__ rows,
                                                          int L, int H, int in, int T, float* __restrict__ rsum,
                                                          float* __restrict__ diag, float* __restrict__ sub,
@@ -325,7 +322,7 @@ __global__ __launch_bounds__(256) void rows_batch_kernel(const BMapDesc* __restr
   const RowInfo ri = rows[b];
   const int in_b = in - (int)ri.pad;
   if (ri.n < 2 || i >= in_b + ri.n) return;
-  rows_body<DT>(RowTab<DT>{tab, b, ri.pad}, L, H, in_b, i, l, ((int64_t)b * L + l) * T + i, rsum, diag, sub,
+  rows_body<ET>(RowTab<ET>{tab, b, ri.pad}, L, H, in_b, i, l, ((int64_t)b * L + l) * T + i, rsum, diag, sub,
                 upper_flags + b);
 }
 
@@ -368,7 +365,7 @@ constexpr int kChainCols = 256;   // columns per chain workgroup (one per thread
 // One layer of the chain, R row `r` = blockIdx.z, rows [b*8, b*8+8) = blockIdx.y, columns [c*256, c*256+256) = blockIdx.x.
 // State in:  v_prev[k][T] (R diag(1/r) of the previous layer) and p_prev[k][nb][T] (its column partials); first layer: the
 // initial R.  Out: v_cur (rows of this block, written by the column-0 workgroups), p_cur[r][b][columns].
-template <int DT>
+template <class ET>
 __global__ __launch_bounds__(256) void chain_kernel(const MapDesc* __restrict__ tab, int L, int H, int in, int T, int l,
                                                     int first, int init_ones, int n, int causal, int nb,
                                                     const float* __restrict__ rsum, const double* __restrict__ v_prev,
@@ -404,7 +401,7 @@ __global__ __launch_bounds__(256) void chain_kernel(const MapDesc* __restrict__ 
     const int64_t kk = (causal && i < in) ? (int64_t)i + 1 : rr.k;  // causal maps: nothing above the diagonal
     if (j >= kk || vp[u] == 0.0) continue;
     bool nz = false;
-    const float m = head_sum<DT>(rr, H, j, nz) / (float)H;
+    const float m = head_sum<ET>(rr, H, j, nz) / (float)H;
     acc += vp[u] * (double)m;
   }
   p_cur[((int64_t)r * nb + b) * T + j] = acc;
@@ -412,12 +409,12 @@ __global__ __launch_bounds__(256) void chain_kernel(const MapDesc* __restrict__ 
 
 // batched: before row b's chain, its own one-row map table (n_b * L views) and its rsum repacked as [L][T_b], so the
 // chain itself is chain_kernel on the row's own maps
-template <int DT>
+template <class ET>
 __global__ __launch_bounds__(256) void chain_row_kernel(const BMapDesc* __restrict__ tab, int b, int pad, int L, int n,
                                                         int T, int T_b, const float* __restrict__ rsum_b,
                                                         MapDesc* __restrict__ row_tab, float* __restrict__ row_rsum) {
   const int64_t e = (int64_t)blockIdx.x * 256 + threadIdx.x;
-  if (e < (int64_t)n * L) row_tab[e] = row_view<DT>(tab[e], b, pad, e < L);
+  if (e < (int64_t)n * L) row_tab[e] = row_view<ET>(tab[e], b, pad, e < L);
   if (e < (int64_t)L * T_b) row_rsum[e] = rsum_b[(e / T_b) * T + e % T_b];
 }
 
@@ -489,16 +486,6 @@ static bool bad_ws(const void* ws, size_t bytes, size_t need) {
   return !ws || bytes < need || (((uintptr_t)ws) & 15) != 0;
 }
 
-template <class F>
-static int dispatch_dtype(int dtype, F f) {
-  switch (dtype) {
-    case kF32: f(std::integral_constant<int, kF32>{}); break;
-    case kF16: f(std::integral_constant<int, kF16>{}); break;
-    default: f(std::integral_constant<int, kBF16>{}); break;
-  }
-  return runia_check_launch();
-}
-
 constexpr int64_t kMaxDim = 1 << 20;
 static bool dims_ok(int64_t n_gen, int64_t L, int64_t H) {
   return n_gen >= 1 && n_gen <= kMaxDim && L >= 1 && L <= 4096 && H >= 1 && H <= 4096;
@@ -514,15 +501,16 @@ extern "C" size_t runia_rauq_workspace_bytes(int64_t L, int64_t n_gen, int64_t i
 
 extern "C" int runia_rauq_gather(const void* table, int dtype, int64_t n_gen, int64_t L, int64_t H, int token_agg, float* w,
                                  runia_stream_t stream) {
-  if (!table || !w || dtype < kF32 || dtype > kBF16 || (token_agg != 0 && token_agg != 1) || !dims_ok(n_gen, L, H))
+  if (!table || !w || !elem_dtype_ok(dtype) || (token_agg != 0 && token_agg != 1) || !dims_ok(n_gen, L, H))
     return RUNIA_E_INVALID;
   const int64_t N = token_agg ? n_gen : n_gen - 1;
   if (N < 1) return RUNIA_E_INVALID;
   const int64_t rows = N * L * H;
   const unsigned grid = (unsigned)((rows + 3) / 4);
   const MapDesc* tab = reinterpret_cast<const MapDesc*>(table);
-  return dispatch_dtype(dtype, [&](auto dt) {
-    gather_kernel<decltype(dt)::value><<<grid, 256, 0, as_stream(stream)>>>(tab, (int)L, (int)H, (int)N, token_agg, w);
+  return dispatch_elem(dtype, [&](auto et) {
+    gather_kernel<decltype(et)><<<grid, 256, 0, as_stream(stream)>>>(tab, (int)L, (int)H, (int)N, token_agg, w);
+    return runia_check_launch();
   });
 }
 
@@ -545,7 +533,7 @@ extern "C" int runia_rauq_score(const float* att, int64_t L, int64_t H, int64_t 
 extern "C" int runia_rauq_rollout_rows(const void* table, int dtype, int64_t n_gen, int64_t L, int64_t H,
                                        int64_t input_length, int* upper_flag, void* workspace, size_t workspace_bytes,
                                        runia_stream_t stream) {
-  if (!table || !upper_flag || dtype < kF32 || dtype > kBF16 || !dims_ok(n_gen, L, H) || n_gen < 2 || input_length < 1 ||
+  if (!table || !upper_flag || !elem_dtype_ok(dtype) || !dims_ok(n_gen, L, H) || n_gen < 2 || input_length < 1 ||
       input_length + n_gen > kMaxDim)
     return RUNIA_E_INVALID;
   const Layout o = layout(L, n_gen, input_length, 0, 0, 1);
@@ -554,17 +542,18 @@ extern "C" int runia_rauq_rollout_rows(const void* table, int dtype, int64_t n_g
   const int T = (int)(input_length + n_gen);
   if (hipMemsetAsync(upper_flag, 0, sizeof(int), as_stream(stream)) != hipSuccess) return RUNIA_E_LAUNCH;
   const MapDesc* tab = reinterpret_cast<const MapDesc*>(table);
-  return dispatch_dtype(dtype, [&](auto dt) {
-    rows_kernel<decltype(dt)::value><<<dim3((unsigned)T, (unsigned)L), 256, 0, as_stream(stream)>>>(
+  return dispatch_elem(dtype, [&](auto et) {
+    rows_kernel<decltype(et)><<<dim3((unsigned)T, (unsigned)L), 256, 0, as_stream(stream)>>>(
         tab, (int)L, (int)H, (int)input_length, T, reinterpret_cast<float*>(ws + o.rsum),
         reinterpret_cast<float*>(ws + o.diag), reinterpret_cast<float*>(ws + o.sub), upper_flag);
+    return runia_check_launch();
   });
 }
 
 extern "C" int runia_rauq_rollout_att(const void* table, int dtype, int64_t n_gen, int64_t L, int64_t H,
                                       int64_t input_length, int token_agg, int route, int64_t n, float* att, void* workspace,
                                       size_t workspace_bytes, runia_stream_t stream) {
-  if (!table || !att || dtype < kF32 || dtype > kBF16 || !dims_ok(n_gen, L, H) || n_gen < 2 || input_length < 1 ||
+  if (!table || !att || !elem_dtype_ok(dtype) || !dims_ok(n_gen, L, H) || n_gen < 2 || input_length < 1 ||
       input_length + n_gen > kMaxDim || (token_agg != 0 && token_agg != 1) || route < 0 || route > 2 ||
       (route == 0 && token_agg != 0) || n < 1)
     return RUNIA_E_INVALID;
@@ -591,10 +580,11 @@ extern "C" int runia_rauq_rollout_att(const void* table, int dtype, int64_t n_ge
   int rc = RUNIA_OK;
   for (int64_t l = L - 1; l >= 0 && rc == RUNIA_OK; --l) {
     const int first = l == L - 1;
-    rc = dispatch_dtype(dtype, [&](auto dt) {
-      chain_kernel<decltype(dt)::value><<<grid, 256, 0, s>>>(tab, (int)L, (int)H, (int)input_length, (int)T, (int)l, first,
-                                                           token_agg, (int)n, route == 1, (int)o.nb, rsum, v[cur ^ 1],
-                                                           p[cur ^ 1], v[cur], p[cur]);
+    rc = dispatch_elem(dtype, [&](auto et) {
+      chain_kernel<decltype(et)><<<grid, 256, 0, s>>>(tab, (int)L, (int)H, (int)input_length, (int)T, (int)l, first,
+                                                    token_agg, (int)n, route == 1, (int)o.nb, rsum, v[cur ^ 1],
+                                                    p[cur ^ 1], v[cur], p[cur]);
+      return runia_check_launch();
     });
     cur ^= 1;
   }
@@ -616,7 +606,7 @@ extern "C" size_t runia_rauqb_workspace_bytes(int64_t B, int64_t L, int64_t n_ge
 
 extern "C" int runia_rauqb_gather(const void* table, const void* rows, int dtype, int64_t B, int64_t n_gen, int64_t L,
                                   int64_t H, int token_agg, float* w, runia_stream_t stream) {
-  if (!table || !rows || !w || dtype < kF32 || dtype > kBF16 || (token_agg != 0 && token_agg != 1) || B < 1 ||
+  if (!table || !rows || !w || !elem_dtype_ok(dtype) || (token_agg != 0 && token_agg != 1) || B < 1 ||
       B > kMaxBatch || !dims_ok(n_gen, L, H))
     return RUNIA_E_INVALID;
   const int64_t N = token_agg ? n_gen : n_gen - 1;
@@ -626,9 +616,10 @@ extern "C" int runia_rauqb_gather(const void* table, const void* rows, int dtype
   const unsigned grid = (unsigned)((waves + 3) / 4);
   const BMapDesc* tab = reinterpret_cast<const BMapDesc*>(table);
   const RowInfo* ri = reinterpret_cast<const RowInfo*>(rows);
-  return dispatch_dtype(dtype, [&](auto dt) {
-    gather_batch_kernel<decltype(dt)::value><<<grid, 256, 0, as_stream(stream)>>>(tab, ri, (int)B, (int)L, (int)H, (int)N,
-                                                                                  token_agg, w);
+  return dispatch_elem(dtype, [&](auto et) {
+    gather_batch_kernel<decltype(et)><<<grid, 256, 0, as_stream(stream)>>>(tab, ri, (int)B, (int)L, (int)H, (int)N,
+                                                                           token_agg, w);
+    return runia_check_launch();
   });
 }
 
@@ -652,7 +643,7 @@ extern "C" int runia_rauqb_score(const float* att, const void* rows, int64_t B, 
 extern "C" int runia_rauqb_rollout_rows(const void* table, const void* rows, int dtype, int64_t B, int64_t n_gen, int64_t L,
                                         int64_t H, int64_t input_length, int* upper_flags, void* workspace,
                                         size_t workspace_bytes, runia_stream_t stream) {
-  if (!table || !rows || !upper_flags || dtype < kF32 || dtype > kBF16 || B < 1 || B > kMaxBatch || !dims_ok(n_gen, L, H) ||
+  if (!table || !rows || !upper_flags || !elem_dtype_ok(dtype) || B < 1 || B > kMaxBatch || !dims_ok(n_gen, L, H) ||
       n_gen < 2 || input_length < 1 || input_length + n_gen > kMaxDim)
     return RUNIA_E_INVALID;
   const Layout o = layout_batch(B, L, n_gen, input_length, 0, 1);
@@ -661,11 +652,12 @@ extern "C" int runia_rauqb_rollout_rows(const void* table, const void* rows, int
   const int T = (int)(input_length + n_gen);
   if (hipMemsetAsync(upper_flags, 0, sizeof(int) * (size_t)B, as_stream(stream)) != hipSuccess) return RUNIA_E_LAUNCH;
   const BMapDesc* tab = reinterpret_cast<const BMapDesc*>(table);
-  return dispatch_dtype(dtype, [&](auto dt) {
-    rows_batch_kernel<decltype(dt)::value><<<dim3((unsigned)T, (unsigned)L, (unsigned)B), 256, 0, as_stream(stream)>>>(
+  return dispatch_elem(dtype, [&](auto et) {
+    rows_batch_kernel<decltype(et)><<<dim3((unsigned)T, (unsigned)L, (unsigned)B), 256, 0, as_stream(stream)>>>(
         tab, reinterpret_cast<const RowInfo*>(rows), (int)L, (int)H, (int)input_length, T,
         reinterpret_cast<float*>(ws + o.rsum), reinterpret_cast<float*>(ws + o.diag), reinterpret_cast<float*>(ws + o.sub),
         upper_flags);
+    return runia_check_launch();
   });
 }
 
@@ -673,7 +665,7 @@ extern "C" int runia_rauqb_rollout_att(const void* table, const void* rows, cons
                                        const int* host_upper, int dtype, int64_t B, int64_t n_gen, int64_t L, int64_t H,
                                        int64_t input_length, int token_agg, float* att, void* workspace,
                                        size_t workspace_bytes, runia_stream_t stream) {
-  if (!table || !rows || !host_rows || !upper_flags || !host_upper || !att || dtype < kF32 || dtype > kBF16 || B < 1 ||
+  if (!table || !rows || !host_rows || !upper_flags || !host_upper || !att || !elem_dtype_ok(dtype) || B < 1 ||
       B > kMaxBatch || !dims_ok(n_gen, L, H) || n_gen < 2 || input_length < 1 || input_length + n_gen > kMaxDim ||
       (token_agg != 0 && token_agg != 1))
     return RUNIA_E_INVALID;
@@ -710,17 +702,19 @@ extern "C" int runia_rauqb_rollout_att(const void* table, const void* rows, cons
     MapDesc* row_tab = reinterpret_cast<MapDesc*>(ws + o.row_tab);
     float* row_rsum = reinterpret_cast<float*>(ws + o.row_rsum);
     const int64_t prep = std::max(n * L, L * T_b);
-    int rc = dispatch_dtype(dtype, [&](auto dt) {
-      chain_row_kernel<decltype(dt)::value><<<(unsigned)((prep + 255) / 256), 256, 0, s>>>(
+    int rc = dispatch_elem(dtype, [&](auto et) {
+      chain_row_kernel<decltype(et)><<<(unsigned)((prep + 255) / 256), 256, 0, s>>>(
           tab, (int)b, (int)pad, (int)L, (int)n, (int)T, (int)T_b, rsum + b * L * T, row_tab, row_rsum);
+      return runia_check_launch();
     });
     int cur = 0;
     for (int64_t l = L - 1; l >= 0 && rc == RUNIA_OK; --l) {
       const int first = l == L - 1;
-      rc = dispatch_dtype(dtype, [&](auto dt) {
-        chain_kernel<decltype(dt)::value><<<grid, 256, 0, s>>>(row_tab, (int)L, (int)H, (int)in_b, (int)T_b, (int)l, first,
-                                                             token_agg, (int)n, route == 1, (int)nb, row_rsum, v[cur ^ 1],
-                                                             p[cur ^ 1], v[cur], p[cur]);
+      rc = dispatch_elem(dtype, [&](auto et) {
+        chain_kernel<decltype(et)><<<grid, 256, 0, s>>>(row_tab, (int)L, (int)H, (int)in_b, (int)T_b, (int)l, first,
+                                                      token_agg, (int)n, route == 1, (int)nb, row_rsum, v[cur ^ 1],
+                                                      p[cur ^ 1], v[cur], p[cur]);
+        return runia_check_launch();
       });
       cur ^= 1;
     }

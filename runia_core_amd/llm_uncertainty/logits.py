@@ -22,7 +22,6 @@ from typing import List, NamedTuple, Optional, Sequence, Tuple
 import torch
 
 from .. import _hip
-from .rauq import _DTYPE_CODES
 
 __all__ = ["GenerationScores", "generation_scores", "token_entropies", "transition_scores"]
 
@@ -52,7 +51,7 @@ def _steps(scores) -> Tuple[List[torch.Tensor], int, int, torch.dtype, Optional[
     for t, s in enumerate(scores):
         if not isinstance(s, torch.Tensor):
             raise ValueError(f"step {t} is not a tensor")
-        if s.dtype not in _DTYPE_CODES:
+        if s.dtype not in _hip.ELEM_DTYPE_CODES:
             raise TypeError(f"scores must be float32, float16 or bfloat16, not {s.dtype} (step {t})")
         if s.dim() == 3 and s.shape[1] == 1:
             s = s[:, 0, :]
@@ -128,7 +127,7 @@ def _run(sequences, scores, normalize: bool, want_log_prob: bool, want_entropy: 
     lp = torch.empty((B, T), dtype=torch.float32, device=dev) if want_log_prob else None
     ent = torch.empty((B, T), dtype=torch.float32, device=dev) if want_entropy else None
     seq = torch.empty(3 * B + 1, dtype=torch.float64, device=dev) if want_seq else None
-    _hip._check(lib.runia_logit_stats(table.data_ptr(), _DTYPE_CODES[dtype], T, B, V, _hip._ptr(tok),
+    _hip._check(lib.runia_logit_stats(table.data_ptr(), _hip.ELEM_DTYPE_CODES[dtype], T, B, V, _hip._ptr(tok),
                                       tok.stride(0) if tok is not None else 0, int(bool(normalize)), None, _hip._ptr(lp),
                                       _hip._ptr(ent), _hip._ptr(seq), ws.data_ptr(), need, _hip._stream()),
                 "runia_logit_stats")

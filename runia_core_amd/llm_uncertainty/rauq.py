@@ -35,7 +35,8 @@ from .. import _hip
 __all__ = ["rauq_uncertainty", "rauq_uncertainty_mean_heads", "rauq_uncertainty_rollout", "RAUQ", "rauq_batch",
            "generated_lengths"]
 
-_DTYPE_CODES = {torch.float32: 0, torch.float16: 1, torch.bfloat16: 2}
+_DTYPE_CODES = _hip.ELEM_DTYPE_CODES  # the name tests and tools read
+
 _TOKEN_AGGREGATION = {"original": 0, "mean_all_tokens": 1}
 _HEAD_ARGMAX, _HEAD_MEAN, _SERIES = 0, 1, 2
 _HEAD_AGGREGATION = {"original": _HEAD_ARGMAX, "mean_heads": _HEAD_MEAN, "rollout": _SERIES}
@@ -53,7 +54,7 @@ def _map_shapes(attentions) -> Tuple[int, int, int, torch.dtype, Optional[torch.
     n_gen, n_layers = len(attentions), len(attentions[0])
     first = attentions[0][0]
     heads, dtype, dev = int(first.shape[1]), first.dtype, (first.device if first.is_cuda else None)
-    if dtype not in _DTYPE_CODES:
+    if dtype not in _hip.ELEM_DTYPE_CODES:
         raise TypeError(f"attention maps must be float32, float16 or bfloat16, not {dtype}")
     for g, step in enumerate(attentions):
         if len(step) != n_layers:
@@ -137,7 +138,7 @@ def _gather_scores(log_probs, attentions, token_aggregation: str, alphas, head_m
     dev = _hip.require_gpu()
     table, keep = _map_table(attentions, dev, first_row_only=True)
     w = torch.empty((n_layers, heads, n), dtype=torch.float32, device=dev)
-    _hip._check(lib.runia_rauq_gather(table.data_ptr(), _DTYPE_CODES[dtype], n_gen, n_layers, heads, tok, w.data_ptr(),
+    _hip._check(lib.runia_rauq_gather(table.data_ptr(), _hip.ELEM_DTYPE_CODES[dtype], n_gen, n_layers, heads, tok, w.data_ptr(),
                                       _hip._stream()), "runia_rauq_gather")
     ws = torch.empty(int(lib.runia_rauq_workspace_bytes(n_layers, n, 0, 0, 0, len(alphas))), dtype=torch.uint8, device=dev)
     scores, chosen = _score(w, n_layers, heads, n, head_mode, lp, alphas, ws)
@@ -176,7 +177,7 @@ def _rollout_scores(log_probs, attentions, token_aggregation: str, input_length:
         return []
     lib = _hip.load_library()
     dev = _hip.require_gpu()
-    code = _DTYPE_CODES[dtype]
+    code = _hip.ELEM_DTYPE_CODES[dtype]
     table, keep = _map_table(attentions, dev, first_row_only=False)
     flag = torch.zeros(1, dtype=torch.int32, device=dev)
 
@@ -348,7 +349,7 @@ def rauq_batch(log_probs: torch.Tensor, attentions: Tuple[Tuple[torch.Tensor, ..
     scores = torch.full((batch, n_alpha), float("nan"), dtype=torch.float32, device=dev)
     if n_alpha == 0:
         return scores if map_dev is not None else scores.cpu()
-    code = _DTYPE_CODES[dtype]
+    code = _hip.ELEM_DTYPE_CODES[dtype]
     rows_h = torch.tensor([[p, n] for p, n in zip(pads, ns)], dtype=torch.int64)
     rows_d = rows_h.to(dev)
     lp_d = _hip.to_device(lp, torch.float32)

@@ -457,6 +457,56 @@ def _ptr(t: Optional[torch.Tensor]) -> Optional[int]:
     return None if t is None else t.data_ptr()
 
 
+def launch(name: str, *args) -> None:
+    """Call the entry point ``name`` with ``args`` and the current stream (always its last parameter); a non-zero code raises
+    ``RuniaHipError`` naming that symbol.  It never asks for the GPU: ``require_gpu()`` stays where each wrapper has it, because
+    which refusal comes first on a box without a device is part of every wrapper's contract."""
+    rc = getattr(load_library(), name)(*args, _raw_stream(torch.cuda.current_device()) if _raw_stream is not None else _stream())
+    if rc != 0:
+        _check(rc, name)
+
+
+def call(name: str, *args) -> None:
+    """``launch`` for the entry points without a stream parameter (the p2p family, ``runia_time_next_launch``,
+    ``runia_pacmap_phase_weights``)."""
+    rc = getattr(load_library(), name)(*args)
+    if rc != 0:
+        _check(rc, name)
+
+
+def query(name: str, *args) -> int:
+    """The value of an entry point that returns a number, not an error code (``*_workspace_bytes``, ``*_bytes``,
+    ``*_supported``, ``runia_eigh_block_padded``, ``runia_knn_piece_products``), as a Python int."""
+    return int(getattr(load_library(), name)(*args))
+
+
+def workspace(nbytes: int, device, floor: int = 16) -> torch.Tensor:
+    """Uninitialised scratch of ``max(nbytes, floor)`` bytes for one call (stream-ordered: the caching allocator hands the block
+    to the next call on the stream).  Blocks are 512-byte aligned whatever the kernel reads them as."""
+    return torch.empty(max(int(nbytes), floor), dtype=torch.uint8, device=device)
+
+
+def _draws(rand: Optional[torch.Tensor], n: int, n_mc: int, h: int, w: int, copy: bool = True):
+    """Check explicit DropBlock draws ([n_mc, H, W] shared by the images, or [N, n_mc, H, W]) -> ``(rand, image stride in
+    elements)``; ``(None, 0)`` without draws.  ``copy=False`` refuses draws that are not contiguous instead of copying them."""
+    if rand is None:
+        return None, 0
+    assert rand.is_cuda and rand.dtype == torch.float32 and (copy or rand.is_contiguous())
+    if copy:
+        rand = rand.contiguous()
+    if rand.dim() == 4:
+        assert rand.shape == (n, n_mc, h, w)
+        return rand, n_mc * h * w
+    assert rand.shape == (n_mc, h, w)
+    return rand, 0
+
+
+def _image_slices(n: int):
+    """``(done, m)``: slices of at most 65 535 images, the grid limit of the sampler kernels."""
+    for done in range(0, n, 65535):
+        yield done, min(65535, n - done)
+
+
 class _UploadCache(threading.local):
     depth = 0
     entries = None
@@ -536,49 +586,26 @@ def to_host(t: torch.Tensor) -> np.ndarray:
 @_device_guard()
 def mc_stack(x: torch.Tensor, rand: Optional[torch.Tensor], n_mc: int, drop_prob: float, block_size: int) -> torch.Tensor:
     """x [N,C,H,W] f32, rand [n_mc,H,W] (shared) or [N,n_mc,H,W] f32 -> [N*n_mc, C] f32."""
-    lib = load_library()
     require_gpu()
     assert x.is_cuda and x.dtype == torch.float32 and x.dim() == 4
     x = x.contiguous()
     n, c, h, w = x.shape
-    stride = 0
     if isinstance(rand, CounterDraws):
         rand = _explicit_counter_draws(rand, n, n_mc, h, w)
-    if rand is not None:
-        assert rand.is_cuda and rand.dtype == torch.float32
-        rand = rand.contiguous()
-        if rand.dim() == 4:
-            assert rand.shape == (n, n_mc, h, w)
-            stride = n_mc * h * w
-        else:
-            assert rand.shape == (n_mc, h, w)
+    rand, stride = _draws(rand, n, n_mc, h, w)
     out = torch.empty((n * n_mc, c), dtype=torch.float32, device=x.device)
-    table_path = n_mc >= 2 and bool(lib.runia_mc_entropy_supported(h, w, n_mc, 5)) and (x.data_ptr() % 16 == 0 or (h * w) % 4)
+    table_path = n_mc >= 2 and bool(query("runia_mc_entropy_supported", h, w, n_mc, 5)) and (x.data_ptr() % 16 == 0 or (h * w) % 4)
     if table_path:
-        ws_bytes = int(lib.runia_mc_entropy_workspace_bytes(min(65535, n), h, w, n_mc))
-        ws = torch.empty(max(ws_bytes, 16), dtype=torch.uint8, device=x.device)
-    done = 0
-    while done < n:  # grid limit of the kernels
-        m = min(65535, n - done)
-        rp = None if rand is None else rand.data_ptr() + (done * stride * 4)
+        ws_bytes = query("runia_mc_entropy_workspace_bytes", min(65535, n), h, w, n_mc)
+        ws = workspace(ws_bytes, x.device)
+    for done, m in _image_slices(n):
+        xp, op = x.data_ptr() + done * c * h * w * 4, out.data_ptr() + done * n_mc * c * 4
+        rp = None if rand is None else rand.data_ptr() + done * stride * 4
         if table_path:
-            _check(
-                lib.runia_mc_stack_table_f32(
-                    x.data_ptr() + done * c * h * w * 4, rp, stride, out.data_ptr() + done * n_mc * c * 4, ws.data_ptr(),
-                    ws_bytes, m, c, h, w, n_mc, float(drop_prob), int(block_size), _stream(),
-                ),
-                "runia_mc_stack_table_f32",
-            )
-            done += m
-            continue
-        _check(
-            lib.runia_mc_stack_f32(
-                x.data_ptr() + done * c * h * w * 4, rp, stride, out.data_ptr() + done * n_mc * c * 4,
-                m, c, h, w, n_mc, float(drop_prob), int(block_size), _stream(),
-            ),
-            "runia_mc_stack_f32",
-        )
-        done += m
+            launch("runia_mc_stack_table_f32", xp, rp, stride, op, ws.data_ptr(), ws_bytes, m, c, h, w, n_mc, float(drop_prob),
+                   int(block_size))
+        else:
+            launch("runia_mc_stack_f32", xp, rp, stride, op, m, c, h, w, n_mc, float(drop_prob), int(block_size))
     return out
 
 
@@ -595,45 +622,28 @@ def _explicit_counter_draws(ticket: CounterDraws, n: int, n_mc: int, h: int, w: 
 def mc_draws(n: int, n_mc: int, h: int, w: int, seed: int, first_image: int = 0) -> torch.Tensor:
     """The counter generator's draws written out: [n, n_mc, h, w] f32 in [0, 1) (same values the counter entry points
     use inside the keep-flag kernel)."""
-    lib = load_library()
     dev = require_gpu()
     out = torch.empty((n, n_mc, h, w), dtype=torch.float32, device=dev)
-    _check(lib.runia_mc_draws_f32(out.data_ptr(), n, n_mc, h, w, int(seed) & (2**64 - 1), int(first_image), _stream()),
-           "runia_mc_draws_f32")
+    launch("runia_mc_draws_f32", out.data_ptr(), n, n_mc, h, w, int(seed) & (2**64 - 1), int(first_image))
     return out
 
 
 @_device_guard()
 def mc_drop_flat(x: torch.Tensor, rand: Optional[torch.Tensor], n_mc: int, drop_prob: float, block_size: int) -> torch.Tensor:
     """``layer_type="FC"/"RPN"`` form of the sampler: x [N,C,H,W] f32 -> [N*n_mc, C*H*W] f32 (no fullmean)."""
-    lib = load_library()
     require_gpu()
     assert x.is_cuda and x.dtype == torch.float32 and x.dim() == 4
     x = x.contiguous()
     n, c, h, w = x.shape
-    stride = 0
     if isinstance(rand, CounterDraws):
         rand = _explicit_counter_draws(rand, n, n_mc, h, w)
-    if rand is not None:
-        assert rand.is_cuda and rand.dtype == torch.float32
-        rand = rand.contiguous()
-        if rand.dim() == 4:
-            assert rand.shape == (n, n_mc, h, w)
-            stride = n_mc * h * w
-        else:
-            assert rand.shape == (n_mc, h, w)
+    rand, stride = _draws(rand, n, n_mc, h, w)
     e = c * h * w
     out = torch.empty((n * n_mc, e), dtype=torch.float32, device=x.device)
-    done = 0
-    while done < n:
-        m = min(65535, n - done)
+    for done, m in _image_slices(n):
         rp = None if rand is None else rand.data_ptr() + done * stride * 4
-        _check(
-            lib.runia_mc_drop_flat_f32(x.data_ptr() + done * e * 4, rp, stride, out.data_ptr() + done * n_mc * e * 4,
-                                       m, c, h, w, n_mc, float(drop_prob), int(block_size), _stream()),
-            "runia_mc_drop_flat_f32",
-        )
-        done += m
+        launch("runia_mc_drop_flat_f32", x.data_ptr() + done * e * 4, rp, stride, out.data_ptr() + done * n_mc * e * 4, m, c, h,
+               w, n_mc, float(drop_prob), int(block_size))
     return out
 
 
@@ -642,14 +652,12 @@ def map_reduce(x: torch.Tensor, h: int, w: int, mode: str) -> torch.Tensor:
     """x [..., h*w] f32 seen as maps of h x w -> ``mode="mean"``: mean over w, [maps, h]; ``mode="std"``: std over the
     rows of the per-row stds, [maps] (the reductions of ``get_mean_or_fullmean_ls_sample(., "mean")`` and
     ``get_std_ls_sample`` upstream)."""
-    lib = load_library()
     require_gpu()
     assert x.is_cuda and x.dtype == torch.float32 and x.numel() % (h * w) == 0 and mode in ("mean", "std")
     x = x.contiguous()
     maps = x.numel() // (h * w)
     out = torch.empty((maps, h) if mode == "mean" else (maps,), dtype=torch.float32, device=x.device)
-    _check(lib.runia_map_reduce_f32(x.data_ptr(), out.data_ptr(), maps, h, w, 0 if mode == "mean" else 1, _stream()),
-           "runia_map_reduce_f32")
+    launch("runia_map_reduce_f32", x.data_ptr(), out.data_ptr(), maps, h, w, 0 if mode == "mean" else 1)
     return out
 
 
@@ -696,7 +704,6 @@ def mcd_reduce_rows(x: torch.Tensor, table: torch.Tensor, mode: str, row0: int =
         f"rows {row0} + b * {row_step}, b < {b}, leave the table of {table.shape[0]} rows"
     assert x.is_cuda, "the activation must be a device tensor"
     assert table.is_cuda and table.device == x.device, "the table must be on the activation's device"
-    lib = load_library()
     require_gpu()
     if b == 0:
         return table
@@ -704,10 +711,9 @@ def mcd_reduce_rows(x: torch.Tensor, table: torch.Tensor, mode: str, row0: int =
         x = x[:, :, None, None]
     k, st, p = (int(v) for v in avg_pooling_parameters) if mode == "avgpool" else (0, 0, 0)
     ld = int(table.stride(0)) if table.shape[0] > 1 else max(int(table.stride(0)), int(table.shape[1]))
-    _check(lib.runia_mcd_reduce_rows(x.data_ptr(), ELEM_DTYPE_CODES[x.dtype], b, x.shape[1], x.shape[2], x.shape[3],
-                                     x.stride(0), x.stride(1), x.stride(2), x.stride(3), _MCD_MODES[mode], k, st, p,
-                                     table.data_ptr(), table.shape[0], ld, row0, row_step, _stream()),
-           "runia_mcd_reduce_rows")
+    launch("runia_mcd_reduce_rows", x.data_ptr(), ELEM_DTYPE_CODES[x.dtype], b, x.shape[1], x.shape[2], x.shape[3], x.stride(0),
+           x.stride(1), x.stride(2), x.stride(3), _MCD_MODES[mode], k, st, p, table.data_ptr(), table.shape[0], ld, row0,
+           row_step)
     return table
 
 
@@ -744,7 +750,6 @@ def ragged_rows(tensors, mode: str = "copy", out: Optional[torch.Tensor] = None,
     assert out.is_cuda and out.device == dev and out.dtype == dtype and out.dim() == 2 and out.shape[0] == total and \
         out.shape[1] >= d and (out.shape[1] <= 1 or out.stride(1) == 1) and (total <= 1 or out.stride(0) >= out.shape[1]), \
         f"the output must be a row-major ({total}, >= {d}) table of {dtype} on the tensors' device"
-    lib = load_library()
     require_gpu()
     seg = torch.empty(total, dtype=torch.int32, device=dev) if return_segments else None
     if total > 0 and d > 0:
@@ -753,42 +758,33 @@ def ragged_rows(tensors, mode: str = "copy", out: Optional[torch.Tensor] = None,
         packed = np.concatenate([desc[:n, :4].reshape(-1), desc[:, 4]])
         up = torch.from_numpy(packed).to(dev, non_blocking=False)
         ld = int(out.stride(0)) if total > 1 else max(int(out.stride(0)), int(out.shape[1]))
-        _check(lib.runia_ragged_rows(up.data_ptr(), up.data_ptr() + 32 * n, n, total, d, ELEM_DTYPE_CODES[dtype],
-                                     _RAGGED_MODES[mode], out.data_ptr(), ld, _ptr(seg), _stream()), "runia_ragged_rows")
+        launch("runia_ragged_rows", up.data_ptr(), up.data_ptr() + 32 * n, n, total, d, ELEM_DTYPE_CODES[dtype],
+               _RAGGED_MODES[mode], out.data_ptr(), ld, _ptr(seg))
     return (out, seg) if return_segments else out
+
+
+def _kl_samples(z: torch.Tensor, n_mc: int):
+    """Prologue of the kl_entropy wrappers: the GPU first, then z [N*n_mc, D] f32 on it -> ``(z contiguous, N, D)``."""
+    require_gpu()
+    assert z.is_cuda and z.dtype == torch.float32 and z.dim() == 2
+    return z.contiguous(), z.shape[0] // n_mc, z.shape[1]
 
 
 @_device_guard()
 def kl_entropy_per_dim(z: torch.Tensor, n_mc: int, k: int, min_dist: float = 1e-5) -> torch.Tensor:
     """z [N*n_mc, D] f32 -> h [N, D] f64."""
-    lib = load_library()
-    require_gpu()
-    assert z.is_cuda and z.dtype == torch.float32 and z.dim() == 2
-    z = z.contiguous()
-    n = z.shape[0] // n_mc
-    d = z.shape[1]
+    z, n, d = _kl_samples(z, n_mc)
     h = torch.empty((n, d), dtype=torch.float64, device=z.device)
-    _check(
-        lib.runia_kl_entropy_per_dim_f32(z.data_ptr(), h.data_ptr(), n, n_mc, d, k, min_dist, _stream()),
-        "runia_kl_entropy_per_dim_f32",
-    )
+    launch("runia_kl_entropy_per_dim_f32", z.data_ptr(), h.data_ptr(), n, n_mc, d, k, min_dist)
     return h
 
 
 @_device_guard()
 def kl_entropy_joint(z: torch.Tensor, n_mc: int, k: int, min_dist: float = 1e-5) -> torch.Tensor:
     """z [N*n_mc, D] f32 -> h_mvn [N] f64."""
-    lib = load_library()
-    require_gpu()
-    assert z.is_cuda and z.dtype == torch.float32 and z.dim() == 2
-    z = z.contiguous()
-    n = z.shape[0] // n_mc
-    d = z.shape[1]
+    z, n, d = _kl_samples(z, n_mc)
     h = torch.empty((n,), dtype=torch.float64, device=z.device)
-    _check(
-        lib.runia_kl_entropy_joint_f32(z.data_ptr(), h.data_ptr(), n, n_mc, d, k, min_dist, _stream()),
-        "runia_kl_entropy_joint_f32",
-    )
+    launch("runia_kl_entropy_joint_f32", z.data_ptr(), h.data_ptr(), n, n_mc, d, k, min_dist)
     return h
 
 
@@ -796,55 +792,43 @@ def kl_entropy_joint(z: torch.Tensor, n_mc: int, k: int, min_dist: float = 1e-5)
 def kl_entropy_both(z: torch.Tensor, n_mc: int, k: int, min_dist: float = 1e-5):
     """z [N*n_mc, D] f32 -> (h_mvn [N] f64, h [N, D] f64): both outputs of ``get_dl_h_z`` from one read of the samples
     (``runia_kl_entropy_both_f32``; same bits as :func:`kl_entropy_joint` and :func:`kl_entropy_per_dim`)."""
-    lib = load_library()
-    require_gpu()
-    assert z.is_cuda and z.dtype == torch.float32 and z.dim() == 2
-    z = z.contiguous()
-    n = z.shape[0] // n_mc
-    d = z.shape[1]
+    z, n, d = _kl_samples(z, n_mc)
     h_mvn = torch.empty((n,), dtype=torch.float64, device=z.device)
     h = torch.empty((n, d), dtype=torch.float64, device=z.device)
-    _check(lib.runia_kl_entropy_both_f32(z.data_ptr(), h_mvn.data_ptr(), h.data_ptr(), n, n_mc, d, k, min_dist, _stream()),
-           "runia_kl_entropy_both_f32")
+    launch("runia_kl_entropy_both_f32", z.data_ptr(), h_mvn.data_ptr(), h.data_ptr(), n, n_mc, d, k, min_dist)
     return h_mvn, h
 
 
 @_device_guard()
 def pack_weights(b: torch.Tensor) -> torch.Tensor:
     """B [K, n] f64 (device) -> fragment-ordered copy for the f64 MFMA kernels."""
-    lib = load_library()
     require_gpu()
     assert b.is_cuda and b.dtype == torch.float64 and b.dim() == 2
     b = b.contiguous()
     k, n = b.shape
-    nbytes = lib.runia_packed_weights_bytes(k, n)
-    packed = torch.empty((nbytes // 8,), dtype=torch.float64, device=b.device)
-    _check(lib.runia_pack_weights_f64(b.data_ptr(), n, k, n, packed.data_ptr(), _stream()), "runia_pack_weights_f64")
+    packed = torch.empty((query("runia_packed_weights_bytes", k, n) // 8,), dtype=torch.float64, device=b.device)
+    launch("runia_pack_weights_f64", b.data_ptr(), n, k, n, packed.data_ptr())
     return packed
 
 
 @_device_guard()
 def pca_transform(x: torch.Tensor, packed_ct: torch.Tensor, bias: torch.Tensor, scale: Optional[torch.Tensor], n: int) -> torch.Tensor:
     """x [N, D] f64/f32 -> y [N, n] f64."""
-    lib = load_library()
     require_gpu()
     assert x.is_cuda and x.dim() == 2 and x.dtype in (torch.float32, torch.float64)
     x = x.contiguous()
     nrow, d = x.shape
     y = torch.empty((nrow, n), dtype=torch.float64, device=x.device)
-    fn = lib.runia_pca_transform_f32in if x.dtype == torch.float32 else lib.runia_pca_transform_f64
-    _check(
-        fn(x.data_ptr(), packed_ct.data_ptr(), bias.data_ptr(), _ptr(scale), y.data_ptr(), nrow, d, n,
-           0 if scale is None else 1, _stream()),
-        "runia_pca_transform",
-    )
+    launch("runia_pca_transform_f32in" if x.dtype == torch.float32 else "runia_pca_transform_f64", x.data_ptr(),
+           packed_ct.data_ptr(), bias.data_ptr(), _ptr(scale), y.data_ptr(), nrow, d, n, 0 if scale is None else 1)
     return y
 
 
 @_device_guard()
-def md_score(x: torch.Tensor, mean: torch.Tensor, packed_p: torch.Tensor) -> torch.Tensor:
+def md_score(x: torch.Tensor, mean: torch.Tensor, packed_p: torch.Tensor, *, _family: str = "runia_md_score_ws") -> torch.Tensor:
     """x [N, n] (f64 or f32), mean [n] (f64 or f32) -> score [N] f64 = -(x-mean) P (x-mean)^T,
-    with ``x - mean`` formed under NumPy's dtype rules (f32 only when both are f32)."""
+    with ``x - mean`` formed under NumPy's dtype rules (f32 only when both are f32).  (``_family``: the entry points' common
+    prefix; ``md_score_tril`` is this body on ``runia_md_score_tril_*``.)"""
     lib = load_library()
     require_gpu()
     assert x.is_cuda and x.dim() == 2 and x.dtype in (torch.float32, torch.float64)
@@ -852,46 +836,25 @@ def md_score(x: torch.Tensor, mean: torch.Tensor, packed_p: torch.Tensor) -> tor
     nrow, n = x.shape
     if x.dtype == torch.float64:
         mean = mean.to(torch.float64)
-        fn = lib.runia_md_score_ws_f64
+        name = _family + "_f64"
     elif mean.dtype == torch.float32:
-        fn = lib.runia_md_score_ws_f32
+        name = _family + "_f32"
     else:
         mean = mean.to(torch.float64)
-        fn = lib.runia_md_score_ws_f32x_f64mean
+        name = _family + "_f32x_f64mean"
     mean = mean.contiguous()
     s = torch.empty((nrow,), dtype=torch.float64, device=x.device)
     # few rows of wide features: column blocks on separate workgroups + a replay launch (same bits, see runia_hip.h)
     ws_bytes = int(lib.runia_md_score_workspace_bytes(nrow, n))
     ws = torch.empty(ws_bytes, dtype=torch.uint8, device=x.device) if ws_bytes else None
-    _check(fn(x.data_ptr(), mean.data_ptr(), packed_p.data_ptr(), s.data_ptr(), _ptr(ws), ws_bytes, nrow, n, _stream()),
-           "runia_md_score_ws")
+    launch(name, x.data_ptr(), mean.data_ptr(), packed_p.data_ptr(), s.data_ptr(), _ptr(ws), ws_bytes, nrow, n)
     return s
 
 
-@_device_guard()
 def md_score_tril(x: torch.Tensor, mean: torch.Tensor, packed_wt: torch.Tensor) -> torch.Tensor:
     """``md_score`` from the triangular factor of the precision (``runia_md_score_tril_*``): precision = W^T W with W lower
     triangular, ``packed_wt = pack_weights(W^T)``; score [N] f64 = -|| W (x - mean) ||^2, same centring rules as ``md_score``."""
-    lib = load_library()
-    require_gpu()
-    assert x.is_cuda and x.dim() == 2 and x.dtype in (torch.float32, torch.float64)
-    x = x.contiguous()
-    nrow, n = x.shape
-    if x.dtype == torch.float64:
-        mean = mean.to(torch.float64)
-        fn = lib.runia_md_score_tril_f64
-    elif mean.dtype == torch.float32:
-        fn = lib.runia_md_score_tril_f32
-    else:
-        mean = mean.to(torch.float64)
-        fn = lib.runia_md_score_tril_f32x_f64mean
-    mean = mean.contiguous()
-    s = torch.empty((nrow,), dtype=torch.float64, device=x.device)
-    ws_bytes = int(lib.runia_md_score_workspace_bytes(nrow, n))  # few rows of wide features: column blocks + replay (same bits)
-    ws = torch.empty(ws_bytes, dtype=torch.uint8, device=x.device) if ws_bytes else None
-    _check(fn(x.data_ptr(), mean.data_ptr(), packed_wt.data_ptr(), s.data_ptr(), _ptr(ws), ws_bytes, nrow, n, _stream()),
-           "runia_md_score_tril")
-    return s
+    return md_score(x, mean, packed_wt, _family="runia_md_score_tril")
 
 
 @_device_guard()
@@ -901,7 +864,6 @@ def mahalanobis_score(x: torch.Tensor, class_mean: torch.Tensor, packed_p: torch
     workspace only (more than 16 classes then take the per-class loop instead of the matrix-core form; tests).
     ``split=False`` (up to 16 classes; tests and measurements) hands over NO workspace: the entry point then keeps the
     one-launch form instead of the column-split launches - the same bits."""
-    lib = load_library()
     require_gpu()
     assert x.is_cuda and x.dim() == 2 and x.dtype == class_mean.dtype
     x = x.contiguous()
@@ -909,40 +871,36 @@ def mahalanobis_score(x: torch.Tensor, class_mean: torch.Tensor, packed_p: torch
     nrow, d = x.shape
     c = class_mean.shape[0]
     s = torch.empty((nrow,), dtype=torch.float64, device=x.device)
-    ws_bytes = lib.runia_mahalanobis_workspace_bytes(nrow, d) if class_loop else lib.runia_mahalanobis_workspace_bytes_classes(nrow, d, c)
-    ws = torch.empty((max(ws_bytes, 8) // 8,), dtype=torch.float64, device=x.device)
+    ws_bytes = (query("runia_mahalanobis_workspace_bytes", nrow, d) if class_loop
+                else query("runia_mahalanobis_workspace_bytes_classes", nrow, d, c))
+    ws = workspace(ws_bytes, x.device, 8)
     no_ws = (not split) and c <= 16
-    fn = lib.runia_mahalanobis_score_f32 if x.dtype == torch.float32 else lib.runia_mahalanobis_score_f64
-    _check(
-        fn(x.data_ptr(), class_mean.data_ptr(), packed_p.data_ptr(), mu_p.data_ptr(), s.data_ptr(),
-           None if no_ws else ws.data_ptr(), 0 if no_ws else ws_bytes, nrow, d, c, _stream()),
-        "runia_mahalanobis_score",
-    )
+    launch("runia_mahalanobis_score_f32" if x.dtype == torch.float32 else "runia_mahalanobis_score_f64", x.data_ptr(),
+           class_mean.data_ptr(), packed_p.data_ptr(), mu_p.data_ptr(), s.data_ptr(), None if no_ws else ws.data_ptr(),
+           0 if no_ws else ws_bytes, nrow, d, c)
     return s
 
 
 @_device_guard()
 def row_lse_msp(logits: torch.Tensor, want_lse: bool = True, want_msp: bool = False):
     """logits [N, C] f32 -> (lse [N] f32 | None, msp [N] f32 | None)."""
-    lib = load_library()
     require_gpu()
     assert logits.is_cuda and logits.dtype == torch.float32 and logits.dim() == 2
     logits = logits.contiguous()
     n, c = logits.shape
     lse = torch.empty((n,), dtype=torch.float32, device=logits.device) if want_lse else None
     msp = torch.empty((n,), dtype=torch.float32, device=logits.device) if want_msp else None
-    _check(lib.runia_row_lse_msp_f32(logits.data_ptr(), _ptr(lse), _ptr(msp), n, c, _stream()), "runia_row_lse_msp_f32")
+    launch("runia_row_lse_msp_f32", logits.data_ptr(), _ptr(lse), _ptr(msp), n, c)
     return lse, msp
 
 
 @_device_guard()
 def l2_normalize(x: torch.Tensor) -> torch.Tensor:
-    lib = load_library()
     require_gpu()
     assert x.is_cuda and x.dtype == torch.float32 and x.dim() == 2
     x = x.contiguous()
     y = torch.empty_like(x)
-    _check(lib.runia_l2_normalize_f32(x.data_ptr(), y.data_ptr(), x.shape[0], x.shape[1], _stream()), "runia_l2_normalize_f32")
+    launch("runia_l2_normalize_f32", x.data_ptr(), y.data_ptr(), x.shape[0], x.shape[1])
     return y
 
 
@@ -951,13 +909,12 @@ def knn_prepare_bank(bank: torch.Tensor) -> torch.Tensor:
     """Once per bank: squared row norms, their maximum and (banks the bf16 kernel can take) the bf16 pieces, as one
     device buffer for ``knn_kth(..., state=)``.  A deployed index scores many batches against the same bank; each call
     then skips the bank passes (50 000 x 2048: 0.4 ms)."""
-    lib = load_library()
     require_gpu()
     assert bank.is_cuda and bank.dtype == torch.float32 and bank.dim() == 2 and bank.is_contiguous()
     m, d = bank.shape
-    nbytes = int(lib.runia_knn_bank_state_bytes(m, d))
+    nbytes = query("runia_knn_bank_state_bytes", m, d)
     state = torch.empty((max(nbytes, 16) + 15) // 16 * 4, dtype=torch.float32, device=bank.device)  # (16-byte granules)
-    _check(lib.runia_knn_prepare_bank_f32(bank.data_ptr(), state.data_ptr(), nbytes, m, d, _stream()), "runia_knn_prepare_bank_f32")
+    launch("runia_knn_prepare_bank_f32", bank.data_ptr(), state.data_ptr(), nbytes, m, d)
     return state
 
 
@@ -978,33 +935,26 @@ def knn_kth(q: torch.Tensor, bank: torch.Tensor, k: int, state: Optional[torch.T
     if state is not None and m > 0 and n > 0:
         ws_bytes = (qc * m + qc) * 4 if f32_only else int(lib.runia_knn_prepared_workspace_bytes(n, m, d, k))
         ws = torch.empty((max(ws_bytes, 4) // 4,), dtype=torch.float32, device=q.device)
-        _check(
-            lib.runia_knn_kth_prepared_f32(q.data_ptr(), bank.data_ptr(), state.data_ptr(), state.numel() * 4, s.data_ptr(),
-                                           ws.data_ptr(), ws_bytes, n, m, d, int(k), _stream()),
-            "runia_knn_kth_prepared_f32",
-        )
+        launch("runia_knn_kth_prepared_f32", q.data_ptr(), bank.data_ptr(), state.data_ptr(), state.numel() * 4, s.data_ptr(),
+               ws.data_ptr(), ws_bytes, n, m, d, int(k))
         return s
     ws_bytes = lib.runia_knn_workspace_bytes(n, m, d, k)
     if f32_only and lib.runia_knn_piece_products(n, m, d) > 0:
         # the f32 kernel's workspace (one chunk of distances, |q|^2, |b|^2, max |b|^2): the entry point then keeps that kernel
         ws_bytes = (qc * m + qc + m + 4) * 4
     ws = torch.empty((max(ws_bytes, 4) // 4,), dtype=torch.float32, device=q.device)
-    _check(
-        lib.runia_knn_kth_f32(q.data_ptr(), bank.data_ptr(), s.data_ptr(), ws.data_ptr(), ws_bytes, n, m, d, int(k), _stream()),
-        "runia_knn_kth_f32",
-    )
+    launch("runia_knn_kth_f32", q.data_ptr(), bank.data_ptr(), s.data_ptr(), ws.data_ptr(), ws_bytes, n, m, d, int(k))
     return s
 
 
 @_device_guard()
 def row_sqnorm(x: torch.Tensor) -> torch.Tensor:
     """x [N, D] f64 -> squared row norms [N] f64."""
-    lib = load_library()
     require_gpu()
     assert x.is_cuda and x.dtype == torch.float64 and x.dim() == 2
     x = x.contiguous()
     out = torch.empty((x.shape[0],), dtype=torch.float64, device=x.device)
-    _check(lib.runia_row_sqnorm_f64(x.data_ptr(), out.data_ptr(), x.shape[0], x.shape[1], _stream()), "runia_row_sqnorm_f64")
+    launch("runia_row_sqnorm_f64", x.data_ptr(), out.data_ptr(), x.shape[0], x.shape[1])
     return out
 
 
@@ -1022,25 +972,22 @@ def kde_pack_train(train: torch.Tensor):
 @_device_guard()
 def kde_score_packed(state, x: torch.Tensor, bandwidth: float = 1.0) -> torch.Tensor:
     """Gaussian-KDE log-density [N] f64 of x [N, D] f64 against a packed training set (matrix-core path)."""
-    lib = load_library()
     require_gpu()
     packed, tn, m, d, mean = state
     assert x.is_cuda and x.dtype == torch.float64 and x.dim() == 2 and x.shape[1] == d
     x = (x - mean).contiguous()
     n = x.shape[0]
     out = torch.empty((n,), dtype=torch.float64, device=x.device)
-    ws_bytes = int(lib.runia_kde_workspace_bytes(n, m))  # query norms (+ the values of the column-split launch on few rows)
-    ws = torch.empty((max(ws_bytes // 8, 1),), dtype=torch.float64, device=x.device)
-    _check(lib.runia_kde_score_packed_f64(packed.data_ptr(), tn.data_ptr(), x.data_ptr(), out.data_ptr(), ws.data_ptr(),
-                                          ws_bytes, m, n, d, float(bandwidth), _stream()),
-           "runia_kde_score_packed_f64")
+    ws_bytes = query("runia_kde_workspace_bytes", n, m)  # query norms (+ the values of the column-split launch on few rows)
+    ws = workspace(ws_bytes, x.device, 8)
+    launch("runia_kde_score_packed_f64", packed.data_ptr(), tn.data_ptr(), x.data_ptr(), out.data_ptr(), ws.data_ptr(), ws_bytes,
+           m, n, d, float(bandwidth))
     return out
 
 
 @_device_guard()
 def kde_score(train: torch.Tensor, x: torch.Tensor, bandwidth: float = 1.0) -> torch.Tensor:
     """train [M, D] f64, x [N, D] f64 -> gaussian-KDE log-density [N] f64."""
-    lib = load_library()
     require_gpu()
     assert train.is_cuda and x.is_cuda and train.dtype == torch.float64 and x.dtype == torch.float64
     train = train.contiguous()
@@ -1048,10 +995,7 @@ def kde_score(train: torch.Tensor, x: torch.Tensor, bandwidth: float = 1.0) -> t
     m, d = train.shape
     n = x.shape[0]
     s = torch.empty((n,), dtype=torch.float64, device=x.device)
-    _check(
-        lib.runia_kde_score_f64(train.data_ptr(), x.data_ptr(), s.data_ptr(), m, n, d, float(bandwidth), _stream()),
-        "runia_kde_score_f64",
-    )
+    launch("runia_kde_score_f64", train.data_ptr(), x.data_ptr(), s.data_ptr(), m, n, d, float(bandwidth))
     return s
 
 
@@ -1079,26 +1023,24 @@ def _timed_launch_events():
     if not pool:
         reserve_timed_events(1)
     e0, e1 = pool.pop()
-    _check(load_library().runia_time_next_launch(e0.cuda_event, e1.cuda_event), "runia_time_next_launch")
+    call("runia_time_next_launch", e0.cuda_event, e1.cuda_event)
     return e0, e1
 
 
-def _timed_call(fn, what: str):
-    """Arm an event pair, run the entry point ``fn()`` (-> return code), and ALWAYS disarm afterwards: an entry point that
-    returns before its timed launch site (unsupported shape, short workspace) must not leave the pair to the thread's next,
-    unrelated launch.  Returns the pair; raises as ``_check`` does (the pair of a failed call never received timestamps and is
-    dropped)."""
+def _timed_call(name: str, *args):
+    """Arm an event pair, ``launch(name, *args)``, and ALWAYS disarm afterwards: an entry point that returns before its
+    timed launch site (unsupported shape, short workspace) must not leave the pair to the thread's next, unrelated launch.
+    Returns the pair; raises as ``launch`` does (the pair of a failed call never received timestamps and is dropped)."""
     e0, e1 = _timed_launch_events()
     try:
-        rc = fn()
+        launch(name, *args)
     finally:
         load_library().runia_time_next_launch(None, None)
-    _check(rc, what)
     return e0, e1
 
 
 def mc_entropy_supported(h: int, w: int, n_mc: int, k: int) -> bool:
-    return bool(load_library().runia_mc_entropy_supported(int(h), int(w), int(n_mc), int(k)))
+    return bool(query("runia_mc_entropy_supported", int(h), int(w), int(n_mc), int(k)))
 
 
 @_device_guard()
@@ -1116,22 +1058,12 @@ def mc_mask_table(rand: Union[torch.Tensor, CounterDraws, None], n: int, h: int,
         out = torch.empty(max(ws_bytes, 16), dtype=torch.uint8, device=dev)
     assert out.is_cuda and out.dtype == torch.uint8 and out.numel() >= ws_bytes
     if isinstance(rand, CounterDraws):
-        _check(lib.runia_mc_mask_table_counter_f32(int(rand.seed) & (2**64 - 1), int(rand.first_image), out.data_ptr(),
-                                                   ws_bytes, n, h, w, n_mc, float(drop_prob), int(block_size),
-                                                   int(bool(rand.redraw_dead_layers)), _stream()),
-               "runia_mc_mask_table_counter_f32")
+        launch("runia_mc_mask_table_counter_f32", int(rand.seed) & (2**64 - 1), int(rand.first_image), out.data_ptr(), ws_bytes,
+               n, h, w, n_mc, float(drop_prob), int(block_size), int(bool(rand.redraw_dead_layers)))
         return out
-    stride = 0
-    if rand is not None:
-        assert rand.is_cuda and rand.dtype == torch.float32 and rand.is_contiguous()
-        if rand.dim() == 4:
-            assert rand.shape == (n, n_mc, h, w)
-            stride = n_mc * h * w
-        else:
-            assert rand.shape == (n_mc, h, w)
-    _check(lib.runia_mc_mask_table_f32(_ptr(rand), stride, out.data_ptr(), ws_bytes, n, h, w, n_mc,
-                                       float(drop_prob) if rand is not None else 0.0, int(block_size), _stream()),
-           "runia_mc_mask_table_f32")
+    rand, stride = _draws(rand, n, n_mc, h, w, copy=False)
+    launch("runia_mc_mask_table_f32", _ptr(rand), stride, out.data_ptr(), ws_bytes, n, h, w, n_mc,
+           float(drop_prob) if rand is not None else 0.0, int(block_size))
     return out
 
 
@@ -1159,25 +1091,15 @@ def mc_entropy(x: torch.Tensor, rand: Union[torch.Tensor, CounterDraws, None], n
         assert table.is_cuda and table.numel() >= ws_bytes and n <= 65535
         if zero_fill is not None:
             assert zero_fill.is_cuda and zero_fill.dtype == torch.float64 and zero_fill.shape == (n,) and zero_fill.is_contiguous()
-        call = lambda: lib.runia_mc_entropy_from_table_f32(x.data_ptr(), table.data_ptr(), ws_bytes, h.data_ptr(), _ptr(z),  # noqa: E731
-                                                           _ptr(zero_fill), n, c, hh, ww, n_mc, int(k), float(min_dist), _stream())
+        args = (x.data_ptr(), table.data_ptr(), ws_bytes, h.data_ptr(), _ptr(z), _ptr(zero_fill), n, c, hh, ww, n_mc, int(k),
+                float(min_dist))
         if kernel_events is not None:
-            kernel_events.append(_timed_call(call, "runia_mc_entropy_from_table_f32"))
+            kernel_events.append(_timed_call("runia_mc_entropy_from_table_f32", *args))
         else:
-            _check(call(), "runia_mc_entropy_from_table_f32")
+            launch("runia_mc_entropy_from_table_f32", *args)
         return (h, z) if want_samples else h
-    stride = 0
     counter = rand if isinstance(rand, CounterDraws) else None
-    if counter is not None:
-        rand = None
-    if rand is not None:
-        assert rand.is_cuda and rand.dtype == torch.float32
-        rand = rand.contiguous()
-        if rand.dim() == 4:
-            assert rand.shape == (n, n_mc, hh, ww)
-            stride = n_mc * hh * ww
-        else:
-            assert rand.shape == (n_mc, hh, ww)
+    rand, stride = _draws(None if counter is not None else rand, n, n_mc, hh, ww)
     if out is None:
         h = torch.empty((n, c), dtype=torch.float64, device=x.device)
     else:
@@ -1188,48 +1110,28 @@ def mc_entropy(x: torch.Tensor, rand: Union[torch.Tensor, CounterDraws, None], n
         assert zero_fill.is_cuda and zero_fill.dtype == torch.float64 and zero_fill.shape == (n,) and zero_fill.is_contiguous()
     ws_bytes = int(lib.runia_mc_entropy_workspace_bytes(min(65535, n), hh, ww, n_mc))
     ws = torch.empty(max(ws_bytes, 16), dtype=torch.uint8, device=x.device)  # stream-ordered: reused per slice
-    done = 0
-    while done < n:
-        m = min(65535, n - done)
+    if counter is not None:
+        seed, redraw = int(counter.seed) & (2**64 - 1), int(bool(counter.redraw_dead_layers))
+    for done, m in _image_slices(n):
+        xp, hp = x.data_ptr() + done * c * hh * ww * 4, h.data_ptr() + done * c * 8
         rp = None if rand is None else rand.data_ptr() + done * stride * 4
         zp = None if z is None else z.data_ptr() + done * n_mc * c * 4
         zf = None if zero_fill is None else zero_fill.data_ptr() + done * 8
-        if counter is not None and kernel_events is None:
-            _check(
-                lib.runia_mc_entropy_counter_f32(x.data_ptr() + done * c * hh * ww * 4, int(counter.seed) & (2**64 - 1),
-                                                 int(counter.first_image) + done, h.data_ptr() + done * c * 8, zp, zf,
-                                                 ws.data_ptr(), ws_bytes, m, c, hh, ww, n_mc, float(drop_prob),
-                                                 int(block_size), int(k), float(min_dist),
-                                                 int(bool(counter.redraw_dead_layers)), _stream()),
-                "runia_mc_entropy_counter_f32",
-            )
-        elif kernel_events is None:
-            _check(
-                lib.runia_mc_entropy_f32(x.data_ptr() + done * c * hh * ww * 4, rp, stride, h.data_ptr() + done * c * 8,
-                                         zp, zf, ws.data_ptr(), ws_bytes, m, c, hh, ww, n_mc, float(drop_prob),
-                                         int(block_size), int(k), float(min_dist), _stream()),
-                "runia_mc_entropy_f32",
-            )
-        else:
+        if kernel_events is not None:  # the keep-flag table on its own, then the timed sampler + entropy launch
             if counter is not None:
-                _check(
-                    lib.runia_mc_mask_table_counter_f32(int(counter.seed) & (2**64 - 1), int(counter.first_image) + done,
-                                                        ws.data_ptr(), ws_bytes, m, hh, ww, n_mc, float(drop_prob),
-                                                        int(block_size), int(bool(counter.redraw_dead_layers)), _stream()),
-                    "runia_mc_mask_table_counter_f32",
-                )
+                launch("runia_mc_mask_table_counter_f32", seed, int(counter.first_image) + done, ws.data_ptr(), ws_bytes, m, hh,
+                       ww, n_mc, float(drop_prob), int(block_size), redraw)
             else:
-                _check(
-                    lib.runia_mc_mask_table_f32(rp, stride, ws.data_ptr(), ws_bytes, m, hh, ww, n_mc, float(drop_prob),
-                                                int(block_size), _stream()),
-                    "runia_mc_mask_table_f32",
-                )
-            kernel_events.append(_timed_call(
-                lambda: lib.runia_mc_entropy_from_table_f32(x.data_ptr() + done * c * hh * ww * 4, ws.data_ptr(), ws_bytes,
-                                                            h.data_ptr() + done * c * 8, zp, zf, m, c, hh, ww, n_mc, int(k),
-                                                            float(min_dist), _stream()),
-                "runia_mc_entropy_from_table_f32"))
-        done += m
+                launch("runia_mc_mask_table_f32", rp, stride, ws.data_ptr(), ws_bytes, m, hh, ww, n_mc, float(drop_prob),
+                       int(block_size))
+            kernel_events.append(_timed_call("runia_mc_entropy_from_table_f32", xp, ws.data_ptr(), ws_bytes, hp, zp, zf, m, c, hh,
+                                             ww, n_mc, int(k), float(min_dist)))
+        elif counter is not None:
+            launch("runia_mc_entropy_counter_f32", xp, seed, int(counter.first_image) + done, hp, zp, zf, ws.data_ptr(), ws_bytes,
+                   m, c, hh, ww, n_mc, float(drop_prob), int(block_size), int(k), float(min_dist), redraw)
+        else:
+            launch("runia_mc_entropy_f32", xp, rp, stride, hp, zp, zf, ws.data_ptr(), ws_bytes, m, c, hh, ww, n_mc,
+                   float(drop_prob), int(block_size), int(k), float(min_dist))
     return (h, z) if want_samples else h
 
 
@@ -1237,15 +1139,12 @@ def mc_entropy(x: torch.Tensor, rand: Union[torch.Tensor, CounterDraws, None], n
 def proj_sq_accumulate(h: torch.Tensor, packed_m: torch.Tensor, c: torch.Tensor, r: int, out: torch.Tensor) -> torch.Tensor:
     """``out`` [N] f64 += -|| M h + c ||^2 where ``out`` was zeroed earlier on the stream (``mc_entropy(zero_fill=out)``):
     the score of ``proj_sq_score`` bit for bit, without its workspace and combine launch."""
-    lib = load_library()
     require_gpu()
     assert h.is_cuda and h.dtype == torch.float64 and h.dim() == 2
     h = h.contiguous()
     nrow, d = h.shape
     assert out.is_cuda and out.dtype == torch.float64 and out.shape == (nrow,) and out.is_contiguous()
-    _check(lib.runia_proj_sq_accumulate_f64(h.data_ptr(), packed_m.data_ptr(), c.data_ptr(), out.data_ptr(), nrow, d, int(r),
-                                            _stream()),
-           "runia_proj_sq_accumulate_f64")
+    launch("runia_proj_sq_accumulate_f64", h.data_ptr(), packed_m.data_ptr(), c.data_ptr(), out.data_ptr(), nrow, d, int(r))
     return out
 
 
@@ -1254,7 +1153,6 @@ def pca_md_score(h: torch.Tensor, packed_ct: Optional[torch.Tensor], bias: Optio
                  scale: Optional[torch.Tensor], md_mean: torch.Tensor, packed_p: torch.Tensor, n: int,
                  want_projection: bool = False, out: Optional[torch.Tensor] = None):
     """Fused PCA transform + LaREM score: h [N, D] f64 -> score [N] f64 (projected rows stay on chip)."""
-    lib = load_library()
     require_gpu()
     assert h.is_cuda and h.dtype == torch.float64 and h.dim() == 2
     h = h.contiguous()
@@ -1265,43 +1163,37 @@ def pca_md_score(h: torch.Tensor, packed_ct: Optional[torch.Tensor], bias: Optio
         assert out.is_cuda and out.dtype == torch.float64 and out.shape == (nrow,) and out.is_contiguous()
         s = out
     y = torch.empty((nrow, n), dtype=torch.float64, device=h.device) if want_projection else None
-    _check(
-        lib.runia_pca_md_score_f64(h.data_ptr(), _ptr(packed_ct), _ptr(bias), _ptr(scale), md_mean.data_ptr(),
-                                   packed_p.data_ptr(), s.data_ptr(), _ptr(y), nrow, d, n, _stream()),
-        "runia_pca_md_score_f64",
-    )
+    launch("runia_pca_md_score_f64", h.data_ptr(), _ptr(packed_ct), _ptr(bias), _ptr(scale), md_mean.data_ptr(),
+           packed_p.data_ptr(), s.data_ptr(), _ptr(y), nrow, d, n)
     return (s, y) if want_projection else s
 
 
 @_device_guard()
 def covariance(x: torch.Tensor):
     """x [N, D] f64/f32 (device) -> (mean [D] f64, cov [D, D] f64) = np.cov(x.T, bias=1) with its column means."""
-    lib = load_library()
     require_gpu()
     assert x.is_cuda and x.dim() == 2 and x.dtype in (torch.float32, torch.float64)
     x = x.contiguous()
     n, d = x.shape
     mean = torch.empty((d,), dtype=torch.float64, device=x.device)
     cov = torch.empty((d, d), dtype=torch.float64, device=x.device)
-    ws_bytes = lib.runia_covariance_workspace_bytes(n, d)
-    ws = torch.empty((max(ws_bytes, 8) // 8,), dtype=torch.float64, device=x.device)
-    fn = lib.runia_covariance_f32in if x.dtype == torch.float32 else lib.runia_covariance_f64
-    _check(fn(x.data_ptr(), mean.data_ptr(), cov.data_ptr(), ws.data_ptr(), ws_bytes, n, d, _stream()), "runia_covariance")
+    ws_bytes = query("runia_covariance_workspace_bytes", n, d)
+    ws = workspace(ws_bytes, x.device, 8)
+    launch("runia_covariance_f32in" if x.dtype == torch.float32 else "runia_covariance_f64", x.data_ptr(), mean.data_ptr(),
+           cov.data_ptr(), ws.data_ptr(), ws_bytes, n, d)
     return mean, cov
 
 
 @_device_guard()
 def linear(x: torch.Tensor, w: torch.Tensor, bias: Optional[torch.Tensor], clip_max: float = float("inf")) -> torch.Tensor:
     """logits [N, C] = min(x, clip_max) @ w.T + bias  (x [N, D], w [C, D], all f32 on the device)."""
-    lib = load_library()
     require_gpu()
     assert x.is_cuda and w.is_cuda and x.dtype == torch.float32 and w.dtype == torch.float32 and x.shape[1] == w.shape[1]
     x, w = x.contiguous(), w.contiguous()
     n, d = x.shape
     c = w.shape[0]
     out = torch.empty((n, c), dtype=torch.float32, device=x.device)
-    _check(lib.runia_linear_f32(x.data_ptr(), w.data_ptr(), _ptr(bias), out.data_ptr(), n, d, c, float(clip_max), _stream()),
-           "runia_linear_f32")
+    launch("runia_linear_f32", x.data_ptr(), w.data_ptr(), _ptr(bias), out.data_ptr(), n, d, c, float(clip_max))
     return out
 
 
@@ -1309,16 +1201,14 @@ def linear(x: torch.Tensor, w: torch.Tensor, bias: Optional[torch.Tensor], clip_
 def ash_s(x: torch.Tensor, percentile: int) -> torch.Tensor:
     """ASH-S of 2-D activations (``ash_s_linear_layer``): rows of up to 4 096 features in registers (wave per row), longer
     rows through the radix-select kernel (workgroup per row)."""
-    lib = load_library()
     require_gpu()
     assert x.is_cuda and x.dtype == torch.float32 and x.dim() == 2
     x = x.contiguous()
     y = torch.empty_like(x)
     if x.shape[1] <= 4096:
-        _check(lib.runia_ash_s_f32(x.data_ptr(), y.data_ptr(), x.shape[0], x.shape[1], int(percentile), _stream()), "runia_ash_s_f32")
+        launch("runia_ash_s_f32", x.data_ptr(), y.data_ptr(), x.shape[0], x.shape[1], int(percentile))
     else:
-        _check(lib.runia_ash_s_rows_f32(x.data_ptr(), y.data_ptr(), None, x.shape[0], x.shape[1], int(percentile), 1, _stream()),
-               "runia_ash_s_rows_f32")
+        launch("runia_ash_s_rows_f32", x.data_ptr(), y.data_ptr(), None, x.shape[0], x.shape[1], int(percentile), 1)
     return y
 
 
@@ -1327,7 +1217,6 @@ def ash_s_conv(x: torch.Tensor, percentile: int, prune_in_place: bool = True) ->
     """ASH-S of (B, C, H, W) maps (``ash_s_conv_layer``): per sample the k largest of its C*H*W activations are kept and
     the sample is multiplied by exp(sum / kept sum).  ``prune_in_place``: ``x`` itself is left pruned, as the
     reference's ``view`` + ``scatter_`` leaves its argument (x must then be contiguous)."""
-    lib = load_library()
     require_gpu()
     assert x.is_cuda and x.dtype == torch.float32 and x.dim() == 4
     assert x.is_contiguous() or not prune_in_place
@@ -1335,21 +1224,19 @@ def ash_s_conv(x: torch.Tensor, percentile: int, prune_in_place: bool = True) ->
     b = xc.shape[0]
     d = xc.numel() // max(b, 1)
     y = torch.empty_like(xc)
-    _check(lib.runia_ash_s_rows_f32(xc.data_ptr(), y.data_ptr(), xc.data_ptr() if prune_in_place else None, b, d, int(percentile),
-                                    0, _stream()), "runia_ash_s_rows_f32")
+    launch("runia_ash_s_rows_f32", xc.data_ptr(), y.data_ptr(), xc.data_ptr() if prune_in_place else None, b, d, int(percentile),
+           0)
     return y
 
 
 @_device_guard()
 def gen_entropy(probs: torch.Tensor, gamma: float, m: int) -> torch.Tensor:
     """``generalized_entropy(probs, gamma, M)`` on rows that already are probabilities -> [N] f32."""
-    lib = load_library()
     require_gpu()
     assert probs.is_cuda and probs.dtype == torch.float32 and probs.dim() == 2
     probs = probs.contiguous()
     s = torch.empty((probs.shape[0],), dtype=torch.float32, device=probs.device)
-    _check(lib.runia_gen_entropy_f32(probs.data_ptr(), s.data_ptr(), probs.shape[0], probs.shape[1], int(m), float(gamma), _stream()),
-           "runia_gen_entropy_f32")
+    launch("runia_gen_entropy_f32", probs.data_ptr(), s.data_ptr(), probs.shape[0], probs.shape[1], int(m), float(gamma))
     return s
 
 
@@ -1357,7 +1244,6 @@ def gen_entropy(probs: torch.Tensor, gamma: float, m: int) -> torch.Tensor:
 def mcd_uncertainty(logits: torch.Tensor, n_mc: int, want_probs: bool = False):
     """logits [N * n_mc, C] f32 (an image's MC rows consecutive) -> (pred_h [N], mi [N], softmax rows or None): the
     predictive entropy of the mean distribution and the mutual information, one launch."""
-    lib = load_library()
     require_gpu()
     assert logits.is_cuda and logits.dtype == torch.float32 and logits.dim() == 2 and logits.shape[0] % n_mc == 0
     logits = logits.contiguous()
@@ -1365,8 +1251,7 @@ def mcd_uncertainty(logits: torch.Tensor, n_mc: int, want_probs: bool = False):
     ph = torch.empty((n,), dtype=torch.float32, device=logits.device)
     mi = torch.empty((n,), dtype=torch.float32, device=logits.device)
     probs = torch.empty_like(logits) if want_probs else None
-    _check(lib.runia_mcd_uncertainty_f32(logits.data_ptr(), _ptr(probs), ph.data_ptr(), mi.data_ptr(), n, int(n_mc), c, _stream()),
-           "runia_mcd_uncertainty_f32")
+    launch("runia_mcd_uncertainty_f32", logits.data_ptr(), _ptr(probs), ph.data_ptr(), mi.data_ptr(), n, int(n_mc), c)
     return ph, mi, probs
 
 
@@ -1394,7 +1279,6 @@ def pixel_uncertainty_maps(passes, n_mc: int, scores=("pred_h", "mi"), want_labe
             t.is_cuda and t.device == first.device and t.shape == first.shape and t.dtype == first.dtype
             and t.stride() == first.stride() for t in passes)
         g = first.shape[0]
-    lib = load_library()
     require_gpu()
     _, c, h, w = (int(v) for v in first.shape)
     dev = first.device
@@ -1407,14 +1291,12 @@ def pixel_uncertainty_maps(passes, n_mc: int, scores=("pred_h", "mi"), want_labe
         return out
     assert out, "at least one map must be requested"
     table = torch.tensor([first.data_ptr()] if single else [t.data_ptr() for t in passes], dtype=torch.int64).to(dev)
-    need = lib.runia_pixel_maps_workspace_bytes(g, c, h, w, n_mc, int("max_logit" in out))
-    ws = torch.empty((need // 4,), dtype=torch.float32, device=dev) if need else None
+    need = query("runia_pixel_maps_workspace_bytes", g, c, h, w, n_mc, int("max_logit" in out))
+    ws = workspace(need, dev, 0) if need else None
     sn, sc, sh, sw = (int(v) for v in first.stride())
-    _check(lib.runia_pixel_uncertainty_maps(
-        table.data_ptr(), int(single), ELEM_DTYPE_CODES[first.dtype], g, n_mc, c, h, w, sn, sc, sh, sw,
-        _ptr(out.get("pred_h")), _ptr(out.get("mi")), _ptr(out.get("msp")), _ptr(out.get("energy")),
-        _ptr(out.get("max_logit")), _ptr(out.get("label")), _ptr(out.get("mean_probs")), _ptr(ws), need, _stream()),
-        "runia_pixel_uncertainty_maps")
+    launch("runia_pixel_uncertainty_maps", table.data_ptr(), int(single), ELEM_DTYPE_CODES[first.dtype], g, n_mc, c, h, w, sn, sc,
+           sh, sw, _ptr(out.get("pred_h")), _ptr(out.get("mi")), _ptr(out.get("msp")), _ptr(out.get("energy")),
+           _ptr(out.get("max_logit")), _ptr(out.get("label")), _ptr(out.get("mean_probs")), _ptr(ws), need)
     return out
 
 
@@ -1423,7 +1305,6 @@ def pixel_map_reduce(score_map: torch.Tensor, valid: Optional[torch.Tensor] = No
     """Per-image (mean, max, count) of a (G, H, W) f32 device map under an optional (G, H, W) bool / uint8 validity mask ->
     (f32 (G,), f32 (G,), int64 (G,)); deterministic.  An image without a valid pixel gives (NaN, -inf, 0)."""
     assert score_map.is_cuda and score_map.dtype == torch.float32 and score_map.dim() == 3
-    lib = load_library()
     require_gpu()
     m = score_map.contiguous()
     g, hw = int(m.shape[0]), int(m.shape[1] * m.shape[2])
@@ -1434,34 +1315,30 @@ def pixel_map_reduce(score_map: torch.Tensor, valid: Optional[torch.Tensor] = No
     mean = torch.empty((g,), dtype=torch.float32, device=m.device)
     mx = torch.empty((g,), dtype=torch.float32, device=m.device)
     cnt = torch.empty((g,), dtype=torch.int64, device=m.device)
-    _check(lib.runia_pixel_map_reduce_f32(m.data_ptr(), _ptr(v), g, hw, mean.data_ptr(), mx.data_ptr(), cnt.data_ptr(),
-                                          _stream()), "runia_pixel_map_reduce_f32")
+    launch("runia_pixel_map_reduce_f32", m.data_ptr(), _ptr(v), g, hw, mean.data_ptr(), mx.data_ptr(), cnt.data_ptr())
     return mean, mx, cnt
 
 
 @_device_guard()
 def gen_score(logits: torch.Tensor, gamma: float, m: int) -> torch.Tensor:
-    lib = load_library()
     require_gpu()
     assert logits.is_cuda and logits.dtype == torch.float32 and logits.dim() == 2
     logits = logits.contiguous()
     s = torch.empty((logits.shape[0],), dtype=torch.float32, device=logits.device)
-    _check(lib.runia_gen_score_f32(logits.data_ptr(), s.data_ptr(), logits.shape[0], logits.shape[1], int(m), float(gamma), _stream()),
-           "runia_gen_score_f32")
+    launch("runia_gen_score_f32", logits.data_ptr(), s.data_ptr(), logits.shape[0], logits.shape[1], int(m), float(gamma))
     return s
 
 
 @_device_guard()
 def proj_norm(x: torch.Tensor, u: torch.Tensor, packed_ns: torch.Tensor, n: int) -> torch.Tensor:
     """|| (x - u) @ NS ||_2 per row -> [N] f64 (x, u both f32 or both f64)."""
-    lib = load_library()
     require_gpu()
     assert x.is_cuda and x.dim() == 2 and x.dtype == u.dtype and x.dtype in (torch.float32, torch.float64)
     x, u = x.contiguous(), u.contiguous()
     nrow, d = x.shape
     out = torch.empty((nrow,), dtype=torch.float64, device=x.device)
-    fn = lib.runia_proj_norm_f32 if x.dtype == torch.float32 else lib.runia_proj_norm_f64
-    _check(fn(x.data_ptr(), u.data_ptr(), packed_ns.data_ptr(), out.data_ptr(), nrow, d, int(n), _stream()), "runia_proj_norm")
+    launch("runia_proj_norm_f32" if x.dtype == torch.float32 else "runia_proj_norm_f64", x.data_ptr(), u.data_ptr(),
+           packed_ns.data_ptr(), out.data_ptr(), nrow, d, int(n))
     return out
 
 
@@ -1476,17 +1353,16 @@ def proj_sq_score(h: torch.Tensor, packed_m: torch.Tensor, c: torch.Tensor, r: i
     s = torch.empty((nrow,), dtype=torch.float64, device=h.device) if out is None else out
     ws_bytes = int(lib.runia_proj_sq_workspace_bytes(nrow))
     ws = torch.empty(max(ws_bytes, 16), dtype=torch.uint8, device=h.device)
-    _check(lib.runia_proj_sq_score_f64(h.data_ptr(), packed_m.data_ptr(), c.data_ptr(), s.data_ptr(), ws.data_ptr(),
-                                       ws_bytes, nrow, d, int(r), _stream()),
-           "runia_proj_sq_score_f64")
+    launch("runia_proj_sq_score_f64", h.data_ptr(), packed_m.data_ptr(), c.data_ptr(), s.data_ptr(), ws.data_ptr(), ws_bytes,
+           nrow, d, int(r))
     return s
 
 
-def _ood_metrics_buffers(lib, n: int, device):
+def _ood_metrics_buffers(n: int, device):
     """The workspace of a runia_ood_metrics_* / runia_ood_clf_curve_* call over n scores, and its [3] f64 result:
     ``(ws, ws_ptr, ws_bytes, out)`` - ``ws`` owns the memory, ``ws_ptr`` is its first 256-byte aligned address."""
-    ws_bytes = int(lib.runia_ood_metrics_workspace_bytes(n))
-    ws = torch.empty(ws_bytes + 256, dtype=torch.uint8, device=device)
+    ws_bytes = query("runia_ood_metrics_workspace_bytes", n)
+    ws = workspace(ws_bytes + 256, device, 0)
     return ws, ws.data_ptr() + (-ws.data_ptr()) % 256, ws_bytes, torch.empty(3, dtype=torch.float64, device=device)
 
 
@@ -1494,15 +1370,14 @@ def _ood_metrics_buffers(lib, n: int, device):
 def ood_metrics(ind_scores: torch.Tensor, ood_scores: torch.Tensor) -> torch.Tensor:
     """Device scores (both f32 or both f64) -> device tensor [3] f64 = (auroc, fpr@95, aupr), InD = positive class
     (``get_auroc_results`` of the reference, evaluation/metrics.py:37-100).  Stream-ordered, no synchronisation."""
-    lib = load_library()
     require_gpu()
     assert ind_scores.is_cuda and ood_scores.is_cuda and ind_scores.dtype == ood_scores.dtype
     assert ind_scores.dtype in (torch.float32, torch.float64)
     a, b = ind_scores.reshape(-1).contiguous(), ood_scores.reshape(-1).contiguous()
     n = a.numel() + b.numel()
-    ws, ws_ptr, ws_bytes, out = _ood_metrics_buffers(lib, n, a.device)
-    fn = lib.runia_ood_metrics_f64 if a.dtype == torch.float64 else lib.runia_ood_metrics_f32
-    _check(fn(a.data_ptr(), a.numel(), b.data_ptr(), b.numel(), out.data_ptr(), ws_ptr, ws_bytes, _stream()), "runia_ood_metrics")
+    ws, ws_ptr, ws_bytes, out = _ood_metrics_buffers(n, a.device)
+    launch("runia_ood_metrics_f64" if a.dtype == torch.float64 else "runia_ood_metrics_f32", a.data_ptr(), a.numel(),
+           b.data_ptr(), b.numel(), out.data_ptr(), ws_ptr, ws_bytes)
     return out
 
 
@@ -1511,18 +1386,17 @@ def ood_clf_curve(ind_scores: torch.Tensor, ood_scores: torch.Tensor):
     """Device scores (both f32 or both f64) -> ``(metrics [3] f64 device, tps [runs] int64 host, fps [runs] int64 host)``:
     torchmetrics' ``_binary_clf_curve`` (cumulative true / false positives at the end of every run of equal scores,
     descending) from the device sort + scans; only the compacted curve leaves the device (one synchronisation)."""
-    lib = load_library()
     require_gpu()
     assert ind_scores.is_cuda and ood_scores.is_cuda and ind_scores.dtype == ood_scores.dtype
     assert ind_scores.dtype in (torch.float32, torch.float64)
     a, b = ind_scores.reshape(-1).contiguous(), ood_scores.reshape(-1).contiguous()
     n = a.numel() + b.numel()
-    ws, ws_ptr, ws_bytes, out = _ood_metrics_buffers(lib, n, a.device)
+    ws, ws_ptr, ws_bytes, out = _ood_metrics_buffers(n, a.device)
     curve = torch.empty((2, n), dtype=torch.int32, device=a.device)  # u32 counts < 2^31 (n is limited to 2^31 - 1)
     n_points = torch.zeros(1, dtype=torch.int64, device=a.device)
-    fn = lib.runia_ood_clf_curve_f64 if a.dtype == torch.float64 else lib.runia_ood_clf_curve_f32
-    _check(fn(a.data_ptr(), a.numel(), b.data_ptr(), b.numel(), out.data_ptr(), curve[0].data_ptr(), curve[1].data_ptr(),
-              n_points.data_ptr(), ws_ptr, ws_bytes, _stream()), "runia_ood_clf_curve")
+    launch("runia_ood_clf_curve_f64" if a.dtype == torch.float64 else "runia_ood_clf_curve_f32", a.data_ptr(), a.numel(),
+           b.data_ptr(), b.numel(), out.data_ptr(), curve[0].data_ptr(), curve[1].data_ptr(), n_points.data_ptr(), ws_ptr,
+           ws_bytes)
     m = int(n_points.item())
     host = to_host(curve[:, :m].contiguous()).astype(np.int64)
     return out, host[0], host[1]
@@ -1535,30 +1409,28 @@ def eigh(a: torch.Tensor, max_sweeps: int = 30, blocked: bool = True, info: Opti
     ``runia_eigh_block_sweep_f64`` - 64 x 64 sub-problems in LDS + matrix-core updates, (n/32 - 1) x 2 launches per sweep;
     ``blocked=False``: the scalar-rotation form ``runia_eigh_sweep_f64`` (2 (n - 1) launches per sweep).
     Setup-time: reads one counter back per sweep.  ``info`` (optional dict) receives ``sweeps`` and ``rotations``."""
-    lib = load_library()
     require_gpu()
     assert a.is_cuda and a.dtype == torch.float64 and a.dim() == 2 and a.shape[0] == a.shape[1]
     n = a.shape[0]
     sym = (a + a.T) * 0.5  # exactly symmetric input
     count = torch.zeros(1, dtype=torch.int32, device=a.device)
     if blocked:
-        big = int(lib.runia_eigh_block_padded(n))
+        big = query("runia_eigh_block_padded", n)
         work = torch.zeros((big, big), dtype=torch.float64, device=a.device)
         work[:n, :n] = sym
-        ws_bytes = int(lib.runia_eigh_block_workspace_bytes(n))
-        init, sweep, size = lib.runia_eigh_block_init_f64, lib.runia_eigh_block_sweep_f64, big
+        ws_bytes = query("runia_eigh_block_workspace_bytes", n)
+        init, sweep, size = "runia_eigh_block_init_f64", "runia_eigh_block_sweep_f64", big
     else:
         work = sym.contiguous()
-        ws_bytes = int(lib.runia_eigh_workspace_bytes(n))
-        init, sweep, size = lib.runia_eigh_init_f64, lib.runia_eigh_sweep_f64, n
+        ws_bytes = query("runia_eigh_workspace_bytes", n)
+        init, sweep, size = "runia_eigh_init_f64", "runia_eigh_sweep_f64", n
     v = torch.empty_like(work)
-    ws = torch.empty(ws_bytes + 16, dtype=torch.uint8, device=a.device)
+    ws = workspace(ws_bytes + 16, a.device, 0)
     off = (-ws.data_ptr()) % 16
-    _check(init(work.data_ptr(), v.data_ptr(), size, ws.data_ptr() + off, ws_bytes, _stream()), "runia_eigh_init")
+    launch(init, work.data_ptr(), v.data_ptr(), size, ws.data_ptr() + off, ws_bytes)
     done = 0
     for sweep_no in range(1, max_sweeps + 1):
-        _check(sweep(work.data_ptr(), v.data_ptr(), size, ws.data_ptr() + off, ws_bytes, count.data_ptr(), _stream()),
-               "runia_eigh_sweep")
+        launch(sweep, work.data_ptr(), v.data_ptr(), size, ws.data_ptr() + off, ws_bytes, count.data_ptr())
         total = int(count.item())
         if total == done:
             break
@@ -1577,7 +1449,6 @@ def eigh(a: torch.Tensor, max_sweeps: int = 30, blocked: bool = True, info: Opti
 
 @_device_guard()
 def matmul_f64(a: torch.Tensor, b: torch.Tensor, transpose_b: bool = False) -> torch.Tensor:
-    lib = load_library()
     require_gpu()
     assert a.is_cuda and b.is_cuda and a.dtype == torch.float64 and b.dtype == torch.float64
     a, b = a.contiguous(), b.contiguous()
@@ -1585,21 +1456,19 @@ def matmul_f64(a: torch.Tensor, b: torch.Tensor, transpose_b: bool = False) -> t
     n = b.shape[0] if transpose_b else b.shape[1]
     assert (b.shape[1] if transpose_b else b.shape[0]) == k
     c = torch.empty((m, n), dtype=torch.float64, device=a.device)
-    _check(lib.runia_matmul_f64(a.data_ptr(), b.data_ptr(), c.data_ptr(), m, n, k, 1 if transpose_b else 0, _stream()),
-           "runia_matmul_f64")
+    launch("runia_matmul_f64", a.data_ptr(), b.data_ptr(), c.data_ptr(), m, n, k, 1 if transpose_b else 0)
     return c
 
 
 @_device_guard()
 def centred_gram(e: torch.Tensor, denom: float) -> torch.Tensor:
     """e [n, H] f32 -> Gram matrix [n, n] f64 of the column-centred rows, divided by ``denom``."""
-    lib = load_library()
     require_gpu()
     assert e.is_cuda and e.dtype == torch.float32 and e.dim() == 2
     e = e.contiguous()
     n, h = e.shape
     g = torch.empty((n, n), dtype=torch.float64, device=e.device)
-    _check(lib.runia_centred_gram_f32(e.data_ptr(), g.data_ptr(), n, h, float(denom), _stream()), "runia_centred_gram_f32")
+    launch("runia_centred_gram_f32", e.data_ptr(), g.data_ptr(), n, h, float(denom))
     return g
 
 
@@ -1612,7 +1481,7 @@ def eigen_scores(e: torch.Tensor, k: int, alpha: float = 1e-3) -> torch.Tensor:
     consecutive rows, all groups in ONE launch of ``runia_eigen_score_batch`` (2 <= k <= 64).  Device rows are read in place
     (a view whose columns are not unit-stride is made contiguous); host rows go up in one copy in their own dtype.  The
     result lies where ``e`` does."""
-    lib = load_library()
+    load_library()  # a missing library is reported before any argument
     if not isinstance(e, torch.Tensor) or e.dim() != 2:
         raise ValueError("eigen_scores takes a 2-D (G * k, hidden) tensor")
     if e.dtype not in ELEM_DTYPE_CODES:
@@ -1631,8 +1500,8 @@ def eigen_scores(e: torch.Tensor, k: int, alpha: float = 1e-3) -> torch.Tensor:
     elif h > 1 and x.stride(1) != 1:
         x = x.contiguous()
     out = torch.empty(n // k, dtype=torch.float64, device=x.device)
-    _check(lib.runia_eigen_score_batch(x.data_ptr(), ELEM_DTYPE_CODES[x.dtype], n // k, k, h, x.stride(0), float(alpha),
-                                       out.data_ptr(), _stream()), "runia_eigen_score_batch")
+    launch("runia_eigen_score_batch", x.data_ptr(), ELEM_DTYPE_CODES[x.dtype], n // k, k, h, x.stride(0), float(alpha),
+           out.data_ptr())
     return out.cpu() if on_host else out
 
 
@@ -1640,7 +1509,6 @@ def eigen_scores(e: torch.Tensor, k: int, alpha: float = 1e-3) -> torch.Tensor:
 def roi_align(x: torch.Tensor, boxes: torch.Tensor, output_size, spatial_scale: float = 1.0, sampling_ratio: int = -1,
               aligned: bool = False, batch_idx: Optional[torch.Tensor] = None) -> torch.Tensor:
     """``torchvision.ops.roi_align``: x [B, C, H, W] f32, boxes [K, 4] f32 (xyxy) -> [K, C, PH, PW] f32 (device)."""
-    lib = load_library()
     require_gpu()
     assert x.is_cuda and x.dtype == torch.float32 and x.dim() == 4
     x = x.contiguous()
@@ -1651,9 +1519,8 @@ def roi_align(x: torch.Tensor, boxes: torch.Tensor, output_size, spatial_scale: 
     if batch_idx is not None:
         batch_idx = batch_idx.to(device=x.device, dtype=torch.int32).contiguous()
     out = torch.empty((k, c, ph, pw), dtype=torch.float32, device=x.device)
-    _check(lib.runia_roi_align_f32(x.data_ptr(), boxes.data_ptr(), _ptr(batch_idx), out.data_ptr(), k, b, c, h, w, int(ph),
-                                   int(pw), float(spatial_scale), int(sampling_ratio), 1 if aligned else 0, _stream()),
-           "runia_roi_align_f32")
+    launch("runia_roi_align_f32", x.data_ptr(), boxes.data_ptr(), _ptr(batch_idx), out.data_ptr(), k, b, c, h, w, int(ph),
+           int(pw), float(spatial_scale), int(sampling_ratio), 1 if aligned else 0)
     return out
 
 
@@ -1661,13 +1528,12 @@ def roi_align(x: torch.Tensor, boxes: torch.Tensor, output_size, spatial_scale: 
 def nchw_to_nhwc(x: torch.Tensor) -> torch.Tensor:
     """x [B, C, H, W] f32 -> [B, H, W, C] f32 (a contiguous copy in channels-last order; the ROI source of
     :func:`roi_mc_entropy`: 64 channels of a wave read a bilinear tap as one contiguous run)."""
-    lib = load_library()
     require_gpu()
     assert x.is_cuda and x.dtype == torch.float32 and x.dim() == 4
     x = x.contiguous()
     b, c, h, w = x.shape
     out = torch.empty((b, h, w, c), dtype=torch.float32, device=x.device)
-    _check(lib.runia_nchw_to_nhwc_f32(x.data_ptr(), out.data_ptr(), b, c, h * w, _stream()), "runia_nchw_to_nhwc_f32")
+    launch("runia_nchw_to_nhwc_f32", x.data_ptr(), out.data_ptr(), b, c, h * w)
     return out
 
 
@@ -1675,7 +1541,7 @@ ROI_FUSED_MAX_IMAGE_BYTES = 1 << 30  # one image's feature map behind a 32-bit b
 
 
 def roi_mc_entropy_supported(ph: int, pw: int, n_mc: int, k: int, sampling_ratio: int) -> bool:
-    return bool(load_library().runia_roi_mc_entropy_supported(int(ph), int(pw), int(n_mc), int(k), int(sampling_ratio)))
+    return bool(query("runia_roi_mc_entropy_supported", int(ph), int(pw), int(n_mc), int(k), int(sampling_ratio)))
 
 
 @_device_guard("boxes", "batch_idx", "rand")
@@ -1686,7 +1552,6 @@ def roi_mc_entropy(x_nhwc: torch.Tensor, boxes: torch.Tensor, output_size, spati
     :func:`nchw_to_nhwc`): x_nhwc [B, H, W, C], boxes [K, 4] xyxy, rand [K, n_mc, PH, PW] -> h [K, C] f64.  The
     (K, C, PH, PW) tensor of ``roi_align`` is never written; same bits as ``roi_align`` + :func:`mc_entropy`.  Calls of
     more than 65 535 ROIs are cut in slices."""
-    lib = load_library()
     require_gpu()
     assert x_nhwc.is_cuda and x_nhwc.dtype == torch.float32 and x_nhwc.dim() == 4 and x_nhwc.is_contiguous()
     b, hh, ww, c = x_nhwc.shape
@@ -1702,17 +1567,14 @@ def roi_mc_entropy(x_nhwc: torch.Tensor, boxes: torch.Tensor, output_size, spati
         assert rand.shape == (kk, n_mc, ph, pw)
     h = torch.empty((kk, c), dtype=torch.float64, device=x_nhwc.device)
     z = torch.empty((kk * n_mc, c), dtype=torch.float32, device=x_nhwc.device) if return_samples else None
-    step = 65535
-    for k0 in range(0, kk, step):
-        n = min(step, kk - k0)
-        ws_bytes = int(lib.runia_roi_mc_entropy_workspace_bytes(n, ph, pw, n_mc, sampling_ratio))
-        ws = torch.empty(max(ws_bytes, 16), dtype=torch.uint8, device=x_nhwc.device)
-        _check(lib.runia_roi_mc_entropy_f32(
-            x_nhwc.data_ptr(), boxes[k0:].data_ptr(), None if batch_idx is None else batch_idx[k0:].data_ptr(),
-            None if rand is None else rand[k0:].data_ptr(), n_mc * ph * pw, h[k0:].data_ptr(),
-            None if z is None else z[k0 * n_mc:].data_ptr(), ws.data_ptr(), ws_bytes, n, b, c, hh, ww, int(ph), int(pw),
-            float(spatial_scale), int(sampling_ratio), 1 if aligned else 0, int(n_mc), float(drop_prob), int(block_size), int(k),
-            float(min_dist), _stream()), "runia_roi_mc_entropy_f32")
+    for k0, n in _image_slices(kk):
+        ws_bytes = query("runia_roi_mc_entropy_workspace_bytes", n, ph, pw, n_mc, sampling_ratio)
+        ws = workspace(ws_bytes, x_nhwc.device)
+        launch("runia_roi_mc_entropy_f32", x_nhwc.data_ptr(), boxes[k0:].data_ptr(),
+               None if batch_idx is None else batch_idx[k0:].data_ptr(), None if rand is None else rand[k0:].data_ptr(),
+               n_mc * ph * pw, h[k0:].data_ptr(), None if z is None else z[k0 * n_mc:].data_ptr(), ws.data_ptr(), ws_bytes, n, b,
+               c, hh, ww, int(ph), int(pw), float(spatial_scale), int(sampling_ratio), 1 if aligned else 0, int(n_mc),
+               float(drop_prob), int(block_size), int(k), float(min_dist))
     return (h, z) if return_samples else h
 
 
@@ -1733,7 +1595,6 @@ def roi_means(x_nhwc: torch.Tensor, boxes: torch.Tensor, output_size, spatial_sc
     feature map (NHWC, :func:`nchw_to_nhwc`): x_nhwc [B, H, W, C], boxes [K, 4] xyxy -> [K, C] f32.  The (K, C, PH, PW)
     tensor is never written.  ``out`` (additive): a ``(K, C_total)`` f32 device matrix with unit column stride whose columns
     ``col_offset : col_offset + C`` receive the means (one slice per hooked layer, no concatenation); it is returned."""
-    lib = load_library()
     require_gpu()
     assert x_nhwc.is_cuda and x_nhwc.dtype == torch.float32 and x_nhwc.dim() == 4 and x_nhwc.is_contiguous()
     b, hh, ww, c = x_nhwc.shape
@@ -1747,10 +1608,9 @@ def roi_means(x_nhwc: torch.Tensor, boxes: torch.Tensor, output_size, spatial_sc
         col_offset = 0
     assert out.dtype == torch.float32 and out.device == x_nhwc.device and out.dim() == 2 and out.shape[0] == kk
     assert out.stride(1) == 1 and 0 <= col_offset and col_offset + c <= out.shape[1]
-    _check(lib.runia_roi_means_f32(x_nhwc.data_ptr(), boxes.data_ptr(), _ptr(batch_idx), out.data_ptr(),
-                                   out.stride(0) if kk > 1 else out.shape[1], int(col_offset), kk, b, c, hh, ww, int(ph),
-                                   int(pw), float(spatial_scale), int(sampling_ratio), 1 if aligned else 0, _stream()),
-           "runia_roi_means_f32")
+    launch("runia_roi_means_f32", x_nhwc.data_ptr(), boxes.data_ptr(), _ptr(batch_idx), out.data_ptr(),
+           out.stride(0) if kk > 1 else out.shape[1], int(col_offset), kk, b, c, hh, ww, int(ph), int(pw), float(spatial_scale),
+           int(sampling_ratio), 1 if aligned else 0)
     return out
 
 
@@ -1761,14 +1621,13 @@ KDE_KERNELS = ("gaussian", "tophat", "epanechnikov", "exponential", "linear", "c
 def kde_score_kernel(train: torch.Tensor, x: torch.Tensor, bandwidth: float, kernel: str) -> torch.Tensor:
     """log-density of ``x`` [N, D] under a kernel density estimate on ``train`` [M, D] (both f64) for any of sklearn's
     kernels (``KDE_KERNELS``) with sklearn's normalisation -> [N] f64."""
-    lib = load_library()
     require_gpu()
     assert kernel in KDE_KERNELS, f"unknown kernel {kernel!r}"
     assert train.is_cuda and x.is_cuda and train.dtype == torch.float64 and x.dtype == torch.float64
     train, x = train.contiguous(), x.contiguous()
     s = torch.empty((x.shape[0],), dtype=torch.float64, device=x.device)
-    _check(lib.runia_kde_score_kernel_f64(train.data_ptr(), x.data_ptr(), s.data_ptr(), train.shape[0], x.shape[0], train.shape[1],
-                                          float(bandwidth), KDE_KERNELS.index(kernel), _stream()), "runia_kde_score_kernel_f64")
+    launch("runia_kde_score_kernel_f64", train.data_ptr(), x.data_ptr(), s.data_ptr(), train.shape[0], x.shape[0], train.shape[1],
+           float(bandwidth), KDE_KERNELS.index(kernel))
     return s
 
 
@@ -1776,11 +1635,10 @@ def kde_score_kernel(train: torch.Tensor, x: torch.Tensor, bandwidth: float, ker
 def clock_probe(chain: int = 8192, device: Optional[torch.device] = None) -> torch.Tensor:
     """Queue one clock probe (``runia_clock_probe``) on the current stream -> device tensor [4] int64
     (shader-clock ticks, 100 MHz ticks, FMAs in the chain, 0).  Read it with :func:`clock_ghz` after a synchronisation."""
-    lib = load_library()
     dev = require_gpu() if device is None else torch.device(device)
     with torch.cuda.device(dev):  # the probe runs on `dev`'s stream and reads `dev`'s clock, whatever device is current
         out = torch.zeros(4, dtype=torch.int64, device=dev)
-        _check(lib.runia_clock_probe(out.data_ptr(), int(chain), _stream()), "runia_clock_probe")
+        launch("runia_clock_probe", out.data_ptr(), int(chain))
     return out
 
 
@@ -1796,12 +1654,11 @@ def clock_ghz(probe: torch.Tensor) -> dict:
 @_device_guard()
 def tril_inverse(tril: torch.Tensor) -> torch.Tensor:
     """tril [B, D, D] f64 lower-triangular (device) -> their inverses [B, D, D] (``runia_tril_inverse_f64``)."""
-    lib = load_library()
     require_gpu()
     assert tril.is_cuda and tril.dtype == torch.float64 and tril.dim() == 3 and tril.shape[1] == tril.shape[2]
     tril = tril.contiguous()
     out = torch.empty_like(tril)
-    _check(lib.runia_tril_inverse_f64(tril.data_ptr(), out.data_ptr(), tril.shape[0], tril.shape[1], _stream()), "runia_tril_inverse_f64")
+    launch("runia_tril_inverse_f64", tril.data_ptr(), out.data_ptr(), tril.shape[0], tril.shape[1])
     return out
 
 
@@ -1813,7 +1670,6 @@ def gmm_log_prob(x: torch.Tensor, means: torch.Tensor, w_tril: torch.Tensor, con
                  want_lse: bool = False):
     """Class-wise Gaussian log densities with the inverse Cholesky factors (``runia_gmm_log_prob_f32``): x [N, D] f32, means [C, D] f32,
     w_tril [C, D, D] f32 lower triangular (= L_c^-1), consts [C] f64 -> ``(log_prob [N, C] f32 or None, lse [N] f32 or None)``."""
-    lib = load_library()
     require_gpu()
     assert x.is_cuda and x.dtype == torch.float32 and x.dim() == 2
     assert means.dtype == torch.float32 and w_tril.dtype == torch.float32 and consts.dtype == torch.float64
@@ -1826,11 +1682,11 @@ def gmm_log_prob(x: torch.Tensor, means: torch.Tensor, w_tril: torch.Tensor, con
     lse = torch.empty((n,), dtype=torch.float32, device=x.device) if want_lse else None
     if n == 0:
         return lp, lse
-    need = int(lib.runia_gmm_log_prob_workspace_bytes(n, d, c))
+    need = query("runia_gmm_log_prob_workspace_bytes", n, d, c)
     ws_bytes = min(need, max(_GMM_WORKSPACE_CAP, need // max(1, n) * 128))  # the entry point scores the rows in chunks that fit
-    ws = torch.empty(((ws_bytes + 7) // 8,), dtype=torch.float64, device=x.device)
-    _check(lib.runia_gmm_log_prob_f32(x.data_ptr(), means.data_ptr(), w_tril.data_ptr(), consts.data_ptr(), _ptr(lp), _ptr(lse),
-                                      ws.data_ptr(), ws.numel() * 8, n, d, c, _stream()), "runia_gmm_log_prob_f32")
+    ws = workspace((ws_bytes + 7) // 8 * 8, x.device, 0)
+    launch("runia_gmm_log_prob_f32", x.data_ptr(), means.data_ptr(), w_tril.data_ptr(), consts.data_ptr(), _ptr(lp), _ptr(lse),
+           ws.data_ptr(), ws.numel(), n, d, c)
     return lp, lse
 
 
@@ -1840,7 +1696,6 @@ def kth_smallest_flat(x: torch.Tensor, ranks) -> list:
     ``ranks`` (0-based), as Python floats holding float32 values.  Radix select: three histogram passes per rank
     (``runia_select_hist_f32``), one 8 KB read-back per pass.  Setup-time (synchronises).  The array must not contain NaNs (their
     keys sort above +inf; NumPy's partition puts them last as well, but its percentile then returns NaN: the caller checks)."""
-    lib = load_library()
     require_gpu()
     assert x.is_cuda and x.dtype == torch.float32
     x = x.contiguous()
@@ -1852,7 +1707,7 @@ def kth_smallest_flat(x: torch.Tensor, ranks) -> list:
         assert 0 <= k < n
         prefix, mask = 0, 0
         for shift, width in ((21, 11), (10, 11), (0, 10)):
-            _check(lib.runia_select_hist_f32(x.data_ptr(), hist.data_ptr(), n, prefix, mask, shift, _stream()), "runia_select_hist_f32")
+            launch("runia_select_hist_f32", x.data_ptr(), hist.data_ptr(), n, prefix, mask, shift)
             h = hist.cpu().numpy().astype(np.int64) & 0xFFFFFFFF
             cum = np.cumsum(h)
             b = int(np.searchsorted(cum, k, side="right"))
@@ -1870,13 +1725,12 @@ def cholesky(a: torch.Tensor, jitter: float = 0.0):
     """a [B, D, D] (or [D, D]) f32 / f64 symmetric on the device -> ``(L, info)``: the lower Cholesky factors of ``a + jitter * I``
     (a new tensor; zeros above the diagonal) and ``info`` [B] int32 on the device - 0, or j + 1 where column j's pivot was not
     positive (``runia_cholesky_*``)."""
-    lib = load_library()
     require_gpu()
     assert a.is_cuda and a.dtype in (torch.float32, torch.float64) and a.dim() in (2, 3) and a.shape[-1] == a.shape[-2]
     m = a.reshape(-1, a.shape[-1], a.shape[-1]).contiguous().clone()
     info = torch.empty((m.shape[0],), dtype=torch.int32, device=a.device)
-    fn = lib.runia_cholesky_f32 if a.dtype == torch.float32 else lib.runia_cholesky_f64
-    _check(fn(m.data_ptr(), info.data_ptr(), m.shape[0], m.shape[1], float(jitter), _stream()), "runia_cholesky")
+    launch("runia_cholesky_f32" if a.dtype == torch.float32 else "runia_cholesky_f64", m.data_ptr(), info.data_ptr(), m.shape[0],
+           m.shape[1], float(jitter))
     return m.reshape(a.shape), info
 
 
@@ -1887,7 +1741,7 @@ YOLO_MAX_ANCHORS = 1 << 22  # RUNIA_YOLO_MAX_ANCHORS
 
 def nms_workspace_bytes(m: int) -> int:
     """Bytes of the IoU bitmask of ``m`` sorted boxes: ``m * ceil(m / 64) * 8``."""
-    return int(load_library().runia_nms_workspace_bytes(int(m)))
+    return query("runia_nms_workspace_bytes", int(m))
 
 
 @_device_guard()
@@ -1895,7 +1749,6 @@ def nms_sorted_keys(scores: torch.Tensor) -> torch.Tensor:
     """scores [n] f32 (device) -> the int64 keys ``(desc(score) << 31) | i`` in ascending order = descending score, ties by
     ascending index (``runia_nms_keys_f32``, then ``runia_nms_sort_keys`` up to :data:`NMS_SORT_MAX` keys, a device
     ``torch.sort`` of the same distinct keys above: one order either way)."""
-    lib = load_library()
     require_gpu()
     assert scores.is_cuda and scores.dtype == torch.float32 and scores.dim() == 1
     n = scores.shape[0]
@@ -1904,9 +1757,9 @@ def nms_sorted_keys(scores: torch.Tensor) -> torch.Tensor:
     if n == 0:
         return keys
     scores = scores.contiguous()
-    _check(lib.runia_nms_keys_f32(scores.data_ptr(), n, keys.data_ptr(), _stream()), "runia_nms_keys_f32")
+    launch("runia_nms_keys_f32", scores.data_ptr(), n, keys.data_ptr())
     if n <= NMS_SORT_MAX:
-        _check(lib.runia_nms_sort_keys(keys.data_ptr(), n, _stream()), "runia_nms_sort_keys")
+        launch("runia_nms_sort_keys", keys.data_ptr(), n)
         return keys
     return torch.sort(keys, stable=True).values
 
@@ -1916,7 +1769,6 @@ def nms_sorted(boxes: torch.Tensor, sorted_keys: torch.Tensor, iou_threshold: fl
     """Greedy NMS of the boxes [*, 4] xyxy f32 (device) in the order of ``sorted_keys`` (:func:`nms_sorted_keys`, possibly
     truncated) -> ``(keep, count)``: int64 device tensors, ``keep[:count]`` the kept boxes' indices (at most ``max_det``),
     in sorted order (``runia_nms_sorted_f32``).  Nothing is read back here."""
-    lib = load_library()
     require_gpu()
     assert boxes.is_cuda and boxes.dtype == torch.float32 and boxes.dim() == 2 and boxes.shape[1] == 4
     assert sorted_keys.dtype == torch.int64 and sorted_keys.dim() == 1 and sorted_keys.device == boxes.device
@@ -1928,9 +1780,9 @@ def nms_sorted(boxes: torch.Tensor, sorted_keys: torch.Tensor, iou_threshold: fl
     keep = torch.empty((max(max_det, 1),), dtype=torch.int64, device=boxes.device)
     count = torch.zeros((1,), dtype=torch.int64, device=boxes.device)
     ws_bytes = nms_workspace_bytes(m)
-    ws = torch.empty(((ws_bytes + 7) // 8,), dtype=torch.int64, device=boxes.device) if ws_bytes else None
-    _check(lib.runia_nms_sorted_f32(boxes.data_ptr(), sorted_keys.data_ptr(), m, float(iou_threshold), max_det,
-                                    keep.data_ptr(), count.data_ptr(), _ptr(ws), ws_bytes, _stream()), "runia_nms_sorted_f32")
+    ws = workspace(ws_bytes, boxes.device, 0) if ws_bytes else None
+    launch("runia_nms_sorted_f32", boxes.data_ptr(), sorted_keys.data_ptr(), m, float(iou_threshold), max_det, keep.data_ptr(),
+           count.data_ptr(), _ptr(ws), ws_bytes)
     return keep, count
 
 
@@ -1939,7 +1791,6 @@ def yolo_candidates(pred: torch.Tensor, nc: int, conf_thres: float, classes=None
     """One image's YOLOv8 head ``pred`` [4 + nc + nm, A] f32 (device, channel-major) -> its candidates in anchor order
     (``runia_yolo_candidates_f32``): ``(boxes [A, 4] = rows 0-3 + best class * max_wh, scores [A], anchor [A] int32,
     cls [A] int32, count)`` with ``count`` an int64 device tensor [1]; the first ``count`` rows are valid."""
-    lib = load_library()
     require_gpu()
     assert pred.is_cuda and pred.dtype == torch.float32 and pred.dim() == 2
     c, a = pred.shape
@@ -1959,13 +1810,12 @@ def yolo_candidates(pred: torch.Tensor, nc: int, conf_thres: float, classes=None
     count = torch.zeros((1,), dtype=torch.int64, device=dev)
     if a == 0:
         return boxes, scores, anchor, cls, count
-    ws_bytes = int(lib.runia_yolo_candidates_workspace_bytes(a))
-    ws = torch.empty(((ws_bytes + 7) // 8,), dtype=torch.int64, device=dev)
+    ws_bytes = query("runia_yolo_candidates_workspace_bytes", a)
+    ws = workspace(ws_bytes, dev, 0)
     n_cls = 0 if cls_list is None else int(cls_list.numel())
-    _check(lib.runia_yolo_candidates_f32(pred.data_ptr(), a, int(nc), nm, float(conf_thres),
-                                         _ptr(cls_list) if n_cls else None, n_cls, float(max_wh), boxes.data_ptr(),
-                                         scores.data_ptr(), anchor.data_ptr(), cls.data_ptr(), count.data_ptr(), ws.data_ptr(),
-                                         ws_bytes, _stream()), "runia_yolo_candidates_f32")
+    launch("runia_yolo_candidates_f32", pred.data_ptr(), a, int(nc), nm, float(conf_thres), _ptr(cls_list) if n_cls else None,
+           n_cls, float(max_wh), boxes.data_ptr(), scores.data_ptr(), anchor.data_ptr(), cls.data_ptr(), count.data_ptr(),
+           ws.data_ptr(), ws_bytes)
     return boxes, scores, anchor, cls, count
 
 
@@ -1980,15 +1830,14 @@ PACMAP_KIND_NB, PACMAP_KIND_MN, PACMAP_KIND_FP = 0, 1, 2  # RUNIA_PACMAP_KIND_*:
 def pacmap_knn(q: torch.Tensor, bank: torch.Tensor, k: int, exclude_self: bool):
     """Exact kNN of the rows of ``q`` [Q, D] among ``bank`` [N, D] (f32, device) -> ``(idx [Q, k] int32, dist [Q, k] f32)``,
     sorted by (distance, index); ``exclude_self`` leaves bank row i out of query row i's list (``runia_pacmap_knn_f32``)."""
-    lib = load_library()
     require_gpu()
     assert q.is_cuda and bank.is_cuda and q.dtype == torch.float32 and bank.dtype == torch.float32
     assert q.dim() == 2 and bank.dim() == 2 and q.shape[1] == bank.shape[1]
     q, bank = q.contiguous(), bank.contiguous()
     idx = torch.empty((q.shape[0], k), dtype=torch.int32, device=q.device)
     dist = torch.empty((q.shape[0], k), dtype=torch.float32, device=q.device)
-    _check(lib.runia_pacmap_knn_f32(q.data_ptr(), q.shape[0], bank.data_ptr(), bank.shape[0], bank.shape[1], int(k),
-                                    int(bool(exclude_self)), idx.data_ptr(), dist.data_ptr(), _stream()), "runia_pacmap_knn_f32")
+    launch("runia_pacmap_knn_f32", q.data_ptr(), q.shape[0], bank.data_ptr(), bank.shape[0], bank.shape[1], int(k),
+           int(bool(exclude_self)), idx.data_ptr(), dist.data_ptr())
     return idx, dist
 
 
@@ -1997,7 +1846,6 @@ def pacmap_pairs(x: torch.Tensor, bank: torch.Tensor, knn_idx: torch.Tensor, knn
                  n_fp: int, seed: int, transform: bool):
     """NB / MN / FP pair lists ``(pair_nb [R * n_nb, 2], pair_mn [R * n_mn, 2], pair_fp [R * n_fp, 2])`` int32 (device) of the
     rows ``x`` [R, D] against ``bank`` [Nb, D] from their kNN table (``runia_pacmap_pairs``; the fit passes ``x is bank``)."""
-    lib = load_library()
     require_gpu()
     assert x.dtype == torch.float32 and bank.dtype == torch.float32 and knn_idx.dtype == torch.int32
     assert knn_dist.dtype == torch.float32 and knn_idx.shape == knn_dist.shape and knn_idx.shape[0] == x.shape[0]
@@ -2007,19 +1855,18 @@ def pacmap_pairs(x: torch.Tensor, bank: torch.Tensor, knn_idx: torch.Tensor, knn
     nb = torch.empty((r * n_nb, 2), dtype=torch.int32, device=dev)
     mn = torch.empty((r * n_mn, 2), dtype=torch.int32, device=dev)
     fp = torch.empty((r * n_fp, 2), dtype=torch.int32, device=dev)
-    ws_bytes = 0 if transform else int(lib.runia_pacmap_pairs_workspace_bytes(r))
-    ws = torch.empty(((ws_bytes + 7) // 8,), dtype=torch.int64, device=dev) if ws_bytes else None
-    _check(lib.runia_pacmap_pairs(x.data_ptr(), r, bank.data_ptr(), bank.shape[0], d, knn_idx.data_ptr(), knn_dist.data_ptr(),
-                                  knn_idx.shape[1], int(n_nb), int(n_mn), int(n_fp), int(seed) & 0xFFFFFFFFFFFFFFFF,
-                                  int(bool(transform)), nb.data_ptr(), mn.data_ptr() if n_mn else None,
-                                  fp.data_ptr() if n_fp else None, _ptr(ws), ws_bytes, _stream()), "runia_pacmap_pairs")
+    ws_bytes = 0 if transform else query("runia_pacmap_pairs_workspace_bytes", r)
+    ws = workspace(ws_bytes, dev, 0) if ws_bytes else None
+    launch("runia_pacmap_pairs", x.data_ptr(), r, bank.data_ptr(), bank.shape[0], d, knn_idx.data_ptr(), knn_dist.data_ptr(),
+           knn_idx.shape[1], int(n_nb), int(n_mn), int(n_fp), int(seed) & 0xFFFFFFFFFFFFFFFF, int(bool(transform)), nb.data_ptr(),
+           mn.data_ptr() if n_mn else None, fp.data_ptr() if n_fp else None, _ptr(ws), ws_bytes)
     return nb, mn, fp
 
 
 def pacmap_phase_weights(t: int):
     """``(w_NB, w_MN, w_FP)`` of iteration ``t`` as the step kernel uses them (``runia_pacmap_phase_weights``, host only)."""
     w = (c_float * 3)()
-    _check(load_library().runia_pacmap_phase_weights(int(t), ctypes.addressof(w)), "runia_pacmap_phase_weights")
+    call("runia_pacmap_phase_weights", int(t), ctypes.addressof(w))
     return tuple(float(v) for v in w)
 
 
@@ -2029,14 +1876,12 @@ def pacmap_step(y_in: torch.Tensor, y_part: torch.Tensor, y_out: torch.Tensor, m
     """One Adam iteration ``t`` of the rows ``y_in`` [R, C] into ``y_out`` (``runia_pacmap_step_f32``); ``m`` / ``v`` are
     updated in place.  Row r's pairs: ``entries[offsets[r]:offsets[r + 1]]`` = ``(kind << 30) | partner``, partners read
     from ``y_part``.  All operands contiguous f32 / int64 / int32 on one device."""
-    lib = load_library()
     require_gpu()
     r, c = y_in.shape
     for a, dt in ((y_in, torch.float32), (y_part, torch.float32), (y_out, torch.float32), (m, torch.float32),
                   (v, torch.float32), (offsets, torch.int64), (entries, torch.int32)):
         assert a.is_cuda and a.dtype == dt and a.is_contiguous()
     assert y_out.shape == y_in.shape == m.shape == v.shape and y_part.shape[1] == c and offsets.shape[0] == r + 1
-    _check(lib.runia_pacmap_step_f32(y_in.data_ptr(), y_part.data_ptr(), y_out.data_ptr(), m.data_ptr(), v.data_ptr(),
-                                     offsets.data_ptr(), entries.data_ptr(), r, c, int(t), float(lr), _stream()),
-           "runia_pacmap_step_f32")
+    launch("runia_pacmap_step_f32", y_in.data_ptr(), y_part.data_ptr(), y_out.data_ptr(), m.data_ptr(), v.data_ptr(),
+           offsets.data_ptr(), entries.data_ptr(), r, c, int(t), float(lr))
     return y_out

@@ -261,7 +261,6 @@ class OneShotGather:
 
         from . import _hip
 
-        self._lib = _hip.load_library()
         _hip.require_gpu()
         self.world, self.rank = _world(group)
         if not (1 <= self.world <= 16):
@@ -275,10 +274,10 @@ class OneShotGather:
         raw, err = None, None
         try:
             buf = ctypes.c_void_p()
-            _hip._check(self._lib.runia_p2p_alloc(self.world, self.capacity, ctypes.byref(buf)), "runia_p2p_alloc")
+            _hip.call("runia_p2p_alloc", self.world, self.capacity, ctypes.byref(buf))
             self._own = buf.value
             handle = ctypes.create_string_buffer(64)
-            _hip._check(self._lib.runia_p2p_export(self._own, handle), "runia_p2p_export")
+            _hip.call("runia_p2p_export", self._own, handle)
             raw = bytes(handle.raw)
         except Exception as e:  # noqa: BLE001 - reported to every rank below
             err = repr(e)
@@ -294,8 +293,7 @@ class OneShotGather:
                         self._peers[r] = self._own
                         continue
                     p = ctypes.c_void_p()
-                    _hip._check(self._lib.runia_p2p_open(ctypes.create_string_buffer(handles[r], 64), ctypes.byref(p)),
-                                "runia_p2p_open")
+                    _hip.call("runia_p2p_open", ctypes.create_string_buffer(handles[r], 64), ctypes.byref(p))
                     self._peers[r] = p.value
                     self._opened.append(p.value)
             except Exception as e:  # noqa: BLE001
@@ -314,10 +312,12 @@ class OneShotGather:
             raise _hip.RuniaHipError(f"OneShotGather could not be set up on every rank: {[e for e in errs if e][:2]}")
 
     def _release(self) -> None:
-        for p in self._opened:
-            self._lib.runia_p2p_close(p)
+        from . import _hip
+
+        for p in self._opened:  # best effort: the codes of close and free are not checked
+            _hip.query("runia_p2p_close", p)
         if self._own is not None:
-            self._lib.runia_p2p_free(self._own)
+            _hip.query("runia_p2p_free", self._own)
         self._own, self._opened = None, []
 
     def __call__(self, local: torch.Tensor, n_rows: int) -> torch.Tensor:
@@ -340,9 +340,8 @@ class OneShotGather:
         if self._out[slot] is None or self._out[slot].numel() != self.world * per:
             self._out[slot] = torch.empty(self.world * per, dtype=self.dtype, device=local.device)
         out = self._out[slot]
-        _hip._check(self._lib.runia_p2p_all_gather(shard.data_ptr(), per * self.elem, out.data_ptr(), self._peers, self.world,
-                                                   self.rank, self.capacity, self._seq, self.timeout_ms, _hip._stream()),
-                    "runia_p2p_all_gather")
+        _hip.launch("runia_p2p_all_gather", shard.data_ptr(), per * self.elem, out.data_ptr(), self._peers, self.world, self.rank,
+                    self.capacity, self._seq, self.timeout_ms)
         return out[:n_rows]
 
     def check(self) -> None:
@@ -352,7 +351,7 @@ class OneShotGather:
         from . import _hip
 
         status = ctypes.c_int(0)
-        _hip._check(self._lib.runia_p2p_status(self._own, ctypes.byref(status)), "runia_p2p_status")
+        _hip.call("runia_p2p_status", self._own, ctypes.byref(status))
         if status.value & 2:
             raise _hip.RuniaHipError("OneShotGather: slot-reuse assertion failed - a slot was overwritten before the peer had "
                                      "copied the step before last out of it (runia_p2p_debug)")
@@ -364,7 +363,7 @@ class OneShotGather:
         """Switch the slot-reuse assertion of the gather launches on / off (every rank alike); returns the previous setting."""
         from . import _hip
 
-        return bool(_hip.load_library().runia_p2p_debug(1 if on else 0))
+        return bool(_hip.query("runia_p2p_debug", 1 if on else 0))
 
     def __del__(self):  # best effort for a gather that was never closed: no collective here, just the local resources
         try:

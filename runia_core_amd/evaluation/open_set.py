@@ -333,15 +333,14 @@ def _hip_dtype(dt) -> torch.dtype:
 
 
 class _Device:
-    """Library, device and stream of one evaluation, with the allocation and call helpers the stages share."""
+    """The binding and the device of one evaluation, with the allocation and call helpers the stages share."""
 
     def __init__(self):
         from .. import _hip
 
         self.hip = _hip
-        self.lib = _hip.load_library()
         self.dev = _hip.require_gpu()
-        self.stream = _hip._stream()
+        self.launch, self.query = _hip.launch, _hip.query
 
     def up(self, a: np.ndarray, dt: torch.dtype) -> torch.Tensor:
         return self.hip.to_device(np.ascontiguousarray(a), dt)
@@ -350,22 +349,18 @@ class _Device:
         return torch.empty(shape, dtype=dt, device=self.dev)
 
     def workspace(self, nbytes: int) -> torch.Tensor:
-        return torch.empty(max(int(nbytes), 16), dtype=torch.uint8, device=self.dev)
-
-    def call(self, name: str, *args) -> None:
-        self.hip._check(getattr(self.lib, name)(*args, self.stream), name)
+        return self.hip.workspace(nbytes, self.dev)
 
     def quantize(self, a: np.ndarray, out: torch.Tensor, period: int, mask: int, decimals: int, key=None, bad=None):
         if a.size:
             t = self.up(a, _hip_dtype(a.dtype))
-            self.call("runia_osod_quantize", t.data_ptr(), _DTYPE_CODES[a.dtype], a.size, period, mask, decimals,
-                      out.data_ptr(), _ptr(key), _KEY_MAX if key is not None else 0, _ptr(bad))
+            self.launch("runia_osod_quantize", t.data_ptr(), _DTYPE_CODES[a.dtype], a.size, period, mask, decimals,
+                        out.data_ptr(), _ptr(key), _KEY_MAX if key is not None else 0, _ptr(bad))
 
     def bucket_sort(self, keys: torch.Tensor, n: int, nb: int) -> Tuple[torch.Tensor, torch.Tensor]:
         perm, starts = self.empty(max(n, 1), torch.int32), self.empty(nb + 1, torch.int64)
-        w = self.workspace(self.lib.runia_osod_sort_workspace_bytes(n, nb))
-        self.call("runia_osod_bucket_sort", keys.data_ptr(), n, nb, perm.data_ptr(), starts.data_ptr(), w.data_ptr(),
-                  w.numel())
+        w = self.workspace(self.query("runia_osod_sort_workspace_bytes", n, nb))
+        self.launch("runia_osod_bucket_sort", keys.data_ptr(), n, nb, perm.data_ptr(), starts.data_ptr(), w.data_ptr(), w.numel())
         return perm, starts
 
 
@@ -391,9 +386,9 @@ class _Base:
         grp = dv.up(det_group, torch.int32)
         self.ov, self.jp = dv.empty((max(n, 1), 2), torch.float64), dv.empty((max(n, 1), 2), torch.int32)
         gtb = dv.up(gt.boxes if len(gt.boxes) else np.zeros((1, 4)), torch.float64)
-        dv.call("runia_osod_overlaps", self.qbox.data_ptr(), self.img.data_ptr(), grp.data_ptr(), n, gtb.data_ptr(),
-                dv.up(gt.off, torch.int32).data_ptr(), gt.n_img, gt.n_groups, gt.unk_group, self.ov.data_ptr(),
-                self.jp.data_ptr())
+        dv.launch("runia_osod_overlaps", self.qbox.data_ptr(), self.img.data_ptr(), grp.data_ptr(), n, gtb.data_ptr(),
+                  dv.up(gt.off, torch.int32).data_ptr(), gt.n_img, gt.n_groups, gt.unk_group, self.ov.data_ptr(),
+                  self.jp.data_ptr())
         self.gcls, self.gst = dv.up(gt.group_of_class, torch.int32), dv.up(gt.gstart, torch.int32)
         self.cbase, self.npos = dv.up(gt.cbase, torch.int64), dv.up(gt.npos, torch.int64)
         self.n_classes, self.n_slots = nc, gt.n_slots
@@ -435,30 +430,29 @@ def _score(inp: _Inputs, gt: _GroundTruth, cmp_scores: List[np.ndarray], thresho
         thr = torch.full((1,), -np.inf, dtype=torch.float64, device=dv.dev)
     cf = dv.up(conf_cmp, torch.float64) if conf_cmp is not None else None
     key2, flags = dv.empty(max(M * n, 1), torch.int32), dv.empty(max(M * n, 1), torch.uint8)
-    w = dv.workspace(dv.lib.runia_osod_match_workspace_bytes(M, base.n_slots))
-    dv.call("runia_osod_match", base.perm.data_ptr(), n, M, nc, base.lab.data_ptr(), base.img.data_ptr(), base.ov.data_ptr(),
-            base.jp.data_ptr(), msc.data_ptr(), thr.data_ptr(), int(bool(open_set and relabel)),
-            int(unk_label) if unk_label is not None else -(1 << 30), _ptr(cf), float(min_conf), base.gcls.data_ptr(),
-            base.gst.data_ptr(), base.cbase.data_ptr(), base.n_slots, float(ovthresh), key2.data_ptr(), flags.data_ptr(),
-            w.data_ptr(), w.numel())
+    w = dv.workspace(dv.query("runia_osod_match_workspace_bytes", M, base.n_slots))
+    dv.launch("runia_osod_match", base.perm.data_ptr(), n, M, nc, base.lab.data_ptr(), base.img.data_ptr(), base.ov.data_ptr(),
+              base.jp.data_ptr(), msc.data_ptr(), thr.data_ptr(), int(bool(open_set and relabel)),
+              int(unk_label) if unk_label is not None else -(1 << 30), _ptr(cf), float(min_conf), base.gcls.data_ptr(),
+              base.gst.data_ptr(), base.cbase.data_ptr(), base.n_slots, float(ovthresh), key2.data_ptr(), flags.data_ptr(),
+              w.data_ptr(), w.numel())
     part, bs2 = dv.bucket_sort(key2, M * n, M * (nc + 1))
     summary = torch.zeros((M, nc, 8), dtype=torch.float64, device=dv.dev)
     arrays = [dv.empty(max(M * n, 1), torch.float64) for _ in range(4)] if curves else None
-    w = dv.workspace(dv.lib.runia_osod_curves_workspace_bytes(M * n))
-    dv.call("runia_osod_curves", part.data_ptr(), bs2.data_ptr(), flags.data_ptr(), n, M, nc, base.npos.data_ptr(),
-            int(use_07), summary.data_ptr(), *([a.data_ptr() for a in arrays] if curves else [None] * 4), w.data_ptr(),
-            w.numel())
+    w = dv.workspace(dv.query("runia_osod_curves_workspace_bytes", M * n))
+    dv.launch("runia_osod_curves", part.data_ptr(), bs2.data_ptr(), flags.data_ptr(), n, M, nc, base.npos.data_ptr(), int(use_07),
+              summary.data_ptr(), *([a.data_ptr() for a in arrays] if curves else [None] * 4), w.data_ptr(), w.numel())
     tail = [summary.reshape(-1), base.bad.to(torch.float64), bs2.to(torch.float64)]
     if gtu_scores is not None:
         qms = dv.empty(max(n, 1), torch.float64)
         dv.quantize(gtu_scores, qms, 1, 0, 3)
         gkey = dv.empty(max(n, 1), torch.int32)
-        dv.call("runia_osod_gtu_keys", key2.data_ptr(), flags.data_ptr(), n, nc, gkey.data_ptr())
+        dv.launch("runia_osod_gtu_keys", key2.data_ptr(), flags.data_ptr(), n, nc, gkey.data_ptr())
         gperm, gbs = dv.bucket_sort(gkey, n, 2 * nc + 1)
         vals, rows = dv.empty(max(n, 1), torch.float64), dv.empty(max(n, 1), torch.float64)
-        dv.call("runia_osod_gather_f64", qms.data_ptr(), n, gperm.data_ptr(), base.perm.data_ptr(), n, vals.data_ptr())
+        dv.launch("runia_osod_gather_f64", qms.data_ptr(), n, gperm.data_ptr(), base.perm.data_ptr(), n, vals.data_ptr())
         src = torch.arange(max(n, 1), dtype=torch.float64, device=dv.dev)
-        dv.call("runia_osod_gather_f64", src.data_ptr(), n, gperm.data_ptr(), base.perm.data_ptr(), n, rows.data_ptr())
+        dv.launch("runia_osod_gather_f64", src.data_ptr(), n, gperm.data_ptr(), base.perm.data_ptr(), n, rows.data_ptr())
         tail.append(gbs.to(torch.float64))
     host = dv.hip.to_host(torch.cat(tail))
     k = M * nc * 8

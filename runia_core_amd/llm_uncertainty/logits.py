@@ -113,9 +113,8 @@ def _run(sequences, scores, normalize: bool, want_log_prob: bool, want_entropy: 
     rows, B, V, dtype, host_dev = _steps(scores)
     T = len(rows)
     tok = _token_ids(sequences, B, T, V) if want_log_prob else None
-    lib = _hip.load_library()
     dev = _hip.require_gpu()
-    need = int(lib.runia_logit_stats_workspace_bytes(T, B, V))
+    need = _hip.query("runia_logit_stats_workspace_bytes", T, B, V)
     if need == 0:
         raise ValueError(f"{T} steps of ({B}, {V}) logits exceed the kernel's size limits")
     table, keep = _table(rows, dev)
@@ -123,14 +122,13 @@ def _run(sequences, scores, normalize: bool, want_log_prob: bool, want_entropy: 
         tok = tok.to(device=dev, dtype=torch.int64)
         if tok.stride(1) != 1:
             tok = tok.contiguous()
-    ws = torch.empty(need, dtype=torch.uint8, device=dev)
+    ws = _hip.workspace(need, dev, 0)
     lp = torch.empty((B, T), dtype=torch.float32, device=dev) if want_log_prob else None
     ent = torch.empty((B, T), dtype=torch.float32, device=dev) if want_entropy else None
     seq = torch.empty(3 * B + 1, dtype=torch.float64, device=dev) if want_seq else None
-    _hip._check(lib.runia_logit_stats(table.data_ptr(), _hip.ELEM_DTYPE_CODES[dtype], T, B, V, _hip._ptr(tok),
-                                      tok.stride(0) if tok is not None else 0, int(bool(normalize)), None, _hip._ptr(lp),
-                                      _hip._ptr(ent), _hip._ptr(seq), ws.data_ptr(), need, _hip._stream()),
-                "runia_logit_stats")
+    _hip.launch("runia_logit_stats", table.data_ptr(), _hip.ELEM_DTYPE_CODES[dtype], T, B, V, _hip._ptr(tok),
+                tok.stride(0) if tok is not None else 0, int(bool(normalize)), None, _hip._ptr(lp), _hip._ptr(ent),
+                _hip._ptr(seq), ws.data_ptr(), need)
     del keep
     if host_dev is None:
         lp = lp.cpu() if lp is not None else None

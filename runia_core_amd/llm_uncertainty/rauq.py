@@ -67,6 +67,26 @@ def _map_shapes(attentions) -> Tuple[int, int, int, torch.dtype, Optional[torch.
     return n_gen, n_layers, heads, dtype, dev
 
 
+def _upload_parts(parts, dev: torch.device):
+    """Host tensors packed into one (pinned, if it can be had) buffer and uploaded in ONE copy -> the device buffer and every
+    part's address in it."""
+    total = sum(p.numel() for p in parts)
+    try:
+        host = torch.empty(total, dtype=parts[0].dtype, pin_memory=True)
+    except RuntimeError:
+        host = torch.empty(total, dtype=parts[0].dtype)
+    at = 0
+    for p in parts:
+        host[at:at + p.numel()].view(p.shape).copy_(p)
+        at += p.numel()
+    dmaps = host.to(dev)
+    size, addresses, at = dmaps.element_size(), [], dmaps.data_ptr()
+    for p in parts:
+        addresses.append(at)
+        at += p.numel() * size
+    return dmaps, addresses
+
+
 def _map_table(attentions, dev: torch.device, first_row_only: bool):
     """Device int64 table [n_gen * L, 6] of map descriptors (batch 0) and the tensors it points into."""
     flat = [t for step in attentions for t in step]
@@ -76,22 +96,8 @@ def _map_table(attentions, dev: torch.device, first_row_only: bool):
     else:
         # host maps: the rows the kernels read, packed into one buffer and uploaded in one copy
         parts = [t[0, :, :1, :] if first_row_only else t[0] for t in flat]
-        total = sum(p.numel() for p in parts)
-        try:
-            host = torch.empty(total, dtype=flat[0].dtype, pin_memory=True)
-        except RuntimeError:
-            host = torch.empty(total, dtype=flat[0].dtype)
-        rows, at = [], 0
-        for p in parts:
-            h, q, k = p.shape
-            host[at:at + p.numel()].view(h, q, k).copy_(p)
-            rows.append([at, q * k, k, 1, k, q])
-            at += p.numel()
-        dmaps = host.to(dev)
-        base, size = dmaps.data_ptr(), dmaps.element_size()
-        for r in rows:
-            r[0] = base + r[0] * size
-        keep = dmaps
+        keep, addresses = _upload_parts(parts, dev)
+        rows = [[at, q * k, k, 1, k, q] for at, (_, q, k) in zip(addresses, (p.shape for p in parts))]
     table = torch.tensor(rows, dtype=torch.int64).to(dev)
     return table, keep
 
@@ -106,14 +112,12 @@ def _probs_source(log_probs: torch.Tensor) -> torch.Tensor:
 
 def _score(att: torch.Tensor, n_layers: int, heads: int, n: int, head_mode: int, lp: torch.Tensor, alphas, ws: torch.Tensor):
     """One score launch; reads back ``n_alpha`` scores and (head_mode 0) the L chosen heads in one copy."""
-    lib = _hip.load_library()
     dev = att.device
     lp_d = _hip.to_device(lp[:n], torch.float32)
     al = torch.tensor([float(a) for a in alphas], dtype=torch.float64).to(dev)
     out = torch.zeros(len(alphas) + n_layers, dtype=torch.int32, device=dev)
-    _hip._check(lib.runia_rauq_score(att.data_ptr(), n_layers, heads, n, head_mode, lp_d.data_ptr(), al.data_ptr(), len(alphas),
-                                     out.data_ptr(), out.data_ptr() + 4 * len(alphas), ws.data_ptr(), ws.numel(), _hip._stream()),
-                "runia_rauq_score")
+    _hip.launch("runia_rauq_score", att.data_ptr(), n_layers, heads, n, head_mode, lp_d.data_ptr(), al.data_ptr(), len(alphas),
+                out.data_ptr(), out.data_ptr() + 4 * len(alphas), ws.data_ptr(), ws.numel())
     host = out.cpu()
     scores = [float(v) for v in host[: len(alphas)].view(torch.float32).tolist()]
     return scores, host[len(alphas):].tolist()
@@ -134,13 +138,11 @@ def _gather_scores(log_probs, attentions, token_aggregation: str, alphas, head_m
                 raise IndexError(f"step {g}: a row of {int(t.shape[3])} keys has no entry -{1 if tok else 2}")
     if len(alphas) == 0:
         return [], []
-    lib = _hip.load_library()
     dev = _hip.require_gpu()
     table, keep = _map_table(attentions, dev, first_row_only=True)
     w = torch.empty((n_layers, heads, n), dtype=torch.float32, device=dev)
-    _hip._check(lib.runia_rauq_gather(table.data_ptr(), _hip.ELEM_DTYPE_CODES[dtype], n_gen, n_layers, heads, tok, w.data_ptr(),
-                                      _hip._stream()), "runia_rauq_gather")
-    ws = torch.empty(int(lib.runia_rauq_workspace_bytes(n_layers, n, 0, 0, 0, len(alphas))), dtype=torch.uint8, device=dev)
+    _hip.launch("runia_rauq_gather", table.data_ptr(), _hip.ELEM_DTYPE_CODES[dtype], n_gen, n_layers, heads, tok, w.data_ptr())
+    ws = _hip.workspace(_hip.query("runia_rauq_workspace_bytes", n_layers, n, 0, 0, 0, len(alphas)), dev, 0)
     scores, chosen = _score(w, n_layers, heads, n, head_mode, lp, alphas, ws)
     del keep
     return scores, (chosen if head_mode == _HEAD_ARGMAX else None)
@@ -175,17 +177,15 @@ def _rollout_scores(log_probs, attentions, token_aggregation: str, input_length:
     lp = log_probs.reshape(-1)
     if len(alphas) == 0:
         return []
-    lib = _hip.load_library()
     dev = _hip.require_gpu()
     code = _hip.ELEM_DTYPE_CODES[dtype]
     table, keep = _map_table(attentions, dev, first_row_only=False)
     flag = torch.zeros(1, dtype=torch.int32, device=dev)
 
     def rows(chain_rows):
-        ws = torch.empty(int(lib.runia_rauq_workspace_bytes(n_layers, n_gen, in_len, n, chain_rows, len(alphas))),
-                         dtype=torch.uint8, device=dev)
-        _hip._check(lib.runia_rauq_rollout_rows(table.data_ptr(), code, n_gen, n_layers, heads, in_len, flag.data_ptr(),
-                                                ws.data_ptr(), ws.numel(), _hip._stream()), "runia_rauq_rollout_rows")
+        ws = _hip.workspace(_hip.query("runia_rauq_workspace_bytes", n_layers, n_gen, in_len, n, chain_rows, len(alphas)), dev, 0)
+        _hip.launch("runia_rauq_rollout_rows", table.data_ptr(), code, n_gen, n_layers, heads, in_len, flag.data_ptr(),
+                    ws.data_ptr(), ws.numel())
         return ws
 
     ws = rows(1 if tok else 0)
@@ -198,8 +198,8 @@ def _rollout_scores(log_probs, attentions, token_aggregation: str, input_length:
     else:
         route, k = 0, 0
     att = torch.empty(n, dtype=torch.float32, device=dev)
-    _hip._check(lib.runia_rauq_rollout_att(table.data_ptr(), code, n_gen, n_layers, heads, in_len, tok, route, n, att.data_ptr(),
-                                           ws.data_ptr(), ws.numel(), _hip._stream()), "runia_rauq_rollout_att")
+    _hip.launch("runia_rauq_rollout_att", table.data_ptr(), code, n_gen, n_layers, heads, in_len, tok, route, n, att.data_ptr(),
+                ws.data_ptr(), ws.numel())
     scores, _ = _score(att, 1, 1, n, _SERIES, lp, alphas, ws)
     if info is not None:
         info.update(route="one_pass" if route == 0 else "chain", upper_nonzero=upper, chain_rows=k, T=T)
@@ -264,21 +264,8 @@ def _batch_table(attentions, dev: torch.device, pads: List[int], first_row_only:
         # step 0: query row pad_b of row b, stored as one query row (which the kernels do not slice by rows again)
         parts = [torch.stack([t[b, :, p:p + 1, :] for b, p in enumerate(pads)]) if t.shape[2] > 1 else t
                  for t in attentions[0]] + [t[:, :, :1, :] for t in flat[len(attentions[0]):]]
-    total = sum(p.numel() for p in parts)
-    try:
-        host = torch.empty(total, dtype=flat[0].dtype, pin_memory=True)
-    except RuntimeError:
-        host = torch.empty(total, dtype=flat[0].dtype)
-    rows, at = [], 0
-    for p in parts:
-        b, h, q, k = p.shape
-        host[at:at + p.numel()].view(b, h, q, k).copy_(p)
-        rows.append([at, h * q * k, q * k, k, 1, k, q])
-        at += p.numel()
-    dmaps = host.to(dev)
-    base, size = dmaps.data_ptr(), dmaps.element_size()
-    for r in rows:
-        r[0] = base + r[0] * size
+    dmaps, addresses = _upload_parts(parts, dev)
+    rows = [[at, h * q * k, q * k, k, 1, k, q] for at, (_, h, q, k) in zip(addresses, (p.shape for p in parts))]
     return torch.tensor(rows, dtype=torch.int64).to(dev), dmaps
 
 
@@ -342,7 +329,6 @@ def rauq_batch(log_probs: torch.Tensor, attentions: Tuple[Tuple[torch.Tensor, ..
     lp = torch.as_tensor(log_probs)
     if lp.dim() != 2 or int(lp.shape[0]) != batch or int(lp.shape[1]) < max(ns):
         raise ValueError(f"log_probs must be ({batch}, >= {max(ns)}), got {tuple(lp.shape)}")
-    lib = _hip.load_library()
     dev = _hip.require_gpu()
     n_alpha = len(alphas)
     out_dev = map_dev if map_dev is not None else dev
@@ -354,22 +340,19 @@ def rauq_batch(log_probs: torch.Tensor, attentions: Tuple[Tuple[torch.Tensor, ..
     rows_d = rows_h.to(dev)
     lp_d = _hip.to_device(lp, torch.float32)
     al = torch.tensor([float(a) for a in alphas], dtype=torch.float64).to(dev)
-    stream = _hip._stream()
 
     def score(att, n_l, n_h, width, mode, ws):
-        _hip._check(lib.runia_rauqb_score(att.data_ptr(), rows_d.data_ptr(), batch, n_l, n_h, width, mode, tok, lp_d.data_ptr(),
-                                          lp_d.stride(0), al.data_ptr(), n_alpha, scores.data_ptr(), ws.data_ptr(), ws.numel(),
-                                          stream), "runia_rauqb_score")
+        _hip.launch("runia_rauqb_score", att.data_ptr(), rows_d.data_ptr(), batch, n_l, n_h, width, mode, tok, lp_d.data_ptr(),
+                    lp_d.stride(0), al.data_ptr(), n_alpha, scores.data_ptr(), ws.data_ptr(), ws.numel())
 
     if head_mode != _SERIES:
         width = n_gen if tok else n_gen - 1
         if width >= 1:
             table, keep = _batch_table(attentions, dev, pads, first_row_only=True)
             w = torch.empty((batch, n_layers, heads, width), dtype=torch.float32, device=dev)
-            _hip._check(lib.runia_rauqb_gather(table.data_ptr(), rows_d.data_ptr(), code, batch, n_gen, n_layers, heads, tok,
-                                               w.data_ptr(), stream), "runia_rauqb_gather")
-            ws = torch.empty(int(lib.runia_rauqb_workspace_bytes(batch, n_layers, width, 0, 0, n_alpha)), dtype=torch.uint8,
-                             device=dev)
+            _hip.launch("runia_rauqb_gather", table.data_ptr(), rows_d.data_ptr(), code, batch, n_gen, n_layers, heads, tok,
+                        w.data_ptr())
+            ws = _hip.workspace(_hip.query("runia_rauqb_workspace_bytes", batch, n_layers, width, 0, 0, n_alpha), dev, 0)
             score(w, n_layers, heads, width, head_mode, ws)
             del keep
     elif n_gen >= 2 and max(ns) >= 2:
@@ -377,11 +360,9 @@ def rauq_batch(log_probs: torch.Tensor, attentions: Tuple[Tuple[torch.Tensor, ..
         flags = torch.zeros(batch, dtype=torch.int32, device=dev)
 
         def row_pass(chain_rows):
-            ws = torch.empty(int(lib.runia_rauqb_workspace_bytes(batch, n_layers, n_gen, in_len, chain_rows, 1)),
-                             dtype=torch.uint8, device=dev)
-            _hip._check(lib.runia_rauqb_rollout_rows(table.data_ptr(), rows_d.data_ptr(), code, batch, n_gen, n_layers, heads,
-                                                     in_len, flags.data_ptr(), ws.data_ptr(), ws.numel(), stream),
-                        "runia_rauqb_rollout_rows")
+            ws = _hip.workspace(_hip.query("runia_rauqb_workspace_bytes", batch, n_layers, n_gen, in_len, chain_rows, 1), dev, 0)
+            _hip.launch("runia_rauqb_rollout_rows", table.data_ptr(), rows_d.data_ptr(), code, batch, n_gen, n_layers, heads,
+                        in_len, flags.data_ptr(), ws.data_ptr(), ws.numel())
             return ws
 
         ws = row_pass(1 if tok else 0)
@@ -391,9 +372,8 @@ def rauq_batch(log_probs: torch.Tensor, attentions: Tuple[Tuple[torch.Tensor, ..
         if k > (1 if tok else 0):
             ws = row_pass(k)  # the n-row chains need the larger workspace: the row pass runs again into it
         att = torch.empty((batch, n_gen), dtype=torch.float32, device=dev)
-        _hip._check(lib.runia_rauqb_rollout_att(table.data_ptr(), rows_d.data_ptr(), rows_h.data_ptr(), flags.data_ptr(),
-                                                upper.data_ptr(), code, batch, n_gen, n_layers, heads, in_len, tok,
-                                                att.data_ptr(), ws.data_ptr(), ws.numel(), stream), "runia_rauqb_rollout_att")
+        _hip.launch("runia_rauqb_rollout_att", table.data_ptr(), rows_d.data_ptr(), rows_h.data_ptr(), flags.data_ptr(),
+                    upper.data_ptr(), code, batch, n_gen, n_layers, heads, in_len, tok, att.data_ptr(), ws.data_ptr(), ws.numel())
         score(att, 1, 1, n_gen, _SERIES, ws)
         del keep
     return scores if map_dev is not None else scores.cpu()

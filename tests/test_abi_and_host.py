@@ -116,6 +116,73 @@ def test_product_path_fails_loudly_without_gpu(monkeypatch):
         rc.evaluation.get_auroc_results("test", np.array([0.9, 0.8]), np.array([0.1, 0.2]))
 
 
+def _refusal_table():
+    """(name, call of valid shape on host tensors, exception class): what every binding wrapper raises first when no HIP
+    device is visible.  Wrappers that check shapes, dtypes and devices before they touch the library refuse a host tensor
+    with an AssertionError; the others ask for the GPU first."""
+    from runia_core_amd import distributed
+    from runia_core_amd.evaluation import open_set
+    from runia_core_amd.llm_uncertainty import rauq_batch, rauq_uncertainty, token_entropies
+
+    f32, f64 = torch.float32, torch.float64
+    x = torch.zeros(2, 3, 4, 4)                      # [N, C, H, W]
+    shared, per_image = torch.zeros(6, 4, 4), torch.zeros(2, 6, 4, 4)
+    z = torch.zeros(12, 3)                           # [N * n_mc, D]
+    rows64, rows32 = torch.zeros(5, 8, dtype=f64), torch.zeros(5, 8)
+    mean64, packed = torch.zeros(8, dtype=f64), torch.zeros(64, dtype=f64)
+    att = tuple(tuple(torch.full((1, 2, 4 if g == 0 else 1, 4 + g), 0.25) for _ in range(2)) for g in range(3))
+    att_b = tuple(tuple(t.repeat(2, 1, 1, 1) for t in step) for step in att)
+    gpu, refused = _hip.RuniaHipError, AssertionError
+    return [
+        ("mc_stack", lambda: _hip.mc_stack(x, shared, 6, 0.5, 2), gpu),
+        ("mc_stack per-image draws", lambda: _hip.mc_stack(x, per_image, 6, 0.5, 2), gpu),
+        ("mc_drop_flat", lambda: _hip.mc_drop_flat(x, shared, 6, 0.5, 2), gpu),
+        ("mc_mask_table", lambda: _hip.mc_mask_table(per_image, 2, 4, 4, 6, 0.5, 2), gpu),
+        ("mc_mask_table counter", lambda: _hip.mc_mask_table(_hip.CounterDraws(7), 2, 4, 4, 6, 0.5, 2), gpu),
+        ("mc_entropy", lambda: _hip.mc_entropy(x, shared, 6, 0.5, 2, 5), gpu),
+        ("mc_entropy counter", lambda: _hip.mc_entropy(x, _hip.CounterDraws(7), 6, 0.5, 2, 5), gpu),
+        ("md_score", lambda: _hip.md_score(rows64, mean64, packed), gpu),
+        ("md_score f32", lambda: _hip.md_score(rows32, mean64, packed), gpu),
+        ("md_score_tril", lambda: _hip.md_score_tril(rows64, mean64, packed), gpu),
+        ("kl_entropy_per_dim", lambda: _hip.kl_entropy_per_dim(z, 6, 5), gpu),
+        ("kl_entropy_joint", lambda: _hip.kl_entropy_joint(z, 6, 5), gpu),
+        ("kl_entropy_both", lambda: _hip.kl_entropy_both(z, 6, 5), gpu),
+        ("knn_kth", lambda: _hip.knn_kth(rows32, torch.zeros(9, 8), 3), gpu),
+        ("knn_kth prepared", lambda: _hip.knn_kth(rows32, torch.zeros(9, 8), 3, state=torch.zeros(64)), gpu),
+        ("covariance", lambda: _hip.covariance(rows64), gpu),
+        ("covariance f32", lambda: _hip.covariance(rows32), gpu),
+        ("pca_transform", lambda: _hip.pca_transform(rows64, packed, mean64, None, 4), gpu),
+        ("proj_sq_score", lambda: _hip.proj_sq_score(rows64, packed, mean64, 4), gpu),
+        ("mahalanobis_score", lambda: _hip.mahalanobis_score(rows32, torch.zeros(3, 8), packed, mean64), gpu),
+        ("ood_metrics", lambda: _hip.ood_metrics(torch.zeros(4), torch.ones(3)), gpu),
+        ("ood_clf_curve", lambda: _hip.ood_clf_curve(torch.zeros(4, dtype=f64), torch.ones(3, dtype=f64)), gpu),
+        ("eigh", lambda: _hip.eigh(torch.eye(4, dtype=f64)), gpu),
+        ("cholesky", lambda: _hip.cholesky(torch.eye(4)), gpu),
+        ("pacmap_phase_weights", lambda: _hip.pacmap_phase_weights(-1), gpu),  # a host query: refuses the iteration
+        ("mcd_reduce_rows", lambda: _hip.mcd_reduce_rows(x, torch.zeros(2, 3), "fullmean"), refused),
+        ("ragged_rows", lambda: _hip.ragged_rows([rows32, rows32[:2]]), refused),
+        ("pixel_uncertainty_maps", lambda: _hip.pixel_uncertainty_maps(torch.zeros(4, 3, 4, 5), 2), refused),
+        ("pixel_map_reduce", lambda: _hip.pixel_map_reduce(torch.zeros(2, 4, 5)), refused),
+        ("rauq_uncertainty", lambda: rauq_uncertainty(torch.zeros(3), att, "original"), gpu),
+        ("rauq_batch", lambda: rauq_batch(torch.zeros(2, 3), att_b, 4, "original", "mean_heads", [0.2]), gpu),
+        ("token_entropies", lambda: token_entropies(tuple(torch.zeros(2, 7) for _ in range(3))), gpu),
+        ("open_set._Device", lambda: open_set._Device(), gpu),
+        ("OneShotGather", lambda: distributed.OneShotGather(8), gpu),
+    ]
+
+
+def test_every_wrapper_keeps_its_first_refusal_without_gpu(monkeypatch):
+    """Which exception a wrapper raises first on a box without a GPU is part of its contract: most ask for the GPU before
+    anything else (RuniaHipError), the newer ones refuse shapes, dtypes and host tensors before they touch the library
+    (AssertionError).  The classes were recorded by running this table against the binding before it got its launch
+    helper; the launch helper itself never asks for the GPU, so each wrapper keeps the order it had."""
+    monkeypatch.setattr(torch.cuda, "is_available", lambda: False)
+    for name, call, expected in _refusal_table():
+        with pytest.raises(Exception) as caught:
+            call()
+        assert type(caught.value) is expected, f"{name}: {type(caught.value).__name__}: {caught.value}"
+
+
 def test_no_product_module_imports_the_oracle():
     pkg = os.path.join(ROOT, "runia_core_amd")
     for dirpath, _, files in os.walk(pkg):

@@ -838,6 +838,38 @@ int runia_pacmap_phase_weights(int t, float* w);
 int runia_pacmap_step_f32(const float* y_in, const float* y_part, float* y_out, float* m, float* v, const int64_t* offsets,
                           const int32_t* entries, int64_t R, int n_components, int t, float lr, runia_stream_t stream);
 
+/* ---- MaxLogit, KL-Matching, fDBD (logit_baselines.hip; inference/extended_postprocessors.py) ------------------ *
+ * Baselines the reference does not ship; the definitions are restated in f64 in tests/extended_baseline_cases.py.
+ *
+ * runia_row_logit_stats_f32: one pass over logits [N, C] f32.  Any output pointer may be NULL (not all four).
+ *     max_logit   f32 [N]  the row maximum (NaN entries are skipped, as by fmaxf)
+ *     lse         f32 [N]  scipy.special.logsumexp of the row, the arithmetic of runia_row_lse_msp_f32
+ *     neg_entropy f32 [N]  sum_k p_k log p_k, p = softmax(row).  A class with p_k == 0 (a logit of -inf, or more than ~104
+ *                          below the maximum) contributes 0 - NOT the 0 * log 0 = NaN of pred_h in
+ *                          runia_mcd_uncertainty_f32 / runia_pixel_uncertainty_maps.  A NaN logit makes lse and neg_entropy NaN.
+ *     argmax      i32 [N]  first index of the maximum (np.argmax on rows without NaN)
+ *   Launch shapes of runia_row_lse_msp_f32: C <= 16 a row per lane in registers, C <= 64 a row per lane through LDS, beyond
+ *   that a wave per row (16-byte loads and the row in registers for C % 4 == 0, aligned, C <= 2048; re-read otherwise).
+ *   Sums in a fixed order that does not depend on N or on the row's place in the batch: bit identical from run to run.
+ * runia_klm_score_f32: score[n] = max over classes c with valid[c] != 0 of sum_k p[n, k] log_q[c, k], minus neg_entropy[n],
+ *   with p[n, k] = exp(logits[n, k] - lse[n]): -min_c KL(softmax(logits[n]) || q_c).  logits [N, C], log_q [K, C] f32
+ *   row-major, lse / neg_entropy [N] (runia_row_logit_stats_f32), valid [K] int32 or NULL (all classes), score [N] f32.
+ *   The N x C x K contraction runs on the f32 matrix cores (k-ordered fma chains); neither p nor the N x K products are
+ *   written.  No atomics, no workspace; a row's score does not depend on the other rows of the call.  A NaN product makes
+ *   the row NaN; no valid class gives -inf.  N < 2^38.
+ * runia_fdbd_score_f32: with c = first argmax of logits[n]: score[n] = (sum over k != c of |logits[n, c] - logits[n, k]| *
+ *   inv_dist[c, k]) / ((C - 1) * feat_dist[n]).  inv_dist [C, C] f32 (1 / ||w_c - w_k||_2, 0 where the norm is 0), feat_dist
+ *   [N] f32.  IEEE results as they fall (feat_dist == 0: inf, or NaN for a zero sum).  A wave per row, the row in registers
+ *   up to C = 4096, re-read beyond.  C >= 2.
+ * runia_row_dist_f32: out[n] = || x[n] - mu ||_2, x [N, D], mu [D], f32. */
+int runia_row_logit_stats_f32(const float* logits, float* max_logit, float* lse, float* neg_entropy, int32_t* argmax,
+                              int64_t N, int64_t C, runia_stream_t stream);
+int runia_klm_score_f32(const float* logits, const float* lse, const float* neg_entropy, const float* log_q,
+                        const int32_t* valid, float* score, int64_t N, int64_t C, int64_t K, runia_stream_t stream);
+int runia_fdbd_score_f32(const float* logits, const float* inv_dist, const float* feat_dist, float* score, int64_t N,
+                         int64_t C, runia_stream_t stream);
+int runia_row_dist_f32(const float* x, const float* mu, float* out, int64_t N, int64_t D, runia_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

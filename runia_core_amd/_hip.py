@@ -284,6 +284,11 @@ _SIGNATURES = {
     "runia_pacmap_phase_weights": (c_int, [c_int, c_void_p]),
     "runia_pacmap_step_f32": (
         c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_int, c_int, c_float, c_void_p]),
+    "runia_row_logit_stats_f32": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_int64, c_void_p]),
+    "runia_klm_score_f32": (
+        c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_int64, c_int64, c_void_p]),
+    "runia_fdbd_score_f32": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_int64, c_void_p]),
+    "runia_row_dist_f32": (c_int, [c_void_p, c_void_p, c_void_p, c_int64, c_int64, c_void_p]),
 }
 
 
@@ -892,6 +897,82 @@ def row_lse_msp(logits: torch.Tensor, want_lse: bool = True, want_msp: bool = Fa
     msp = torch.empty((n,), dtype=torch.float32, device=logits.device) if want_msp else None
     launch("runia_row_lse_msp_f32", logits.data_ptr(), _ptr(lse), _ptr(msp), n, c)
     return lse, msp
+
+
+class LogitRowStats(NamedTuple):
+    """What ``logit_row_stats`` returns: [N] device tensors, ``None`` for a statistic that was not asked for."""
+
+    max_logit: Optional[torch.Tensor]
+    lse: Optional[torch.Tensor]
+    neg_entropy: Optional[torch.Tensor]
+    argmax: Optional[torch.Tensor]
+
+
+@_device_guard()
+def logit_row_stats(logits: torch.Tensor, max_logit: bool = True, lse: bool = True, neg_entropy: bool = True,
+                    argmax: bool = True) -> LogitRowStats:
+    """logits [N, C] f32 -> row maximum, logsumexp, ``sum p log p`` of the softmax (f32) and the first argmax (int32) in
+    one pass (``runia_row_logit_stats_f32``); at least one statistic must be asked for."""
+    require_gpu()
+    assert logits.is_cuda and logits.dtype == torch.float32 and logits.dim() == 2
+    assert max_logit or lse or neg_entropy or argmax, "ask for at least one statistic"
+    logits = logits.contiguous()
+    n, c = logits.shape
+    f32 = lambda want: torch.empty((n,), dtype=torch.float32, device=logits.device) if want else None  # noqa: E731
+    out = LogitRowStats(f32(max_logit), f32(lse), f32(neg_entropy),
+                        torch.empty((n,), dtype=torch.int32, device=logits.device) if argmax else None)
+    launch("runia_row_logit_stats_f32", logits.data_ptr(), _ptr(out.max_logit), _ptr(out.lse), _ptr(out.neg_entropy),
+           _ptr(out.argmax), n, c)
+    return out
+
+
+@_device_guard()
+def klm_score(logits: torch.Tensor, lse: torch.Tensor, neg_entropy: torch.Tensor, log_q: torch.Tensor,
+              valid: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """``max_c sum_k softmax(logits)[n, k] log_q[c, k] - neg_entropy[n]`` over the classes with ``valid[c] != 0`` -> [N] f32
+    (``runia_klm_score_f32``).  logits [N, C], log_q [K, C] f32; lse, neg_entropy [N] f32 from ``logit_row_stats``; valid [K]
+    int32 or None."""
+    require_gpu()
+    assert logits.is_cuda and logits.dtype == torch.float32 and logits.dim() == 2
+    assert log_q.is_cuda and log_q.dtype == torch.float32 and log_q.dim() == 2 and log_q.shape[1] == logits.shape[1]
+    n, c = logits.shape
+    k = log_q.shape[0]
+    assert lse.dtype == torch.float32 and neg_entropy.dtype == torch.float32 and lse.shape == (n,) and neg_entropy.shape == (n,)
+    assert valid is None or (valid.is_cuda and valid.dtype == torch.int32 and valid.shape == (k,))
+    logits, log_q = logits.contiguous(), log_q.contiguous()
+    lse, neg_entropy = lse.contiguous(), neg_entropy.contiguous()
+    valid = None if valid is None else valid.contiguous()
+    score = torch.empty((n,), dtype=torch.float32, device=logits.device)
+    launch("runia_klm_score_f32", logits.data_ptr(), lse.data_ptr(), neg_entropy.data_ptr(), log_q.data_ptr(), _ptr(valid),
+           score.data_ptr(), n, c, k)
+    return score
+
+
+@_device_guard()
+def fdbd_score(logits: torch.Tensor, inv_dist: torch.Tensor, feat_dist: torch.Tensor) -> torch.Tensor:
+    """logits [N, C], inv_dist [C, C], feat_dist [N], all f32 -> [N] f32 (``runia_fdbd_score_f32``); C >= 2."""
+    require_gpu()
+    assert logits.is_cuda and logits.dtype == torch.float32 and logits.dim() == 2
+    n, c = logits.shape
+    assert c >= 2, "fDBD needs at least two classes"
+    assert inv_dist.is_cuda and inv_dist.dtype == torch.float32 and inv_dist.shape == (c, c)
+    assert feat_dist.is_cuda and feat_dist.dtype == torch.float32 and feat_dist.shape == (n,)
+    logits, inv_dist, feat_dist = logits.contiguous(), inv_dist.contiguous(), feat_dist.contiguous()
+    score = torch.empty((n,), dtype=torch.float32, device=logits.device)
+    launch("runia_fdbd_score_f32", logits.data_ptr(), inv_dist.data_ptr(), feat_dist.data_ptr(), score.data_ptr(), n, c)
+    return score
+
+
+@_device_guard()
+def row_dist(x: torch.Tensor, mu: torch.Tensor) -> torch.Tensor:
+    """``|| x[n] - mu ||_2`` -> [N] f32 (x [N, D], mu [D], f32; ``runia_row_dist_f32``)."""
+    require_gpu()
+    assert x.is_cuda and x.dtype == torch.float32 and x.dim() == 2
+    assert mu.is_cuda and mu.dtype == torch.float32 and mu.numel() == x.shape[1]
+    x, mu = x.contiguous(), mu.contiguous()
+    out = torch.empty((x.shape[0],), dtype=torch.float32, device=x.device)
+    launch("runia_row_dist_f32", x.data_ptr(), mu.data_ptr(), out.data_ptr(), x.shape[0], x.shape[1])
+    return out
 
 
 @_device_guard()

@@ -53,3 +53,12 @@ from .postprocessors import (  # noqa: F401
     postprocessors_dict,
     register_postprocessor,
 )
+from .extended_postprocessors import (  # noqa: F401
+    FDBD,
+    KLMatching,
+    MaxLogit,
+    RelativeMahalanobis,
+    extended_postprocessor_input_dict,
+    extended_postprocessors_dict,
+    fdbd_inverse_distances,
+)

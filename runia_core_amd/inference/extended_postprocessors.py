@@ -11,16 +11,16 @@ in-distribution for all four.  The definitions are restated in float64 in ``test
 from __future__ import annotations
 
 import warnings
-from typing import Dict, List, Union
+from typing import Dict, List
 
 import numpy as np
 import torch
 from torch import Tensor
 
 from .. import _hip
-from .abstract_classes import OodPostprocessor, Postprocessor
-from .funcs import MahalanobisState, _maha_dtype, mahalanobis_preprocess
-from .postprocessors import (_fc_params, _feats_to_device, _logits_to_device, _restore_dtype, postprocessor_input_dict,
+from .abstract_classes import Postprocessor
+from .funcs import MahalanobisState, mahalanobis_preprocess
+from .postprocessors import (_DeviceScored, _fc_params, _LogitScored, _MahalanobisScored, postprocessor_input_dict,
                              postprocessors_dict)
 
 __all__ = ["extended_postprocessors_dict", "extended_postprocessor_input_dict", "MaxLogit", "KLMatching", "FDBD",
@@ -34,31 +34,17 @@ def _host(a) -> np.ndarray:
     return _hip.to_host(a.detach()) if isinstance(a, Tensor) else np.asarray(a)
 
 
-class MaxLogit(OodPostprocessor):
+class MaxLogit(_LogitScored):
     """MaxLogit: the largest logit of the row."""
 
-    def __init__(self, flip_sign: bool, cfg=None):
-        super().__init__(flip_sign, cfg)
-
-    def _scores(self, logits) -> np.ndarray:
-        if isinstance(logits, Tensor):
-            logits = logits.detach()
-        m = _hip.logit_row_stats(_logits_to_device(logits), True, False, False, False).max_logit
-        return _restore_dtype(m, logits)
+    def _score_device(self, logits: Tensor) -> Tensor:
+        return _hip.logit_row_stats(logits, True, False, False, False).max_logit
 
     def setup(self, ind_train_data: np.ndarray, **kwargs):
-        self.set_threshold(self.flip_sign_fn(self._scores(ind_train_data)))
-
-    def postprocess_device(self, logits: Tensor) -> Tensor:
-        m = _hip.logit_row_stats(logits, True, False, False, False).max_logit
-        return -m if self.flip_sign else m
-
-    def postprocess(self, test_data: np.ndarray, **kwargs) -> np.ndarray:
-        assert self._setup_flag, "setup() must be called before postprocess()"
-        return self.flip_sign_fn(self._scores(test_data))
+        self._threshold_from(ind_train_data)
 
 
-class KLMatching(OodPostprocessor):
+class KLMatching(_LogitScored):
     """KL-Matching: ``-min_c KL(softmax(x) || q_c)``, ``q_c`` the mean softmax of the training rows predicted as class ``c``.
 
     Fitted state: ``log_q`` [num_classes, num_classes] float32 = ``log(max(q, 1e-30))`` and ``valid`` [num_classes] int32 (0 for
@@ -120,25 +106,12 @@ class KLMatching(OodPostprocessor):
         rs = _hip.logit_row_stats(logits, False, True, True, False)
         return _hip.klm_score(logits, rs.lse, rs.neg_entropy, st["log_q"], st["valid"])
 
-    def _scores(self, logits) -> np.ndarray:
-        if isinstance(logits, Tensor):
-            logits = logits.detach()
-        return _restore_dtype(self._score_device(_logits_to_device(logits)), logits)
-
     def setup(self, ind_train_data: np.ndarray, **kwargs):
         """``ind_train_data``: the training logits [N, num_classes]."""
         train = ind_train_data.detach() if isinstance(ind_train_data, Tensor) else np.asarray(ind_train_data)
         self._check_width(train)
-        self._fit(_logits_to_device(train))
-        self.set_threshold(self.flip_sign_fn(self._scores(train)))
-
-    def postprocess_device(self, logits: Tensor) -> Tensor:
-        s = self._score_device(logits)
-        return -s if self.flip_sign else s
-
-    def postprocess(self, test_data: np.ndarray, **kwargs) -> np.ndarray:
-        assert self._setup_flag, "setup() must be called before postprocess()"
-        return self.flip_sign_fn(self._scores(test_data))
+        self._fit(self._to_device(train))
+        self._threshold_from(train)
 
 
 def fdbd_inverse_distances(weight: np.ndarray) -> np.ndarray:
@@ -159,7 +132,7 @@ def fdbd_inverse_distances(weight: np.ndarray) -> np.ndarray:
     return inv.astype(np.float32)
 
 
-class FDBD(OodPostprocessor):
+class FDBD(_DeviceScored):
     """fDBD: the mean distance of the feature to the decision boundaries of the final linear layer,
     ``|l_c - l_k| / ||w_c - w_k||_2`` over the classes ``k`` other than the predicted ``c``, divided by the feature's distance
     to the mean of the training features.
@@ -188,9 +161,6 @@ class FDBD(OodPostprocessor):
         logits = _hip.linear(feats, st["w"], st["b"])
         return _hip.fdbd_score(logits, st["inv"], _hip.row_dist(feats, st["mu"]))
 
-    def _scores(self, feats) -> np.ndarray:
-        return _hip.to_host(self._score_device(_feats_to_device(feats)))
-
     def setup(self, ind_train_data: np.ndarray, **kwargs):
         self.w, self.b = _fc_params(kwargs, "FDBD")
         if np.asarray(self.w).ndim != 2 or np.asarray(self.w).shape[0] < 2:
@@ -200,18 +170,10 @@ class FDBD(OodPostprocessor):
         self.train_mean = torch.Tensor(_host(ind_train_data)).mean(0).numpy()
         self.inv_dist = fdbd_inverse_distances(self.w)
         self._dev = None
-        self.set_threshold(self.flip_sign_fn(self._scores(kwargs["valid_feats"])))
-
-    def postprocess_device(self, feats: Tensor) -> Tensor:
-        s = self._score_device(feats)
-        return -s if self.flip_sign else s
-
-    def postprocess(self, test_data: np.ndarray, **kwargs) -> np.ndarray:
-        assert self._setup_flag, "setup() must be called before postprocess()"
-        return self.flip_sign_fn(self._scores(test_data))
+        self._threshold_from(kwargs["valid_feats"])
 
 
-class RelativeMahalanobis(OodPostprocessor):
+class RelativeMahalanobis(_MahalanobisScored):
     """Relative Mahalanobis: the class-conditional Mahalanobis score minus the score under ONE background Gaussian fitted to
     all training rows, ``-min_c (d_c(x) - d_0(x))``.  Both terms are ``mahalanobis_preprocess`` fits scored by the
     Mahalanobis kernels (float64 scores)."""
@@ -227,19 +189,12 @@ class RelativeMahalanobis(OodPostprocessor):
         self.background_precision = None
         self._state = None
 
-    def _states(self):
+    def _score_device(self, x: Tensor) -> Tensor:
         if self._state is None:
             self._state = (MahalanobisState(self.class_mean[: self.num_classes], self.precision),
                            MahalanobisState(self.background_mean[:1], self.background_precision))
-        return self._state
-
-    def _score_device(self, x: Tensor) -> Tensor:
-        classes, background = self._states()
+        classes, background = self._state
         return classes.score_device(x) - background.score_device(x)
-
-    def _scores(self, feats) -> np.ndarray:
-        x = _hip.to_device(feats, _maha_dtype(feats, self.class_mean))
-        return _hip.to_host(self._score_device(x))
 
     def setup(self, ind_train_data: np.ndarray, **kwargs):
         assert "train_labels" in kwargs, "train_labels must be provided for RelativeMahalanobis"
@@ -250,17 +205,7 @@ class RelativeMahalanobis(OodPostprocessor):
         self.background_mean, self.background_precision = mahalanobis_preprocess(
             ind_data={"train features": ind_train_data, "train labels": np.zeros_like(labels)}, num_classes=1)
         self._state = None
-        self.set_threshold(self.flip_sign_fn(self._scores(kwargs["valid_feats"])))
-
-    def postprocess_device(self, feats: Tensor) -> Tensor:
-        s = self._score_device(feats)
-        return -s if self.flip_sign else s
-
-    def postprocess(self, test_data: Union[np.ndarray, Tensor], **kwargs) -> np.ndarray:
-        assert self._setup_flag, "setup() must be called before postprocess()"
-        if isinstance(test_data, Tensor):
-            test_data = _hip.to_host(test_data)
-        return self.flip_sign_fn(self._scores(test_data))
+        self._threshold_from(kwargs["valid_feats"])
 
 
 extended_postprocessors_dict: Dict[str, Postprocessor] = {**postprocessors_dict, "mls": MaxLogit, "klm": KLMatching,

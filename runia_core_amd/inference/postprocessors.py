@@ -572,10 +572,6 @@ class GMMLatentSpace(Postprocessor):
 # --------------------------------------------------------------------------------------
 # logits / features family
 # --------------------------------------------------------------------------------------
-def _logits_to_device(test_data) -> Tensor:
-    return _hip.to_device(test_data, torch.float32)
-
-
 def _restore_dtype(scores: Tensor, src) -> np.ndarray:
     out = _hip.to_host(scores)
     want = np.asarray(src).dtype if not isinstance(src, Tensor) else np.float32
@@ -588,62 +584,91 @@ def _host_logits() -> bool:
     return bool(config.host_logits_without_gpu) and not torch.cuda.is_available()
 
 
-@register_postprocessor("energy", postprocessor_input=["logits"])
-class Energy(OodPostprocessor):
-    """Energy score: ``logsumexp(logits, axis=1)``."""
+class _DeviceScored(OodPostprocessor):
+    """An OOD postprocessor written as ONE device scoring body.  A subclass fits in ``setup`` (and ends it with
+    ``_threshold_from(split)``) and implements ``_score_device``: device rows in, unflipped device scores out.  The host
+    path (upload, ``_score_device``, download), the sign flip and the threshold are derived here.  Rows go up as float32
+    and the scores come down in the kernel's dtype unless a subclass overrides ``_to_device`` / ``_to_host``."""
 
-    def _score(self, data) -> np.ndarray:
+    def _score_device(self, x: Tensor) -> Tensor:
+        raise NotImplementedError
+
+    def _to_device(self, data) -> Tensor:
+        return _hip.to_device(data, torch.float32)
+
+    def _to_host(self, scores: Tensor, data) -> np.ndarray:
+        return _hip.to_host(scores)
+
+    def _scores(self, data) -> np.ndarray:
+        """Unflipped host scores; no setup assertion (``setup`` itself scores a split through it)."""
         if isinstance(data, Tensor):
             data = data.detach()
+        return self._to_host(self._score_device(self._to_device(data)), data)
+
+    def _threshold_from(self, split) -> None:
+        self.set_threshold(self.flip_sign_fn(self._scores(split)))
+
+    def postprocess_device(self, test_data: Tensor) -> Tensor:
+        s = self._score_device(test_data)
+        return -s if self.flip_sign else s
+
+    def postprocess(self, test_data: Union[np.ndarray, Tensor], **kwargs) -> np.ndarray:
+        assert self._setup_flag, "setup() must be called before postprocess()"
+        return self.flip_sign_fn(self._scores(test_data))
+
+
+class _LogitScored(_DeviceScored):
+    """Logits rule: float32 on the device, the scores restored to the dtype of the host logits (``_restore_dtype``)."""
+
+    def _to_host(self, scores: Tensor, data) -> np.ndarray:
+        return _restore_dtype(scores, data)
+
+
+class _MahalanobisScored(_DeviceScored):
+    """Mahalanobis rule: rows go up as ``_maha_dtype(rows, class_mean)``; the kernels return float64 scores."""
+
+    def _to_device(self, data) -> Tensor:
+        return _hip.to_device(data, _maha_dtype(data, self.class_mean))
+
+
+@register_postprocessor("energy", postprocessor_input=["logits"])
+class Energy(_LogitScored):
+    """Energy score: ``logsumexp(logits, axis=1)``."""
+
+    def _score_device(self, logits: Tensor) -> Tensor:
+        return _hip.row_lse_msp(logits, True, False)[0]
+
+    def _scores(self, data) -> np.ndarray:
         if _host_logits():  # explicit opt-in on a GPU-less box (config.host_logits_without_gpu): the reference's own call
             from scipy.special import logsumexp
 
-            return logsumexp(data.cpu().numpy() if isinstance(data, Tensor) else data, axis=1)
-        lse, _ = _hip.row_lse_msp(_logits_to_device(data), True, False)
-        return _restore_dtype(lse, data)
+            return logsumexp(data.detach().cpu().numpy() if isinstance(data, Tensor) else data, axis=1)
+        return super()._scores(data)
 
     def setup(self, ind_train_data: np.ndarray, **kwargs):
-        ind_scores = self.flip_sign_fn(self._score(ind_train_data))
-        self.set_threshold(ind_scores)
-
-    def postprocess_device(self, logits: Tensor) -> Tensor:
-        lse, _ = _hip.row_lse_msp(logits, True, False)
-        return -lse if self.flip_sign else lse
-
-    def postprocess(self, test_data: np.ndarray, **kwargs) -> np.ndarray:
-        assert self._setup_flag, "setup() must be called before postprocess()"
-        return self.flip_sign_fn(self._score(test_data))
+        self._threshold_from(ind_train_data)
 
 
 @register_postprocessor("msp", postprocessor_input=["logits"])
-class MSP(OodPostprocessor):
+class MSP(_LogitScored):
     """Maximum softmax probability."""
 
-    def _score(self, data) -> np.ndarray:
-        if isinstance(data, Tensor):
-            data = data.detach()
+    def _score_device(self, logits: Tensor) -> Tensor:
+        return _hip.row_lse_msp(logits, False, True)[1]
+
+    def _scores(self, data) -> np.ndarray:
         if _host_logits():  # explicit opt-in on a GPU-less box (config.host_logits_without_gpu): the reference's own call
             from scipy.special import softmax
 
-            return np.max(softmax(data.cpu().numpy() if isinstance(data, Tensor) else data, axis=1), axis=1)
-        _, msp = _hip.row_lse_msp(_logits_to_device(data), False, True)
-        return _restore_dtype(msp, data)
+            return np.max(softmax(data.detach().cpu().numpy() if isinstance(data, Tensor) else data, axis=1), axis=1)
+        return super()._scores(data)
 
     def setup(self, ind_train_data: np.ndarray, **kwargs):
-        ind_scores = self.flip_sign_fn(self._score(ind_train_data))
-        self.set_threshold(ind_scores)
-
-    def postprocess_device(self, logits: Tensor) -> Tensor:
-        _, msp = _hip.row_lse_msp(logits, False, True)
-        return -msp if self.flip_sign else msp
-
-    def postprocess(self, test_data: np.ndarray, **kwargs) -> np.ndarray:
-        assert self._setup_flag, "setup() must be called before postprocess()"
-        return self.flip_sign_fn(self._score(test_data))
+        self._threshold_from(ind_train_data)
 
 
 @register_postprocessor("knn", postprocessor_input=["features"])
-class KNN(OodPostprocessor):
+class KNN(_DeviceScored):
     """k-th nearest-neighbour distance on L2-normalised features (flat exact index)."""
 
     def __init__(self, flip_sign: bool, k_neighbors: int, cfg=None):
@@ -653,29 +678,26 @@ class KNN(OodPostprocessor):
         self.device = "cuda" if torch.cuda.is_available() else "cpu"
         self.index = None
 
+    def _score_device(self, feats: Tensor) -> Tensor:
+        return self.index.kth_score_device(_hip.l2_normalize(feats.to(torch.float32)), self.k_neighbors)
+
     def setup(self, ind_train_data: np.ndarray, **kwargs):
         assert "valid_feats" in kwargs, "valid_feats must be provided for KNN setup"
         train = np.asarray(ind_train_data)
         self.index = FlatL2Bank(train.shape[1])
         # the normalised bank stays where it was made (the host copy - pickling, a later `add` - is read back when asked for)
         self.index.add_device(_hip.l2_normalize(_hip.to_device(train, torch.float32)))
-        ind_scores = self.postprocess(kwargs["valid_feats"])
-        ind_scores = self.flip_sign_fn(ind_scores)
-        self.set_threshold(ind_scores)
-
-    def postprocess_device(self, feats: Tensor) -> Tensor:
-        s = self.index.kth_score_device(_hip.l2_normalize(feats.to(torch.float32)), self.k_neighbors)
-        return -s if self.flip_sign else s
+        # the reference flips twice here (inside its postprocess, then flip_sign_fn once more): whatever flip_sign says, the
+        # threshold is that of the unflipped scores
+        self.set_threshold(self.flip_sign_fn(self.postprocess(kwargs["valid_feats"])))
 
     def postprocess(self, test_data: np.ndarray, **kwargs) -> np.ndarray:
-        if isinstance(test_data, Tensor):
-            test_data = _hip.to_host(test_data)
-        scores = self.index.kth_score(np.asarray(test_data), self.k_neighbors)
-        return self.flip_sign_fn(scores)
+        # no setup assertion, as in the reference: setup scores valid_feats through here before the flag is set
+        return self.flip_sign_fn(self._scores(test_data))
 
 
 @register_postprocessor("mahalanobis", postprocessor_input=["features"])
-class Mahalanobis(OodPostprocessor):
+class Mahalanobis(_MahalanobisScored):
     """Class-conditional Mahalanobis distance with a shared precision matrix."""
 
     def __init__(self, flip_sign: bool, num_classes: int, cfg=None):
@@ -685,11 +707,10 @@ class Mahalanobis(OodPostprocessor):
         self.precision = None
         self._state = None
 
-    def _scores(self, feats) -> np.ndarray:
+    def _score_device(self, feats: Tensor) -> Tensor:
         if self._state is None:
             self._state = MahalanobisState(self.class_mean[: self.num_classes], self.precision)
-        x = _hip.to_device(feats, _maha_dtype(feats, self.class_mean))
-        return _hip.to_host(self._state.score_device(x))
+        return self._state.score_device(feats)
 
     def setup(self, ind_train_data: np.ndarray, **kwargs):
         assert "train_labels" in kwargs, "train_labels must be provided for Mahalanobis"
@@ -697,20 +718,7 @@ class Mahalanobis(OodPostprocessor):
         ind_data_dict = {"train features": ind_train_data, "train labels": kwargs["train_labels"]}
         self.class_mean, self.precision = mahalanobis_preprocess(ind_data=ind_data_dict, num_classes=self.num_classes)
         self._state = None
-        ind_scores = self.flip_sign_fn(self._scores(kwargs["valid_feats"]))
-        self.set_threshold(ind_scores)
-
-    def postprocess_device(self, feats: Tensor) -> Tensor:
-        if self._state is None:
-            self._state = MahalanobisState(self.class_mean[: self.num_classes], self.precision)
-        s = self._state.score_device(feats)
-        return -s if self.flip_sign else s
-
-    def postprocess(self, test_data: Union[np.ndarray, Tensor], **kwargs) -> np.ndarray:
-        assert self._setup_flag, "setup() must be called before postprocess()"
-        if isinstance(test_data, Tensor):
-            test_data = _hip.to_host(test_data)
-        return self.flip_sign_fn(self._scores(test_data))
+        self._threshold_from(kwargs["valid_feats"])
 
 
 # --------------------------------------------------------------------------------------
@@ -727,16 +735,11 @@ def _fc_params(kwargs, who: str):
     return w, b
 
 
-def _feats_to_device(x) -> Tensor:
-    if isinstance(x, Tensor):
-        x = x.detach()
-    return _hip.to_device(x, torch.float32)
-
-
-class _LinearEnergy(OodPostprocessor):
+class _LinearEnergy(_DeviceScored):
     """``logsumexp(transform(x) @ W.T + b)`` on the GPU: f32 MFMA linear layer + the row LSE kernel."""
 
-    def _init_linear(self):
+    def __init__(self, flip_sign: bool, cfg=None):
+        super().__init__(flip_sign, cfg)
         self.w = None
         self.b = None
         self._wd = None
@@ -757,21 +760,10 @@ class _LinearEnergy(OodPostprocessor):
     def _transform(self, x: Tensor) -> Tensor:
         return x
 
-    def postprocess_device(self, feats: Tensor) -> Tensor:
+    def _score_device(self, feats: Tensor) -> Tensor:
         w, b = self._device_linear()
         logits = _hip.linear(self._transform(feats), w, b, self._clip())
-        lse, _ = _hip.row_lse_msp(logits, True, False)
-        return -lse if self.flip_sign else lse
-
-    def _scores(self, feats) -> np.ndarray:
-        w, b = self._device_linear()
-        logits = _hip.linear(self._transform(_feats_to_device(feats)), w, b, self._clip())
-        lse, _ = _hip.row_lse_msp(logits, True, False)
-        return _hip.to_host(lse)
-
-    def postprocess(self, test_data: np.ndarray, **kwargs) -> np.ndarray:
-        assert self._setup_flag, "setup() must be called before postprocess()"
-        return self.flip_sign_fn(self._scores(test_data))
+        return _hip.row_lse_msp(logits, True, False)[0]
 
 
 @register_postprocessor("ash", postprocessor_input=["features"])
@@ -781,7 +773,6 @@ class ASH(_LinearEnergy):
     def __init__(self, flip_sign: bool, ash_percentile: int = 85, cfg=None):
         super().__init__(flip_sign, cfg)
         self.ash_percentile = ash_percentile
-        self._init_linear()
 
     def _transform(self, x: Tensor) -> Tensor:
         return _hip.ash_s(x, self.ash_percentile)
@@ -790,7 +781,7 @@ class ASH(_LinearEnergy):
         self.w, self.b = _fc_params(kwargs, "ASH")
         self._wd = None
         # the reference scores ind_train_data here (not valid_feats) to set the threshold
-        self.set_threshold(self.flip_sign_fn(self._scores(ind_train_data)))
+        self._threshold_from(ind_train_data)
 
 
 @register_postprocessor("react", postprocessor_input=["features"])
@@ -801,7 +792,6 @@ class ReAct(_LinearEnergy):
         super().__init__(flip_sign, cfg)
         self.react_percentile = react_percentile
         self.activation_threshold = None
-        self._init_linear()
 
     def _clip(self) -> float:
         return float(np.float32(self.activation_threshold))
@@ -810,7 +800,7 @@ class ReAct(_LinearEnergy):
         self.w, self.b = _fc_params(kwargs, "ReAct")
         self._wd = None
         self.activation_threshold = percentile_flat(ind_train_data, self.react_percentile)
-        self.set_threshold(self.flip_sign_fn(self._scores(kwargs["valid_feats"])))
+        self._threshold_from(kwargs["valid_feats"])
 
 
 class MaskedLinear:
@@ -837,7 +827,6 @@ class DICE(_LinearEnergy):
         self.num_classes = num_classes
         self.dice_layer = None
         self.device = "cuda" if torch.cuda.is_available() else "cpu"
-        self._init_linear()
 
     def _effective_weight(self):
         return self.dice_layer.masked_w
@@ -850,7 +839,7 @@ class DICE(_LinearEnergy):
 
     def setup(self, ind_train_data: np.ndarray, **kwargs):
         self._fit_layer(ind_train_data, kwargs, "DICE")
-        self.set_threshold(self.flip_sign_fn(self._scores(kwargs["valid_feats"])))
+        self._threshold_from(kwargs["valid_feats"])
 
 
 @register_postprocessor("dice_react", postprocessor_input=["features"])
@@ -869,11 +858,11 @@ class DICEReAct(DICE):
     def setup(self, ind_train_data: np.ndarray, **kwargs):
         self._fit_layer(ind_train_data, kwargs, "DICE")
         self.react_activation_threshold = percentile_flat(ind_train_data, self.react_percentile)
-        self.set_threshold(self.flip_sign_fn(self._scores(kwargs["valid_feats"])))
+        self._threshold_from(kwargs["valid_feats"])
 
 
 @register_postprocessor("gen", postprocessor_input=["logits"])
-class GEN(OodPostprocessor):
+class GEN(_DeviceScored):
     """Generalized entropy of the ``num_classes`` largest softmax probabilities (negated)."""
 
     def __init__(self, flip_sign: bool, gamma: float, num_classes: int, cfg=None):
@@ -881,21 +870,11 @@ class GEN(OodPostprocessor):
         self.gamma = gamma
         self.num_classes = num_classes
 
-    def _scores(self, logits) -> np.ndarray:
-        if isinstance(logits, Tensor):
-            logits = logits.detach()
-        return _hip.to_host(_hip.gen_score(_hip.to_device(logits, torch.float32), self.gamma, self.num_classes))
-
-    def postprocess_device(self, logits: Tensor) -> Tensor:
-        s = _hip.gen_score(logits, self.gamma, self.num_classes)
-        return -s if self.flip_sign else s
+    def _score_device(self, logits: Tensor) -> Tensor:
+        return _hip.gen_score(logits, self.gamma, self.num_classes)
 
     def setup(self, ind_train_data: np.ndarray, **kwargs):
-        self.set_threshold(self.flip_sign_fn(self._scores(ind_train_data)))
-
-    def postprocess(self, test_data: np.ndarray, **kwargs) -> np.ndarray:
-        assert self._setup_flag, "setup() must be called before postprocess()"
-        return self.flip_sign_fn(self._scores(test_data))
+        self._threshold_from(ind_train_data)
 
 
 @register_postprocessor("vim", postprocessor_input=["features", "logits"])
@@ -991,7 +970,7 @@ class ViM(OodPostprocessor):
 
 
 @register_postprocessor("ddu", postprocessor_input=["features"])
-class DDU(OodPostprocessor):
+class DDU(_DeviceScored):
     """Deep Deterministic Uncertainty: log-sum-exp of class-wise Gaussian log-densities of the features."""
 
     def __init__(self, flip_sign: bool, num_classes: int, cfg=None):
@@ -1001,18 +980,10 @@ class DDU(OodPostprocessor):
         self.device = "cuda" if torch.cuda.is_available() else "cpu"
         self._state = None
 
-    def _scores(self, feats) -> np.ndarray:
+    def _score_device(self, feats: Tensor) -> Tensor:
         if self._state is None:
             self._state = GmmState(self.gmm)
-        if isinstance(feats, Tensor):
-            feats = feats.detach()
-        return _hip.to_host(self._state.energy_device(_hip.to_device(feats, torch.float32)))
-
-    def postprocess_device(self, feats: Tensor) -> Tensor:
-        if self._state is None:
-            self._state = GmmState(self.gmm)
-        s = self._state.energy_device(feats)
-        return -s if self.flip_sign else s
+        return self._state.energy_device(feats)
 
     def setup(self, ind_train_data: np.ndarray, **kwargs):
         assert "valid_feats" in kwargs, "valid_feats must be provided for DDU"
@@ -1022,8 +993,4 @@ class DDU(OodPostprocessor):
         emb = torch.from_numpy(rows) if rows.dtype == np.float32 and rows.flags.c_contiguous and rows.flags.writeable else Tensor(ind_train_data)
         self.gmm, _ = gmm_fit(embeddings=emb, labels=Tensor(kwargs["train_labels"]), num_classes=self.num_classes)
         self._state = None
-        self.set_threshold(self.flip_sign_fn(self._scores(kwargs["valid_feats"])))
-
-    def postprocess(self, test_data: np.ndarray, **kwargs) -> np.ndarray:
-        assert self._setup_flag, "setup() must be called before postprocess()"
-        return self.flip_sign_fn(self._scores(test_data))
+        self._threshold_from(kwargs["valid_feats"])

@@ -10,6 +10,7 @@ import torch
 
 import extended_baseline_cases as cases
 from conftest import generate_test_data, rel_err
+from test_postprocessor_template import THRESHOLD_SPLIT
 
 pytestmark = pytest.mark.gpu
 
@@ -310,6 +311,60 @@ def test_every_class_host_device_flip_threshold_auroc(fitted, name):
     assert abs(auroc - auroc64) <= 2e-5
     back = pickle.loads(pickle.dumps(pp))
     assert np.array_equal(back.postprocess(a), got_a)
+
+
+# ---------------- the template: every class of the logits / features family ---------------------------------
+FAMILY_CTOR = {"knn": dict(k_neighbors=5), "mahalanobis": dict(num_classes=10), "gen": dict(gamma=0.1, num_classes=10),
+               "ddu": dict(num_classes=10), "klm": dict(num_classes=10), "rmds": dict(num_classes=10)}
+
+
+@pytest.fixture(scope="module")
+def family_inputs():
+    """rows -> the splits of one case: conftest's recipe at 10 rows (its default) and at 70 (more than one wave of rows, a
+    ragged last workgroup in the wave-per-row kernels), 32 features, 10 classes, a 10 x 32 final layer."""
+    w, b = cases.fc_layer(10, 32, 5)
+    out = {}
+    for rows in (10, 70):
+        tf, labels, tl = generate_test_data(num_samples=rows, seed=42)
+        vf, _, _ = generate_test_data(num_samples=rows, seed=44)
+        ef, _, el = generate_test_data(num_samples=rows, seed=43)
+        out[rows] = {"train features": tf, "train logits": tl, "valid features": vf, "test features": ef, "test logits": el,
+                     "labels": labels, "fc": {"weight": w, "bias": b}}
+    return out
+
+
+def same_bits(a, b):
+    return a.dtype == b.dtype and a.shape == b.shape and a.tobytes() == b.tobytes()
+
+
+@pytest.mark.parametrize("flip", [False, True])
+@pytest.mark.parametrize("rows", [10, 70])
+@pytest.mark.parametrize("name", sorted(THRESHOLD_SPLIT))
+def test_family_host_path_is_the_device_path_and_threshold_split(family_inputs, name, rows, flip):
+    """``postprocess`` of a host array and of the device tensor give the bits of ``postprocess_device``, flipped or not, and
+    the threshold is that of the host scores of the split in ``THRESHOLD_SPLIT``.  KNN's is that of those scores flipped
+    once more: its ``setup`` mirrors the reference's, which flips inside ``postprocess`` and then again."""
+    import warnings
+
+    from runia_core_amd import _hip as hip
+    from runia_core_amd.inference import extended_postprocessor_input_dict as inputs
+    from runia_core_amd.inference import extended_postprocessors_dict as reg
+    from runia_core_amd.inference.abstract_classes import get_method_threshold
+
+    d = family_inputs[rows]
+    kind = "features" if inputs[name] == ["features"] else "logits"
+    pp = reg[name](flip_sign=flip, **FAMILY_CTOR.get(name, {}))
+    with warnings.catch_warnings():
+        warnings.simplefilter("ignore")   # classes without a training row at 10 rows
+        pp.setup(d[f"train {kind}"], valid_feats=d["valid features"], train_labels=d["labels"], final_linear_layer_params=d["fc"])
+    split = d[f"train {kind}"] if THRESHOLD_SPLIT[name] == "train" else d["valid features"]
+    for x in (d[f"test {kind}"], split):
+        up = dev(x)
+        want = hip.to_host(pp.postprocess_device(up))
+        assert want.shape == (rows,)
+        assert same_bits(pp.postprocess(x), want) and same_bits(pp.postprocess(up), want)
+    scores = pp.postprocess(split)
+    assert pp.threshold == get_method_threshold(pp.flip_sign_fn(scores) if name == "knn" else scores, 1.645)
 
 
 def test_klm_invalid_class_warns_and_all_invalid_raises():

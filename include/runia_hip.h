@@ -870,6 +870,40 @@ int runia_fdbd_score_f32(const float* logits, const float* inv_dist, const float
                          int64_t C, runia_stream_t stream);
 int runia_row_dist_f32(const float* x, const float* mu, float* out, int64_t N, int64_t D, runia_stream_t stream);
 
+/* ---- Confidence calibration (calibration.hip; evaluation/calibration.py) ------------------------------------- *
+ * runia_calib_rows: one read of logits [N, C] (row-contiguous; `dtype` 0 f32, 1 f16, 2 bf16, widened exactly, f32 arithmetic)
+ *   at the temperature 1 / beta (0 < beta < inf).  labels [N] int32 (labels_i64 == 0) or int64, or NULL (no labels: pred and
+ *   conf only; the other four pointers must be NULL).  With m = max_k x_k, d_k = x_k - m, p = softmax(beta x) and y the label:
+ *     pred  i32 [N]  first index of the maximum (np.argmax on rows without NaN)
+ *     conf  f32 [N]  1 / sum_k exp(beta d_k) = max_k p_k
+ *     nll   f32 [N]  log sum_k exp(beta d_k) - beta d_y          (+inf for x_y = -inf)
+ *     brier f32 [N]  sum_k p_k^2 - 2 p_y + 1
+ *     g     f32 [N]  sum_k p_k d_k - d_y                          = d nll / d beta
+ *     h     f32 [N]  max(0, sum_k p_k d_k^2 - (sum_k p_k d_k)^2)  = d2 nll / d beta2
+ *   Any output pointer may be NULL (not all six).  A class at -inf contributes 0; a NaN logit (and a row without a finite
+ *   logit) makes the row's five float outputs NaN.  A row whose label equals ignore_index (has_ignore != 0) writes pred and
+ *   NaN elsewhere; so does a label outside [0, C) - callers validate labels, the kernel only never reads through one.
+ *   Launch shapes (the same for the three dtypes, so a 16-bit call gives the bits of the f32 call on the widened values):
+ *   C <= 16 a row per lane in registers; C <= 64 a row per lane through LDS; beyond, a wave per row: C % 4 == 0 and the base
+ *   aligned to four elements: four elements per lane and load, the row in registers up to C = 2048 (1, 2, 4 or 8 loads per
+ *   lane); longer or unaligned rows in ONE chunked pass that rescales its sums when the running maximum moves.  Sums in a
+ *   fixed order that depends on C alone: bit identical from run to run and wherever the row sits in the batch.  C < 2^31.
+ * runia_calib_reduce_f32: the per-row table -> out, (6 + 3 n_bins) 8-byte slots:
+ *     [0] n_used  [1] n_correct (int64)   [2] sum nll  [3] sum brier  [4] sum g  [5] sum h (f64)
+ *     [6 ..) count[n_bins]  n_correct[n_bins] (int64)  conf_sum[n_bins] (f64)
+ *   over the rows whose label is not ignore_index, with the bin b = clamp((int)ceilf(conf * (float)n_bins) - 1, 0, n_bins - 1)
+ *   (f32 arithmetic; a NaN conf counts in bin 0).  nll, brier, g, h, pred may be NULL (their sums / counts stay 0); conf may be
+ *   NULL when n_bins == 0.  0 <= n_bins <= 512.  Two launches: per-workgroup partials over contiguous row ranges (f64 sums in a
+ *   fixed order, integer counts), then one pass that adds the partials in order - no floating-point atomics, the same inputs give
+ *   the same bits.  workspace: runia_calib_reduce_workspace_bytes(N, n_bins) bytes (RUNIA_E_WORKSPACE if short).  N == 0: zeros. */
+int runia_calib_rows(const void* logits, int dtype, const void* labels, int labels_i64, int has_ignore, int64_t ignore_index,
+                     float beta, int32_t* pred, float* conf, float* nll, float* brier, float* g, float* h, int64_t N, int64_t C,
+                     runia_stream_t stream);
+size_t runia_calib_reduce_workspace_bytes(int64_t N, int n_bins);
+int runia_calib_reduce_f32(const int32_t* pred, const float* conf, const float* nll, const float* brier, const float* g,
+                           const float* h, const void* labels, int labels_i64, int has_ignore, int64_t ignore_index, int64_t N,
+                           int n_bins, void* out, void* workspace, size_t workspace_bytes, runia_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -289,6 +289,13 @@ _SIGNATURES = {
         c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_int64, c_int64, c_void_p]),
     "runia_fdbd_score_f32": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_int64, c_void_p]),
     "runia_row_dist_f32": (c_int, [c_void_p, c_void_p, c_void_p, c_int64, c_int64, c_void_p]),
+    "runia_calib_rows": (
+        c_int, [c_void_p, c_int, c_void_p, c_int, c_int, c_int64, c_float, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
+                c_void_p, c_int64, c_int64, c_void_p]),
+    "runia_calib_reduce_workspace_bytes": (c_size_t, [c_int64, c_int]),
+    "runia_calib_reduce_f32": (
+        c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int64, c_int64, c_int,
+                c_void_p, c_void_p, c_size_t, c_void_p]),
 }
 
 
@@ -973,6 +980,74 @@ def row_dist(x: torch.Tensor, mu: torch.Tensor) -> torch.Tensor:
     out = torch.empty((x.shape[0],), dtype=torch.float32, device=x.device)
     launch("runia_row_dist_f32", x.data_ptr(), mu.data_ptr(), out.data_ptr(), x.shape[0], x.shape[1])
     return out
+
+
+class CalibrationRows(NamedTuple):
+    """What ``calibration_rows`` returns: [N] device tensors (``pred`` int32, the rest float32), ``None`` where not asked for."""
+
+    pred: Optional[torch.Tensor]
+    conf: Optional[torch.Tensor]
+    nll: Optional[torch.Tensor]
+    brier: Optional[torch.Tensor]
+    g: Optional[torch.Tensor]
+    h: Optional[torch.Tensor]
+
+
+def _calib_labels(labels: Optional[torch.Tensor], n: int, ignore_index: Optional[int]):
+    """-> (labels contiguous | None, is-int64 flag, has-ignore flag, ignore value) as the calibration entry points take them."""
+    if labels is not None:
+        assert labels.is_cuda and labels.dtype in (torch.int32, torch.int64) and labels.shape == (n,)
+        labels = labels.contiguous()
+    return (labels, int(labels is not None and labels.dtype == torch.int64), int(ignore_index is not None),
+            0 if ignore_index is None else int(ignore_index))
+
+
+@_device_guard()
+def calibration_rows(logits: torch.Tensor, labels: Optional[torch.Tensor], beta: float = 1.0, ignore_index: Optional[int] = None,
+                     want=("pred", "conf", "nll", "brier", "g", "h")) -> CalibrationRows:
+    """One read of logits [N, C] (f32 / f16 / bf16, read where they lie) at the temperature ``1 / beta`` -> the per-row outputs
+    named in ``want`` (``runia_calib_rows``).  labels [N] int32 / int64, or None (``pred`` and ``conf`` only).  A row whose label is
+    ``ignore_index`` or outside ``[0, C)`` gets ``pred`` and NaN elsewhere; callers validate labels."""
+    require_gpu()
+    assert logits.is_cuda and logits.dim() == 2 and logits.dtype in ELEM_DTYPE_CODES, \
+        f"logits: a [N, C] device tensor of float32, float16 or bfloat16, got {tuple(logits.shape)} {logits.dtype}"
+    names = CalibrationRows._fields
+    assert want and set(want) <= set(names), f"want: a non-empty subset of {names}"
+    assert labels is not None or set(want) <= {"pred", "conf"}, "nll, brier, g and h need labels"
+    logits = logits.contiguous()
+    n, c = logits.shape
+    labels, is64, has_ignore, ignore = _calib_labels(labels, n, ignore_index)
+    out = CalibrationRows(*(torch.empty((n,), dtype=torch.int32 if k == "pred" else torch.float32, device=logits.device)
+                            if k in want else None for k in names))
+    launch("runia_calib_rows", logits.data_ptr(), ELEM_DTYPE_CODES[logits.dtype], _ptr(labels), is64, has_ignore, ignore,
+           float(beta), *(_ptr(t) for t in out), n, c)
+    return out
+
+
+@_device_guard()
+def calibration_reduce(rows: CalibrationRows, labels: torch.Tensor, n_bins: int, ignore_index: Optional[int] = None) -> torch.Tensor:
+    """The per-row table -> the device record of ``runia_calib_reduce_f32``: int64 [6 + 3 n_bins] whose slots 2..5 and the last
+    ``n_bins`` hold float64 bits (``calibration_record`` splits a host copy).  Fixed summation order: the same bits every run."""
+    require_gpu()
+    n = labels.shape[0]
+    assert 0 <= n_bins <= 512, "n_bins: 0 .. 512"
+    assert n_bins == 0 or rows.conf is not None, "the reliability table needs conf"
+    assert all(t is None or (t.is_cuda and t.shape == (n,) and t.is_contiguous()) for t in rows)
+    labels, is64, has_ignore, ignore = _calib_labels(labels, n, ignore_index)
+    out = torch.empty((6 + 3 * n_bins,), dtype=torch.int64, device=labels.device)
+    ws_bytes = query("runia_calib_reduce_workspace_bytes", n, n_bins)
+    ws = workspace(ws_bytes, labels.device)
+    launch("runia_calib_reduce_f32", _ptr(rows.pred), _ptr(rows.conf), _ptr(rows.nll), _ptr(rows.brier), _ptr(rows.g), _ptr(rows.h),
+           labels.data_ptr(), is64, has_ignore, ignore, n, n_bins, out.data_ptr(), ws.data_ptr(), ws_bytes)
+    return out
+
+
+def calibration_record(record: np.ndarray, n_bins: int) -> dict:
+    """A host copy of ``calibration_reduce``'s record -> its named parts (ints and float64 arrays)."""
+    f = record.view(np.float64)
+    return {"n_used": int(record[0]), "n_correct": int(record[1]), "nll": float(f[2]), "brier": float(f[3]), "g": float(f[4]),
+            "h": float(f[5]), "count": record[6:6 + n_bins].copy(), "correct": record[6 + n_bins:6 + 2 * n_bins].copy(),
+            "conf_sum": f[6 + 2 * n_bins:6 + 3 * n_bins].copy()}
 
 
 @_device_guard()

@@ -144,6 +144,19 @@ __device__ __forceinline__ float wave_sum_f32(float v) {
   for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
   return v;
 }
+// (value, index) of a row maximum, first index on ties (np.argmax); a NaN entry never wins (fmaxf drops it as well)
+constexpr int kNoIndex = 0x7fffffff;
+__device__ __forceinline__ void best_take(float& bv, int& bi, float v, int i) {
+  if (v > bv || (v == bv && i < bi)) { bv = v; bi = i; }
+}
+__device__ __forceinline__ void wave_best(float& bv, int& bi) {
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) {
+    const float v = __shfl_xor(bv, o, 64);
+    const int i = __shfl_xor(bi, o, 64);
+    best_take(bv, bi, v, i);
+  }
+}
 __device__ __forceinline__ double shfl_xor_f64(double v, int o) {
   int lo = __double2loint(v), hi = __double2hiint(v);
   lo = __shfl_xor(lo, o, 64);

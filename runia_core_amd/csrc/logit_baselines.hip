@@ -11,20 +11,7 @@
 namespace {
 
 // ---- row statistics ------------------------------------------------------------------------------------------------------
-// (value, index) of the row maximum, first index on ties (np.argmax); a NaN entry never wins (fmaxf drops it as well)
-__device__ __forceinline__ void best_take(float& bv, int& bi, float v, int i) {
-  if (v > bv || (v == bv && i < bi)) { bv = v; bi = i; }
-}
-__device__ __forceinline__ void wave_best(float& bv, int& bi) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) {
-    const float v = __shfl_xor(bv, o, 64);
-    const int i = __shfl_xor(bi, o, 64);
-    best_take(bv, bi, v, i);
-  }
-}
-constexpr int kNoIndex = 0x7fffffff;
-
+// (best_take / wave_best / kNoIndex: the first-argmax helpers of common.hpp)
 // e = exp(x - m) and its share of sum e (x - m); a class with e == 0 (x = -inf included) adds nothing: p log p -> 0 as p -> 0
 __device__ __forceinline__ void stat_term(float x, float m, float& s, float& t) {
   const float d = x - m, e = expf(d);

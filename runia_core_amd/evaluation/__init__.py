@@ -19,3 +19,10 @@ from .open_set import (  # noqa: F401
     voc_eval,
 )
 from .box_subsets import get_gtu_uu_metrics, subset_boxes  # noqa: F401
+from .calibration import (  # noqa: F401
+    CalibrationResult,
+    ReliabilityBins,
+    TemperatureScaler,
+    calibration_metrics,
+    fit_temperature,
+)

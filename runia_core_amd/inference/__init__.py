@@ -58,6 +58,7 @@ from .extended_postprocessors import (  # noqa: F401
     KLMatching,
     MaxLogit,
     RelativeMahalanobis,
+    TempScale,
     extended_postprocessor_input_dict,
     extended_postprocessors_dict,
     fdbd_inverse_distances,

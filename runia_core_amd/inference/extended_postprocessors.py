@@ -1,5 +1,6 @@
 """Post-hoc baselines that current OOD benchmark tables carry and the reference does not ship: MaxLogit (``mls``),
-KL-Matching (``klm``), fDBD (``fdbd``, Liu & Qin 2024) and Relative Mahalanobis (``rmds``).
+KL-Matching (``klm``), fDBD (``fdbd``, Liu & Qin 2024) and Relative Mahalanobis (``rmds``); and, outside the registries,
+temperature-scaled MSP (``TempScale``).
 
 ``postprocessors_dict`` mirrors the reference's registry key for key and stays as it is; this module adds a second registry,
 ``extended_postprocessors_dict`` (the 16 reference keys plus the four above) with its ``extended_postprocessor_input_dict``.
@@ -24,7 +25,7 @@ from .postprocessors import (_DeviceScored, _fc_params, _LogitScored, _Mahalanob
                              postprocessors_dict)
 
 __all__ = ["extended_postprocessors_dict", "extended_postprocessor_input_dict", "MaxLogit", "KLMatching", "FDBD",
-           "RelativeMahalanobis", "fdbd_inverse_distances"]
+           "RelativeMahalanobis", "TempScale", "fdbd_inverse_distances"]
 
 _KLM_Q_FLOOR = 1e-30  # log_q = log(max(q, floor)): a class the fit never saw in a prototype costs 69 nats, not inf
 _FIT_ROWS = 1 << 14   # training rows per slice of the KL-Matching fit (bounds the f64 tables of a slice)
@@ -112,6 +113,31 @@ class KLMatching(_LogitScored):
         self._check_width(train)
         self._fit(self._to_device(train))
         self._threshold_from(train)
+
+
+class TempScale(_LogitScored):
+    """Temperature-scaled MSP (``tempscale`` of the benchmark tables): ``max_k softmax(x / T)_k`` with ``T`` fitted on labelled
+    logits by ``evaluation.calibration.fit_temperature``.  Scored by the calibration row pass (``runia_calib_rows``) at ``1 / T``.
+
+    Fitted state: ``temperature`` (one float).  It is exported but sits in NO registry: ``postprocessors_dict`` mirrors the
+    reference's keys and ``extended_postprocessors_dict`` / ``extended_baseline_names`` are pinned by their tests; construct it
+    directly."""
+
+    def __init__(self, flip_sign: bool, cfg=None):
+        super().__init__(flip_sign, cfg)
+        self.temperature = None
+
+    def _score_device(self, logits: Tensor) -> Tensor:
+        assert self.temperature is not None, "setup() fits the temperature first"
+        return _hip.calibration_rows(logits, None, 1.0 / self.temperature, want=("conf",)).conf
+
+    def setup(self, ind_train_data: np.ndarray, **kwargs):
+        """``ind_train_data``: labelled logits [N, C]; ``train_labels``: their classes [N]."""
+        assert "train_labels" in kwargs, "train_labels must be provided for TempScale"
+        from ..evaluation.calibration import fit_temperature  # (evaluation imports this package: resolved at call time)
+
+        self.temperature = fit_temperature(ind_train_data, kwargs["train_labels"])
+        self._threshold_from(ind_train_data)
 
 
 def fdbd_inverse_distances(weight: np.ndarray) -> np.ndarray:

@@ -1,6 +1,6 @@
 """Randomised differential check of the stand-alone stages against the CPU oracle (one MI355X, a few minutes): joint /
 per-dimension entropy, Energy / MSP, normaliser, PCA transform + MD at sizes around the tile switches, kNN (k-th
-distance) and LaRED on both kernel forms, the LLM logit scores and RAUQ's row means.  Shapes are drawn around the places
+distance) and LaRED on both kernel forms, the LLM logit scores, RAUQ's row means and the calibration row pass / reduce.  Shapes are drawn around the places
 where a kernel changes its launch shape or code path (vector widths, register-resident row limits, 16- / 32-row tiles,
 column halves, chunk limits).
 
@@ -16,6 +16,7 @@ from runia_core_amd.llm_uncertainty import RAUQ, generation_scores, rauq_batch
 from runia_core_amd.llm_uncertainty import rauq as rq
 # the RAUQ block's inputs and f64 restatement are the test suite's (tests/rauq_switch_cases.py, tests/test_rauq_host.py)
 import rauq_switch_cases as sw
+import calibration_cases as cal  # the calibration block's inputs and f64 restatement
 from test_rauq_host import f32_mean_lastdim, restate as rauq_restate
 
 ap = argparse.ArgumentParser()
@@ -534,6 +535,30 @@ for t in range(a.rounds):
         exp_m = (f32_mean_lastdim(am) if km < 512 else sw.wave_order_mean(am))
         check("rauq row means bits", (km,), 0.0 if np.array_equal(wm.cpu().numpy().view(np.uint32), exp_m.view(np.uint32)) else 1.0, 0.5)
         del attm, keepm
+
+    # ---- calibration (calibration.hip): C around the launch-shape switches of the row pass, every dtype, beta on both sides
+    # of 1; the reduce against NumPy on the row pass's own table around its 2 048-row workgroup ranges ----
+    cc = int(rng.choice([*cal.CALIB_SWITCH_WIDTHS, 2, 10, 63, 1000, 1001, 2051, 4100, 5003]))
+    nc_ = int(rng.choice([1, 63, 65, 257, 2047, 2049, 4100]))
+    bc = float(rng.choice([0.2, 1.0, 3.0]))
+    xc, yc = cal.seeded_case(nc_, cc, int(rng.integers(1 << 30)))
+    dtc = [torch.float32, torch.float16, torch.bfloat16][int(rng.integers(3))]
+    xcd, ycd = dev(xc).to(dtc), dev(yc)
+    if rng.random() < 0.5:
+        yc[:: 3] = -100
+        ycd = dev(yc)
+    rc_ = _hip.calibration_rows(xcd, ycd, bc, -100)
+    keep_c = yc != -100
+    qc = cal.rows_f64(xcd.to(torch.float32).cpu().numpy()[keep_c], yc[keep_c], bc)
+    check("calibration pred", (nc_, cc, dtc), 0.0 if np.array_equal(rc_.pred.cpu().numpy()[keep_c], qc["pred"]) else 1.0, 0.5)
+    for kc in ("conf", "nll", "brier", "g", "h"):
+        check("calibration " + kc, (nc_, cc, dtc, bc), rel(getattr(rc_, kc).cpu().numpy()[keep_c], qc[kc]), 1e-5)
+    nb = int(rng.choice([1, 10, 15, 100]))
+    got_c = _hip.calibration_record(_hip.calibration_reduce(rc_, ycd, nb, -100).cpu().numpy(), nb)
+    cnt_c, hit_c, sum_c = cal.reliability_table(rc_.conf.cpu().numpy()[keep_c], rc_.pred.cpu().numpy()[keep_c] == yc[keep_c], nb)
+    same_c = np.array_equal(got_c["count"], cnt_c) and np.array_equal(got_c["correct"], hit_c) and got_c["n_used"] == keep_c.sum()
+    check("calibration bin counts", (nc_, cc, nb), 0.0 if same_c else 1.0, 0.5)
+    check("calibration conf_sum", (nc_, cc, nb), rel(got_c["conf_sum"], sum_c), 1e-12)
 
     if (t + 1) % 10 == 0:
         print(f"round {t + 1}/{a.rounds}, mismatches so far: {bad}", flush=True)

@@ -359,6 +359,25 @@ int runia_proj_sq_accumulate_f64(const double* h, const double* packed_m, const 
 int runia_proj_sq_score_f64(const double* h, const double* packed_m, const double* c, double* score,
                             void* workspace, size_t workspace_bytes, int64_t N, int64_t D, int64_t r,
                             runia_stream_t stream);
+/*     runia_proj_sq_*_trap_f64: the same two calls for an upper-TRAPEZOIDAL M (r <= D and M[j][k] = 0 for k < j, the
+ *     caller's promise; runia_qr_trapezoid_f64 makes one).  Column tile t of M^T holds only zeros in its rows k < 16 t, so
+ *     the contraction starts behind them: 0.78 of the matrix instructions at r = 256, D = 512.  Same packed layout (zero
+ *     blocks stored), same summation order, and on such a matrix the same bits as the plain calls for finite h.  A row
+ *     with a NaN h scores NaN in both (column tile 0 skips nothing); a row with an infinite h never scores a finite
+ *     value, but where the plain call says NaN (0 * inf in a zero block) the trap call may say -inf: that happens for an
+ *     infinity at the last k of a skipped chunk (k = 32 q - 1), whose only zeros lie in skipped blocks. */
+int runia_proj_sq_accumulate_trap_f64(const double* h, const double* packed_m, const double* c, double* score,
+                                      int64_t N, int64_t D, int64_t r, runia_stream_t stream);
+int runia_proj_sq_score_trap_f64(const double* h, const double* packed_m, const double* c, double* score,
+                                 void* workspace, size_t workspace_bytes, int64_t N, int64_t D, int64_t r,
+                                 runia_stream_t stream);
+/*     runia_qr_trapezoid_f64: r_out [r, D] = Q m, c_out [r] = Q c for the orthogonal Q (Householder reflections on
+ *     [m | c], r <= D, r <= 4096) that makes r_out upper-trapezoidal: r_out^T r_out = m^T m, || r_out h + c_out || =
+ *     || m h + c ||, and r_out[j][k] is exactly 0.0 for k < j.  A column that is already zero below the diagonal gets
+ *     no reflection (rank-deficient m is fine).  One workgroup, every sum in an order fixed by the code: the same input
+ *     gives the same bits on every call and every rank.  r_out may be m and c_out may be c (in place). */
+int runia_qr_trapezoid_f64(const double* m, const double* c, double* r_out, double* c_out, int64_t r, int64_t D,
+                           runia_stream_t stream);
 
 /* ---- f1  setup-time covariance on the device (SURVEY 8f "next #1") ----------- *
  * Replaces np.cov(X.T, bias=1) inside sklearn EmpiricalCovariance.fit

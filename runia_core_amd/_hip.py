@@ -11,7 +11,7 @@ import ctypes
 import os
 import threading
 from ctypes import c_char_p, c_double, c_float, c_int, c_int64, c_size_t, c_uint64, c_void_p
-from typing import NamedTuple, Optional, Union
+from typing import NamedTuple, Optional, Tuple, Union
 
 import numpy as np
 import torch  # imported before the library so that both share one HIP runtime
@@ -191,7 +191,13 @@ _SIGNATURES = {
     "runia_proj_norm_f64": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_int64, c_int64, c_void_p]),
     "runia_proj_sq_workspace_bytes": (c_size_t, [c_int64]),
     "runia_proj_sq_accumulate_f64": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_int64, c_int64, c_void_p]),
+    "runia_proj_sq_accumulate_trap_f64": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_int64, c_int64, c_void_p]),
+    "runia_qr_trapezoid_f64": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_int64, c_void_p]),
     "runia_proj_sq_score_f64": (
+        c_int,
+        [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, c_int64, c_int64, c_int64, c_void_p],
+    ),
+    "runia_proj_sq_score_trap_f64": (
         c_int,
         [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, c_int64, c_int64, c_int64, c_void_p],
     ),
@@ -1292,15 +1298,18 @@ def mc_entropy(x: torch.Tensor, rand: Union[torch.Tensor, CounterDraws, None], n
 
 
 @_device_guard()
-def proj_sq_accumulate(h: torch.Tensor, packed_m: torch.Tensor, c: torch.Tensor, r: int, out: torch.Tensor) -> torch.Tensor:
+def proj_sq_accumulate(h: torch.Tensor, packed_m: torch.Tensor, c: torch.Tensor, r: int, out: torch.Tensor,
+                       trap: bool = False) -> torch.Tensor:
     """``out`` [N] f64 += -|| M h + c ||^2 where ``out`` was zeroed earlier on the stream (``mc_entropy(zero_fill=out)``):
-    the score of ``proj_sq_score`` bit for bit, without its workspace and combine launch."""
+    the score of ``proj_sq_score`` bit for bit, without its workspace and combine launch.  ``trap``: M is upper-trapezoidal
+    (``qr_trapezoid``); the launch skips its zero blocks (``runia_proj_sq_accumulate_trap_f64``)."""
     require_gpu()
     assert h.is_cuda and h.dtype == torch.float64 and h.dim() == 2
     h = h.contiguous()
     nrow, d = h.shape
     assert out.is_cuda and out.dtype == torch.float64 and out.shape == (nrow,) and out.is_contiguous()
-    launch("runia_proj_sq_accumulate_f64", h.data_ptr(), packed_m.data_ptr(), c.data_ptr(), out.data_ptr(), nrow, d, int(r))
+    launch("runia_proj_sq_accumulate_trap_f64" if trap else "runia_proj_sq_accumulate_f64", h.data_ptr(), packed_m.data_ptr(),
+           c.data_ptr(), out.data_ptr(), nrow, d, int(r))
     return out
 
 
@@ -1499,8 +1508,10 @@ def proj_norm(x: torch.Tensor, u: torch.Tensor, packed_ns: torch.Tensor, n: int)
 
 
 @_device_guard()
-def proj_sq_score(h: torch.Tensor, packed_m: torch.Tensor, c: torch.Tensor, r: int, out: Optional[torch.Tensor] = None) -> torch.Tensor:
-    """score [N] = -|| M h + c ||^2 (h [N, D] f64, packed_m = pack(M.T), c [r])."""
+def proj_sq_score(h: torch.Tensor, packed_m: torch.Tensor, c: torch.Tensor, r: int, out: Optional[torch.Tensor] = None,
+                  trap: bool = False) -> torch.Tensor:
+    """score [N] = -|| M h + c ||^2 (h [N, D] f64, packed_m = pack(M.T), c [r]).  ``trap``: M is upper-trapezoidal
+    (``qr_trapezoid``); the launch skips its zero blocks (``runia_proj_sq_score_trap_f64``)."""
     lib = load_library()
     require_gpu()
     assert h.is_cuda and h.dtype == torch.float64 and h.dim() == 2
@@ -1509,9 +1520,23 @@ def proj_sq_score(h: torch.Tensor, packed_m: torch.Tensor, c: torch.Tensor, r: i
     s = torch.empty((nrow,), dtype=torch.float64, device=h.device) if out is None else out
     ws_bytes = int(lib.runia_proj_sq_workspace_bytes(nrow))
     ws = torch.empty(max(ws_bytes, 16), dtype=torch.uint8, device=h.device)
-    launch("runia_proj_sq_score_f64", h.data_ptr(), packed_m.data_ptr(), c.data_ptr(), s.data_ptr(), ws.data_ptr(), ws_bytes,
-           nrow, d, int(r))
+    launch("runia_proj_sq_score_trap_f64" if trap else "runia_proj_sq_score_f64", h.data_ptr(), packed_m.data_ptr(),
+           c.data_ptr(), s.data_ptr(), ws.data_ptr(), ws_bytes, nrow, d, int(r))
     return s
+
+
+@_device_guard()
+def qr_trapezoid(m: torch.Tensor, c: torch.Tensor) -> Tuple[torch.Tensor, torch.Tensor]:
+    """m [r, D] f64 (r <= D), c [r] -> (R, Q c) with R = Q m upper-trapezoidal (``R[j, k]`` exactly 0 for k < j), Q orthogonal:
+    ``|| R h + Q c || = || m h + c ||``.  Householder reflections in one workgroup, every sum in a fixed order
+    (``runia_qr_trapezoid_f64``): equal input, equal bits."""
+    require_gpu()
+    assert m.is_cuda and m.dtype == torch.float64 and m.dim() == 2 and m.shape[0] <= m.shape[1]
+    assert c.is_cuda and c.dtype == torch.float64 and c.shape == (m.shape[0],)
+    m, c = m.contiguous(), c.contiguous()
+    r_out, c_out = torch.empty_like(m), torch.empty_like(c)
+    launch("runia_qr_trapezoid_f64", m.data_ptr(), c.data_ptr(), r_out.data_ptr(), c_out.data_ptr(), m.shape[0], m.shape[1])
+    return r_out, c_out
 
 
 def _ood_metrics_buffers(n: int, device):

@@ -712,10 +712,39 @@ struct ProjSqArgs {
 #ifndef K2_WAVES_DMA
 #define K2_WAVES_DMA 5  // (the DMA form needs 74 vector registers, but 6 waves per SIMD measured 2 % slower than 5)
 #endif
-template <int RT, int NCT, bool ACCUMULATE, bool SPLIT, bool DMA>
+// TRAP: the caller promises an upper-trapezoidal M (M[j][k] = 0 for k < j; runia_qr_trapezoid_f64 makes one at setup: the
+// score does not change under an orthogonal factor from the left).  Column tile t of M^T then holds only zeros in its
+// rows k < 16 t, and the products with them are 0.0 * h: adding them changes nothing for finite h, so the K loop may start
+// behind them.  With r = 256, D = 512 and the column split, the wave that owns 32-column group q = 0..7 can skip q of the
+// 16 chunks: 100 of 128 chunk-waves are left, 0.78 of the matrix instructions and weight-fragment loads (the parameter
+// count of a rank-256 form on 512 dimensions allows 0.75).  Column tile 0 skips nothing, so a row with a NaN h still
+// scores NaN, and a row with an infinite h never scores a finite value (NaN like the dense form wherever a computed
+// column meets the infinity with a zero; -inf instead of NaN only for +-inf exactly at k = 32 q - 1 under TRAP = 2).
+//   TRAP = 0  dense: the code of the plain entry points, unchanged
+//   TRAP = 1  workgroup-uniform skip: the chunk loop of a workgroup starts at the first chunk in which any of its columns
+//             is non-zero (chunk 4 for column half 1 of the case above: 0.875 of the work; nothing for the unsplit forms
+//             below 256 columns); DMA prologue and B ring start there
+//   TRAP = 2  per-wave skip (16-row DMA forms; the others fall back to TRAP = 1): below its own first live chunk a wave
+//             only issues its share of the row DMA and joins the barrier.  Which wave owns which 32-column group rotates
+//             between the workgroups that share a CU (`grp`) - the four waves of a workgroup sit on the four SIMDs of a CU, and with a fixed assignment
+//             the SIMD of the wave that skips least would set the pace; `part` is indexed by group, so the summation
+//             order below is the documented one whichever wave computed a group.
+#ifndef K2_TRAP_FORM
+#define K2_TRAP_FORM 2  // the form behind runia_proj_sq_*_trap_f64
+#endif
+// K2_TRAP_ROT: how the owner of a column group rotates under TRAP = 2.  Workgroup ids go round-robin over the 8 XCDs
+// (bits 0-2), so `tile & 3` (= id & 3) is one value per XCD and rotates nothing inside a CU; which higher bits separate
+// the workgroups of one CU is the dispatcher's business.  Measured, accumulate form, N = 10 000, trap / dense: id bits
+// 4-5 + 8-9 0.958, bits 8-9 alone 0.964 (one session); `tile & 3` 0.933 in an earlier session on its own - not
+// compared side by side, and none near the 0.78 of the instruction count: SIMD balance is not what holds the kernel back.
+#ifndef K2_TRAP_ROT
+#define K2_TRAP_ROT 2  // 0 none, 1 tile & 3, 2 id bits 4-5 + 8-9, 3 id bits 8-9
+#endif
+template <int RT, int NCT, bool ACCUMULATE, bool SPLIT, bool DMA, int TRAP = 0>
 __global__ __launch_bounds__(256, (RT == 1 && NCT <= 2) ? (DMA ? K2_WAVES_DMA : K2_WAVES) : 1) void proj_sq_kernel(ProjSqArgs g) {
 #if defined(__HIP_DEVICE_COMPILE__)  // (the host pass only needs the launch stub; the body uses device-only buffer builtins)
   constexpr int BM = 16 * RT;
+  constexpr bool WAVE_SKIP = TRAP == 2 && DMA && RT == 1;
   __shared__ double lds_a[DMA ? 1 : 2 * BM * APITCH];
   // the DMA form's two chunk buffers are separate objects: the compiler orders a ds_read behind every LDS DMA it cannot
   // prove disjoint (one array: `s_waitcnt vmcnt(0)` in front of each chunk's first read, the DMA of the NEXT chunk included)
@@ -741,6 +770,12 @@ __global__ __launch_bounds__(256, (RT == 1 && NCT <= 2) ? (DMA ? K2_WAVES_DMA : 
   }
   const int64_t r0 = tile * BM;
   const int nchunks = (int)(k_padded(g.D) / KC);
+  // The 32 * NG-column group of every block this wave owns; under WAVE_SKIP the owner rotates from workgroup to workgroup
+  // (K2_TRAP_ROT, measured above).
+  const int rot = K2_TRAP_ROT == 1 ? (int)(tile & 3)
+                  : K2_TRAP_ROT == 2 ? (int)(((blockIdx.x >> 4) + (blockIdx.x >> 8)) & 3)
+                  : K2_TRAP_ROT == 3 ? (int)((blockIdx.x >> 8) & 3) : 0;
+  const int grp = WAVE_SKIP ? (wave + rot) & 3 : wave;
   constexpr int PER_T = BM * KC / 256;
   double rowsq[NG][RT][4];
 #pragma unroll
@@ -750,7 +785,12 @@ __global__ __launch_bounds__(256, (RT == 1 && NCT <= 2) ? (DMA ? K2_WAVES_DMA : 
 #pragma unroll
       for (int r = 0; r < 4; ++r) rowsq[q][a][r] = 0.0;
   for (int64_t cb = 0; cb < n_pad / BN; ++cb) {
-    const int64_t ctbase = cb * 16 + (int64_t)half * (4 * NCT) + wave * NCT;
+    const int64_t ctbase = cb * 16 + (int64_t)half * (4 * NCT) + grp * NCT;
+    // first chunk with a non-zero column of this workgroup (ch0) and of this wave (ws); never past the last chunk, so the
+    // row DMA stays inside the rows (all-zero padding columns beyond r just run that one chunk)
+    const int64_t wg_chunk = (cb * 16 + (int64_t)half * (4 * NCT)) * 16 / KC, wave_chunk = ctbase * 16 / KC;
+    const int ch0 = TRAP ? (int)(wg_chunk < nchunks - 1 ? wg_chunk : nchunks - 1) : 0;
+    [[maybe_unused]] const int ws = WAVE_SKIP ? (int)(wave_chunk < nchunks - 1 ? wave_chunk : nchunks - 1) : ch0;
     d4 acc[RT][NCT];
 #pragma unroll
     for (int a = 0; a < RT; ++a)
@@ -799,21 +839,40 @@ __global__ __launch_bounds__(256, (RT == 1 && NCT <= 2) ? (DMA ? K2_WAVES_DMA : 
       // prologue in the loop's own order - DMA first, then the three ring pairs - so the count in body() holds for chunk 0
       // too (and the compiler's own wait for its DMA -> ds_read dependence merges to the same vmcnt(3 * NCT) at the loop
       // header instead of vmcnt(0))
-      dma_rows(0, 0);
+      dma_rows(0, ch0 * KC);
+      int ch = ch0;
+      if constexpr (WAVE_SKIP) {
+        // chunks below this wave's first live one: its quarter of the rows and the barrier, no B load, no matrix
+        // instruction.  No load of this wave is younger than its DMA here, so no count above zero says the DMA has landed:
+        // vmcnt(0).  The next DMA goes out behind the barrier like in body(); the last one of this loop (chunk ws) is
+        // followed by the ring prologue, so body(ws) finds its DMA older than 3 * NCT B loads again.
+        for (; ch < ws; ++ch) {
+          asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+          __syncthreads();
+          dma_rows((ch + 1 - ch0) & 1, (ch + 1) * KC);
+        }
+      }
 #pragma unroll
       for (int j = 0; j < 3; ++j)
 #pragma unroll
         for (int c = 0; c < NCT; ++c)
           bring[j][c] = __builtin_bit_cast(double2, __builtin_amdgcn_raw_buffer_load_b128(
-                                                        brsrc, lane_bytes + c * 1024u, ct_bytes + j * pair_stride_bytes, 0));
-      int ch = 0;
+                                                        brsrc, lane_bytes + c * 1024u,
+                                                        ct_bytes + (unsigned)(4 * ch + j) * pair_stride_bytes, 0));
+      if constexpr (WAVE_SKIP) {
+        // an odd number of skipped chunks leaves chunk ws in buffer 1
+        if ((ch - ch0) & 1) {
+          body(std::integral_constant<int, 1>{}, ch);
+          ++ch;
+        }
+      }
       for (; ch + 1 < nchunks; ch += 2) {
         body(std::integral_constant<int, 0>{}, ch);
         body(std::integral_constant<int, 1>{}, ch + 1);
       }
       if (ch < nchunks) body(std::integral_constant<int, 0>{}, ch);
     } else {
-      const double2* bp = reinterpret_cast<const double2*>(g.packed_m) + ctbase * 64 + lane;
+      const double2* bp = reinterpret_cast<const double2*>(g.packed_m) + ctbase * 64 + lane + (int64_t)ch0 * 4 * NT * 64;
     #pragma unroll
       for (int j = 0; j < 3; ++j)
   #pragma unroll
@@ -838,14 +897,14 @@ __global__ __launch_bounds__(256, (RT == 1 && NCT <= 2) ? (DMA ? K2_WAVES_DMA : 
           areg[q] = (gr < g.N && gk < g.D) ? g.h[gr * g.D + gk] : 0.0;
         }
       };
-      load_a(0);
+      load_a((int64_t)ch0 * KC);
       int buf = 0;
-      for (int64_t ch = 0; ch < nchunks; ++ch) {
+      for (int64_t ch = ch0; ch < nchunks; ++ch) {
   #pragma unroll
         for (int q = 0; q < PER_T; ++q) lds_a[(buf * BM + srow + q * (256 / KC)) * APITCH + skk] = areg[q];
         __syncthreads();
         if (ch + 1 < nchunks) load_a((ch + 1) * KC);
-        mfma_chunk_ring<RT, NCT>(acc, lds_a + buf * BM * APITCH, APITCH, li, lg, bp + ch * 4 * NT * 64, NT * 64, bring);
+        mfma_chunk_ring<RT, NCT>(acc, lds_a + buf * BM * APITCH, APITCH, li, lg, bp + (ch - ch0) * 4 * NT * 64, NT * 64, bring);
         buf ^= 1;
       }
     }
@@ -877,7 +936,7 @@ __global__ __launch_bounds__(256, (RT == 1 && NCT <= 2) ? (DMA ? K2_WAVES_DMA : 
         v += shfl_xor_f64(v, 2);
         v += shfl_xor_f64(v, 4);
         v += shfl_xor_f64(v, 8);
-        if (li == 0) part[(wave * NG + q) * BM + 16 * a + lg + 4 * r] = v;
+        if (li == 0) part[(grp * NG + q) * BM + 16 * a + lg + 4 * r] = v;
       }
   __syncthreads();
   if (tid < BM) {
@@ -1229,10 +1288,19 @@ static bool proj_sq_dma_ok(int64_t D, int64_t r) {
   return K2_DMA && D % KC == 0 && D < (1 << 23) && packed_elems(D, r) < ((int64_t)1 << 29);
 }
 static bool proj_sq_one_round(unsigned grid) { return (int64_t)grid <= (int64_t)K2_WAVES_DMA * runia_cu_count(); }
-template <int RT, int NCT, bool ACCUMULATE, bool SPLIT>
+template <bool TRAP, int RT, int NCT, bool ACCUMULATE, bool SPLIT>
 static void launch_proj_sq(unsigned grid, hipStream_t s, const ProjSqArgs& g, bool dma) {
-  if (dma && (RT > 1 || proj_sq_one_round(grid))) proj_sq_kernel<RT, NCT, ACCUMULATE, SPLIT, true><<<grid, 256, 0, s>>>(g);
-  else proj_sq_kernel<RT, NCT, ACCUMULATE, SPLIT, false><<<grid, 256, 0, s>>>(g);
+  const bool use_dma = dma && (RT > 1 || proj_sq_one_round(grid));
+  if constexpr (TRAP) {
+    // The register-staged 16-row forms stay dense (same bits): with the start chunk to carry they spill 12-20 bytes of scratch at
+    // the 96 of 5 waves per SIMD and measured 85.3 us against 83.5 us dense at N = 20 000.
+    if (use_dma) proj_sq_kernel<RT, NCT, ACCUMULATE, SPLIT, true, K2_TRAP_FORM><<<grid, 256, 0, s>>>(g);
+    else if constexpr (RT > 1) proj_sq_kernel<RT, NCT, ACCUMULATE, SPLIT, false, K2_TRAP_FORM><<<grid, 256, 0, s>>>(g);
+    else proj_sq_kernel<RT, NCT, ACCUMULATE, SPLIT, false><<<grid, 256, 0, s>>>(g);
+  } else {
+    if (use_dma) proj_sq_kernel<RT, NCT, ACCUMULATE, SPLIT, true><<<grid, 256, 0, s>>>(g);
+    else proj_sq_kernel<RT, NCT, ACCUMULATE, SPLIT, false><<<grid, 256, 0, s>>>(g);
+  }
 }
 
 // 32 x 256 tiles (fewer re-reads of M, 65 TFLOP/s when they fill the chip evenly) or 16 x 128 half tiles (62 TFLOP/s,
@@ -1244,8 +1312,9 @@ static bool proj_sq_large_tiles(int64_t N, int64_t cus) {
   return tiles32 >= 2 * cus && 100 * tiles32 >= 93 * rounds * cus;
 }
 
-extern "C" int runia_proj_sq_accumulate_f64(const double* h, const double* packed_m, const double* c, double* score,
-                                            int64_t N, int64_t D, int64_t r, runia_stream_t stream) {
+template <bool TRAP>
+static int proj_sq_accumulate(const double* h, const double* packed_m, const double* c, double* score, int64_t N, int64_t D,
+                              int64_t r, runia_stream_t stream) {
   if (N < 0 || D <= 0 || r <= 0) return RUNIA_E_INVALID;
   if (N == 0) return RUNIA_OK;
   if (!h || !packed_m || !c || !score) return RUNIA_E_INVALID;
@@ -1253,19 +1322,30 @@ extern "C" int runia_proj_sq_accumulate_f64(const double* h, const double* packe
   hipStream_t s = as_stream(stream);
   const int64_t tiles16 = (N + 15) / 16, cus = runia_cu_count();
   const bool dma = proj_sq_dma_ok(D, r);
-  if (r <= 64) launch_proj_sq<1, 1, true, false>((unsigned)tiles16, s, g, dma);
-  else if (r <= 128) launch_proj_sq<1, 2, true, false>((unsigned)tiles16, s, g, dma);
-  else if (proj_sq_large_tiles(N, cus)) launch_proj_sq<2, 4, false, false>((unsigned)((N + 31) / 32), s, g, dma);
-  else if (tiles16 > cus / 2) launch_proj_sq<1, 2, true, true>((unsigned)((tiles16 + 7) / 8 * 16), s, g, dma);
-  else launch_proj_sq<1, 4, false, false>((unsigned)tiles16, s, g, dma);
+  if (r <= 64) launch_proj_sq<TRAP, 1, 1, true, false>((unsigned)tiles16, s, g, dma);
+  else if (r <= 128) launch_proj_sq<TRAP, 1, 2, true, false>((unsigned)tiles16, s, g, dma);
+  else if (proj_sq_large_tiles(N, cus)) launch_proj_sq<TRAP, 2, 4, false, false>((unsigned)((N + 31) / 32), s, g, dma);
+  else if (tiles16 > cus / 2) launch_proj_sq<TRAP, 1, 2, true, true>((unsigned)((tiles16 + 7) / 8 * 16), s, g, dma);
+  else launch_proj_sq<TRAP, 1, 4, false, false>((unsigned)tiles16, s, g, dma);
   return runia_check_launch();
+}
+
+extern "C" int runia_proj_sq_accumulate_f64(const double* h, const double* packed_m, const double* c, double* score,
+                                            int64_t N, int64_t D, int64_t r, runia_stream_t stream) {
+  return proj_sq_accumulate<false>(h, packed_m, c, score, N, D, r, stream);
+}
+// the caller promises M[j][k] = 0 for k < j (r <= D): same bits as the plain entry point on that matrix, fewer chunks
+extern "C" int runia_proj_sq_accumulate_trap_f64(const double* h, const double* packed_m, const double* c, double* score,
+                                                 int64_t N, int64_t D, int64_t r, runia_stream_t stream) {
+  if (r > D) return RUNIA_E_INVALID;
+  return proj_sq_accumulate<true>(h, packed_m, c, score, N, D, r, stream);
 }
 
 extern "C" size_t runia_proj_sq_workspace_bytes(int64_t N) { return N > 0 ? (size_t)N * 2 * sizeof(double) : 0; }
 
-extern "C" int runia_proj_sq_score_f64(const double* h, const double* packed_m, const double* c, double* score,
-                                       void* workspace, size_t workspace_bytes, int64_t N, int64_t D, int64_t r,
-                                       runia_stream_t stream) {
+template <bool TRAP>
+static int proj_sq_score(const double* h, const double* packed_m, const double* c, double* score, void* workspace,
+                         size_t workspace_bytes, int64_t N, int64_t D, int64_t r, runia_stream_t stream) {
   if (N < 0 || D <= 0 || r <= 0) return RUNIA_E_INVALID;
   if (N == 0) return RUNIA_OK;
   if (!h || !packed_m || !c || !score) return RUNIA_E_INVALID;
@@ -1274,17 +1354,29 @@ extern "C" int runia_proj_sq_score_f64(const double* h, const double* packed_m, 
   const int64_t tiles16 = (N + 15) / 16, cus = runia_cu_count();
   const bool dma = proj_sq_dma_ok(D, r);
   if (r <= 64) {
-    launch_proj_sq<1, 1, false, false>((unsigned)tiles16, s, g, dma);
+    launch_proj_sq<TRAP, 1, 1, false, false>((unsigned)tiles16, s, g, dma);
   } else if (r <= 128) {
-    launch_proj_sq<1, 2, false, false>((unsigned)tiles16, s, g, dma);
+    launch_proj_sq<TRAP, 1, 2, false, false>((unsigned)tiles16, s, g, dma);
   } else if (proj_sq_large_tiles(N, cus)) {
-    launch_proj_sq<2, 4, false, false>((unsigned)((N + 31) / 32), s, g, dma);
+    launch_proj_sq<TRAP, 2, 4, false, false>((unsigned)((N + 31) / 32), s, g, dma);
   } else if (tiles16 > cus / 2 && workspace && workspace_bytes >= runia_proj_sq_workspace_bytes(N)) {
     // (32-, 48- and 64-row tiles with the same column split measured 64, 64 and 78 us against 59 us)
-    launch_proj_sq<1, 2, false, true>((unsigned)((tiles16 + 7) / 8 * 16), s, g, dma);
+    launch_proj_sq<TRAP, 1, 2, false, true>((unsigned)((tiles16 + 7) / 8 * 16), s, g, dma);
     proj_sq_combine_kernel<<<(unsigned)((N + 255) / 256), 256, 0, s>>>(g.partial, score, N);
   } else {
-    launch_proj_sq<1, 4, false, false>((unsigned)tiles16, s, g, dma);
+    launch_proj_sq<TRAP, 1, 4, false, false>((unsigned)tiles16, s, g, dma);
   }
   return runia_check_launch();
+}
+
+extern "C" int runia_proj_sq_score_f64(const double* h, const double* packed_m, const double* c, double* score,
+                                       void* workspace, size_t workspace_bytes, int64_t N, int64_t D, int64_t r,
+                                       runia_stream_t stream) {
+  return proj_sq_score<false>(h, packed_m, c, score, workspace, workspace_bytes, N, D, r, stream);
+}
+extern "C" int runia_proj_sq_score_trap_f64(const double* h, const double* packed_m, const double* c, double* score,
+                                            void* workspace, size_t workspace_bytes, int64_t N, int64_t D, int64_t r,
+                                            runia_stream_t stream) {
+  if (r > D) return RUNIA_E_INVALID;
+  return proj_sq_score<true>(h, packed_m, c, score, workspace, workspace_bytes, N, D, r, stream);
 }

@@ -73,6 +73,10 @@ class LaREMPipeline:
         # (score = -||M h + c||^2, exact algebra in f64; `runia_proj_sq_score_f64`).  Set False to keep the two-stage
         # K2 (`runia_pca_md_score_f64`), which also materialises the projection in LDS.
         self.fold_weights = True
+        # Rotate the folded M to upper-trapezoidal form (R = Q M, c' = Q c with Q orthogonal: the same score to rounding) so
+        # that the contraction skips R's zero blocks (`runia_proj_sq_*_trap_f64`: 0.78 of the matrix work at 256 x 512).
+        # Set False for the dense launch on the unrotated M.
+        self.fold_trapezoid = True
         self._folded = None
         self._folded_fp = None
         self._k0 = None  # side stream + two table buffers of prepare_draws
@@ -151,11 +155,12 @@ class LaREMPipeline:
         return pp._mean(torch.float64), st["packed_p"]
 
     def _folded_state(self):
-        """(packed M^T, c, r) with M = W diag(1/scale) C, c = W (-bias/scale - mu), precision = W^T W; None when the
-        precision matrix is not positive semi-definite to rounding (then the two-stage kernel is used)."""
+        """(packed M^T, c, r, trapezoidal) with M = W diag(1/scale) C, c = W (-bias/scale - mu), precision = W^T W - rotated
+        to upper-trapezoidal form when ``fold_trapezoid`` is set; None when the precision matrix is not positive
+        semi-definite to rounding (then the two-stage kernel is used)."""
         pp = self.postprocessor
         fp = (_hip.array_fingerprint(pp.precision), _hip.array_fingerprint(pp.feats_mean),
-              None if self.pca is None else id(self.pca))
+              None if self.pca is None else id(self.pca), bool(self.fold_trapezoid))
         if self._folded is None or self._folded_fp != fp:
             self._folded_fp = fp
             # Everything below runs on the device with the library's own kernels (Jacobi eigen-solver, f64 products) and
@@ -180,7 +185,11 @@ class LaREMPipeline:
                 b = -mu
                 m = w
             c = _hip.matmul_f64(w, b.reshape(-1, 1).contiguous()).reshape(-1).contiguous()
-            self._folded = (_hip.pack_weights(m.t().contiguous()), c, int(m.shape[0]))
+            # any Q M with Q orthogonal scores the same; the fixed-order device QR keeps the folded bits equal on every rank
+            trap = bool(self.fold_trapezoid) and m.shape[0] <= m.shape[1]
+            if trap:
+                m, c = _hip.qr_trapezoid(m.contiguous(), c)
+            self._folded = (_hip.pack_weights(m.t().contiguous()), c, int(m.shape[0]), trap)
         return self._folded or None
 
     def score_entropies(self, h: Tensor) -> Tensor:
@@ -194,7 +203,7 @@ class LaREMPipeline:
             if self.fold_weights:
                 folded = self._folded_state()
                 if folded is not None:
-                    return _hip.proj_sq_score(h, *folded)
+                    return _hip.proj_sq_score(h, *folded[:3], trap=folded[3])
             if self.pca is not None:
                 if h.shape[1] != self.pca.n_features:
                     raise ValueError(f"X has {h.shape[1]} features, but PCA is expecting {self.pca.n_features} features as input.")
@@ -208,7 +217,7 @@ class LaREMPipeline:
         """LaREM score of entropy rows ``h`` written into ``out`` (folded single contraction or two-stage K2)."""
         folded = self._folded_state() if self.fold_weights else None
         if folded is not None:
-            _hip.proj_sq_score(h, *folded, out=out)
+            _hip.proj_sq_score(h, *folded[:3], out=out, trap=folded[3])
         elif self.pca is not None:
             _hip.pca_md_score(h, self.pca.packed_ct, self.pca.bias, self.pca.scale, mean, packed_p,
                               self.pca.n_components, out=out)
@@ -246,7 +255,7 @@ class LaREMPipeline:
                 # workspace, no combine launch (bit-identical to the store form)
                 scores = torch.empty((n,), dtype=torch.float64, device=latents.device)
                 h = self.entropy_from_latents(latents, rand, k1_events, zero_fill=scores, prepared=prepared)
-                return _hip.proj_sq_accumulate(h, *folded, out=scores)
+                return _hip.proj_sq_accumulate(h, *folded[:3], out=scores, trap=folded[3])
             return self.score_entropies(self.entropy_from_latents(latents, rand, k1_events if fused else None,
                                                                   prepared=prepared))
         latents = latents.contiguous()

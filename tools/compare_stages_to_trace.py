@@ -60,7 +60,7 @@ def add(label, in_run, parts, note=""):
 
 add("roofline K1 `mc_entropy_kernel<4,4,16,5>` (10 000 images)", bench["roofline"]["avg_launch_ms"], [("mc_entropy_kernel<4, 4, 16, 5, true, true, 0>", 40000)],
     "events attached to the dispatch")
-k2, _ = med("proj_sq_kernel<1, 2, true, true, true>", 1264)
+k2, _ = med("proj_sq_kernel<1, 2, true, true, true", 1264)
 k0, _ = med("mc_mask_bits_kernel<4, 4, 16, true>", 2500)
 k1, _ = med("mc_entropy_kernel<4, 4, 16, 5, true, true, 0>", 40000)
 rows.append(("step = K0 + K1 + K2' (kernel time only)", bench["ms_per_step_stats"]["median"], (k0 or 0) + (k1 or 0) + (k2 or 0), "median step (events) vs sum of the three kernels: the difference is dispatch gaps"))

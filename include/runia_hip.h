@@ -923,6 +923,45 @@ int runia_calib_reduce_f32(const int32_t* pred, const float* conf, const float* 
                            const float* h, const void* labels, int labels_i64, int has_ignore, int64_t ignore_index, int64_t N,
                            int n_bins, void* out, void* workspace, size_t workspace_bytes, runia_stream_t stream);
 
+/* ---- Conformal prediction sets (conformal.hip; evaluation/conformal.py) -------------------------------------- *
+ * logits [N, C], row r at logits + r * row_stride elements (row_stride >= C); `dtype` 0 f32, 1 f16, 2 bf16, widened exactly,
+ * f32 arithmetic.  Per row, with m = max_k x_k, e_k = exp(beta (x_k - m)), S0 = sum e_k, p_k = e_k / S0 (0 < beta < inf):
+ *   order : classes by logit, descending; equal logits by lower class index first (the stable argsort of -x)
+ *   r_c   : the 1-based rank of class c;  B_c: the sum of p_k over the classes ordered before c
+ *   method 0 lac : s_c = 1 - p_c
+ *          1 aps : s_c = B_c + u p_c
+ *          2 raps: s_c = B_c + u p_c + lam * max(0, r_c - k_reg)        (lam >= 0, k_reg >= 0)
+ *   u f32 [N] in [0, 1], one number per row; NULL: u = 1.
+ * A class at -inf has p = 0 and is ordered last.  A row with a NaN or +inf logit, or without a finite logit, has no softmax:
+ * NaN scores, rank 0, size 0, no members, not covered.  labels [N] int32 (labels_i64 == 0) or int64; a row whose label equals
+ * ignore_index (has_ignore != 0) or lies outside [0, C) gets a NaN score, rank 0, covered 0 - callers validate labels.
+ * runia_conformal_label_scores: score f32 [N] = s_y and rank i32 [N] = r_y (either may be NULL) from one read of the logits and
+ *   no sort: B_y = sum_k p_k [x_k > x_y or (x_k == x_y and k < y)].  C <= 64 a row per lane through LDS; beyond, a wave per row,
+ *   four consecutive classes per lane and load (one aligned load when C % 4 == 0, row_stride % 4 == 0 and the base is aligned to
+ *   four elements, four guarded loads otherwise: the same sums either way), the row in registers up to C = 2048, ONE chunked pass
+ *   that rescales its sums when the running maximum moves beyond.  C < 2^31 - 2048.
+ * runia_conformal_sets: the set {c : s_c <= qhat} (f32 compare; qhat = +inf: every class) of every row.  size i32 [N]; members
+ *   i32 [N, ceil(C / 32)] or NULL, bit c % 32 of word c / 32 is class c; covered u8 [N] or NULL (needs labels): the label's bit.
+ *   size is the population count of the row's words.  The row is ordered inside the workgroup (a bitonic network on (key, index)
+ *   in LDS; lac skips it), the logits are read once and nothing [N, C] is written.  1 <= C <= runia_conformal_max_classes()
+ *   (8192), RUNIA_E_INVALID beyond.
+ * Both: sums in a fixed order that depends on C alone - the same bits from run to run, wherever the row sits in the batch, and
+ *   for a 16-bit call the bits of the f32 call on the widened values.
+ * runia_conformal_reduce: size / covered / labels -> out, runia_conformal_record_slots(C) = 3 + H + 2 C int64 slots, H = min(C + 1, 512):
+ *     [0] rows used  [1] rows covered  [2] sum of sizes  [3 ..) hist[H] (the last slot: that size or more)
+ *     class_count[C]  class_covered[C]
+ *   over the rows whose label lies in [0, C) and is not ignore_index.  Integer atomics only: exact in any order.  N == 0: zeros. */
+int runia_conformal_max_classes(void);
+int runia_conformal_label_scores(const void* logits, int dtype, int64_t row_stride, const void* labels, int labels_i64,
+                                 int has_ignore, int64_t ignore_index, const float* u, int method, float beta, float lam,
+                                 int k_reg, float* score, int32_t* rank, int64_t N, int64_t C, runia_stream_t stream);
+int runia_conformal_sets(const void* logits, int dtype, int64_t row_stride, const void* labels, int labels_i64, int has_ignore,
+                         int64_t ignore_index, const float* u, int method, float beta, float lam, int k_reg, float qhat,
+                         int32_t* size, int32_t* members, uint8_t* covered, int64_t N, int64_t C, runia_stream_t stream);
+int64_t runia_conformal_record_slots(int64_t C);
+int runia_conformal_reduce(const int32_t* size, const uint8_t* covered, const void* labels, int labels_i64, int has_ignore,
+                           int64_t ignore_index, int64_t N, int64_t C, void* out, runia_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -302,6 +302,15 @@ _SIGNATURES = {
     "runia_calib_reduce_f32": (
         c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int64, c_int64, c_int,
                 c_void_p, c_void_p, c_size_t, c_void_p]),
+    "runia_conformal_max_classes": (c_int, []),
+    "runia_conformal_label_scores": (
+        c_int, [c_void_p, c_int, c_int64, c_void_p, c_int, c_int, c_int64, c_void_p, c_int, c_float, c_float, c_int, c_void_p,
+                c_void_p, c_int64, c_int64, c_void_p]),
+    "runia_conformal_sets": (
+        c_int, [c_void_p, c_int, c_int64, c_void_p, c_int, c_int, c_int64, c_void_p, c_int, c_float, c_float, c_int, c_float,
+                c_void_p, c_void_p, c_void_p, c_int64, c_int64, c_void_p]),
+    "runia_conformal_record_slots": (c_int64, [c_int64]),
+    "runia_conformal_reduce": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_int64, c_int64, c_int64, c_void_p, c_void_p]),
 }
 
 
@@ -1054,6 +1063,100 @@ def calibration_record(record: np.ndarray, n_bins: int) -> dict:
     return {"n_used": int(record[0]), "n_correct": int(record[1]), "nll": float(f[2]), "brier": float(f[3]), "g": float(f[4]),
             "h": float(f[5]), "count": record[6:6 + n_bins].copy(), "correct": record[6 + n_bins:6 + 2 * n_bins].copy(),
             "conf_sum": f[6 + 2 * n_bins:6 + 3 * n_bins].copy()}
+
+
+CONFORMAL_METHODS = {"lac": 0, "aps": 1, "raps": 2}  # `method` of the runia_conformal_* entry points
+
+
+class ConformalSets(NamedTuple):
+    """What ``conformal_sets`` returns: ``size`` [N] int32, ``members`` [N, ceil(C / 32)] int32 (bit ``c % 32`` of word ``c // 32``
+    is class ``c``) or None, ``covered`` [N] uint8 or None (no labels)."""
+
+    size: torch.Tensor
+    members: Optional[torch.Tensor]
+    covered: Optional[torch.Tensor]
+
+
+def conformal_max_classes() -> int:
+    """The widest row ``conformal_sets`` orders (``runia_conformal_max_classes``)."""
+    return query("runia_conformal_max_classes")
+
+
+def _conformal_rows(logits: torch.Tensor, u: Optional[torch.Tensor], method: str):
+    """Checks shared by the two conformal row kernels -> (logits with unit column stride, u contiguous | None, method code)."""
+    assert logits.is_cuda and logits.dim() == 2 and logits.shape[1] >= 1 and logits.dtype in ELEM_DTYPE_CODES, \
+        f"logits: a [N, C] device tensor of float32, float16 or bfloat16, got {tuple(logits.shape)} {logits.dtype}"
+    assert method in CONFORMAL_METHODS, f"method: one of {tuple(CONFORMAL_METHODS)}, got {method!r}"
+    n, c = logits.shape
+    if (c > 1 and logits.stride(1) != 1) or (n > 1 and logits.stride(0) < c):  # (row-sliced views are read where they lie)
+        logits = logits.contiguous()
+    if u is not None:
+        assert u.is_cuda and u.dtype == torch.float32 and u.shape == (n,), "u: a [N] float32 device tensor"
+        u = u.contiguous()
+    return logits, u, CONFORMAL_METHODS[method]
+
+
+@_device_guard()
+def conformal_label_scores(logits: torch.Tensor, labels: torch.Tensor, method: str = "aps", beta: float = 1.0,
+                           u: Optional[torch.Tensor] = None, lam: float = 0.0, k_reg: int = 0,
+                           ignore_index: Optional[int] = None) -> Tuple[torch.Tensor, torch.Tensor]:
+    """The conformal score ``s_y`` (float32) and the 1-based rank ``r_y`` (int32) of every row's label from one read of logits
+    [N, C] at the temperature ``1 / beta`` (``runia_conformal_label_scores``).  ``u`` [N] float32 or None (u = 1).  A row whose
+    label is ``ignore_index`` or outside ``[0, C)``, and a row without a softmax, gets NaN and rank 0."""
+    require_gpu()
+    logits, u, code = _conformal_rows(logits, u, method)
+    n, c = logits.shape
+    labels, is64, has_ignore, ignore = _calib_labels(labels, n, ignore_index)
+    assert labels is not None, "the label scores need labels"
+    score = torch.empty((n,), dtype=torch.float32, device=logits.device)
+    rank = torch.empty((n,), dtype=torch.int32, device=logits.device)
+    launch("runia_conformal_label_scores", logits.data_ptr(), ELEM_DTYPE_CODES[logits.dtype], logits.stride(0) if n > 1 else c,
+           labels.data_ptr(), is64, has_ignore, ignore, _ptr(u), code, float(beta), float(lam), int(k_reg), score.data_ptr(),
+           rank.data_ptr(), n, c)
+    return score, rank
+
+
+@_device_guard()
+def conformal_sets(logits: torch.Tensor, qhat: float, method: str = "aps", beta: float = 1.0, u: Optional[torch.Tensor] = None,
+                   lam: float = 0.0, k_reg: int = 0, labels: Optional[torch.Tensor] = None, ignore_index: Optional[int] = None,
+                   want_members: bool = True) -> ConformalSets:
+    """The sets ``{c : s_c <= qhat}`` of logits [N, C] (``runia_conformal_sets``; C <= ``conformal_max_classes()``): the row is
+    ordered inside the workgroup, the logits are read once.  With ``labels``, ``covered`` says whether the set holds the label."""
+    require_gpu()
+    logits, u, code = _conformal_rows(logits, u, method)
+    n, c = logits.shape
+    assert c <= conformal_max_classes(), f"C = {c} is above the limit of {conformal_max_classes()} classes"
+    assert qhat == qhat, "qhat is NaN"
+    labels, is64, has_ignore, ignore = _calib_labels(labels, n, ignore_index)
+    dev = logits.device
+    size = torch.empty((n,), dtype=torch.int32, device=dev)
+    members = torch.empty((n, (c + 31) // 32), dtype=torch.int32, device=dev) if want_members else None
+    covered = torch.empty((n,), dtype=torch.uint8, device=dev) if labels is not None else None
+    launch("runia_conformal_sets", logits.data_ptr(), ELEM_DTYPE_CODES[logits.dtype], logits.stride(0) if n > 1 else c,
+           _ptr(labels), is64, has_ignore, ignore, _ptr(u), code, float(beta), float(lam), int(k_reg), float(qhat),
+           size.data_ptr(), _ptr(members), _ptr(covered), n, c)
+    return ConformalSets(size, members, covered)
+
+
+@_device_guard()
+def conformal_reduce(sets: ConformalSets, labels: torch.Tensor, c: int, ignore_index: Optional[int] = None) -> torch.Tensor:
+    """``size`` / ``covered`` / labels -> the int64 device record of ``runia_conformal_reduce`` (``conformal_record`` splits a
+    host copy)."""
+    require_gpu()
+    n = labels.shape[0]
+    assert sets.covered is not None and sets.size.shape == (n,) and sets.covered.shape == (n,)
+    labels, is64, has_ignore, ignore = _calib_labels(labels, n, ignore_index)
+    out = torch.empty((query("runia_conformal_record_slots", c),), dtype=torch.int64, device=labels.device)
+    launch("runia_conformal_reduce", sets.size.data_ptr(), sets.covered.data_ptr(), labels.data_ptr(), is64, has_ignore, ignore, n,
+           c, out.data_ptr())
+    return out
+
+
+def conformal_record(record: np.ndarray, c: int) -> dict:
+    """A host copy of ``conformal_reduce``'s record -> its named parts."""
+    h = min(c + 1, 512)
+    return {"n_used": int(record[0]), "n_covered": int(record[1]), "size_sum": int(record[2]), "hist": record[3:3 + h].copy(),
+            "class_count": record[3 + h:3 + h + c].copy(), "class_covered": record[3 + h + c:3 + h + 2 * c].copy()}
 
 
 @_device_guard()

@@ -26,3 +26,10 @@ from .calibration import (  # noqa: F401
     calibration_metrics,
     fit_temperature,
 )
+from .conformal import (  # noqa: F401
+    ConformalClassifier,
+    ConformalResult,
+    PredictionSets,
+    conformal_quantile,
+    conformal_scores,
+)

@@ -41,13 +41,27 @@ class CalibrationResult(NamedTuple):
     temperature: float
 
 
-def _prepare(logits, labels, ignore_index) -> Tuple[Tensor, Tensor]:
-    """Check shapes and labels (once: the fit loop does not repeat it) -> logits and labels on the device.  Host logits go up in
-    their own 16-bit dtype or as float32; device logits are read where they lie."""
-    if ignore_index is not None and not isinstance(ignore_index, (int, np.integer)):
-        raise ValueError(f"ignore_index must be an integer or None, got {ignore_index!r}")
+def _check_logits(logits) -> None:
     if logits.ndim != 2 or logits.shape[1] < 1:
         raise ValueError(f"logits must be [N, C] with C >= 1, got shape {tuple(logits.shape)}")
+
+
+def _logits_to_device(logits) -> Tensor:
+    """Host logits go up in their own 16-bit dtype or as float32; device logits are read where they lie."""
+    if isinstance(logits, Tensor):
+        x = logits.detach()
+        return x if x.is_cuda and x.dtype in _hip.ELEM_DTYPE_CODES else _hip.to_device(
+            x, x.dtype if x.dtype in _hip.ELEM_DTYPE_CODES else torch.float32)
+    logits = np.asarray(logits)
+    return _hip.to_device(logits, torch.float16 if logits.dtype == np.float16 else torch.float32)
+
+
+def _prepare(logits, labels, ignore_index) -> Tuple[Tensor, Tensor]:
+    """Check shapes and labels (once: the fit loop does not repeat it) -> logits and labels on the device (shared with
+    ``evaluation/conformal.py``)."""
+    if ignore_index is not None and not isinstance(ignore_index, (int, np.integer)):
+        raise ValueError(f"ignore_index must be an integer or None, got {ignore_index!r}")
+    _check_logits(logits)
     n, c = logits.shape
     if labels.ndim != 1 or labels.shape[0] != n:
         raise ValueError(f"labels must hold one class per row of logits: logits {tuple(logits.shape)}, labels "
@@ -70,13 +84,7 @@ def _prepare(logits, labels, ignore_index) -> Tuple[Tensor, Tensor]:
         bad = bool(off.any())
     if bad:
         raise ValueError(f"labels must lie in [0, {c}) or equal ignore_index ({ignore_index!r})")
-    if isinstance(logits, Tensor):
-        x = logits.detach()
-        x = x if x.is_cuda and x.dtype in _hip.ELEM_DTYPE_CODES else _hip.to_device(
-            x, x.dtype if x.dtype in _hip.ELEM_DTYPE_CODES else torch.float32)
-    else:
-        logits = np.asarray(logits)
-        x = _hip.to_device(logits, torch.float16 if logits.dtype == np.float16 else torch.float32)
+    x = _logits_to_device(logits)
     wide = labels.dtype == (torch.int64 if isinstance(labels, Tensor) else np.int64)
     y = labels if isinstance(labels, Tensor) and labels.is_cuda else _hip.to_device(labels, torch.int64 if wide else torch.int32)
     if y.device != x.device:

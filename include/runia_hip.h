@@ -962,6 +962,25 @@ int64_t runia_conformal_record_slots(int64_t C);
 int runia_conformal_reduce(const int32_t* size, const uint8_t* covered, const void* labels, int labels_i64, int has_ignore,
                            int64_t ignore_index, int64_t N, int64_t C, void* out, runia_stream_t stream);
 
+/* ---- Conformal sets of rows of any width (conformal_wide.hip; llm_uncertainty/conformal.py) ------------------- *
+ * The sets of runia_conformal_sets - the same definitions, methods, u, qhat and labels - for 1 <= V <= 2^20 classes, read in place
+ * through the step table of runia_logit_stats: table [n_steps, 2] int64 on the device, {pointer to row 0, row stride in
+ * elements} per step, n_steps steps of B rows of V logits (unit stride along V).  A plain [N, V] matrix is n_steps = 1, B = N.
+ * Output row b * n_steps + t: size i32 [B * n_steps]; members i32 [B * n_steps, ceil(V / 32)] or NULL; covered u8 [B * n_steps]
+ * or NULL (needs labels); u f32 [B * n_steps] or NULL.  labels: token ids, int32 or int64, the id of (b, t) at
+ * labels[b * label_stride + t]; NULL: none.  B * n_steps <= 2^26.
+ * The row is not ordered: for aps and raps the set is a prefix of the order, and the cut (a key value and how many of the
+ * classes with that key are in, lower index first) is found by a radix descent over the 32-bit key of the logit, 11 / 11 / 10
+ * bits, with per-bin counts and fixed-point masses (e * 2^40, 64-bit integer adds in LDS: exact in any order) - five reads of
+ * the row by one workgroup, three for lac.  No workspace, nothing [N, V] written but the members.  The same bits from run to
+ * run, wherever the row sits and however the steps are allocated; a 16-bit call gives the bits of the f32 call on the widened
+ * values.  The scores differ from runia_conformal_sets' by f32 rounding (sums are formed in another order), so the two can
+ * disagree on a class whose score lies within ~1e-6 of qhat. */
+int runia_conformal_sets_wide(const void* table, int dtype, int64_t n_steps, int64_t B, int64_t V, const void* labels,
+                              int labels_i64, int64_t label_stride, int has_ignore, int64_t ignore_index, const float* u,
+                              int method, float beta, float lam, int k_reg, float qhat, int32_t* size, int32_t* members,
+                              uint8_t* covered, runia_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

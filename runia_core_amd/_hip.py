@@ -311,6 +311,9 @@ _SIGNATURES = {
                 c_void_p, c_void_p, c_void_p, c_int64, c_int64, c_void_p]),
     "runia_conformal_record_slots": (c_int64, [c_int64]),
     "runia_conformal_reduce": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_int64, c_int64, c_int64, c_void_p, c_void_p]),
+    "runia_conformal_sets_wide": (
+        c_int, [c_void_p, c_int, c_int64, c_int64, c_int64, c_void_p, c_int, c_int64, c_int, c_int64, c_void_p, c_int, c_float,
+                c_float, c_int, c_float, c_void_p, c_void_p, c_void_p, c_void_p]),
 }
 
 
@@ -1135,6 +1138,46 @@ def conformal_sets(logits: torch.Tensor, qhat: float, method: str = "aps", beta:
     launch("runia_conformal_sets", logits.data_ptr(), ELEM_DTYPE_CODES[logits.dtype], logits.stride(0) if n > 1 else c,
            _ptr(labels), is64, has_ignore, ignore, _ptr(u), code, float(beta), float(lam), int(k_reg), float(qhat),
            size.data_ptr(), _ptr(members), _ptr(covered), n, c)
+    return ConformalSets(size, members, covered)
+
+
+CONFORMAL_WIDE_MAX_CLASSES = 1 << 20  # runia_conformal_sets_wide: the fixed-point masses of a row fit 64 bits
+CONFORMAL_WIDE_MAX_ROWS = 1 << 26
+
+
+@_device_guard()
+def conformal_sets_wide(table: torch.Tensor, dtype: torch.dtype, T: int, B: int, V: int, qhat: float, method: str = "aps",
+                        beta: float = 1.0, u: Optional[torch.Tensor] = None, lam: float = 0.0, k_reg: int = 0,
+                        labels: Optional[torch.Tensor] = None, ignore_index: Optional[int] = None,
+                        want_members: bool = True) -> ConformalSets:
+    """The sets ``{c : s_c <= qhat}`` of ``T`` steps of ``B`` rows of ``V`` logits behind the device step ``table`` [T, 2] int64
+    of {row 0 pointer, row stride} (``runia_conformal_sets_wide``, any ``V`` up to 2^20: the row is not ordered, the cut is
+    found by a radix descent).  Row ``b * T + t`` of the result is step ``t`` of row ``b``: ``size`` [B * T] reshapes to (B, T).
+    ``u`` [B * T] float32 or None; ``labels`` (B, T) int32 / int64 token ids (any row stride) or None.  The caller keeps the
+    tensors behind ``table`` alive."""
+    require_gpu()
+    assert table.is_cuda and table.dtype == torch.int64 and table.shape == (T, 2) and table.is_contiguous(), \
+        f"table: a contiguous [{T}, 2] int64 device tensor"
+    assert dtype in ELEM_DTYPE_CODES, f"dtype: float32, float16 or bfloat16, got {dtype}"
+    assert method in CONFORMAL_METHODS, f"method: one of {tuple(CONFORMAL_METHODS)}, got {method!r}"
+    assert T >= 1 and B >= 1 and 1 <= V <= CONFORMAL_WIDE_MAX_CLASSES and B * T <= CONFORMAL_WIDE_MAX_ROWS, \
+        f"{T} steps of ({B}, {V}) logits exceed the kernel's size limits"
+    assert qhat == qhat, "qhat is NaN"
+    n, dev = B * T, table.device
+    if u is not None:
+        assert u.is_cuda and u.dtype == torch.float32 and u.shape == (n,), "u: a [B * T] float32 device tensor"
+        u = u.contiguous()
+    if labels is not None:
+        assert labels.is_cuda and labels.dtype in (torch.int32, torch.int64) and labels.shape == (B, T)
+        if T > 1 and labels.stride(1) != 1:
+            labels = labels.contiguous()
+    size = torch.empty((n,), dtype=torch.int32, device=dev)
+    members = torch.empty((n, (V + 31) // 32), dtype=torch.int32, device=dev) if want_members else None
+    covered = torch.empty((n,), dtype=torch.uint8, device=dev) if labels is not None else None
+    launch("runia_conformal_sets_wide", table.data_ptr(), ELEM_DTYPE_CODES[dtype], T, B, V, _ptr(labels),
+           int(labels is not None and labels.dtype == torch.int64), labels.stride(0) if labels is not None and B > 1 else T,
+           int(ignore_index is not None), 0 if ignore_index is None else int(ignore_index), _ptr(u), CONFORMAL_METHODS[method],
+           float(beta), float(lam), int(k_reg), float(qhat), size.data_ptr(), _ptr(members), _ptr(covered))
     return ConformalSets(size, members, covered)
 
 

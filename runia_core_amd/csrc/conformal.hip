@@ -10,49 +10,11 @@
 // logit, has no softmax: NaN scores, rank 0, size 0, no members, not covered.
 #include "common.hpp"
 #include "elem.hpp"
+#include "conformal_core.hpp"
 
 namespace {
 
-enum { kLac = 0, kAps = 1, kRaps = 2 };
 constexpr int kMaxSetClasses = 8192;  // runia_conformal_sets: the row's keys and indices in 48 KB of LDS
-
-struct Labels {
-  const void* p;   // int32 or int64 [N]; NULL: no labels
-  int is_i64, has_ignore;
-  int64_t ignore;
-};
-
-struct Method {
-  int kind;
-  float beta, lam;
-  int k_reg;
-};
-
-__device__ __forceinline__ int64_t label_at(const Labels& L, int64_t row) {
-  return L.is_i64 ? static_cast<const int64_t*>(L.p)[row] : (int64_t) static_cast<const int32_t*>(L.p)[row];
-}
-
-// the class whose logit the row needs (0 for a row without one) and whether the row is scored against a label
-__device__ __forceinline__ int row_class(const Labels& L, int64_t row, int64_t C, bool& used) {
-  used = false;
-  if (!L.p) return 0;
-  const int64_t y = label_at(L, row);
-  used = y >= 0 && y < C && !(L.has_ignore && y == L.ignore);
-  return used ? (int)y : 0;
-}
-
-__device__ __forceinline__ float softmax_term(float x, float m, float beta) {
-  return (x == -INFINITY) ? 0.f : exp_nonpos(beta * (x - m));
-}
-
-// s from the row's normalised parts: p of the class, B the mass ordered before it, rank 1-based
-__device__ __forceinline__ float score_of(const Method& M, float p, float B, float u, int rank) {
-  if (M.kind == kLac) return 1.f - p;
-  const float s = B + u * p;
-  if (M.kind == kAps) return s;
-  const int over = rank - M.k_reg;
-  return s + M.lam * (float)(over > 0 ? over : 0);
-}
 
 // ---- label scores ----------------------------------------------------------------------------------------------------------
 struct Acc {
@@ -248,15 +210,6 @@ int launch_label(const void* logits, int64_t stride, const Labels& L, const floa
 //      scan of those sums -> S0 and the thread's offset
 //   4. sets: s of each slot from the running sum, the compare with qhat, the bit of its class (integer atomic-or in LDS)
 //   5. out: the words, size = their popcount, covered = the label's bit
-__device__ __forceinline__ uint32_t descending_key(float x) {
-  x = (x == 0.f) ? 0.f : x;  // -0 and +0 are equal logits
-  const uint32_t b = __float_as_uint(x);
-  return (b & 0x80000000u) ? b : (b ^ 0x7fffffffu);  // ~(orderable ascending key)
-}
-__device__ __forceinline__ float key_logit(uint32_t k) {
-  return __uint_as_float((k & 0x80000000u) ? k : (k ^ 0x7fffffffu));
-}
-
 template <int TPR>
 struct Group {
   static constexpr int kWidth = TPR < 64 ? TPR : 64;  // lanes of one wave that belong to the group
@@ -510,10 +463,6 @@ __global__ __launch_bounds__(kRedThreads) void conformal_reduce_kernel(const int
       if (cls[1][i]) add_i64(class_covered + i, cls[1][i]);
     }
   }
-}
-
-static inline bool method_ok(int method, float beta, float lam, int k_reg) {
-  return method >= kLac && method <= kRaps && beta > 0.f && beta < INFINITY && lam >= 0.f && lam < INFINITY && k_reg >= 0;
 }
 
 }  // namespace

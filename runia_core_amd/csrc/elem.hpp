@@ -1,7 +1,7 @@
 // The element layer of the kernels that read the caller's tensors where they lie, in f32, f16 or bf16: the dtype codes
 // of the C ABI, one tag type per element type, the exact widening to f32, the rounding back (to nearest even, as torch's
-// casts), the aligned 8- and 16-byte loads, and the host-side step from a run-time code to a tag.  A kernel is written
-// once as `template <class T>` over the tags.  Include after common.hpp.
+// casts), the aligned 8- and 16-byte loads, the rows of a step table, and the host-side step from a run-time code to a
+// tag.  A kernel is written once as `template <class T>` over the tags.  Include after common.hpp.
 #pragma once
 
 enum { kF32 = 0, kF16 = 1, kBF16 = 2 };  // `dtype` of runia_hip.h; _hip.ELEM_DTYPE_CODES on the Python side
@@ -64,6 +64,33 @@ __device__ __forceinline__ void ld8(const typename T::elem* p, float* v) {
   v[1] = widen(T{}, (uint16_t)(r.x >> 16));
   v[2] = widen(T{}, (uint16_t)(r.y & 0xffffu));
   v[3] = widen(T{}, (uint16_t)(r.y >> 16));
+}
+
+// ---- rows behind a step table (logits.hip, conformal_wide.hip) ----------------------------------------------------------------
+struct StepDesc {  // one generation step: row b of it starts at ptr + b * row_stride elements
+  int64_t ptr, row_stride;
+};
+
+// row b of a step (rows are addressed in bytes: `aligned` below is a property of the address), and element j of a row
+template <class T>
+__device__ __forceinline__ const char* step_row(const StepDesc& sd, int64_t b) {
+  return reinterpret_cast<const char*>(sd.ptr) + b * sd.row_stride * T::kBytes;
+}
+template <class T>
+__device__ __forceinline__ const typename T::elem* elem_at(const char* row, int64_t j) {
+  return reinterpret_cast<const typename T::elem*>(row) + j;
+}
+
+// T::V consecutive logits from element j: one 16-byte load when the row is 16-byte aligned and all of them lie inside the
+// row, element loads otherwise (-inf past V)
+template <class T>
+__device__ __forceinline__ void load_vec(const char* row, int64_t j, int64_t V, bool aligned, float* out) {
+  if (aligned && j + T::V <= V) {
+    ld16<T>(elem_at<T>(row, j), out);
+  } else {
+#pragma unroll
+    for (int e = 0; e < T::V; ++e) out[e] = j + e < V ? ld1<T>(elem_at<T>(row, j + e)) : -__builtin_inff();
+  }
 }
 
 // f(tag) for a code that elem_dtype_ok() accepted

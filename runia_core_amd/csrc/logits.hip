@@ -35,36 +35,10 @@ constexpr int kChunk = 4096;  // logits per partial: 256 lanes x 16
 constexpr int kThreads = 256;
 constexpr int kPerLane = kChunk / kThreads;
 
-struct StepDesc {  // one generation step: row b of it starts at ptr + b * row_stride elements
-  int64_t ptr, row_stride;
-};
-
 struct Partial {  // 16 bytes, one per (row, chunk) in the workspace
   float m, s, u;
   int bad;
 };
-
-// row b of a step (rows are addressed in bytes: `aligned` below is a property of the address), and element j of a row
-template <class T>
-__device__ __forceinline__ const char* step_row(const StepDesc& sd, int64_t b) {
-  return reinterpret_cast<const char*>(sd.ptr) + b * sd.row_stride * T::kBytes;
-}
-template <class T>
-__device__ __forceinline__ const typename T::elem* elem_at(const char* row, int64_t j) {
-  return reinterpret_cast<const typename T::elem*>(row) + j;
-}
-
-// T::V consecutive logits from element j: one 16-byte load when the row is 16-byte aligned and all of them lie inside the
-// row, element loads otherwise (-inf past V)
-template <class T>
-__device__ __forceinline__ void load_vec(const char* row, int64_t j, int64_t V, bool aligned, float* out) {
-  if (aligned && j + T::V <= V) {
-    ld16<T>(elem_at<T>(row, j), out);
-  } else {
-#pragma unroll
-    for (int e = 0; e < T::V; ++e) out[e] = j + e < V ? ld1<T>(elem_at<T>(row, j + e)) : -__builtin_inff();
-  }
-}
 
 // p <- p (+) q: the partial of the union of two disjoint element sets.  hi is the partial with the larger max; the lower
 // one's terms are rescaled by r = e^(lo.m - hi.m) and its max's own term (1) joins the sum.

@@ -1,3 +1,4 @@
+from .conformal import TokenConformal, TokenSets  # noqa: F401
 from .logits import GenerationScores, generation_scores, token_entropies, transition_scores  # noqa: F401
 from .pipeline import compute_uncertainties, compute_uncertainties_batch, eigen_scores  # noqa: F401
 from .rauq import (RAUQ, generated_lengths, rauq_batch, rauq_uncertainty, rauq_uncertainty_mean_heads,  # noqa: F401
@@ -6,4 +7,5 @@ from .scores import eigen_score, semantic_entropy  # noqa: F401
 
 __all__ = ["eigen_score", "semantic_entropy", "rauq_uncertainty", "rauq_uncertainty_mean_heads", "rauq_uncertainty_rollout",
            "RAUQ", "rauq_batch", "generated_lengths", "GenerationScores", "generation_scores", "token_entropies",
-           "transition_scores", "compute_uncertainties", "compute_uncertainties_batch", "eigen_scores"]
+           "transition_scores", "compute_uncertainties", "compute_uncertainties_batch", "eigen_scores", "TokenConformal",
+           "TokenSets"]

@@ -1735,7 +1735,13 @@ def eigh(a: torch.Tensor, max_sweeps: int = 30, blocked: bool = True, info: Opti
     columns), like ``numpy.linalg.eigh``.  Cyclic Jacobi sweeps until one applies no rotation; ``blocked`` (default):
     ``runia_eigh_block_sweep_f64`` - 64 x 64 sub-problems in LDS + matrix-core updates, (n/32 - 1) x 2 launches per sweep;
     ``blocked=False``: the scalar-rotation form ``runia_eigh_sweep_f64`` (2 (n - 1) launches per sweep).
-    Setup-time: reads one counter back per sweep.  ``info`` (optional dict) receives ``sweeps`` and ``rotations``."""
+    Setup-time: reads one counter back per sweep.  ``info`` (optional dict) receives ``sweeps`` and ``rotations``.
+
+    Non-finite input: when the Frobenius norm of ``a`` is not finite in f64 (a NaN or an infinite entry, or entries above
+    ~1e154 whose squares overflow) EVERY returned eigenvalue is NaN and the eigenvectors mean nothing.  The sweeps are
+    bounded by ``max_sweeps`` on the host, so the call returns (both forms stop rotating once the NaN has spread over the
+    matrix; an infinite norm makes every rotation threshold infinite, so no rotation is applied at all and the diagonal
+    left behind is not a spectrum) or raises ``RuniaHipError`` like any matrix that has not settled."""
     require_gpu()
     assert a.is_cuda and a.dtype == torch.float64 and a.dim() == 2 and a.shape[0] == a.shape[1]
     n = a.shape[0]
@@ -1768,7 +1774,8 @@ def eigh(a: torch.Tensor, max_sweeps: int = 30, blocked: bool = True, info: Opti
         info["sweeps"] = info.get("sweeps", 0) + sweep_no
         info["rotations"] = info.get("rotations", 0) + done
         info["calls"] = info.get("calls", 0) + 1
-    w = torch.diagonal(work)[:n].clone()
+    anorm = ws[off:off + 8].view(torch.float64)  # what the init kernel left: the norm that scales the rotation threshold
+    w = torch.where(torch.isfinite(anorm), torch.diagonal(work)[:n], torch.full_like(anorm, float("nan")))
     # ascending order: n scalars, ranked on the host (the convergence loop has synchronised already; no device sort)
     order = torch.from_numpy(np.argsort(w.cpu().numpy(), kind="stable")).to(a.device)
     return w[order], v[:n, :n][:, order].contiguous()

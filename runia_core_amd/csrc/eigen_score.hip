@@ -17,8 +17,10 @@
 //            rows <= tile columns): one tile per thread, 16 accumulators, 8 LDS reads per 16 products; R = 256 / Q
 //            threads share a tile and take every R-th column.  The R partials are summed in slot order into G (half 1).
 //   Jacobi   cyclic two-sided Jacobi on G in LDS without eigenvectors: round-robin (circle method) ordering of m/2 disjoint
-//            pairs per step, the rotation rule and threshold of jacobi_angles_kernel (eigh.hip), 2 x 2 block updates of
-//            the upper block triangle mirrored (G stays exactly symmetric).  The "rotated" flag lives in LDS; the loop
+//            pairs per step, the rotation rule of jacobi_angles_kernel (eigh.hip) with the threshold
+//            max(1e-19 |G|_F, 1e-17 sqrt|g_pp g_qq|) on every pair (only eigenvalues are wanted here: an entry left under
+//            the absolute floor enters them squared; eigh.hip, which returns eigenvectors, keeps the floor for noise-level
+//            diagonals only), 2 x 2 block updates of the upper block triangle mirrored (G stays exactly symmetric).  The "rotated" flag lives in LDS; the loop
 //            stops after the first sweep that applies no rotation, and a group still rotating after 30 sweeps gets NaN.
 //   Score    diag(G) clamped at 0, ranked in descending order, the top min(k, hidden) summed in that order in f64.
 #include <math.h>

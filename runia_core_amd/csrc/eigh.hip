@@ -40,7 +40,16 @@ __global__ __launch_bounds__(256) void jacobi_angles_kernel(const double* __rest
   bool rotated = false;
   if (q < n) {
     const double app = A[(int64_t)p * n + p], aqq = A[(int64_t)q * n + q], apq = A[(int64_t)p * n + q];
-    const double thr = fmax(1e-19 * anorm[0], 1e-17 * sqrt(fabs(app * aqq)));
+    // rotate when |apq| > 1e-17 sqrt|app aqq|: the relative rule, under which the small eigenvalues of a graded matrix AND
+    // their eigenvectors come out accurately (Demmel & Veselic 1992).  The absolute floor 1e-19 |A|_F joins it only where a
+    // diagonal entry of the pair is itself rounding noise (<= 1e-16 |A|_F: zero diagonals, the null space of a
+    // rank-deficient matrix - below the pinvh cut-off n eps max|w|), where the relative rule alone would chase noise.
+    // With the floor on EVERY pair the eigenvalues stayed accurate (an off-diagonal entry enters them squared) but two
+    // small eigenvalues w kept a residue of 1e-19 |A|_F between them, their vectors mixed by that over their gap, and
+    // U diag(1/w) U^T of a matrix scaled over ten decades was off by 3e-10 where 1e-14 is to be had.
+    const double rel = 1e-17 * sqrt(fabs(app * aqq));
+    const bool noise = fmin(fabs(app), fabs(aqq)) <= 1e-16 * anorm[0];
+    const double thr = noise ? fmax(1e-19 * anorm[0], rel) : rel;
     if (fabs(apq) > thr) {
       const double theta = (aqq - app) / (2.0 * apq);
       const double tt = (theta >= 0.0 ? 1.0 : -1.0) / (fabs(theta) + sqrt(theta * theta + 1.0));

@@ -378,6 +378,26 @@ int runia_proj_sq_score_trap_f64(const double* h, const double* packed_m, const 
  *     gives the same bits on every call and every rank.  r_out may be m and c_out may be c (in place). */
 int runia_qr_trapezoid_f64(const double* m, const double* c, double* r_out, double* c_out, int64_t r, int64_t D,
                            runia_stream_t stream);
+/*     Balanced block order (csrc/trap_order.hpp).  Block b of an upper-trapezoidal R (rows 32 b .. 32 b + 31) is zero for
+ *     k < 32 b, and a row permutation of [R | c] does not change || R h + c ||.  With the column split, the 32-column
+ *     groups 0-3 of a 256-column block of R^T belong to one workgroup and 4-7 to another; in the natural order they skip
+ *     6 and 22 of their 64 chunk-waves.  The balanced order gives the first R blocks {0, 3, 5, 6} and the second
+ *     {1, 2, 4, 7} of every FULL 256-row block (14 each); a last partial block and every r < 256 keep the natural order.
+ *     runia_trap_balance_order: src_rows [r] (HOST memory) = the row of R that stands at each row of the balanced matrix.
+ *     runia_trap_balance_rows_f64: r_out [r, D] and c_out [r] = r_in and c_in with their rows in that order (device,
+ *     not in place: r_out != r_in, c_out != c_in).
+ *     runia_proj_sq_*_btrap_f64: runia_proj_sq_*_trap_f64 for such a matrix (the caller's promise, r <= D): every column
+ *     group starts at the first live chunk of the block it holds.  Same packed layout, same summation order, same bits
+ *     as the plain calls on that matrix for finite h; NaN and infinity as documented for the trap calls (R block 0 stays
+ *     in column tile 0, which skips nothing). */
+int runia_trap_balance_order(int64_t* src_rows, int64_t r);
+int runia_trap_balance_rows_f64(const double* r_in, const double* c_in, double* r_out, double* c_out, int64_t r, int64_t D,
+                                runia_stream_t stream);
+int runia_proj_sq_accumulate_btrap_f64(const double* h, const double* packed_m, const double* c, double* score,
+                                       int64_t N, int64_t D, int64_t r, runia_stream_t stream);
+int runia_proj_sq_score_btrap_f64(const double* h, const double* packed_m, const double* c, double* score,
+                                  void* workspace, size_t workspace_bytes, int64_t N, int64_t D, int64_t r,
+                                  runia_stream_t stream);
 
 /* ---- f1  setup-time covariance on the device (SURVEY 8f "next #1") ----------- *
  * Replaces np.cov(X.T, bias=1) inside sklearn EmpiricalCovariance.fit

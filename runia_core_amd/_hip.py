@@ -192,7 +192,14 @@ _SIGNATURES = {
     "runia_proj_sq_workspace_bytes": (c_size_t, [c_int64]),
     "runia_proj_sq_accumulate_f64": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_int64, c_int64, c_void_p]),
     "runia_proj_sq_accumulate_trap_f64": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_int64, c_int64, c_void_p]),
+    "runia_proj_sq_accumulate_btrap_f64": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_int64, c_int64, c_void_p]),
     "runia_qr_trapezoid_f64": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_int64, c_void_p]),
+    "runia_trap_balance_order": (c_int, [c_void_p, c_int64]),
+    "runia_trap_balance_rows_f64": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_int64, c_void_p]),
+    "runia_proj_sq_score_btrap_f64": (
+        c_int,
+        [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, c_int64, c_int64, c_int64, c_void_p],
+    ),
     "runia_proj_sq_score_f64": (
         c_int,
         [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, c_int64, c_int64, c_int64, c_void_p],
@@ -1443,18 +1450,25 @@ def mc_entropy(x: torch.Tensor, rand: Union[torch.Tensor, CounterDraws, None], n
     return (h, z) if want_samples else h
 
 
+def _proj_sq_entry(kind: str, trap: bool, balanced: bool) -> str:
+    if balanced and not trap:
+        raise ValueError("balanced=True describes an upper-trapezoidal matrix: pass trap=True with it")
+    return f"runia_proj_sq_{kind}_{'btrap_' if balanced else 'trap_' if trap else ''}f64"
+
+
 @_device_guard()
 def proj_sq_accumulate(h: torch.Tensor, packed_m: torch.Tensor, c: torch.Tensor, r: int, out: torch.Tensor,
-                       trap: bool = False) -> torch.Tensor:
+                       trap: bool = False, balanced: bool = False) -> torch.Tensor:
     """``out`` [N] f64 += -|| M h + c ||^2 where ``out`` was zeroed earlier on the stream (``mc_entropy(zero_fill=out)``):
     the score of ``proj_sq_score`` bit for bit, without its workspace and combine launch.  ``trap``: M is upper-trapezoidal
-    (``qr_trapezoid``); the launch skips its zero blocks (``runia_proj_sq_accumulate_trap_f64``)."""
+    (``qr_trapezoid``); the launch skips its zero blocks (``runia_proj_sq_accumulate_trap_f64``).  ``balanced`` (with
+    ``trap``): its row blocks stand in the balanced order (``trap_balance_rows``; ``runia_proj_sq_accumulate_btrap_f64``)."""
     require_gpu()
     assert h.is_cuda and h.dtype == torch.float64 and h.dim() == 2
     h = h.contiguous()
     nrow, d = h.shape
     assert out.is_cuda and out.dtype == torch.float64 and out.shape == (nrow,) and out.is_contiguous()
-    launch("runia_proj_sq_accumulate_trap_f64" if trap else "runia_proj_sq_accumulate_f64", h.data_ptr(), packed_m.data_ptr(),
+    launch(_proj_sq_entry("accumulate", trap, balanced), h.data_ptr(), packed_m.data_ptr(),
            c.data_ptr(), out.data_ptr(), nrow, d, int(r))
     return out
 
@@ -1655,9 +1669,10 @@ def proj_norm(x: torch.Tensor, u: torch.Tensor, packed_ns: torch.Tensor, n: int)
 
 @_device_guard()
 def proj_sq_score(h: torch.Tensor, packed_m: torch.Tensor, c: torch.Tensor, r: int, out: Optional[torch.Tensor] = None,
-                  trap: bool = False) -> torch.Tensor:
+                  trap: bool = False, balanced: bool = False) -> torch.Tensor:
     """score [N] = -|| M h + c ||^2 (h [N, D] f64, packed_m = pack(M.T), c [r]).  ``trap``: M is upper-trapezoidal
-    (``qr_trapezoid``); the launch skips its zero blocks (``runia_proj_sq_score_trap_f64``)."""
+    (``qr_trapezoid``); the launch skips its zero blocks (``runia_proj_sq_score_trap_f64``).  ``balanced`` (with ``trap``):
+    its row blocks stand in the balanced order (``trap_balance_rows``; ``runia_proj_sq_score_btrap_f64``)."""
     lib = load_library()
     require_gpu()
     assert h.is_cuda and h.dtype == torch.float64 and h.dim() == 2
@@ -1666,7 +1681,7 @@ def proj_sq_score(h: torch.Tensor, packed_m: torch.Tensor, c: torch.Tensor, r: i
     s = torch.empty((nrow,), dtype=torch.float64, device=h.device) if out is None else out
     ws_bytes = int(lib.runia_proj_sq_workspace_bytes(nrow))
     ws = torch.empty(max(ws_bytes, 16), dtype=torch.uint8, device=h.device)
-    launch("runia_proj_sq_score_trap_f64" if trap else "runia_proj_sq_score_f64", h.data_ptr(), packed_m.data_ptr(),
+    launch(_proj_sq_entry("score", trap, balanced), h.data_ptr(), packed_m.data_ptr(),
            c.data_ptr(), s.data_ptr(), ws.data_ptr(), ws_bytes, nrow, d, int(r))
     return s
 
@@ -1683,6 +1698,28 @@ def qr_trapezoid(m: torch.Tensor, c: torch.Tensor) -> Tuple[torch.Tensor, torch.
     r_out, c_out = torch.empty_like(m), torch.empty_like(c)
     launch("runia_qr_trapezoid_f64", m.data_ptr(), c.data_ptr(), r_out.data_ptr(), c_out.data_ptr(), m.shape[0], m.shape[1])
     return r_out, c_out
+
+
+def trap_balance_order(r: int) -> np.ndarray:
+    """[r] int64: the row of an upper-trapezoidal R that stands at each row of its balanced form (``runia_trap_balance_order``,
+    the rule of ``csrc/trap_order.hpp``; identity for r < 256 and on a last partial block of 256).  Host only: no GPU needed."""
+    idx = np.empty(int(r), dtype=np.int64)
+    call("runia_trap_balance_order", idx.ctypes.data, int(r))
+    return idx
+
+
+@_device_guard()
+def trap_balance_rows(m: torch.Tensor, c: torch.Tensor) -> Tuple[torch.Tensor, torch.Tensor]:
+    """m [r, D] f64 upper-trapezoidal (``qr_trapezoid``), c [r] -> both with their rows in the balanced order of
+    ``trap_balance_order`` (``runia_trap_balance_rows_f64``): the same score, and the two column halves of K2' skip equally
+    many chunks (``proj_sq_score(..., trap=True, balanced=True)``)."""
+    require_gpu()
+    assert m.is_cuda and m.dtype == torch.float64 and m.dim() == 2 and m.shape[0] <= m.shape[1]
+    assert c.is_cuda and c.dtype == torch.float64 and c.shape == (m.shape[0],)
+    m, c = m.contiguous(), c.contiguous()
+    m_out, c_out = torch.empty_like(m), torch.empty_like(c)
+    launch("runia_trap_balance_rows_f64", m.data_ptr(), c.data_ptr(), m_out.data_ptr(), c_out.data_ptr(), m.shape[0], m.shape[1])
+    return m_out, c_out
 
 
 def _ood_metrics_buffers(n: int, device):

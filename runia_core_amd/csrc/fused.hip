@@ -24,6 +24,7 @@
 #include "mfma_f64_tile.hpp"
 #include "philox.hpp"
 #include "div_consts.hpp"
+#include "trap_order.hpp"
 
 namespace {
 
@@ -740,11 +741,28 @@ struct ProjSqArgs {
 #ifndef K2_TRAP_ROT
 #define K2_TRAP_ROT 2  // 0 none, 1 tile & 3, 2 id bits 4-5 + 8-9, 3 id bits 8-9
 #endif
+//   TRAP = 3  TRAP = 2 for an R whose 32-row blocks stand in the balanced order of trap_order.hpp (runia_trap_balance_rows_f64;
+//             the runia_proj_sq_*_btrap_f64 entry points): a group's first live chunk comes from trap_balanced_first_k
+//             instead of its own position, the workgroup's start is the minimum over its groups.  Both column halves then
+//             keep 50 of their 64 chunk-waves (58 and 42 under TRAP = 2) - and both run 16 and 15 chunk STEPS (row DMA +
+//             barrier, paid by all four waves) where TRAP = 2 runs 16 and 12.  Measured, the steps are what costs: 40.15 us
+//             against 40.33 (TRAP = 2) and 41.56 (dense) at N = 10 000, nothing in the step.  Not the pipeline's default.
+// K2_TRAP_HALFMAP: which of the two ids of a row tile (i, i ^ 8: same XCD, one dispatch round apart) takes which column
+// half.  0: half = bit 0 of j = id >> 3, the index of the workgroup inside its XCD.  A dispatcher that deals an XCD's
+// workgroups round-robin over its 32 CUs then gives every CU workgroups of ONE half only, and under TRAP the half-0 CUs
+// (16 chunk steps, 58 of 64 chunk-waves) set the kernel's time while the half-1 CUs (12 steps, 42 of 64) idle at the end.
+// 1: the halves swap in every second group of 32 dispatch rounds, so a CU holds both kinds.  Measured at N = 10 000,
+// accumulate form, trap / dense: 0.970 with 0, 0.889 with 1 (36.97 us); dense itself does not move (41.56 / 41.61).  The
+// mapping only changes which workgroup computes which half - never a bit of the result - and where workgroups land is the
+// dispatcher's business: on another placement it is worth what 0 is worth.  (profiles/README.md, "K2' column halves per CU")
+#ifndef K2_TRAP_HALFMAP
+#define K2_TRAP_HALFMAP 1
+#endif
 template <int RT, int NCT, bool ACCUMULATE, bool SPLIT, bool DMA, int TRAP = 0>
 __global__ __launch_bounds__(256, (RT == 1 && NCT <= 2) ? (DMA ? K2_WAVES_DMA : K2_WAVES) : 1) void proj_sq_kernel(ProjSqArgs g) {
 #if defined(__HIP_DEVICE_COMPILE__)  // (the host pass only needs the launch stub; the body uses device-only buffer builtins)
   constexpr int BM = 16 * RT;
-  constexpr bool WAVE_SKIP = TRAP == 2 && DMA && RT == 1;
+  constexpr bool WAVE_SKIP = TRAP >= 2 && DMA && RT == 1;
   __shared__ double lds_a[DMA ? 1 : 2 * BM * APITCH];
   // the DMA form's two chunk buffers are separate objects: the compiler orders a ds_read behind every LDS DMA it cannot
   // prove disjoint (one array: `s_waitcnt vmcnt(0)` in front of each chunk's first read, the DMA of the NEXT chunk included)
@@ -765,7 +783,8 @@ __global__ __launch_bounds__(256, (RT == 1 && NCT <= 2) ? (DMA ? K2_WAVES_DMA : 
   int half = 0;
   if constexpr (SPLIT) {
     tile = (int64_t)(blockIdx.x >> 4) * 8 + (blockIdx.x & 7);
-    half = (blockIdx.x >> 3) & 1;
+    const unsigned j = blockIdx.x >> 3;
+    half = (int)((K2_TRAP_HALFMAP ? j ^ (j >> 5) : j) & 1);
     if (tile * BM >= g.N) return;  // padding of the last group of 8 tiles (uniform over the workgroup)
   }
   const int64_t r0 = tile * BM;
@@ -788,7 +807,23 @@ __global__ __launch_bounds__(256, (RT == 1 && NCT <= 2) ? (DMA ? K2_WAVES_DMA : 
     const int64_t ctbase = cb * 16 + (int64_t)half * (4 * NCT) + grp * NCT;
     // first chunk with a non-zero column of this workgroup (ch0) and of this wave (ws); never past the last chunk, so the
     // row DMA stays inside the rows (all-zero padding columns beyond r just run that one chunk)
-    const int64_t wg_chunk = (cb * 16 + (int64_t)half * (4 * NCT)) * 16 / KC, wave_chunk = ctbase * 16 / KC;
+    int64_t wg_chunk = (cb * 16 + (int64_t)half * (4 * NCT)) * 16 / KC, wave_chunk = ctbase * 16 / KC;
+    if constexpr (TRAP == 3) {
+      // balanced order: the 2 * NCT groups of this workgroup and the NG groups of this wave, by 32-column position
+      const int64_t wg_pos = (cb * 16 + (int64_t)half * (4 * NCT)) / 2, wave_pos = ctbase / 2;
+      wg_chunk = trap_balanced_first_k(wg_pos, g.r) / KC;
+#pragma unroll
+      for (int i = 1; i < 2 * NCT; ++i) {
+        const int64_t f = trap_balanced_first_k(wg_pos + i, g.r) / KC;
+        wg_chunk = f < wg_chunk ? f : wg_chunk;
+      }
+      wave_chunk = trap_balanced_first_k(wave_pos, g.r) / KC;
+#pragma unroll
+      for (int q = 1; q < NG; ++q) {
+        const int64_t f = trap_balanced_first_k(wave_pos + q, g.r) / KC;
+        wave_chunk = f < wave_chunk ? f : wave_chunk;
+      }
+    }
     const int ch0 = TRAP ? (int)(wg_chunk < nchunks - 1 ? wg_chunk : nchunks - 1) : 0;
     [[maybe_unused]] const int ws = WAVE_SKIP ? (int)(wave_chunk < nchunks - 1 ? wave_chunk : nchunks - 1) : ch0;
     d4 acc[RT][NCT];
@@ -1288,14 +1323,16 @@ static bool proj_sq_dma_ok(int64_t D, int64_t r) {
   return K2_DMA && D % KC == 0 && D < (1 << 23) && packed_elems(D, r) < ((int64_t)1 << 29);
 }
 static bool proj_sq_one_round(unsigned grid) { return (int64_t)grid <= (int64_t)K2_WAVES_DMA * runia_cu_count(); }
-template <bool TRAP, int RT, int NCT, bool ACCUMULATE, bool SPLIT>
+// TRAP here: 0 dense, 1 upper-trapezoidal M (kernel form K2_TRAP_FORM), 2 its row blocks in balanced order (kernel form 3)
+template <int TRAP, int RT, int NCT, bool ACCUMULATE, bool SPLIT>
 static void launch_proj_sq(unsigned grid, hipStream_t s, const ProjSqArgs& g, bool dma) {
   const bool use_dma = dma && (RT > 1 || proj_sq_one_round(grid));
   if constexpr (TRAP) {
+    constexpr int FORM = TRAP == 2 ? 3 : K2_TRAP_FORM;
     // The register-staged 16-row forms stay dense (same bits): with the start chunk to carry they spill 12-20 bytes of scratch at
     // the 96 of 5 waves per SIMD and measured 85.3 us against 83.5 us dense at N = 20 000.
-    if (use_dma) proj_sq_kernel<RT, NCT, ACCUMULATE, SPLIT, true, K2_TRAP_FORM><<<grid, 256, 0, s>>>(g);
-    else if constexpr (RT > 1) proj_sq_kernel<RT, NCT, ACCUMULATE, SPLIT, false, K2_TRAP_FORM><<<grid, 256, 0, s>>>(g);
+    if (use_dma) proj_sq_kernel<RT, NCT, ACCUMULATE, SPLIT, true, FORM><<<grid, 256, 0, s>>>(g);
+    else if constexpr (RT > 1) proj_sq_kernel<RT, NCT, ACCUMULATE, SPLIT, false, FORM><<<grid, 256, 0, s>>>(g);
     else proj_sq_kernel<RT, NCT, ACCUMULATE, SPLIT, false><<<grid, 256, 0, s>>>(g);
   } else {
     if (use_dma) proj_sq_kernel<RT, NCT, ACCUMULATE, SPLIT, true><<<grid, 256, 0, s>>>(g);
@@ -1312,7 +1349,7 @@ static bool proj_sq_large_tiles(int64_t N, int64_t cus) {
   return tiles32 >= 2 * cus && 100 * tiles32 >= 93 * rounds * cus;
 }
 
-template <bool TRAP>
+template <int TRAP>
 static int proj_sq_accumulate(const double* h, const double* packed_m, const double* c, double* score, int64_t N, int64_t D,
                               int64_t r, runia_stream_t stream) {
   if (N < 0 || D <= 0 || r <= 0) return RUNIA_E_INVALID;
@@ -1332,18 +1369,24 @@ static int proj_sq_accumulate(const double* h, const double* packed_m, const dou
 
 extern "C" int runia_proj_sq_accumulate_f64(const double* h, const double* packed_m, const double* c, double* score,
                                             int64_t N, int64_t D, int64_t r, runia_stream_t stream) {
-  return proj_sq_accumulate<false>(h, packed_m, c, score, N, D, r, stream);
+  return proj_sq_accumulate<0>(h, packed_m, c, score, N, D, r, stream);
 }
 // the caller promises M[j][k] = 0 for k < j (r <= D): same bits as the plain entry point on that matrix, fewer chunks
 extern "C" int runia_proj_sq_accumulate_trap_f64(const double* h, const double* packed_m, const double* c, double* score,
                                                  int64_t N, int64_t D, int64_t r, runia_stream_t stream) {
   if (r > D) return RUNIA_E_INVALID;
-  return proj_sq_accumulate<true>(h, packed_m, c, score, N, D, r, stream);
+  return proj_sq_accumulate<1>(h, packed_m, c, score, N, D, r, stream);
+}
+// the caller promises that M with its 32-row blocks in the balanced order of trap_order.hpp (runia_trap_balance_rows_f64)
+extern "C" int runia_proj_sq_accumulate_btrap_f64(const double* h, const double* packed_m, const double* c, double* score,
+                                                  int64_t N, int64_t D, int64_t r, runia_stream_t stream) {
+  if (r > D) return RUNIA_E_INVALID;
+  return proj_sq_accumulate<2>(h, packed_m, c, score, N, D, r, stream);
 }
 
 extern "C" size_t runia_proj_sq_workspace_bytes(int64_t N) { return N > 0 ? (size_t)N * 2 * sizeof(double) : 0; }
 
-template <bool TRAP>
+template <int TRAP>
 static int proj_sq_score(const double* h, const double* packed_m, const double* c, double* score, void* workspace,
                          size_t workspace_bytes, int64_t N, int64_t D, int64_t r, runia_stream_t stream) {
   if (N < 0 || D <= 0 || r <= 0) return RUNIA_E_INVALID;
@@ -1372,11 +1415,17 @@ static int proj_sq_score(const double* h, const double* packed_m, const double* 
 extern "C" int runia_proj_sq_score_f64(const double* h, const double* packed_m, const double* c, double* score,
                                        void* workspace, size_t workspace_bytes, int64_t N, int64_t D, int64_t r,
                                        runia_stream_t stream) {
-  return proj_sq_score<false>(h, packed_m, c, score, workspace, workspace_bytes, N, D, r, stream);
+  return proj_sq_score<0>(h, packed_m, c, score, workspace, workspace_bytes, N, D, r, stream);
 }
 extern "C" int runia_proj_sq_score_trap_f64(const double* h, const double* packed_m, const double* c, double* score,
                                             void* workspace, size_t workspace_bytes, int64_t N, int64_t D, int64_t r,
                                             runia_stream_t stream) {
   if (r > D) return RUNIA_E_INVALID;
-  return proj_sq_score<true>(h, packed_m, c, score, workspace, workspace_bytes, N, D, r, stream);
+  return proj_sq_score<1>(h, packed_m, c, score, workspace, workspace_bytes, N, D, r, stream);
+}
+extern "C" int runia_proj_sq_score_btrap_f64(const double* h, const double* packed_m, const double* c, double* score,
+                                             void* workspace, size_t workspace_bytes, int64_t N, int64_t D, int64_t r,
+                                             runia_stream_t stream) {
+  if (r > D) return RUNIA_E_INVALID;
+  return proj_sq_score<2>(h, packed_m, c, score, workspace, workspace_bytes, N, D, r, stream);
 }

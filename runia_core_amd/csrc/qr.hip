@@ -6,6 +6,7 @@
 // every sum below is added up in an order this code fixes - no atomics, nothing that follows the grid - because every rank
 // of a sharded job has to fold the same fitted arrays into the same bits.
 #include "common.hpp"
+#include "trap_order.hpp"
 
 namespace {
 
@@ -89,6 +90,17 @@ __global__ __launch_bounds__(kQrThreads) void qr_trapezoid_kernel(const double* 
   }
 }
 
+// Row gather into the balanced block order (trap_order.hpp): output row i, in 32-column group i / 32 of pack(out^T),
+// is the row of `a` with the same offset in the R block that group holds; c goes with its rows.  One workgroup per row.
+__global__ __launch_bounds__(256) void trap_balance_rows_kernel(const double* __restrict__ a, const double* __restrict__ q,
+                                                                 double* __restrict__ a_out, double* __restrict__ q_out,
+                                                                 int64_t r, int64_t D) {
+  const int64_t i = blockIdx.x;
+  const int64_t src = trap_balanced_block(i / 32, r) * 32 + i % 32;
+  for (int64_t k = threadIdx.x; k < D; k += 256) a_out[i * D + k] = a[src * D + k];
+  if (threadIdx.x == 0) q_out[i] = q[src];
+}
+
 }  // namespace
 
 extern "C" int runia_qr_trapezoid_f64(const double* m, const double* c, double* r_out, double* c_out, int64_t r, int64_t D,
@@ -96,5 +108,19 @@ extern "C" int runia_qr_trapezoid_f64(const double* m, const double* c, double* 
   if (r <= 0 || D <= 0 || r > D || r > kQrMaxRows) return RUNIA_E_INVALID;
   if (!m || !c || !r_out || !c_out) return RUNIA_E_INVALID;
   qr_trapezoid_kernel<<<1, kQrThreads, 0, as_stream(stream)>>>(m, c, r_out, c_out, r, D);
+  return runia_check_launch();
+}
+
+extern "C" int runia_trap_balance_order(int64_t* src_rows, int64_t r) {
+  if (r <= 0 || !src_rows) return RUNIA_E_INVALID;
+  for (int64_t i = 0; i < r; ++i) src_rows[i] = trap_balanced_block(i / 32, r) * 32 + i % 32;
+  return RUNIA_OK;
+}
+
+extern "C" int runia_trap_balance_rows_f64(const double* r_in, const double* c_in, double* r_out, double* c_out, int64_t r,
+                                           int64_t D, runia_stream_t stream) {
+  if (r <= 0 || D <= 0 || r > D || r > 0x7fffffff) return RUNIA_E_INVALID;
+  if (!r_in || !c_in || !r_out || !c_out || r_in == r_out || c_in == c_out) return RUNIA_E_INVALID;
+  trap_balance_rows_kernel<<<(unsigned)r, 256, 0, as_stream(stream)>>>(r_in, c_in, r_out, c_out, r, D);
   return runia_check_launch();
 }

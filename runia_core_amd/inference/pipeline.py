@@ -77,6 +77,10 @@ class LaREMPipeline:
         # that the contraction skips R's zero blocks (`runia_proj_sq_*_trap_f64`: 0.78 of the matrix work at 256 x 512).
         # Set False for the dense launch on the unrotated M.
         self.fold_trapezoid = True
+        # Put R's 32-row blocks into the balanced order (`runia_trap_balance_rows_f64`, r >= 256) so that the two column
+        # halves of the split K2' skip equally many chunks (`runia_proj_sq_*_btrap_f64`).  Off: it measured no faster than the
+        # natural order (every workgroup then runs all 16 chunk steps); kept reachable for comparison.
+        self.fold_balanced = False
         self._folded = None
         self._folded_fp = None
         self._k0 = None  # side stream + two table buffers of prepare_draws
@@ -155,12 +159,13 @@ class LaREMPipeline:
         return pp._mean(torch.float64), st["packed_p"]
 
     def _folded_state(self):
-        """(packed M^T, c, r, trapezoidal) with M = W diag(1/scale) C, c = W (-bias/scale - mu), precision = W^T W - rotated
-        to upper-trapezoidal form when ``fold_trapezoid`` is set; None when the precision matrix is not positive
-        semi-definite to rounding (then the two-stage kernel is used)."""
+        """(packed M^T, c, r, trapezoidal, balanced) with M = W diag(1/scale) C, c = W (-bias/scale - mu), precision = W^T W -
+        rotated to upper-trapezoidal form when ``fold_trapezoid`` is set, its row blocks then in the balanced order when
+        ``fold_balanced`` is set and r >= 256; None when the precision matrix is not positive semi-definite to rounding
+        (then the two-stage kernel is used)."""
         pp = self.postprocessor
         fp = (_hip.array_fingerprint(pp.precision), _hip.array_fingerprint(pp.feats_mean),
-              None if self.pca is None else id(self.pca), bool(self.fold_trapezoid))
+              None if self.pca is None else id(self.pca), bool(self.fold_trapezoid), bool(self.fold_balanced))
         if self._folded is None or self._folded_fp != fp:
             self._folded_fp = fp
             # Everything below runs on the device with the library's own kernels (Jacobi eigen-solver, f64 products) and
@@ -189,7 +194,10 @@ class LaREMPipeline:
             trap = bool(self.fold_trapezoid) and m.shape[0] <= m.shape[1]
             if trap:
                 m, c = _hip.qr_trapezoid(m.contiguous(), c)
-            self._folded = (_hip.pack_weights(m.t().contiguous()), c, int(m.shape[0]), trap)
+            balanced = trap and bool(self.fold_balanced) and m.shape[0] >= 256
+            if balanced:
+                m, c = _hip.trap_balance_rows(m, c)
+            self._folded = (_hip.pack_weights(m.t().contiguous()), c, int(m.shape[0]), trap, balanced)
         return self._folded or None
 
     def score_entropies(self, h: Tensor) -> Tensor:
@@ -203,7 +211,7 @@ class LaREMPipeline:
             if self.fold_weights:
                 folded = self._folded_state()
                 if folded is not None:
-                    return _hip.proj_sq_score(h, *folded[:3], trap=folded[3])
+                    return _hip.proj_sq_score(h, *folded[:3], trap=folded[3], balanced=folded[4])
             if self.pca is not None:
                 if h.shape[1] != self.pca.n_features:
                     raise ValueError(f"X has {h.shape[1]} features, but PCA is expecting {self.pca.n_features} features as input.")
@@ -217,7 +225,7 @@ class LaREMPipeline:
         """LaREM score of entropy rows ``h`` written into ``out`` (folded single contraction or two-stage K2)."""
         folded = self._folded_state() if self.fold_weights else None
         if folded is not None:
-            _hip.proj_sq_score(h, *folded[:3], out=out, trap=folded[3])
+            _hip.proj_sq_score(h, *folded[:3], out=out, trap=folded[3], balanced=folded[4])
         elif self.pca is not None:
             _hip.pca_md_score(h, self.pca.packed_ct, self.pca.bias, self.pca.scale, mean, packed_p,
                               self.pca.n_components, out=out)
@@ -255,7 +263,7 @@ class LaREMPipeline:
                 # workspace, no combine launch (bit-identical to the store form)
                 scores = torch.empty((n,), dtype=torch.float64, device=latents.device)
                 h = self.entropy_from_latents(latents, rand, k1_events, zero_fill=scores, prepared=prepared)
-                return _hip.proj_sq_accumulate(h, *folded[:3], out=scores, trap=folded[3])
+                return _hip.proj_sq_accumulate(h, *folded[:3], out=scores, trap=folded[3], balanced=folded[4])
             return self.score_entropies(self.entropy_from_latents(latents, rand, k1_events if fused else None,
                                                                   prepared=prepared))
         latents = latents.contiguous()

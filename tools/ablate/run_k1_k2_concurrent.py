@@ -27,7 +27,7 @@ out_s = torch.empty(n, dtype=torch.float64, device="cuda")
 def chain_k1():
     for _ in range(R1): _hip.mc_entropy(x, None, n_mc, 0.5, 2, 5, table=table, out=out_h)
 def chain_k2():
-    for _ in range(R2): _hip.proj_sq_score(h_b, *folded[:3], out=out_s, trap=folded[3])
+    for _ in range(R2): _hip.proj_sq_score(h_b, *folded[:3], out=out_s, trap=folded[3], balanced=folded[4])
 
 def graph_of(fn, stream):
     with torch.cuda.stream(stream):

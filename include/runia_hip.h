@@ -1001,6 +1001,42 @@ int runia_conformal_sets_wide(const void* table, int dtype, int64_t n_steps, int
                               int method, float beta, float lam, int k_reg, float qhat, int32_t* size, int32_t* members,
                               uint8_t* covered, runia_stream_t stream);
 
+/* ---- Bootstrap replicates of the OoD metrics (bootstrap.hip; evaluation/bootstrap.py) ------------------------ *
+ * Poisson bootstrap: in replicate b, row r of the score table (InD rows 0 .. n_ind - 1, OoD rows n_ind .. n - 1) is present
+ * w(b, id(r)) times, id(r) = r or group_of_row[r] (cluster bootstrap; the caller keeps InD and OoD group ids apart):
+ *   blk  = philox4x32_10(counter = (id, b >> 2, 0, 0x626f6f74), key = (seed.lo, seed.hi)),  word = component b & 3 of blk,
+ *   w    = number of k in 0 .. 12 with T_k <= word,  T_k = floor(2^32 e^-1 sum_{j<=k} 1/j!)       (Poisson(1), at most 13)
+ * - a pure function of (seed, b, id): methods scored on the same rows see the same resample, and replicates may be computed in
+ * any chunking.
+ * runia_boot_keys_f32/_f64: keys int64 [n_ind + n_ood], ascending signed order = descending order of the score as the metrics
+ *   step sees it (sigmoid in the scores' dtype if any score lies outside [0, 1] or is NaN; f64 key; equal keys = a tie).
+ *   any_outside: one device word, set to whether the sigmoid was applied.  n_ind, n_ood >= 1, n < 2^31.
+ * runia_boot_metrics: sorted_keys [n] ascending with sorted_rows [n] int32 the row each key belongs to (a permutation of
+ *   0 .. n - 1), group_of_row [n] int32 or NULL.  out f64 [n_boot, 3] = (AUROC, FPR@95, AUPR) of the replicates
+ *   first_replicate .. first_replicate + n_boot - 1, one curve point per run of equal keys, TP / FP = cumulative InD / OoD
+ *   weight, P / N their totals:
+ *     AUROC  = sum_g (FP_g - FP_g-1)(TP_g + TP_g-1) / (2 P N), the sum in unsigned 64-bit integers;
+ *     FPR@95 = FP_g / N at the first run with 20 TP_g >= 19 P (integers);
+ *     AUPR   = sum_g ((TP_g - TP_g-1) / P)(prec_g + prec_g-1) / 2, prec = TP / (TP + FP), 1 where TP + FP = 0; f64, fixed order;
+ *   P = 0 or N = 0: three NaN.  The same bits from call to call and for any split of a replicate range into calls.
+ *   RUNIA_E_INVALID (before anything else is looked at) unless 1 <= n_ind < n < 2^31 and n_ind * (n - n_ind) < 2^55 (the bound of
+ *   the integer sum: 13^2 * 2 * n_ind * n_ood < 2^64), n_boot >= 1, first_replicate >= 0, first_replicate + n_boot <= 2^31.
+ *   workspace: runia_boot_workspace_bytes(n, n_boot) bytes, 8-byte aligned, uninitialised.
+ * runia_boot_tile_rows: rows of a tile of the walk (test sizes are derived from it).
+ * runia_boot_weight_of_word_host: the weight of one 32-bit random word (host; pins the threshold table).
+ * runia_boot_weights_host: HOST pointers, no GPU touched: out u8 [n_boot, n], out[r * n + i] = w(first_replicate + r, ids[i]). */
+int runia_boot_tile_rows(void);
+int runia_boot_keys_f32(const float* ind_scores, int64_t n_ind, const float* ood_scores, int64_t n_ood, int64_t* keys,
+                        unsigned* any_outside, runia_stream_t stream);
+int runia_boot_keys_f64(const double* ind_scores, int64_t n_ind, const double* ood_scores, int64_t n_ood, int64_t* keys,
+                        unsigned* any_outside, runia_stream_t stream);
+size_t runia_boot_workspace_bytes(int64_t n, int64_t n_boot);
+int runia_boot_metrics(const int64_t* sorted_keys, const int32_t* sorted_rows, int64_t n, int64_t n_ind,
+                       const int32_t* group_of_row, uint64_t seed, int64_t first_replicate, int64_t n_boot, double* out,
+                       void* workspace, size_t workspace_bytes, runia_stream_t stream);
+int runia_boot_weight_of_word_host(uint32_t word);
+int runia_boot_weights_host(uint64_t seed, int64_t first_replicate, int64_t n_boot, const int32_t* ids, int64_t n, uint8_t* out);
+
 #ifdef __cplusplus
 }
 #endif

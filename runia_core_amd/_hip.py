@@ -321,6 +321,15 @@ _SIGNATURES = {
     "runia_conformal_sets_wide": (
         c_int, [c_void_p, c_int, c_int64, c_int64, c_int64, c_void_p, c_int, c_int64, c_int, c_int64, c_void_p, c_int, c_float,
                 c_float, c_int, c_float, c_void_p, c_void_p, c_void_p, c_void_p]),
+    "runia_boot_tile_rows": (c_int, []),
+    "runia_boot_keys_f32": (c_int, [c_void_p, c_int64, c_void_p, c_int64, c_void_p, c_void_p, c_void_p]),
+    "runia_boot_keys_f64": (c_int, [c_void_p, c_int64, c_void_p, c_int64, c_void_p, c_void_p, c_void_p]),
+    "runia_boot_workspace_bytes": (c_size_t, [c_int64, c_int64]),
+    "runia_boot_metrics": (
+        c_int, [c_void_p, c_void_p, c_int64, c_int64, c_void_p, c_uint64, c_int64, c_int64, c_void_p, c_void_p, c_size_t,
+                c_void_p]),
+    "runia_boot_weight_of_word_host": (c_int, [ctypes.c_uint32]),
+    "runia_boot_weights_host": (c_int, [c_uint64, c_int64, c_int64, c_void_p, c_int64, c_void_p]),
 }
 
 
@@ -1764,6 +1773,81 @@ def ood_clf_curve(ind_scores: torch.Tensor, ood_scores: torch.Tensor):
     m = int(n_points.item())
     host = to_host(curve[:, :m].contiguous()).astype(np.int64)
     return out, host[0], host[1]
+
+
+def boot_tile_rows() -> int:
+    """Rows of one tile of the bootstrap walk (``runia_boot_tile_rows``; a host query)."""
+    return query("runia_boot_tile_rows")
+
+
+def boot_weights_host(seed: int, first_replicate: int, n_boot: int, ids) -> np.ndarray:
+    """The Poisson(1) bootstrap weights ``[n_boot, len(ids)]`` uint8 of the replicates ``first_replicate ...`` for the row or
+    group ids ``ids`` (``runia_boot_weights_host``): plain host code over the kernel's weight function, no GPU touched."""
+    ids = np.ascontiguousarray(np.asarray(ids, dtype=np.int64).astype(np.int32))
+    out = np.empty((int(n_boot), ids.size), dtype=np.uint8)
+    call("runia_boot_weights_host", int(seed) & (2**64 - 1), int(first_replicate), int(n_boot), ids.ctypes.data, ids.size,
+         out.ctypes.data)
+    return out
+
+
+class BootOrder(NamedTuple):
+    """A score table ordered for :func:`boot_metrics`: ``keys`` int64 [n] ascending (= descending score), ``rows`` int32 [n] the
+    row of every key (InD rows first), ``n_ind``, and ``squashed`` [1] (device) - whether the scores went through the sigmoid."""
+
+    keys: torch.Tensor
+    rows: torch.Tensor
+    n_ind: int
+    squashed: torch.Tensor
+
+
+@_device_guard()
+def boot_order(ind_scores: torch.Tensor, ood_scores: torch.Tensor) -> BootOrder:
+    """Device scores (both f32 or both f64) -> their :class:`BootOrder`: the metrics step's keys (``runia_boot_keys_*``) and one
+    stable device sort of them - once per method, whatever the number of replicates."""
+    require_gpu()
+    if not (isinstance(ind_scores, torch.Tensor) and isinstance(ood_scores, torch.Tensor) and ind_scores.is_cuda and ood_scores.is_cuda):
+        raise RuniaHipError("boot_order: scores must be device tensors")
+    if ind_scores.dtype != ood_scores.dtype or ind_scores.dtype not in (torch.float32, torch.float64):
+        raise RuniaHipError("boot_order: scores must both be float32 or both float64")
+    a, b = ind_scores.reshape(-1).contiguous(), ood_scores.reshape(-1).contiguous()
+    if a.numel() < 1 or b.numel() < 1:
+        raise RuniaHipError("boot_order: n_ind >= 1 and n_ood >= 1 are required")
+    n = a.numel() + b.numel()
+    keys = torch.empty(n, dtype=torch.int64, device=a.device)
+    flag = torch.empty(1, dtype=torch.int32, device=a.device)
+    launch("runia_boot_keys_f64" if a.dtype == torch.float64 else "runia_boot_keys_f32", a.data_ptr(), a.numel(), b.data_ptr(),
+           b.numel(), keys.data_ptr(), flag.data_ptr())
+    skeys, order = torch.sort(keys, stable=True)
+    return BootOrder(skeys, order.to(torch.int32), a.numel(), flag)
+
+
+@_device_guard()
+def boot_metrics(order: BootOrder, n_boot: int, seed: int = 0, first_replicate: int = 0,
+                 group_of_row: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """``(AUROC, FPR@95, AUPR)`` of the Poisson-bootstrap replicates ``first_replicate .. first_replicate + n_boot - 1`` of an
+    ordered score table -> device tensor ``[n_boot, 3]`` f64 (``runia_boot_metrics``; NaN rows: replicates in which one side drew
+    nothing).  ``group_of_row`` int32 ``[n]``: resample by group.  Stream-ordered, no synchronisation."""
+    require_gpu()
+    keys, rows, n_ind = order.keys, order.rows, int(order.n_ind)
+    n, n_boot, first_replicate = keys.numel(), int(n_boot), int(first_replicate)
+    if not (keys.is_cuda and rows.is_cuda and keys.dtype == torch.int64 and rows.dtype == torch.int32):
+        raise RuniaHipError("boot_metrics: keys must be int64 and rows int32 device tensors")
+    if not (keys.is_contiguous() and rows.is_contiguous() and rows.numel() == n and rows.device == keys.device):
+        raise RuniaHipError("boot_metrics: keys and rows must be contiguous, of one length, on one device")
+    if n_ind < 1 or n - n_ind < 1:
+        raise RuniaHipError("boot_metrics: n_ind >= 1 and n_ood >= 1 are required")
+    if n_boot < 1 or first_replicate < 0:
+        raise RuniaHipError("boot_metrics: n_boot >= 1 and first_replicate >= 0 are required")
+    if group_of_row is not None:
+        if not (group_of_row.is_cuda and group_of_row.dtype == torch.int32 and group_of_row.is_contiguous()
+                and group_of_row.numel() == n and group_of_row.device == keys.device):
+            raise RuniaHipError("boot_metrics: group_of_row must be a contiguous int32 device tensor with one entry per row")
+    out = torch.empty((n_boot, 3), dtype=torch.float64, device=keys.device)
+    ws_bytes = query("runia_boot_workspace_bytes", n, n_boot)
+    ws = workspace(ws_bytes, keys.device)
+    launch("runia_boot_metrics", keys.data_ptr(), rows.data_ptr(), n, n_ind, _ptr(group_of_row), int(seed) & (2**64 - 1),
+           first_replicate, n_boot, out.data_ptr(), ws.data_ptr(), ws_bytes)
+    return out
 
 
 @_device_guard()

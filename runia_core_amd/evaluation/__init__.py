@@ -33,3 +33,11 @@ from .conformal import (  # noqa: F401
     conformal_quantile,
     conformal_scores,
 )
+from .bootstrap import (  # noqa: F401
+    BootstrapResult,
+    ComparisonResult,
+    bootstrap_ood_metrics,
+    bootstrap_p_value,
+    bootstrap_results_table,
+    compare_ood_methods,
+)

@@ -26,6 +26,8 @@
 // Loads are 4 pixels wide when w has unit stride and every other stride and base is a multiple of four elements; a group cut
 // by the end of a row, an odd base or any other stride pattern (channels_last: sc == 1; crops) is read element by element
 // through the strides, in place.  Rows that follow one another in memory (sh == W * sw) are treated as one long row.
+#include <cfloat>
+
 #include "common.hpp"
 #include "elem.hpp"
 
@@ -215,8 +217,16 @@ __device__ __forceinline__ void two_pass_item(const PixArgs& a, const Stats<PPL,
     const typename T::elem* p = sample_base<T>(a, g, s) + off;
     float m[PPL], sum[PPL];
     load_px<T, PPL, VEC>(p, a.sw, nv, m);
+    // A row that opens with -inf (masked classes) starts from (-FLT_MAX, 0) instead of (-inf, 1): a second -inf would give
+    // d = -inf - (-inf) = NaN below and leave the NaN in the sum.  From there every -inf adds 0, the first finite logit
+    // rescales the sum by exp(-huge) = 0, and only a row of nothing but -inf ends with sum == 0: it gets its -inf back.
+    // Rows that open with a finite logit run as before, bit for bit.
 #pragma unroll
-    for (int j = 0; j < PPL; ++j) sum[j] = 1.f;
+    for (int j = 0; j < PPL; ++j) {
+      const bool masked = m[j] == -INFINITY;
+      sum[j] = masked ? 0.f : 1.f;
+      m[j] = masked ? -FLT_MAX : m[j];
+    }
 #pragma unroll 4
     for (int c = 1; c < C; ++c) {
       float x[PPL];
@@ -229,6 +239,8 @@ __device__ __forceinline__ void two_pass_item(const PixArgs& a, const Stats<PPL,
         m[j] = fmaxf(m[j], x[j]);
       }
     }
+#pragma unroll
+    for (int j = 0; j < PPL; ++j) m[j] = sum[j] == 0.f ? -INFINITY : m[j];
 #pragma unroll
     for (int j = 0; j < PPL; ++j) {
       if (LDS || j < nv) {

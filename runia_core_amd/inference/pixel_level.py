@@ -94,7 +94,9 @@ def pixel_uncertainty_maps(logits: Union[Tensor, Sequence[Tensor]], mcd_nro_samp
 
     ``0 * log 0`` is NaN, exactly as the reference's torch expression and ``get_predictive_uncertainty_score`` here give
     it: a pixel with a class more than ~104 below the maximum of one sample (its f32 softmax underflows to 0) has NaN
-    ``pred_h`` and ``mi``.
+    ``pred_h`` and ``mi``.  A class masked to ``-inf`` has probability 0: ``msp``, ``energy``, ``max_logit``, ``label`` and
+    ``mean_probs`` stay finite (whichever classes are masked, as long as one is left), ``mi`` is NaN at that pixel, and
+    ``pred_h`` where the class is masked in every sample.
 
     One launch; results are run-to-run bit identical.  Raises ``ValueError`` for unknown scores and mismatching inputs,
     ``RuniaHipError`` without a GPU."""

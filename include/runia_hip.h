@@ -31,6 +31,7 @@ extern "C" {
 #define RUNIA_E_LAUNCH (-2)    /* hipGetLastError() after the launch was not hipSuccess */
 #define RUNIA_E_NODEVICE (-3)  /* no HIP device visible */
 #define RUNIA_E_WORKSPACE (-4) /* caller-provided workspace too small */
+#define RUNIA_E_STEPCAP (-5)   /* a bounded device loop ran into its step cap (runia_cc_label); the output is not valid */
 
 typedef void* runia_stream_t;
 
@@ -1036,6 +1037,49 @@ int runia_boot_metrics(const int64_t* sorted_keys, const int32_t* sorted_rows, i
                        void* workspace, size_t workspace_bytes, runia_stream_t stream);
 int runia_boot_weight_of_word_host(uint32_t word);
 int runia_boot_weights_host(uint64_t seed, int64_t first_replicate, int64_t n_boot, const int32_t* ids, int64_t n, uint8_t* out);
+
+/* ---- Connected components and component-level overlap statistics (components.hip; evaluation/components.py) - *
+ * runia_cc_label: labels int32 [N, H, W] of N binary images: 0 = background, 1 .. counts[n] in raster order of each
+ *   component's first pixel (the per-image contract of scipy.ndimage.label), connectivity 4 or 8; counts int32 [N].  Nothing
+ *   links across the left / right edge of a row or from one image to the next.  The images come from ONE of
+ *     mask   uint8 [N, H, W] (non-zero = set), score == NULL, T == 1, N = G;   valid uint8 [N, H, W] or NULL;
+ *     score  f32 [G, H, W] with thresholds f32 [T], mask == NULL: N = G * T and image n = t * G + g is score[g] > thresholds[t]
+ *            (less != 0: <; a NaN score is never set), compared inside the tile kernel;   valid uint8 [G, H, W] or NULL.
+ *   A pixel whose valid byte is 0 is background.  The same labels from call to call (canonical numbering; integer atomics only).
+ *   Tiles of RUNIA_CC_TILE_H x RUNIA_CC_TILE_W pixels (runia_cc_tile_h / _w report what the library was built with).
+ *   N * H * W < 2^31 (parents are int32), RUNIA_E_INVALID otherwise.  N == 0 or H * W == 0: 0, nothing launched.
+ *   workspace: runia_cc_label_workspace_bytes(N, H, W) bytes, 16-byte aligned, uninitialised (RUNIA_E_WORKSPACE if short).
+ *   Unlike the other entry points this one waits for the stream before it returns: every device loop carries a step cap
+ *   derived from the image size, and a cap that was hit comes back as RUNIA_E_STEPCAP.
+ * runia_cc_overlap: from gt_labels int32 [G, H, W] and pred_labels int32 [G * T, H, W] (image t * G + g) with the exclusive
+ *   prefix sums of their counts, gt_offsets int32 [G] and pred_offsets [G * T] (component k of image g is row gt_offsets[g] + k - 1):
+ *     stats != 0: ADDS to  gt_size [Kg] (NULL: skipped)  the pixels of every GT component (counted for t = 0 only),
+ *                          gt_inter [T, Kg]              its pixels that are predicted under threshold t,
+ *                          pred_size / pred_inter [Kp]   the pixels of every predicted component / those inside any GT component;
+ *     n_keys (one uint64, ADDED to): the number of candidate pairs - pixels set in both whose left neighbour in the row holds
+ *       another (k, k_hat) pair; keys != NULL: the candidates, int64 ((t * Kg + k) << 32 | k_hat) (rows as above), in arrival
+ *       order, at most key_capacity of them (sort + unique gives the distinct pairs).
+ *   Either label image may be NULL (sizes of the other one only; no keys).  Integer atomics: order-independent.
+ *   G * T * H * W < 2^31, T * Kg < 2^31; RUNIA_E_INVALID otherwise.  No workspace.
+ * runia_cc_relabel: labels[n, p] = map[offsets[n] + labels[n, p] - 1] where labels[n, p] > 0, in place. */
+#ifndef RUNIA_CC_TILE_H
+#define RUNIA_CC_TILE_H 32
+#endif
+#ifndef RUNIA_CC_TILE_W
+#define RUNIA_CC_TILE_W 32
+#endif
+int runia_cc_tile_h(void);
+int runia_cc_tile_w(void);
+size_t runia_cc_label_workspace_bytes(int64_t N, int64_t H, int64_t W);
+int runia_cc_label(const uint8_t* mask, const float* score, const float* thresholds, int64_t T, int less, const uint8_t* valid,
+                   int64_t G, int64_t H, int64_t W, int connectivity, int32_t* labels, int32_t* counts, void* workspace,
+                   size_t workspace_bytes, runia_stream_t stream);
+int runia_cc_overlap(const int32_t* gt_labels, const int32_t* gt_offsets, const int32_t* pred_labels, const int32_t* pred_offsets,
+                     int64_t G, int64_t T, int64_t H, int64_t W, int64_t Kg, int32_t* gt_size, int32_t* gt_inter,
+                     int32_t* pred_size, int32_t* pred_inter, int64_t* keys, int64_t key_capacity, uint64_t* n_keys, int stats,
+                     runia_stream_t stream);
+int runia_cc_relabel(int32_t* labels, const int32_t* offsets, const int32_t* map, int64_t N, int64_t H, int64_t W,
+                     runia_stream_t stream);
 
 #ifdef __cplusplus
 }

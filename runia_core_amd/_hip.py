@@ -330,6 +330,16 @@ _SIGNATURES = {
                 c_void_p]),
     "runia_boot_weight_of_word_host": (c_int, [ctypes.c_uint32]),
     "runia_boot_weights_host": (c_int, [c_uint64, c_int64, c_int64, c_void_p, c_int64, c_void_p]),
+    "runia_cc_tile_h": (c_int, []),
+    "runia_cc_tile_w": (c_int, []),
+    "runia_cc_label_workspace_bytes": (c_size_t, [c_int64, c_int64, c_int64]),
+    "runia_cc_label": (
+        c_int, [c_void_p, c_void_p, c_void_p, c_int64, c_int, c_void_p, c_int64, c_int64, c_int64, c_int, c_void_p, c_void_p,
+                c_void_p, c_size_t, c_void_p]),
+    "runia_cc_overlap": (
+        c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_int64, c_int64, c_int64, c_int64, c_void_p, c_void_p,
+                c_void_p, c_void_p, c_void_p, c_int64, c_void_p, c_int, c_void_p]),
+    "runia_cc_relabel": (c_int, [c_void_p, c_void_p, c_void_p, c_int64, c_int64, c_int64, c_void_p]),
 }
 
 
@@ -1651,6 +1661,122 @@ def pixel_map_reduce(score_map: torch.Tensor, valid: Optional[torch.Tensor] = No
     cnt = torch.empty((g,), dtype=torch.int64, device=m.device)
     launch("runia_pixel_map_reduce_f32", m.data_ptr(), _ptr(v), g, hw, mean.data_ptr(), mx.data_ptr(), cnt.data_ptr())
     return mean, mx, cnt
+
+
+# (RUNIA_CC_TILE_H, RUNIA_CC_TILE_W) of include/runia_hip.h: the tile one workgroup of the labelling kernel owns
+CC_TILE = (32, 32)
+CC_MAX_PIXELS = (1 << 31) - 1  # N * H * W of one labelling call (parents are int32)
+
+
+def _cc_bytes(t: Optional[torch.Tensor], shape, name: str) -> Optional[torch.Tensor]:
+    if t is None:
+        return None
+    assert t.is_cuda and tuple(t.shape) == tuple(shape) and t.dtype in (torch.bool, torch.uint8), name
+    return t.contiguous().view(torch.uint8)
+
+
+@_device_guard()
+def cc_label(mask: Optional[torch.Tensor] = None, score: Optional[torch.Tensor] = None,
+             thresholds: Optional[torch.Tensor] = None, less: bool = False, valid: Optional[torch.Tensor] = None,
+             connectivity: int = 8):
+    """Connected components of N binary images (``runia_cc_label``) -> (labels int32 (N, H, W), counts int32 (N,)): 0 is
+    background, 1 .. counts[n] in raster order of each component's first pixel.  Either ``mask`` (N, H, W) bool / uint8, or
+    ``score`` (G, H, W) f32 with ``thresholds`` (T,) f32: N = T * G, image t * G + g is ``score[g] > thresholds[t]``
+    (``less``: <).  ``valid`` has the shape of the mask / of the score map.  Waits for the stream (the step caps' error word)."""
+    assert (mask is None) != (score is None) and connectivity in (4, 8)
+    src = mask if score is None else score
+    assert src.is_cuda and src.dim() == 3
+    require_gpu()
+    g, h, w = (int(v) for v in src.shape)
+    dev = src.device
+    if score is None:
+        m, sc, thr, t = _cc_bytes(mask, src.shape, "mask"), None, None, 1
+    else:
+        assert score.dtype == torch.float32 and thresholds.is_cuda and thresholds.dtype == torch.float32 and thresholds.dim() == 1
+        m, sc, thr, t = None, score.contiguous(), thresholds.contiguous(), int(thresholds.shape[0])
+    v = _cc_bytes(valid, src.shape, "valid")
+    n = g * t
+    assert n * h * w <= CC_MAX_PIXELS, "N * H * W of one labelling call must stay below 2^31"
+    labels = torch.empty((n, h, w), dtype=torch.int32, device=dev)
+    counts = torch.zeros((n,), dtype=torch.int32, device=dev)
+    if n == 0 or h * w == 0:
+        return labels, counts
+    need = query("runia_cc_label_workspace_bytes", n, h, w)
+    ws = workspace(need, dev)
+    launch("runia_cc_label", _ptr(m), _ptr(sc), _ptr(thr), t, int(bool(less)), _ptr(v), g, h, w, int(connectivity),
+           labels.data_ptr(), counts.data_ptr(), ws.data_ptr(), need)
+    return labels, counts
+
+
+def _cc_offsets(counts: torch.Tensor) -> torch.Tensor:
+    return (torch.cumsum(counts, 0, dtype=torch.int64) - counts).to(torch.int32)
+
+
+@_device_guard()
+def cc_overlap(gt_labels: Optional[torch.Tensor], gt_counts: Optional[torch.Tensor], pred_labels: Optional[torch.Tensor],
+               pred_counts: Optional[torch.Tensor], want_gt_size: bool = True):
+    """Integer overlap tables of label images (``runia_cc_overlap``): ``gt_labels`` (G, H, W) and ``pred_labels`` (T * G, H, W)
+    (image t * G + g) with their per-image ``counts``; either may be None.  Returns a dict of device tensors: ``gt_size``
+    (Kg,), ``gt_inter`` (T, Kg), ``pred_size`` / ``pred_inter`` (Kp,) int32, ``pairs`` int64 (P,) - the distinct
+    ``(t * Kg + k) << 32 | k_hat`` keys, ascending - and the offsets.  Components are rows in image order."""
+    first = gt_labels if gt_labels is not None else pred_labels
+    assert first is not None and first.is_cuda and first.dim() == 3 and first.dtype == torch.int32
+    require_gpu()
+    dev = first.device
+    h, w = int(first.shape[1]), int(first.shape[2])
+    out = {}
+    g = int(gt_labels.shape[0]) if gt_labels is not None else int(pred_labels.shape[0])
+    t = 0
+    kg = kp = 0
+    goff = poff = None
+    if gt_labels is not None:
+        assert gt_labels.is_contiguous() and gt_counts.dtype == torch.int32 and gt_counts.shape == (g,)
+        goff = _cc_offsets(gt_counts)
+    if pred_labels is not None:
+        assert pred_labels.is_contiguous() and pred_labels.dtype == torch.int32 and tuple(pred_labels.shape[1:]) == (h, w)
+        t = int(pred_labels.shape[0]) // g if g else 0
+        assert pred_labels.shape[0] == g * t and pred_counts.dtype == torch.int32 and pred_counts.shape == (g * t,)
+        poff = _cc_offsets(pred_counts)
+    totals = [int(c.sum().item()) if c is not None else 0 for c in (gt_counts, pred_counts)]  # (one wait for both tables' sizes)
+    kg, kp = totals
+
+    def table(rows, wanted=True):  # (never an empty allocation: its null address would read as "not wanted")
+        return torch.zeros((max(rows, 1),), dtype=torch.int32, device=dev) if wanted else None
+
+    gt_size_b = table(kg, gt_labels is not None and want_gt_size)
+    gt_inter_b = table(t * kg, gt_labels is not None)
+    pred_size_b, pred_inter_b = table(kp, pred_labels is not None), table(kp, pred_labels is not None)
+    n_keys = torch.zeros((1,), dtype=torch.int64, device=dev)
+    pairs = torch.empty((0,), dtype=torch.int64, device=dev)
+    if g > 0 and h * w > 0 and (gt_labels is None or pred_labels is None or t > 0):
+        args = (_ptr(gt_labels), _ptr(goff), _ptr(pred_labels), _ptr(poff), g, t, h, w, kg)
+        launch("runia_cc_overlap", *args, _ptr(gt_size_b), _ptr(gt_inter_b), _ptr(pred_size_b), _ptr(pred_inter_b), None, 0,
+               n_keys.data_ptr(), 1)
+        cand = int(n_keys.item()) if (gt_labels is not None and pred_labels is not None) else 0
+        if cand:
+            keys = torch.empty((cand,), dtype=torch.int64, device=dev)
+            n_keys.zero_()
+            launch("runia_cc_overlap", *args, None, None, None, None, keys.data_ptr(), cand, n_keys.data_ptr(), 0)
+            pairs = torch.unique(keys)  # sorted: the result does not depend on the order the candidates arrived in
+    gt_size = None if gt_size_b is None else gt_size_b[:kg]
+    gt_inter = None if gt_inter_b is None else gt_inter_b[:t * kg].view(t, kg)
+    pred_size = None if pred_size_b is None else pred_size_b[:kp]
+    pred_inter = None if pred_inter_b is None else pred_inter_b[:kp]
+    out.update(gt_size=gt_size, gt_inter=gt_inter, pred_size=pred_size, pred_inter=pred_inter, pairs=pairs, gt_offsets=goff,
+               pred_offsets=poff, n_gt=kg, n_pred=kp)
+    return out
+
+
+@_device_guard()
+def cc_relabel(labels: torch.Tensor, offsets: torch.Tensor, table: torch.Tensor) -> torch.Tensor:
+    """``labels[n, p] = table[offsets[n] + labels[n, p] - 1]`` where the label is positive, in place (``runia_cc_relabel``)."""
+    assert labels.is_cuda and labels.dtype == torch.int32 and labels.dim() == 3 and labels.is_contiguous()
+    assert offsets.dtype == torch.int32 and table.dtype == torch.int32 and offsets.shape == (labels.shape[0],)
+    require_gpu()
+    n, h, w = (int(v) for v in labels.shape)
+    if n and h * w and table.numel():
+        launch("runia_cc_relabel", labels.data_ptr(), offsets.contiguous().data_ptr(), table.contiguous().data_ptr(), n, h, w)
+    return labels
 
 
 @_device_guard()

@@ -10,6 +10,7 @@ extern "C" const char* runia_error_string(int code) {
     case RUNIA_E_LAUNCH: return "HIP kernel launch failed";
     case RUNIA_E_NODEVICE: return "no HIP device visible";
     case RUNIA_E_WORKSPACE: return "workspace too small";
+    case RUNIA_E_STEPCAP: return "a bounded device loop ran into its step cap";
     default: return "unknown error";
   }
 }

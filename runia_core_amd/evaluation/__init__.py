@@ -41,3 +41,4 @@ from .bootstrap import (  # noqa: F401
     bootstrap_results_table,
     compare_ood_methods,
 )
+from .components import ComponentResult, component_metrics, label_components  # noqa: F401

@@ -762,7 +762,8 @@ def kde_score_kernel(train: np.ndarray, x: np.ndarray, bandwidth: float, kernel:
     """sklearn.neighbors.KernelDensity(kernel=..., bandwidth=h).fit(train).score_samples(x) by its definition (what
     DetectorKDE(kernel=...) forwards to, inference/postprocessors.py:78-128; kernels and normalisation of
     sklearn/neighbors/_binary_tree.pxi.tp): log(sum_i K(|x - t_i| / h)) - log N + log_norm(kernel, d, h); compact kernels
-    are 0 from |x - t| >= h on."""
+    are 0 from |x - t| >= h on (a plain sum of values in [0, 1]); the exponential kernel, which has no such edge, is summed
+    in log space."""
     from scipy.special import gammaln
 
     train, x = np.asarray(train, np.float64), np.asarray(x, np.float64)
@@ -779,7 +780,8 @@ def kde_score_kernel(train: np.ndarray, x: np.ndarray, bandwidth: float, kernel:
         elif kernel == "epanechnikov":
             kv, factor = np.where(dist < h, 1.0 - (dist * dist) / (h * h), 0.0), log_vn(d) + np.log(2.0 / (d + 2.0))
         elif kernel == "exponential":
-            kv, factor = np.exp(-dist / h), log_sn(d - 1) + gammaln(d)
+            # in log space, as sklearn accumulates: a query further than ~745 h from every training row has a finite score
+            return logsumexp(-dist / h, axis=1) - np.log(m) - (log_sn(d - 1) + gammaln(d)) - d * np.log(h)
         elif kernel == "linear":
             kv, factor = np.where(dist < h, 1.0 - dist / h, 0.0), log_vn(d) - np.log(d + 1.0)
         elif kernel == "cosine":

@@ -192,20 +192,28 @@ __device__ __forceinline__ void kde_online_update(const double (&val)[NCT], doub
   double gmax = -kInfD();
 #pragma unroll
   for (int c = 0; c < NCT; ++c) gmax = fmax(gmax, val[c]);
-  if (gmax > -kInfD()) {
+  if (gmax > -kInfD()) {  // (a NaN among the values makes `part`, and with it the running sum, NaN)
     const double mnew = fmax(rowmax, gmax);
     double part = 0.0;
 #pragma unroll
     for (int c = 0; c < NCT; ++c) part += exp(val[c] - mnew);
     rowdot = rowdot * exp(rowmax - mnew) + part;
     rowmax = mnew;
+  } else {  // nothing but -inf (columns beyond M) and NaN (a NaN training row): fmax dropped the NaNs, their sum keeps them
+    double all = val[0];
+#pragma unroll
+    for (int c = 1; c < NCT; ++c) all += val[c];
+    if (all != all) rowdot = all;
   }
 }
-// the (max, sum) pairs of the 16 lanes that share a row, then of the four waves -> out[row]
+// the (max, sum) pairs of the 16 lanes that share a row, then of the four waves -> out[row].  Non-finite rows: a NaN sum
+// (NaN training row) stays NaN through both merges; a query whose squared norm is NaN scores NaN and one whose norm is
+// infinite -inf (infinitely far from every training row) - its products are NaN either way, so the norm decides.
 template <int RT>
 __device__ __forceinline__ void kde_merge_store(double (&rowdot)[RT][4], double (&rowmax)[RT][4], double (*lds_m)[16 * RT],
                                                 double (*lds_s)[16 * RT], int wave, int li, int lg, int tid, int64_t r0,
-                                                int64_t N, double addc, double* __restrict__ out) {
+                                                int64_t N, double addc, const double* __restrict__ rown,
+                                                double* __restrict__ out) {
   constexpr int BM = 16 * RT;
 #pragma unroll
   for (int a = 0; a < RT; ++a)
@@ -216,7 +224,7 @@ __device__ __forceinline__ void kde_merge_store(double (&rowdot)[RT][4], double 
       for (int o = 1; o < 16; o <<= 1) {
         const double m2 = shfl_xor_f64(m, o), s2 = shfl_xor_f64(sm, o);
         const double mn = fmax(m, m2);
-        sm = (mn > -kInfD()) ? sm * exp(m - mn) + s2 * exp(m2 - mn) : 0.0;
+        sm = (mn > -kInfD()) ? sm * exp(m - mn) + s2 * exp(m2 - mn) : sm + s2;  // (no column yet: 0 + 0, or a NaN)
         m = mn;
       }
       if (li == 0) {
@@ -232,8 +240,9 @@ __device__ __forceinline__ void kde_merge_store(double (&rowdot)[RT][4], double 
       double gs = 0.0;
 #pragma unroll
       for (int w = 0; w < 4; ++w)
-        if (lds_s[w][tid] > 0.0) gs += lds_s[w][tid] * exp(lds_m[w][tid] - gm);
-      out[row] = log(gs) + gm + addc;
+        if (lds_s[w][tid] != 0.0) gs += lds_s[w][tid] * exp(lds_m[w][tid] - gm);  // (!= 0: a NaN sum is kept)
+      const double rn = rown[row];
+      out[row] = (rn != rn) ? rn : (rn == kInfD()) ? -kInfD() : log(gs) + gm + addc;
     }
   }
 }
@@ -525,7 +534,7 @@ __global__ __launch_bounds__(256) void gemm_rows_kernel(GemmArgs g) {
   }
   if constexpr (EPI == EPI_KDE) {
     if (g.kde_vals) return;
-    kde_merge_store<RT>(rowdot, rowmax, lds_part, lds_part2, wave, li, lg, tid, r0, g.N, g.addc, g.out);
+    kde_merge_store<RT>(rowdot, rowmax, lds_part, lds_part2, wave, li, lg, tid, r0, g.N, g.addc, g.rown, g.out);
   }
   if constexpr (EPI == EPI_ROWDOT || EPI == EPI_ROWNORM) {
     if ((EPI == EPI_ROWDOT || EPI == EPI_ROWNORM) && g.md_vals) return;
@@ -998,8 +1007,8 @@ extern "C" int runia_row_sqnorm_f64(const double* x, double* out, int64_t N, int
 
 // Second half of the column-split KDE launch: per 16-row tile, the blocks' values in block order through the same
 // update and the same merges as the fused kernel (thread t of the tile's workgroup is thread t of the fused kernel).
-__global__ __launch_bounds__(256) void kde_replay_kernel(const double* __restrict__ vals, double* __restrict__ out,
-                                                          int64_t N, int64_t nb, double addc) {
+__global__ __launch_bounds__(256) void kde_replay_kernel(const double* __restrict__ vals, const double* __restrict__ rown,
+                                                          double* __restrict__ out, int64_t N, int64_t nb, double addc) {
   constexpr int RT = 1, NCT = 4;
   __shared__ double lds_m[4][16 * RT], lds_s[4][16 * RT];
   const int tid = threadIdx.x, lane = tid & 63;
@@ -1023,7 +1032,7 @@ __global__ __launch_bounds__(256) void kde_replay_kernel(const double* __restric
         kde_online_update<NCT>(val, rowmax[a][r], rowdot[a][r]);
       }
   }
-  kde_merge_store<RT>(rowdot, rowmax, lds_m, lds_s, wave, li, lg, tid, r0, N, addc, out);
+  kde_merge_store<RT>(rowdot, rowmax, lds_m, lds_s, wave, li, lg, tid, r0, N, addc, rown, out);
 }
 
 // query norms, + the values of the column-split launch when the batch has fewer 16-row tiles than the chip has compute units
@@ -1073,7 +1082,7 @@ extern "C" int runia_kde_score_packed_f64(const double* packed_train_t, const do
     const int64_t tiles = (N + 15) / 16, nb = n_padded(M) / BN;
     g.kde_vals = reinterpret_cast<double*>(reinterpret_cast<char*>(workspace) + (((size_t)N * sizeof(double)) + 255) / 256 * 256);
     gemm_rows_kernel<double, double, EPI_KDE, 1, 4><<<(unsigned)(tiles * nb), 256, 0, s>>>(g);
-    kde_replay_kernel<<<(unsigned)tiles, 256, 0, s>>>(g.kde_vals, score, N, nb, g.addc);
+    kde_replay_kernel<<<(unsigned)tiles, 256, 0, s>>>(g.kde_vals, g.rown, score, N, nb, g.addc);
     return runia_check_launch();
   }
   if (const int64_t rest = kde_last_round_rows(N, M); rest > 0 && workspace_bytes >= runia_kde_workspace_bytes(N, M)) {
@@ -1086,7 +1095,7 @@ extern "C" int runia_kde_score_packed_f64(const double* packed_train_t, const do
       GemmArgs t = gemm_rows_from<double>(g, head, 1);
       t.kde_vals = reinterpret_cast<double*>(reinterpret_cast<char*>(workspace) + (((size_t)N * sizeof(double)) + 255) / 256 * 256);
       gemm_rows_kernel<double, double, EPI_KDE, 1, 4><<<(unsigned)(tiles * nb), 256, 0, s>>>(t);
-      kde_replay_kernel<<<(unsigned)tiles, 256, 0, s>>>(t.kde_vals, t.out, rest, nb, g.addc);
+      kde_replay_kernel<<<(unsigned)tiles, 256, 0, s>>>(t.kde_vals, t.rown, t.out, rest, nb, g.addc);
       return runia_check_launch();
     }
   }

@@ -2,6 +2,8 @@
 //     (reference inference/postprocessors.py:78-128).  The matrix-core form of the Gaussian kernel (|x|^2 + |t|^2 - 2 x.t with an
 //     online logsumexp) lives in gemm_f64.hip; this file keeps the direct f64 kernels: low dimensions, the five non-Gaussian
 //     kernels of sklearn, and the reference for the matrix-core form's tests.
+//     Non-finite rows (sklearn raises on them; INTEGRATION.md, known divergences): a NaN coordinate, in the query or in any
+//     training row, gives a NaN score; an infinite query is infinitely far from every training row and scores -inf.
 #include "common.hpp"
 
 namespace {
@@ -31,8 +33,8 @@ __global__ __launch_bounds__(256) void kde_kernel(const double* __restrict__ tra
       if (v > mx) {
         s = s * exp(mx - v) + 1.0;
         mx = v;
-      } else {
-        s += exp(v - mx);
+      } else if (v != -kInfD()) {  // (-inf: an infinitely far row adds nothing - exp(-inf - mx) is NaN while mx is -inf;
+        s += exp(v - mx);          //  a NaN v lands here and makes the sum NaN)
       }
     }
     if (lane == 0) { wm[wave] = mx; wsum[wave] = s; }
@@ -41,7 +43,7 @@ __global__ __launch_bounds__(256) void kde_kernel(const double* __restrict__ tra
       double gm = fmax(fmax(wm[0], wm[1]), fmax(wm[2], wm[3]));
       double gs = 0.0;
       for (int w = 0; w < 4; ++w)
-        if (wsum[w] > 0.0) gs += wsum[w] * exp(wm[w] - gm);
+        if (wsum[w] != 0.0) gs += wsum[w] * exp(wm[w] - gm);  // (!= 0: a NaN sum is kept)
       score[row] = log(gs) + gm + log_norm;
     }
   }
@@ -49,21 +51,24 @@ __global__ __launch_bounds__(256) void kde_kernel(const double* __restrict__ tra
 
 // The other kernels sklearn's KernelDensity offers (DetectorKDE(kernel=...) forwards any of them, reference
 // inference/postprocessors.py:78-128): tophat, epanechnikov, exponential, linear, cosine - values in [0, 1], so the
-// density is a plain f64 sum over the training rows (one wave per training row, fixed order), then one log.
+// density of the compact ones is a plain f64 sum over the training rows (one wave per training row, fixed order), then
+// one log.  The exponential kernel has no edge: further than ~745 h from every training row its plain sum is empty while
+// the density is not, so it keeps the online (max, sum) pair of kde_kernel, as sklearn accumulates in log space.
 // KIND: 1 tophat [d < h], 2 epanechnikov 1 - d^2 / h^2, 3 exponential exp(-d / h), 4 linear 1 - d / h, 5 cosine
 // cos(pi d / 2 h); compact kernels are 0 from d >= h on (sklearn's strict d < h).  No training row in range: log(0) = -inf.
+// A NaN distance is neither: it is added as it is.
 template <int KIND>
 __global__ __launch_bounds__(256) void kde_other_kernel(const double* __restrict__ train, const double* __restrict__ x,
                                                          double* __restrict__ score, int64_t M, int64_t N, int64_t D, double h,
                                                          double log_norm) {
   extern __shared__ double xs[];  // D doubles
-  __shared__ double wsum[4];
+  __shared__ double wm[4], wsum[4];
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   for (int64_t row = blockIdx.x; row < N; row += gridDim.x) {
     __syncthreads();
     for (int64_t i = tid; i < D; i += 256) xs[i] = x[row * D + i];
     __syncthreads();
-    double s = 0.0;
+    double s = 0.0, mx = -kInfD();  // mx: KIND 3 only
     for (int64_t m = wave; m < M; m += 4) {
       const double* t = train + m * D;
       double acc = 0.0;
@@ -74,17 +79,37 @@ __global__ __launch_bounds__(256) void kde_other_kernel(const double* __restrict
 #pragma unroll
       for (int o = 32; o > 0; o >>= 1) acc += shfl_xor_f64(acc, o);
       const double dist = sqrt(acc);
-      double kv;
-      if (KIND == 1) kv = dist < h ? 1.0 : 0.0;
-      else if (KIND == 2) kv = dist < h ? 1.0 - (dist * dist) / (h * h) : 0.0;
-      else if (KIND == 3) kv = exp(-dist / h);
-      else if (KIND == 4) kv = dist < h ? 1.0 - dist / h : 0.0;
-      else kv = dist < h ? cos(0.5 * M_PI * dist / h) : 0.0;
-      s += kv;
+      if constexpr (KIND == 3) {
+        const double v = -dist / h;
+        if (v > mx) {
+          s = s * exp(mx - v) + 1.0;
+          mx = v;
+        } else if (v != -kInfD()) {  // (as in kde_kernel: -inf adds nothing, NaN makes the sum NaN)
+          s += exp(v - mx);
+        }
+      } else {
+        double kv;
+        if (KIND == 1) kv = dist < h ? 1.0 : 0.0;
+        else if (KIND == 2) kv = dist < h ? 1.0 - (dist * dist) / (h * h) : 0.0;
+        else if (KIND == 4) kv = dist < h ? 1.0 - dist / h : 0.0;
+        else kv = dist < h ? cos(0.5 * M_PI * dist / h) : 0.0;
+        if (dist != dist) kv = dist;  // (NaN < h is false: it would count as out of reach)
+        s += kv;
+      }
     }
-    if (lane == 0) wsum[wave] = s;
+    if (lane == 0) { wm[wave] = mx; wsum[wave] = s; }
     __syncthreads();
-    if (tid == 0) score[row] = log((wsum[0] + wsum[1]) + (wsum[2] + wsum[3])) + log_norm;
+    if (tid == 0) {
+      if constexpr (KIND == 3) {
+        const double gm = fmax(fmax(wm[0], wm[1]), fmax(wm[2], wm[3]));
+        double gs = 0.0;
+        for (int w = 0; w < 4; ++w)
+          if (wsum[w] != 0.0) gs += wsum[w] * exp(wm[w] - gm);
+        score[row] = log(gs) + gm + log_norm;
+      } else {
+        score[row] = log((wsum[0] + wsum[1]) + (wsum[2] + wsum[3])) + log_norm;
+      }
+    }
   }
 }
 
@@ -135,13 +160,18 @@ __global__ __launch_bounds__(64 * NW) void kde_small_kernel(const double* __rest
         v[j] = (r0 + j < rows) ? acc * neg_half_inv_h2 : -kInfD();
         gmax = fmax(gmax, v[j]);
       }
-      if (gmax > -kInfD()) {
+      if (gmax > -kInfD()) {  // (a NaN among the values makes `part`, and with it the running sum, NaN)
         const double mnew = fmax(mx, gmax);
         double part = 0.0;
 #pragma unroll
         for (int j = 0; j < GS; ++j) part += exp(v[j] - mnew);
         sum = sum * exp(mx - mnew) + part;
         mx = mnew;
+      } else {  // nothing but -inf (rows beyond M, an infinite query) and NaN: fmax dropped the NaNs, their sum keeps them
+        double all = v[0];
+#pragma unroll
+        for (int j = 1; j < GS; ++j) all += v[j];
+        if (all != all) sum = all;
       }
     }
   }
@@ -155,7 +185,7 @@ __global__ __launch_bounds__(64 * NW) void kde_small_kernel(const double* __rest
     double gs = 0.0;
 #pragma unroll
     for (int w = 0; w < NW; ++w)
-      if (ps[w][lane] > 0.0) gs += ps[w][lane] * exp(pm[w][lane] - gm);
+      if (ps[w][lane] != 0.0) gs += ps[w][lane] * exp(pm[w][lane] - gm);  // (!= 0: a NaN sum is kept)
     score[qrow] = log(gs) + gm + log_norm;
   }
 }
@@ -210,10 +240,13 @@ static double kde_log_norm(int kind, int64_t D, double h) {
     case 3: factor = logSn(d - 1.0) + lgamma(d); break;
     case 4: factor = logVn(d) - log(d + 1.0); break;
     default: {
+      // an alternating sum that cancels from D ~ 8 on: what is left depends on every rounding, so sklearn's own order -
+      // tmp *= (integer product) * (2 / pi)^2.  (Multiplied by 2 / pi twice, the sum came out twice sklearn's at D = 65.)
+      const double c2 = (2.0 / M_PI) * (2.0 / M_PI);
       double tmp = 2.0 / M_PI;
       for (int64_t k = 1; k < D + 1; k += 2) {
         factor += tmp;
-        tmp *= -(d - (double)k) * (d - (double)k - 1.0) * (2.0 / M_PI) * (2.0 / M_PI);
+        tmp *= -(d - (double)k) * (d - (double)k - 1.0) * c2;
       }
       factor = log(factor) + logSn(d - 1.0);
     }

@@ -1081,6 +1081,55 @@ int runia_cc_overlap(const int32_t* gt_labels, const int32_t* gt_offsets, const 
 int runia_cc_relabel(int32_t* labels, const int32_t* offsets, const int32_t* map, int64_t N, int64_t H, int64_t W,
                      runia_stream_t stream);
 
+/* ---- Selective prediction: risk-coverage curve, AURC, AUGRC, equal-mass bins (selective.hip; evaluation/selective.py) *
+ * A table of n rows, each with a confidence kappa (higher = kept first) and a finite loss l.  Rows are ordered by descending
+ * confidence; -0.0 == +0.0, +-inf are ordinary values, NaN is an error.  A run is a maximal set of equal confidences at the
+ * sorted positions s + 1 .. e (1-based); L_k / S_k: cumulative loss / confidence of the first k sorted rows.  For s < k <= e
+ *     Lbar_k = L_s + (k - s)(L_e - L_s) / (e - s)      (the mean of L_k over the orders of the rows inside the tie; Sbar_k likewise)
+ *     aurc   = (1 / n)   sum_k Lbar_k / k              (without ties: mean(cumsum(l_sorted) / arange(1, n + 1)))
+ *     augrc  = (1 / n^2) sum_k Lbar_k
+ * - nothing depends on the order in which tied rows arrive.
+ * runia_sel_keys_f32/_f64: keys int64 [n], ascending signed order = descending confidence; f32 is widened to f64 exactly (one key
+ *   space), the two zeros share a key.  bad: one device word, set to whether any confidence is NaN.  1 <= n < 2^31.
+ * runia_sel_key_of_f64_host: the same key of one value (host; pins the order).
+ * runia_sel_curve: sorted_keys [n] ascending with sorted_rows [n] int32 the row each key belongs to (a permutation of 0 .. n - 1;
+ *   the pair has the shape of the bootstrap's ordered table), loss [n] f32 (loss_f64 == 0) or f64, read through the rows.  The
+ *   confidences are not an argument: a key is the f64 confidence, one to one (but for the sign of zero), and is turned back
+ *   into it, so the order and the confidence sums cannot disagree and nothing but the loss is gathered.
+ *   record f64 [5] = (n_points, L_n, S_n, aurc, augrc).  run_end / cum_loss / cum_conf: all three NULL, or
+ *   room for n entries each - the compacted curve, one point per run: run_end int32 ascending (= e), cum_loss = L_e and
+ *   cum_conf = S_e f64; n_points: one device int64 (needed with the curve, otherwise optional).
+ *   Every sum is f64 in an order fixed by n alone; no floating-point atomics; the same inputs give the same bits.  Cumulative sums
+ *   of integer-valued losses (the 0/1 error) are exact: every output is then bit-identical under ANY permutation of the input
+ *   rows.  The cost does not depend on the lengths of the runs.
+ *   RUNIA_E_INVALID (before anything else is looked at) unless 1 <= n < 2^31.
+ *   workspace: runia_sel_workspace_bytes(n) bytes, 8-byte aligned, uninitialised (RUNIA_E_WORKSPACE if short).
+ * runia_sel_query: from the compacted curve (device pointers; n_points is read on the device, clamped to n).
+ *   targets int64 [n_targets]: k_c = ceil(c n) of the coverage targets, formed exactly by the caller, 1 <= k_c <= n (clamped);
+ *     risk_at / coverage_at f64 [n_targets] = L_e / e and e / n at the first run end e >= k_c (a cut falls between distinct
+ *     confidences only).
+ *   risks f64 [n_risks]: coverage_at_risk f64 [n_risks] = the largest e / n over ALL run ends with L_e <= r * e (f64, as
+ *     written), 0 if none: a reduction by integer atomicMax, not a search - the curve is not monotone.
+ *   n_bins = B >= 1: bins f64 [B, 3] = (count, loss sum, confidence sum) of the equal-mass bins counted from the LEAST confident
+ *     row: bin b holds the ascending positions [floor(b n / B), floor((b + 1) n / B)), its sums are differences of Lbar and Sbar
+ *     at the two boundaries (a tie that straddles a boundary is shared in proportion); an empty bin holds three zeros.
+ *     B == 0: no table.
+ *   RUNIA_E_INVALID (before anything else is looked at) unless 1 <= n < 2^31, n_targets and n_risks in 0 .. 64, n_bins in 0 .. 512.
+ *   workspace: 256 bytes or more, 8-byte aligned, uninitialised (runia_sel_workspace_bytes(n) covers it).
+ * runia_sel_tile_rows: rows of a tile of the scan (test sizes are derived from it). */
+int runia_sel_tile_rows(void);
+int runia_sel_keys_f32(const float* conf, int64_t n, int64_t* keys, unsigned* bad, runia_stream_t stream);
+int runia_sel_keys_f64(const double* conf, int64_t n, int64_t* keys, unsigned* bad, runia_stream_t stream);
+int64_t runia_sel_key_of_f64_host(double conf);
+size_t runia_sel_workspace_bytes(int64_t n);
+int runia_sel_curve(const int64_t* sorted_keys, const int32_t* sorted_rows, const void* loss, int loss_f64, int64_t n,
+                    double* record, int32_t* run_end, double* cum_loss, double* cum_conf, int64_t* n_points, void* workspace,
+                    size_t workspace_bytes, runia_stream_t stream);
+int runia_sel_query(const int32_t* run_end, const double* cum_loss, const double* cum_conf, const int64_t* n_points, int64_t n,
+                    const int64_t* targets, int n_targets, const double* risks, int n_risks, int n_bins, double* risk_at,
+                    double* coverage_at, double* coverage_at_risk, double* bins, void* workspace, size_t workspace_bytes,
+                    runia_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

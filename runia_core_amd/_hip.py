@@ -340,6 +340,17 @@ _SIGNATURES = {
         c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_int64, c_int64, c_int64, c_int64, c_void_p, c_void_p,
                 c_void_p, c_void_p, c_void_p, c_int64, c_void_p, c_int, c_void_p]),
     "runia_cc_relabel": (c_int, [c_void_p, c_void_p, c_void_p, c_int64, c_int64, c_int64, c_void_p]),
+    "runia_sel_tile_rows": (c_int, []),
+    "runia_sel_keys_f32": (c_int, [c_void_p, c_int64, c_void_p, c_void_p, c_void_p]),
+    "runia_sel_keys_f64": (c_int, [c_void_p, c_int64, c_void_p, c_void_p, c_void_p]),
+    "runia_sel_key_of_f64_host": (c_int64, [c_double]),
+    "runia_sel_workspace_bytes": (c_size_t, [c_int64]),
+    "runia_sel_curve": (
+        c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int64, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_size_t,
+                c_void_p]),
+    "runia_sel_query": (
+        c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_void_p, c_int, c_void_p, c_int, c_int, c_void_p, c_void_p,
+                c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]),
 }
 
 
@@ -1974,6 +1985,130 @@ def boot_metrics(order: BootOrder, n_boot: int, seed: int = 0, first_replicate: 
     launch("runia_boot_metrics", keys.data_ptr(), rows.data_ptr(), n, n_ind, _ptr(group_of_row), int(seed) & (2**64 - 1),
            first_replicate, n_boot, out.data_ptr(), ws.data_ptr(), ws_bytes)
     return out
+
+
+def sel_tile_rows() -> int:
+    """Rows of one tile of the selective-prediction scan (``runia_sel_tile_rows``; a host query)."""
+    return query("runia_sel_tile_rows")
+
+
+def sel_key_of_host(confidence: float) -> int:
+    """The sort key ``runia_sel_keys_*`` gives one confidence (``runia_sel_key_of_f64_host``: plain host code, no GPU touched)."""
+    return query("runia_sel_key_of_f64_host", float(confidence))
+
+
+class SelOrder(NamedTuple):
+    """A confidence table ordered for :func:`sel_curve`: ``keys`` int64 [n] ascending (= descending confidence), ``rows`` int32 [n]
+    the row of every key - the shape of :class:`BootOrder` - and ``bad`` [1] (device): whether any confidence is NaN."""
+
+    keys: torch.Tensor
+    rows: torch.Tensor
+    bad: torch.Tensor
+
+
+class SelCurve(NamedTuple):
+    """What :func:`sel_curve` leaves on the device: ``record`` f64 [5] = (n_points, L_n, S_n, aurc, augrc); the compacted curve
+    ``run_end`` int32 / ``cum_loss`` / ``cum_conf`` f64, allocated for ``n`` points with the first ``n_points`` [1] int64 (device)
+    filled, or three ``None`` when it was not asked for."""
+
+    record: torch.Tensor
+    run_end: Optional[torch.Tensor]
+    cum_loss: Optional[torch.Tensor]
+    cum_conf: Optional[torch.Tensor]
+    n_points: torch.Tensor
+    n: int
+
+
+def _sel_vector(name: str, what: str, t, n: Optional[int] = None) -> torch.Tensor:
+    if not (isinstance(t, torch.Tensor) and t.is_cuda):
+        raise RuniaHipError(f"{name}: {what} must be a device tensor")
+    if t.dtype not in (torch.float32, torch.float64):
+        raise RuniaHipError(f"{name}: {what} must be float32 or float64, got {t.dtype}")
+    if t.dim() != 1 or t.numel() < 1 or t.numel() >= 2**31 or (n is not None and t.numel() != n):
+        raise RuniaHipError(f"{name}: {what} must be a vector of {'1 .. 2^31 - 1' if n is None else n} entries, got shape "
+                            f"{tuple(t.shape)}")
+    return t.contiguous()
+
+
+@_device_guard()
+def sel_order(confidence: torch.Tensor) -> SelOrder:
+    """Device confidences [n] (f32 or f64) -> their :class:`SelOrder`: the keys of ``runia_sel_keys_*`` and one stable device sort
+    of them (plumbing, as in :func:`boot_order`)."""
+    require_gpu()
+    conf = _sel_vector("sel_order", "confidence", confidence)
+    n = conf.numel()
+    keys = torch.empty(n, dtype=torch.int64, device=conf.device)
+    bad = torch.empty(1, dtype=torch.int32, device=conf.device)
+    launch("runia_sel_keys_f64" if conf.dtype == torch.float64 else "runia_sel_keys_f32", conf.data_ptr(), n, keys.data_ptr(),
+           bad.data_ptr())
+    skeys, order = torch.sort(keys, stable=True)
+    return SelOrder(skeys, order.to(torch.int32), bad)
+
+
+@_device_guard()
+def sel_curve(order: SelOrder, loss: torch.Tensor, want_curve: bool = True) -> SelCurve:
+    """The risk-coverage scan of an ordered table (``runia_sel_curve``): ``loss`` [n] (f32 or f64) is read through ``order.rows``;
+    the confidences come back out of the keys.  Stream-ordered, no synchronisation.  The same inputs give the same bits; with
+    integer-valued losses any permutation of the rows does."""
+    require_gpu()
+    keys, rows = order.keys, order.rows
+    if not (isinstance(keys, torch.Tensor) and isinstance(rows, torch.Tensor) and keys.is_cuda and rows.is_cuda
+            and keys.dtype == torch.int64 and rows.dtype == torch.int32):
+        raise RuniaHipError("sel_curve: keys must be int64 and rows int32 device tensors")
+    n = keys.numel()
+    if not (keys.dim() == 1 and keys.is_contiguous() and rows.is_contiguous() and rows.shape == keys.shape and 1 <= n < 2**31):
+        raise RuniaHipError("sel_curve: keys and rows must be contiguous vectors of one length in 1 .. 2^31 - 1")
+    loss = _sel_vector("sel_curve", "loss", loss, n)
+    dev = keys.device
+    record = torch.empty(5, dtype=torch.float64, device=dev)
+    n_points = torch.empty(1, dtype=torch.int64, device=dev)
+    run_end = torch.empty(n, dtype=torch.int32, device=dev) if want_curve else None
+    cum_loss = torch.empty(n, dtype=torch.float64, device=dev) if want_curve else None
+    cum_conf = torch.empty(n, dtype=torch.float64, device=dev) if want_curve else None
+    ws_bytes = query("runia_sel_workspace_bytes", n)
+    ws = workspace(ws_bytes, dev)
+    launch("runia_sel_curve", keys.data_ptr(), rows.data_ptr(), loss.data_ptr(), int(loss.dtype == torch.float64), n,
+           record.data_ptr(), _ptr(run_end), _ptr(cum_loss), _ptr(cum_conf), n_points.data_ptr(), ws.data_ptr(), ws_bytes)
+    return SelCurve(record, run_end, cum_loss, cum_conf, n_points, n)
+
+
+@_device_guard()
+def sel_query(curve: SelCurve, targets=(), risks=(), n_bins: int = 0):
+    """Queries on a compacted curve (``runia_sel_query``): ``targets`` - the integers ``k_c = ceil(c n)`` of at most 64 coverage
+    targets; ``risks`` - at most 64 risk levels; ``n_bins`` in 0 .. 512 equal-mass bins.  -> device tensors ``(risk_at [Q],
+    coverage_at [Q], coverage_at_risk [R], bins [n_bins, 3])`` f64 (``bins``: count, loss sum, confidence sum, least confident
+    bin first).  Stream-ordered, no synchronisation."""
+    require_gpu()
+    targets = [int(k) for k in targets]
+    risks = [float(r) for r in risks]
+    n_bins, n = int(n_bins), int(curve.n)
+    if len(targets) > 64 or len(risks) > 64:
+        raise RuniaHipError("sel_query: at most 64 coverage targets and 64 risk levels")
+    if not 0 <= n_bins <= 512:
+        raise RuniaHipError("sel_query: n_bins must lie in 0 .. 512")
+    if any(k < 1 or k > n for k in targets):
+        raise RuniaHipError(f"sel_query: coverage targets must lie in 1 .. n = {n}")
+    if curve.run_end is None:
+        raise RuniaHipError("sel_query: the curve was not kept (sel_curve(..., want_curve=True))")
+    for name, t, dt in (("run_end", curve.run_end, torch.int32), ("cum_loss", curve.cum_loss, torch.float64),
+                        ("cum_conf", curve.cum_conf, torch.float64)):
+        if not (isinstance(t, torch.Tensor) and t.is_cuda and t.dtype == dt and t.is_contiguous() and t.numel() >= n
+                and t.device == curve.n_points.device):
+            raise RuniaHipError(f"sel_query: {name} must be a contiguous {dt} device tensor of n = {n} entries")
+    if not (curve.n_points.is_cuda and curve.n_points.dtype == torch.int64 and curve.n_points.numel() == 1):
+        raise RuniaHipError("sel_query: n_points must be one int64 on the device")
+    dev = curve.n_points.device
+    q, r = len(targets), len(risks)
+    tg = torch.tensor(targets, dtype=torch.int64).to(dev) if q else None
+    rk = torch.tensor(risks, dtype=torch.float64).to(dev) if r else None
+    out = torch.empty(2 * q + r + 3 * n_bins, dtype=torch.float64, device=dev)
+    risk_at, cov_at, cov_risk, bins = out[:q], out[q:2 * q], out[2 * q:2 * q + r], out[2 * q + r:].view(n_bins, 3)
+    ws = workspace(256, dev, 256)
+    launch("runia_sel_query", curve.run_end.data_ptr(), curve.cum_loss.data_ptr(), curve.cum_conf.data_ptr(),
+           curve.n_points.data_ptr(), n, _ptr(tg), q, _ptr(rk), r, n_bins, risk_at.data_ptr() if q else None,
+           cov_at.data_ptr() if q else None, cov_risk.data_ptr() if r else None, bins.data_ptr() if n_bins else None,
+           ws.data_ptr(), 256)
+    return risk_at, cov_at, cov_risk, bins
 
 
 @_device_guard()

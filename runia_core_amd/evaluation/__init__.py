@@ -42,3 +42,11 @@ from .bootstrap import (  # noqa: F401
     compare_ood_methods,
 )
 from .components import ComponentResult, component_metrics, label_components  # noqa: F401
+from .selective import (  # noqa: F401
+    RiskCoverageCurve,
+    SelectiveResult,
+    adaptive_calibration_error,
+    selective_metrics,
+    selective_metrics_from_logits,
+    selective_results_table,
+)

@@ -33,6 +33,21 @@ using namespace runia_mfma;
 
 constexpr int kMaxMC = 64;
 typedef float f2 __attribute__((ext_vector_type(2)));
+typedef float f4 __attribute__((ext_vector_type(4)));
+
+// K0_NT_STORE / K1_NT_STORE: K0's table and K1's entropies leave as streaming (non-temporal) stores instead of ordinary
+// write-back ones.  Both measured and left off (profiles/README.md, "K1 without the z_out branches").
+#ifndef K0_NT_STORE
+#define K0_NT_STORE 0
+#endif
+#ifndef K1_NT_STORE
+#define K1_NT_STORE 0
+#endif
+template <int NT, typename T>
+__device__ __forceinline__ void store_out(T* p, T v) {
+  if constexpr (NT != 0) __builtin_nontemporal_store(v, p);
+  else *p = v;
+}
 
 // Keep-flag table of one image (K0 -> K1), n_mc*(HW+2) floats:
 //   n_mc records of HW floats: 0.0 where the drop layer removes the position, 2^-a where it keeps it, with the layer's
@@ -201,19 +216,20 @@ __global__ __launch_bounds__(64 * kMaskBitsWaves) void mc_mask_bits_kernel(const
   if constexpr (HW % 4 == 0) {
 #pragma unroll
     for (int c = 0; c < HW / 4; ++c) {
-      float4 v;
+      f4 v;
       v.x = ((keep >> slot_position<HT, WT>(4 * c)) & 1ull) ? flag : 0.f;
       v.y = ((keep >> slot_position<HT, WT>(4 * c + 1)) & 1ull) ? flag : 0.f;
       v.z = ((keep >> slot_position<HT, WT>(4 * c + 2)) & 1ull) ? flag : 0.f;
       v.w = ((keep >> slot_position<HT, WT>(4 * c + 3)) & 1ull) ? flag : 0.f;
-      reinterpret_cast<float4*>(rec)[c] = v;
+      store_out<K0_NT_STORE>(reinterpret_cast<f4*>(rec) + c, v);
     }
   } else {
 #pragma unroll
-    for (int q = 0; q < HW; ++q) rec[q] = ((keep >> slot_position<HT, WT>(q)) & 1ull) ? flag : 0.f;
+    for (int q = 0; q < HW; ++q)
+      store_out<K0_NT_STORE>(rec + q, ((keep >> slot_position<HT, WT>(q)) & 1ull) ? flag : 0.f);
   }
-  out[n_mc * HW + rank] = zh;
-  out[n_mc * (HW + 1) + rank] = zl;
+  store_out<K0_NT_STORE>(out + n_mc * HW + rank, zh);
+  store_out<K0_NT_STORE>(out + n_mc * (HW + 1) + rank, zl);
 }
 
 // ------------------------------------------------------------------------------------------
@@ -333,7 +349,9 @@ __device__ __forceinline__ void roi_load_map(float (&u)[HT * WT], const RoiSourc
 #ifndef K1_IMGS
 #define K1_IMGS 1  // images per workgroup, one after the other (timing experiments: fewer, longer waves)
 #endif
-template <int HT, int WT, int NP, int K, bool FULL, bool ENTROPY, int ROI_G>
+// ZOUT: the launch also writes the MC samples to z_out (the sampler-only entry point and the tests); the product launch
+// passes no z_out and takes the instantiation without the stores, whose drop layers are then free of branches on it.
+template <int HT, int WT, int NP, int K, bool FULL, bool ENTROPY, int ROI_G, bool ZOUT>
 __device__ __forceinline__ void mc_entropy_item(const float* __restrict__ x, const float* __restrict__ table,
                                                 double* __restrict__ h, float* __restrict__ z_out,
                                                 double* __restrict__ zero_fill, int64_t N, int C, int n_mc_rt,
@@ -409,7 +427,10 @@ __device__ __forceinline__ void mc_entropy_item(const float* __restrict__ x, con
 #pragma unroll K1_TRIP_UNROLL
   for (int s0 = 0; s0 < NP; s0 += G) {
     float znew[G];
-    // all scalar operands of this trip are requested up front (one wait instead of one per drop layer)
+    // The scalar operands of this trip.  They are NOT all requested here in the emitted code: G * HW flags do not fit the
+    // scalar registers, so the compiler loads each drop layer's 16 flags into the same registers in front of that layer's
+    // arithmetic and waits there.  Requesting layer g + 1's set ahead of layer g's arithmetic (a second register set,
+    // scheduling barriers) measured slower in this loop: profiles/README.md, "K1 without the z_out branches".
     float dg[G], rg[G], mg[G][HW];
     // FULL: one base pointer per trip and constant offsets from it (the scalar loads then carry the layer's offset as an
     // immediate; with sc = s0 + g inside the index the compiler kept one 64-bit address per drop layer in scalar registers)
@@ -486,8 +507,12 @@ __device__ __forceinline__ void mc_entropy_item(const float* __restrict__ x, con
         }
         if constexpr (hw_pow2 && PAIRS) znew[g] = col;
         else znew[g] = h_pow2 ? col * rH : div_newton(col, (float)HT, rH);
-        if (z_out)  // optional copy of the MC samples (drop-layer order is the table's; tests only)
-          z_out[(img * n_mc + s) * (int64_t)C + c] = znew[g];
+        // copy of the MC samples (drop-layer order is the table's; the sampler-only entry point and the tests).  Still a
+        // run-time test inside the ZOUT instantiation: it parts the drop layers, and with a bare store the compiler
+        // requests several layers' flags at once and spills scalar registers to vector lanes (4x4: 140 lane moves)
+        if constexpr (ZOUT) {
+          if (z_out) z_out[(img * n_mc + s) * (int64_t)C + c] = znew[g];
+        }
       }
     }
 #pragma unroll
@@ -506,11 +531,11 @@ __device__ __forceinline__ void mc_entropy_item(const float* __restrict__ x, con
     sort_asc<NP>(z);
     double res = const_term + inv_n * column_log_sum<NP, K, FULL>(z, n_mc, min_dist);
     if (bad) res = NAN;
-    h[img * C + c] = res;
+    store_out<K1_NT_STORE>(h + (img * C + c), res);
   }
 }
 
-template <int HT, int WT, int NP, int K, bool FULL, bool ENTROPY = true, int ROI_G = 0>
+template <int HT, int WT, int NP, int K, bool FULL, bool ENTROPY, int ROI_G, bool ZOUT>
 #ifdef K1_WAVES
 __attribute__((amdgpu_waves_per_eu(K1_WAVES, 8)))
 #endif
@@ -529,9 +554,29 @@ __global__ __launch_bounds__(kK1Block) void mc_entropy_kernel(const float* __res
 #pragma unroll 1
   for (int rep = 0; rep < K1_IMGS; ++rep) {
     const int64_t img = ((int64_t)(slot / chunks) * K1_IMGS + rep) * 8 + (blockIdx.x & 7);
-    mc_entropy_item<HT, WT, NP, K, FULL, ENTROPY, ROI_G>(x, table, h, z_out, zero_fill, N, C, n_mc_rt, min_dist, const_term,
-                                                        inv_n, img, c);
+    mc_entropy_item<HT, WT, NP, K, FULL, ENTROPY, ROI_G, ZOUT>(x, table, h, z_out, zero_fill, N, C, n_mc_rt, min_dist,
+                                                              const_term, inv_n, img, c);
   }
+}
+
+// The entropy launch.  The 4x4 maps have an instantiation without the z_out stores, taken when the caller passes no
+// z_out (the product path).  The other maps keep the one kernel with its run-time test, which their code needs between
+// the drop layers: without it the 7x7 form held two layers' quotients (200 vector registers, 64 scalar registers spilled
+// to lanes) and the 2x2 x 32 form, one trip of 32 layers, requested all its flags at once (228 lane moves).
+template <int HT, int WT, int NP, int K, bool FULL, int ROI_G>
+void launch_mc_entropy(unsigned grid, hipStream_t s, const float* x, const float* table, double* h, float* z_out,
+                       double* zero_fill, int64_t N, int C, int n_mc, double min_dist, double ct, double inv_n) {
+  auto go = [&](auto kernel) {
+    if constexpr (ROI_G == 0)
+      RUNIA_LAUNCH_TIMED(kernel, grid, kK1Block, 0, s, x, table, h, z_out, zero_fill, N, C, n_mc, min_dist, ct, inv_n);
+    else
+      hipLaunchKernelGGL(kernel, dim3(grid), dim3(kK1Block), 0, s, x, table, h, z_out, zero_fill, N, C, n_mc, min_dist, ct,
+                         inv_n);
+  };
+  if constexpr (HT == 4 && WT == 4) {
+    if (!z_out) return go(mc_entropy_kernel<HT, WT, NP, K, FULL, true, ROI_G, false>);
+  }
+  go(mc_entropy_kernel<HT, WT, NP, K, FULL, true, ROI_G, true>);
 }
 
 // ------------------------------------------------------------------------------------------
@@ -1132,11 +1177,11 @@ extern "C" int runia_mc_stack_table_f32(const float* x, const float* rnd, int64_
 #define RUNIA_MCE(HH, WW, NPP, KK)                                                                          \
   if (H == HH && W == WW && n_mc <= NPP && n_mc > NPP / 2) {                                                \
     if (n_mc == NPP)                                                                                        \
-      mc_entropy_kernel<HH, WW, NPP, KK, true, false><<<grid, kK1Block, 0, s>>>(x, table, nullptr, z,       \
+      mc_entropy_kernel<HH, WW, NPP, KK, true, false, 0, true><<<grid, kK1Block, 0, s>>>(x, table, nullptr, z, \
                                                                                 nullptr, N, C, n_mc, 0.0,   \
                                                                                 0.0, 0.0);                  \
     else                                                                                                    \
-      mc_entropy_kernel<HH, WW, NPP, KK, false, false><<<grid, kK1Block, 0, s>>>(x, table, nullptr, z,      \
+      mc_entropy_kernel<HH, WW, NPP, KK, false, false, 0, true><<<grid, kK1Block, 0, s>>>(x, table, nullptr, z, \
                                                                                  nullptr, N, C, n_mc, 0.0,  \
                                                                                  0.0, 0.0);                 \
     return runia_check_launch();                                                                            \
@@ -1163,11 +1208,11 @@ extern "C" int runia_mc_entropy_from_table_f32(const float* x, const void* works
 #define RUNIA_MCE(HH, WW, NPP, KK)                                                                          \
   if (H == HH && W == WW && n_mc <= NPP && n_mc > NPP / 2 && k == KK && (x16 || (HH * WW) % 4 != 0)) {      \
     if (n_mc == NPP)                                                                                        \
-      RUNIA_LAUNCH_TIMED((mc_entropy_kernel<HH, WW, NPP, KK, true>), grid, kK1Block, 0, s, x, table, h, z_out, \
-                         zero_fill, N, C, n_mc, min_dist, ct, inv_n);                                       \
+      launch_mc_entropy<HH, WW, NPP, KK, true, 0>(grid, s, x, table, h, z_out, zero_fill, N, C, n_mc, min_dist, ct, \
+                                                  inv_n);                                                   \
     else                                                                                                    \
-      RUNIA_LAUNCH_TIMED((mc_entropy_kernel<HH, WW, NPP, KK, false>), grid, kK1Block, 0, s, x, table, h, z_out, \
-                         zero_fill, N, C, n_mc, min_dist, ct, inv_n);                                       \
+      launch_mc_entropy<HH, WW, NPP, KK, false, 0>(grid, s, x, table, h, z_out, zero_fill, N, C, n_mc, min_dist, ct, \
+                                                   inv_n);                                                  \
     return runia_check_launch();                                                                            \
   }
   RUNIA_MCE_SHAPES(RUNIA_MCE)
@@ -1250,11 +1295,11 @@ extern "C" int runia_roi_mc_entropy_f32(const float* feat_nhwc, const float* box
 #define RUNIA_ROI_MCE(HH, WW, NPP, KK, GG)                                                                         \
   if (PH == HH && PW == WW && n_mc <= NPP && n_mc > NPP / 2 && k == KK && sampling_ratio == GG) {                  \
     if (n_mc == NPP)                                                                                               \
-      mc_entropy_kernel<HH, WW, NPP, KK, true, true, GG><<<grid, kK1Block, 0, s>>>(src, table, h, z_out, nullptr,  \
-                                                                                   K, C, n_mc, min_dist, ct, inv_n); \
+      launch_mc_entropy<HH, WW, NPP, KK, true, GG>(grid, s, src, table, h, z_out, nullptr, K, C, n_mc, min_dist, ct, \
+                                                   inv_n);                                                         \
     else                                                                                                           \
-      mc_entropy_kernel<HH, WW, NPP, KK, false, true, GG><<<grid, kK1Block, 0, s>>>(src, table, h, z_out, nullptr, \
-                                                                                    K, C, n_mc, min_dist, ct, inv_n); \
+      launch_mc_entropy<HH, WW, NPP, KK, false, GG>(grid, s, src, table, h, z_out, nullptr, K, C, n_mc, min_dist, ct, \
+                                                    inv_n);                                                        \
     return runia_check_launch();                                                                                   \
   }
   RUNIA_ROI_MCE_SHAPES(RUNIA_ROI_MCE)

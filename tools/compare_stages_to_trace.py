@@ -58,11 +58,11 @@ def add(label, in_run, parts, note=""):
     rows.append((label, in_run, t if not missing else None, note + (" MISSING " + ",".join(missing) if missing else "")))
 
 
-add("roofline K1 `mc_entropy_kernel<4,4,16,5>` (10 000 images)", bench["roofline"]["avg_launch_ms"], [("mc_entropy_kernel<4, 4, 16, 5, true, true, 0>", 40000)],
+add("roofline K1 `mc_entropy_kernel<4,4,16,5>` (10 000 images)", bench["roofline"]["avg_launch_ms"], [("mc_entropy_kernel<4, 4, 16, 5, true, true, 0,", 40000)],
     "events attached to the dispatch")
 k2, _ = med("proj_sq_kernel<1, 2, true, true, true", 1264)
 k0, _ = med("mc_mask_bits_kernel<4, 4, 16, true>", 2500)
-k1, _ = med("mc_entropy_kernel<4, 4, 16, 5, true, true, 0>", 40000)
+k1, _ = med("mc_entropy_kernel<4, 4, 16, 5, true, true, 0,", 40000)
 rows.append(("step = K0 + K1 + K2' (kernel time only)", bench["ms_per_step_stats"]["median"], (k0 or 0) + (k1 or 0) + (k2 or 0), "median step (events) vs sum of the three kernels: the difference is dispatch gaps"))
 add("stages.mahalanobis (1 M x 2048)", stg["mahalanobis"]["ms"], [("gemm_rows_kernel<float, double, 5, 2, 4>", 31250)])
 add("stages.energy_c1000", stg["energy_c1000"]["ms"], [("lse_wave_kernel<4>", 125000)])
@@ -87,7 +87,7 @@ add("cfg4_lared.kde", L["kde"]["ms"], [("gemm_rows_kernel<double, double, 4, 2, 
 M = stg["cfg4_from_feature_maps"]
 add("cfg4_from_feature_maps.channels_last_copy", M["channels_last_copy"]["ms"], [("nchw_to_nhwc_kernel", 57)])
 add("cfg4_from_feature_maps.roi_sampler_entropy", M["roi_sampler_entropy"]["ms"],
-    [("mc_entropy_kernel<7, 7, 16, 5, true, true, 2>", 524288), ("mc_entropy_kernel<7, 7, 16, 5, true, true, 2>", 275776),
+    [("mc_entropy_kernel<7, 7, 16, 5, true, true, 2,", 524288), ("mc_entropy_kernel<7, 7, 16, 5, true, true, 2,", 275776),
      ("mc_mask_bits_kernel<7, 7, 16, false>", 16384), ("mc_mask_bits_kernel<7, 7, 16, false>", 8617), ("roi_sample_table_kernel", None)],
     "two slices of <= 65 535 proposals: sampler launches + keep-flag tables + one sample table (median of both slices)")
 F = stg["fits"]

@@ -4,7 +4,8 @@
     python tools/isa_stats.py runia_core_amd/csrc/fused.hip [name-filter]
 
 Compiles the file to gfx950 assembly with the Makefile's flags and prints, per kernel: vector / scalar instruction
-counts, v_readlane + v_writelane (scalar registers spilled to vector lanes), MFMA count, VGPRs, SGPRs, scratch bytes.
+counts, v_readlane + v_writelane (scalar registers spilled to vector lanes), MFMA count, VGPRs, SGPRs, scratch bytes,
+v_mov count and branch count (s_cbranch_* + s_branch).
 The hot kernels are sensitive to small source changes (K1 went from 722 to 937 vector instructions when one more
 scalar load entered its loop), so this is run before a GPU measurement."""
 import re
@@ -46,14 +47,16 @@ def main():
         mfma = sum(1 for i in ins if "mfma" in i)
         salu = sum(1 for i in ins if i.startswith("s_"))
         lanes = sum(1 for i in ins if i.startswith(("v_readlane", "v_writelane")))
+        vmov = sum(1 for i in ins if i.startswith("v_mov"))
+        br = sum(1 for i in ins if i.startswith(("s_cbranch", "s_branch")))
         short = subprocess.run(["c++filt", name], capture_output=True, text=True).stdout.strip()
         short = short.replace("(anonymous namespace)::", "").replace("void ", "").split("(")[0]
         if flt and flt not in short:
             continue
-        rows.append((short, valu, salu, lanes, mfma, vg, sg, scratch, lds))
-    print(f"{'kernel':64s} {'valu':>5s} {'salu':>5s} {'lane':>5s} {'mfma':>5s} {'vgpr':>5s} {'sgpr':>5s} {'scr':>5s} {'lds':>6s}")
+        rows.append((short, valu, salu, lanes, mfma, vg, sg, scratch, lds, vmov, br))
+    print(f"{'kernel':64s} {'valu':>5s} {'salu':>5s} {'lane':>5s} {'mfma':>5s} {'vgpr':>5s} {'sgpr':>5s} {'scr':>5s} {'lds':>6s} {'vmov':>5s} {'br':>4s}")
     for r in rows:
-        print(f"{r[0][:64]:64s} " + " ".join(f"{v:5d}" for v in r[1:8]) + f" {r[8]:6d}")
+        print(f"{r[0][:64]:64s} " + " ".join(f"{v:5d}" for v in r[1:8]) + f" {r[8]:6d} {r[9]:5d} {r[10]:4d}")
 
 
 if __name__ == "__main__":

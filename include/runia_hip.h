@@ -1130,6 +1130,62 @@ int runia_sel_query(const int32_t* run_end, const double* cum_loss, const double
                     double* coverage_at, double* coverage_at_risk, double* bins, void* workspace, size_t workspace_bytes,
                     runia_stream_t stream);
 
+/* ---- per-pixel Mahalanobis maps from segmentation features (csrc/pixel_features.hip) ------------------------------------------
+ * runia_pixfeat_score: the distance of every pixel of G feature maps to the nearest of K class Gaussians with one shared
+ * covariance, ONE launch, the maps read where the model left them.
+ *   features   base of a (G, C, H, W) map, dtype 0 f32, 1 f16, 2 bf16 (the codes of runia_pixel_uncertainty_maps), widened
+ *              exactly; all arithmetic in f32.
+ *   sn sc sh sw element strides (>= 0) of the image, channel, h and w dimensions: NCHW, channels_last (sc == 1) and sliced
+ *              views are read in place.
+ *   m0         f32 [C]: the centre that is subtracted first.
+ *   W          f32 [C, C] row-major, LOWER TRIANGULAR (= L^-1 of the pooled covariance): what lies above the diagonal is
+ *              never read past the 128-column block of its row, and must be zero.
+ *   mz         f32 [K, C]: mz_c = W (mu_c - m0).  A row whose first entry is +inf marks an excluded (empty) class.
+ *   outputs    contiguous, each may be NULL, at least one set:
+ *                distance        f32 (G, H, W)    min_c |W (x - m0) - mz_c|^2
+ *                nearest         int32 (G, H, W)  its argmin, lowest index on ties
+ *                class_distances f32 (G, K, H, W)
+ *              The sum over the channels is the difference form sum_j (z_j - mz_cj)^2 (the expanded form cancels in f32 when
+ *              the features sit away from zero).  An excluded class scores +inf and is never `nearest` unless all are
+ *              excluded (then 0).  A distance that is not finite - NaN or inf among the pixel's features - is written as NaN
+ *              in every output of THAT pixel (nearest 0); no other pixel is touched by it.
+ *   A 256-thread workgroup owns 128 consecutive pixels of the flattened G * H * W axis; 32 channels at a time are staged into
+ *   LDS (16- / 8-byte loads of four pixels when w has unit stride and the other strides, H * W resp. W and the base are
+ *   multiples of four elements; 16-byte loads of neighbouring channels when sc == 1, C >= 16 and the other strides and the
+ *   base are multiples of 16 bytes - channels_last; element loads through the strides otherwise: the same bits on every
+ *   path) and multiplied on the f32 matrix cores; the zero blocks of W are skipped.  Fixed summation order, no atomics: run-to-run bit identical, and a pixel's result does not
+ *   depend on its position in the batch.  The running sums of 32 classes live in registers: K > 32 repeats the product per
+ *   group of 32 classes.
+ *   1 <= C <= 1024, 1 <= K <= 256, G, H, W < 2^31, G * H * W <= 2^37; RUNIA_E_INVALID otherwise (checked on the host before
+ *   anything else).  G == 0 or H * W == 0: 0, nothing launched.  workspace: runia_pixfeat_workspace_bytes(C, K) bytes - a
+ *   function of C and K alone, never of the pixels (0 today: the arguments are kept for the ABI).
+ * runia_pixfeat_label_hist: labels [N] int64 (label_dtype 0), int32 (1) or uint8 (2) -> counts int64 [K] of the labels in
+ *   [0, K) other than ignore_index, dropped int64 [1] of all the others.  Integer counts: deterministic.  1 <= K <= 256,
+ *   0 <= N <= 2^37.
+ * runia_pixfeat_gather_rows: a deterministic subsample of the labelled pixels as rows.  Pixel p (row-major over H * W) of
+ *   image g is kept iff its label l is in [0, K), is not ignore_index, and the Philox4x32-10 draw with counter
+ *   ((image_offset + g) * H * W + p, 0) and key `seed` (first word, 24 bits) is below keep_prob[l] (f32 [K] on the device:
+ *   1 keeps all, 0 none).  The subset depends on (seed, image_offset + g, p) alone, not on the batching.
+ *   labels (G, H, W) contiguous; features as for runia_pixfeat_score.  n_out: one device int64, the number of kept pixels
+ *   (always written).  rows f32 (n, C) = the widened features, row_labels int32 (n): both NULL (count only) or both given
+ *   with room for max_rows rows; rows beyond max_rows are not written.  Rows come in pixel order: a count per 1024-pixel
+ *   chunk, a scan, then the write - no atomic decides a position.
+ *   workspace: runia_pixfeat_gather_workspace_bytes(G * H * W) bytes, 8-byte aligned (RUNIA_E_WORKSPACE if short).
+ *   Limits as for runia_pixfeat_score; 0 <= image_offset < 2^31. */
+size_t runia_pixfeat_workspace_bytes(int64_t C, int64_t K);
+int runia_pixfeat_score(const void* features, int dtype, int64_t G, int64_t C, int64_t H, int64_t W, int64_t sn, int64_t sc,
+                        int64_t sh, int64_t sw, const float* m0, const float* Wmat, const float* mz, int64_t K, float* distance,
+                        int32_t* nearest, float* class_distances, void* workspace, size_t workspace_bytes,
+                        runia_stream_t stream);
+int runia_pixfeat_label_hist(const void* labels, int label_dtype, int64_t N, int64_t K, int64_t ignore_index, int64_t* counts,
+                             int64_t* dropped, runia_stream_t stream);
+size_t runia_pixfeat_gather_workspace_bytes(int64_t pixels);
+int runia_pixfeat_gather_rows(const void* features, int dtype, int64_t G, int64_t C, int64_t H, int64_t W, int64_t sn,
+                              int64_t sc, int64_t sh, int64_t sw, const void* labels, int label_dtype, int64_t K,
+                              int64_t ignore_index, const float* keep_prob, uint64_t seed, int64_t image_offset, float* rows,
+                              int32_t* row_labels, int64_t max_rows, int64_t* n_out, void* workspace, size_t workspace_bytes,
+                              runia_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

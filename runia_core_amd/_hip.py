@@ -351,6 +351,16 @@ _SIGNATURES = {
     "runia_sel_query": (
         c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_void_p, c_int, c_void_p, c_int, c_int, c_void_p, c_void_p,
                 c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]),
+    "runia_pixfeat_workspace_bytes": (c_size_t, [c_int64, c_int64]),
+    "runia_pixfeat_score": (
+        c_int, [c_void_p, c_int, c_int64, c_int64, c_int64, c_int64, c_int64, c_int64, c_int64, c_int64, c_void_p, c_void_p,
+                c_void_p, c_int64, c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]),
+    "runia_pixfeat_label_hist": (c_int, [c_void_p, c_int, c_int64, c_int64, c_int64, c_void_p, c_void_p, c_void_p]),
+    "runia_pixfeat_gather_workspace_bytes": (c_size_t, [c_int64]),
+    "runia_pixfeat_gather_rows": (
+        c_int, [c_void_p, c_int, c_int64, c_int64, c_int64, c_int64, c_int64, c_int64, c_int64, c_int64, c_void_p, c_int,
+                c_int64, c_int64, c_void_p, c_uint64, c_int64, c_void_p, c_void_p, c_int64, c_void_p, c_void_p, c_size_t,
+                c_void_p]),
 }
 
 
@@ -1672,6 +1682,92 @@ def pixel_map_reduce(score_map: torch.Tensor, valid: Optional[torch.Tensor] = No
     cnt = torch.empty((g,), dtype=torch.int64, device=m.device)
     launch("runia_pixel_map_reduce_f32", m.data_ptr(), _ptr(v), g, hw, mean.data_ptr(), mx.data_ptr(), cnt.data_ptr())
     return mean, mx, cnt
+
+
+PIXFEAT_OUTPUTS = ("distance", "nearest", "class_distances")
+PIXFEAT_MAX_CHANNELS, PIXFEAT_MAX_CLASSES = 1024, 256  # the limits of runia_pixfeat_score
+# label dtype of the maps -> the `label_dtype` code of runia_pixfeat_label_hist / runia_pixfeat_gather_rows
+PIXFEAT_LABEL_CODES = {torch.int64: 0, torch.int32: 1, torch.uint8: 2}
+
+
+@_device_guard()
+def pixfeat_score(features: torch.Tensor, m0: torch.Tensor, w: torch.Tensor, mz: torch.Tensor, outputs=("distance",)):
+    """Per-pixel Mahalanobis maps, one launch (``runia_pixfeat_score``).  ``features`` (G, C, h, w) f32 / f16 / bf16 on the
+    device, any strides, read in place; ``m0`` [C], ``w`` [C, C] lower triangular, ``mz`` [K, C] f32 on the device (a row
+    of ``+inf`` excludes its class).  Returns a dict with the requested ``outputs``: ``"distance"`` f32 (G, h, w),
+    ``"nearest"`` int32 (G, h, w), ``"class_distances"`` f32 (G, K, h, w)."""
+    assert all(o in PIXFEAT_OUTPUTS for o in outputs) and len(outputs) > 0, f"outputs must be among {PIXFEAT_OUTPUTS}"
+    assert features.is_cuda and features.dim() == 4 and features.dtype in ELEM_DTYPE_CODES
+    g, c, h, wd = (int(v) for v in features.shape)
+    k = int(mz.shape[0])
+    for t, shape in ((m0, (c,)), (w, (c, c)), (mz, (k, c))):
+        assert t.is_cuda and t.dtype == torch.float32 and tuple(t.shape) == shape and t.is_contiguous()
+    require_gpu()
+    dev = features.device
+    out = {}
+    if "distance" in outputs:
+        out["distance"] = torch.empty((g, h, wd), dtype=torch.float32, device=dev)
+    if "nearest" in outputs:
+        out["nearest"] = torch.empty((g, h, wd), dtype=torch.int32, device=dev)
+    if "class_distances" in outputs:
+        out["class_distances"] = torch.empty((g, k, h, wd), dtype=torch.float32, device=dev)
+    need = query("runia_pixfeat_workspace_bytes", c, k)
+    ws = workspace(need, dev, 0) if need else None
+    sn, sc, sh, sw = (int(v) for v in features.stride())
+    launch("runia_pixfeat_score", features.data_ptr(), ELEM_DTYPE_CODES[features.dtype], g, c, h, wd, sn, sc, sh, sw,
+           m0.data_ptr(), w.data_ptr(), mz.data_ptr(), k, _ptr(out.get("distance")), _ptr(out.get("nearest")),
+           _ptr(out.get("class_distances")), _ptr(ws), need)
+    return out
+
+
+def _pixfeat_labels(labels: torch.Tensor) -> torch.Tensor:
+    assert labels.is_cuda and labels.dim() == 3 and labels.dtype in PIXFEAT_LABEL_CODES, \
+        f"labels: a (G, h, w) device tensor of int64, int32 or uint8, got {tuple(labels.shape)} {labels.dtype}"
+    return labels.contiguous()
+
+
+@_device_guard()
+def pixfeat_label_hist(labels: torch.Tensor, n_classes: int, ignore_index: int = 255):
+    """labels (G, h, w) int64 / int32 / uint8 on the device -> (counts int64 [n_classes], dropped int64 [1]) on the device:
+    the pixels per class, and those ignored or outside ``[0, n_classes)``."""
+    labels = _pixfeat_labels(labels)
+    require_gpu()
+    counts = torch.empty((int(n_classes),), dtype=torch.int64, device=labels.device)
+    dropped = torch.empty((1,), dtype=torch.int64, device=labels.device)
+    launch("runia_pixfeat_label_hist", labels.data_ptr(), PIXFEAT_LABEL_CODES[labels.dtype], labels.numel(), int(n_classes),
+           int(ignore_index), counts.data_ptr(), dropped.data_ptr())
+    return counts, dropped
+
+
+@_device_guard()
+def pixfeat_gather_rows(features: torch.Tensor, labels: torch.Tensor, keep_prob: torch.Tensor, ignore_index: int = 255,
+                        seed: int = 0, image_offset: int = 0):
+    """The labelled pixels of ``features`` (G, C, h, w) kept by the counter draw (``runia_pixfeat_gather_rows``) ->
+    ``(rows f32 (n, C), row_labels int32 (n,))`` on the device, in pixel order.  ``keep_prob`` f32 [K] on the device.  The
+    count is read back once (a host synchronisation) to size the table."""
+    assert features.is_cuda and features.dim() == 4 and features.dtype in ELEM_DTYPE_CODES
+    labels = _pixfeat_labels(labels)
+    g, c, h, wd = (int(v) for v in features.shape)
+    assert tuple(labels.shape) == (g, h, wd), f"labels {tuple(labels.shape)} do not match the features {(g, h, wd)}"
+    assert keep_prob.is_cuda and keep_prob.dtype == torch.float32 and keep_prob.dim() == 1 and keep_prob.is_contiguous()
+    require_gpu()
+    dev = features.device
+    k = int(keep_prob.shape[0])
+    n_out = torch.zeros((1,), dtype=torch.int64, device=dev)
+    need = query("runia_pixfeat_gather_workspace_bytes", g * h * wd)
+    ws = workspace(need, dev, 8)
+    sn, sc, sh, sw = (int(v) for v in features.stride())
+    head = (features.data_ptr(), ELEM_DTYPE_CODES[features.dtype], g, c, h, wd, sn, sc, sh, sw, labels.data_ptr(),
+            PIXFEAT_LABEL_CODES[labels.dtype], k, int(ignore_index), keep_prob.data_ptr(), int(seed) & ((1 << 64) - 1),
+            int(image_offset))
+    launch("runia_pixfeat_gather_rows", *head, None, None, 0, n_out.data_ptr(), ws.data_ptr(), need)
+    n = int(n_out.item())
+    rows = torch.empty((n, c), dtype=torch.float32, device=dev)
+    row_labels = torch.empty((n,), dtype=torch.int32, device=dev)
+    if n:
+        launch("runia_pixfeat_gather_rows", *head, rows.data_ptr(), row_labels.data_ptr(), n, n_out.data_ptr(), ws.data_ptr(),
+               need)
+    return rows, row_labels
 
 
 # (RUNIA_CC_TILE_H, RUNIA_CC_TILE_W) of include/runia_hip.h: the tile one workgroup of the labelling kernel owns

@@ -30,6 +30,12 @@ from .pixel_level import (  # noqa: F401
     pixel_ood_metrics,
     pixel_uncertainty_maps,
 )
+from .pixel_features import (  # noqa: F401
+    PixelMahalanobis,
+    fit_pixel_mahalanobis,
+    get_pixel_mahalanobis_maps,
+    pixel_feature_rows,
+)
 from .postprocessors import (  # noqa: F401
     ASH,
     DDU,

@@ -1130,6 +1130,32 @@ int runia_sel_query(const int32_t* run_end, const double* cum_loss, const double
                     double* coverage_at, double* coverage_at_risk, double* bins, void* workspace, size_t workspace_bytes,
                     runia_stream_t stream);
 
+/* ---- bootstrap replicates of the selective-prediction summaries (csrc/boot_selective.hip) ------------------------------------
+ * Replicate b gives row r the Poisson(1) weight w(seed, b, id(r)) of the bootstrap section above, unchanged - id(r) = r, or
+ * group_of_row[r] - so two methods scored on the same rows, and runia_boot_metrics on the same ids, see the same resample.  A
+ * replicate is the tie-aware definition of the selective section on the table with every row physically repeated w times.
+ * For a run of equal keys write s, e for the cumulative weight before the run and at its end, L_s, L_e for the cumulative
+ * weighted loss sum w l there, m = e - s, d = L_e - L_s, n' for the total weight.  A run with m == 0 is no curve point; else
+ *     sum_{k = s+1 .. e} Lbar_k     = m L_s + d (m + 1) / 2
+ *     sum_{k = s+1 .. e} Lbar_k / k = L_s dH + (d / m)(m - s dH),    dH = sum_{k = s+1 .. e} 1 / k
+ *     aurc = (1 / n') sum_runs sum Lbar_k / k,    augrc = (1 / n'^2) sum_runs sum Lbar_k,    risk = L_n' / n'.
+ * dH: the per-copy terms themselves for m <= 32; beyond, the first terms up to s0 = max(s, 32) directly and
+ *     log1p((e - s0) / s0) + t(e) - t(s0), t(x) = 1/(2x) - 1/(12x^2) + 1/(120x^4) - 1/(252x^6): no loop over the copies of a run.
+ * runia_boot_sel_metrics: sorted_keys [n] ascending with sorted_rows [n] int32 (the ordered table of runia_sel_keys_* and
+ *   runia_sel_curve), loss [n] f32 (loss_f64 == 0) or f64, finite, read through the rows; group_of_row int32 [n] or NULL.
+ *   out f64 [n_boot, 4] = (aurc, augrc, risk, n') of the replicates first_replicate .. first_replicate + n_boot - 1; a
+ *   replicate with n' == 0 holds three NaN and 0.
+ *   One workgroup per Philox block of four replicates walks the table once, tile by tile; the weight counts are integers, the
+ *   weighted loss sums f64 in an order fixed by n alone; no atomics, no workspace: the same bits from call to call and for
+ *   any split of the replicates into calls.  Integer-valued losses (the 0/1 error) give exact cumulative sums.
+ *   RUNIA_E_INVALID (before any pointer is looked at) unless 1 <= n < 2^31, n_boot >= 1, first_replicate >= 0 and
+ *   first_replicate + n_boot <= 2^31.
+ * runia_boot_sel_tile_rows: rows of a tile of the walk (test sizes are derived from it). */
+int runia_boot_sel_tile_rows(void);
+int runia_boot_sel_metrics(const int64_t* sorted_keys, const int32_t* sorted_rows, const void* loss, int loss_f64, int64_t n,
+                           const int32_t* group_of_row, uint64_t seed, int64_t first_replicate, int64_t n_boot, double* out,
+                           runia_stream_t stream);
+
 /* ---- per-pixel Mahalanobis maps from segmentation features (csrc/pixel_features.hip) ------------------------------------------
  * runia_pixfeat_score: the distance of every pixel of G feature maps to the nearest of K class Gaussians with one shared
  * covariance, ONE launch, the maps read where the model left them.

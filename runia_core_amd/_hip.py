@@ -351,6 +351,9 @@ _SIGNATURES = {
     "runia_sel_query": (
         c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_void_p, c_int, c_void_p, c_int, c_int, c_void_p, c_void_p,
                 c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]),
+    "runia_boot_sel_tile_rows": (c_int, []),
+    "runia_boot_sel_metrics": (
+        c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int64, c_void_p, c_uint64, c_int64, c_int64, c_void_p, c_void_p]),
     "runia_pixfeat_workspace_bytes": (c_size_t, [c_int64, c_int64]),
     "runia_pixfeat_score": (
         c_int, [c_void_p, c_int, c_int64, c_int64, c_int64, c_int64, c_int64, c_int64, c_int64, c_int64, c_void_p, c_void_p,
@@ -2205,6 +2208,42 @@ def sel_query(curve: SelCurve, targets=(), risks=(), n_bins: int = 0):
            cov_at.data_ptr() if q else None, cov_risk.data_ptr() if r else None, bins.data_ptr() if n_bins else None,
            ws.data_ptr(), 256)
     return risk_at, cov_at, cov_risk, bins
+
+
+def boot_sel_tile_rows() -> int:
+    """Rows of one tile of the selective bootstrap walk (``runia_boot_sel_tile_rows``; a host query)."""
+    return query("runia_boot_sel_tile_rows")
+
+
+@_device_guard()
+def boot_sel_metrics(order: SelOrder, loss: torch.Tensor, n_boot: int, seed: int = 0, first_replicate: int = 0,
+                     group_of_row: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """``(aurc, augrc, risk, n')`` of the Poisson-bootstrap replicates ``first_replicate .. first_replicate + n_boot - 1`` of an
+    ordered confidence table -> device tensor ``[n_boot, 4]`` f64 (``runia_boot_sel_metrics``; three NaN where a replicate drew
+    nothing).  ``loss`` [n] (f32 or f64, finite) is read through ``order.rows``; ``group_of_row`` int32 ``[n]``: resample by
+    group.  The weights are those of :func:`boot_metrics` for the same ids.  Stream-ordered, no synchronisation."""
+    require_gpu()
+    keys, rows = order.keys, order.rows
+    if not (isinstance(keys, torch.Tensor) and isinstance(rows, torch.Tensor) and keys.is_cuda and rows.is_cuda
+            and keys.dtype == torch.int64 and rows.dtype == torch.int32):
+        raise RuniaHipError("boot_sel_metrics: keys must be int64 and rows int32 device tensors")
+    n, n_boot, first_replicate = keys.numel(), int(n_boot), int(first_replicate)
+    if not (keys.dim() == 1 and keys.is_contiguous() and rows.is_contiguous() and rows.shape == keys.shape
+            and rows.device == keys.device and 1 <= n < 2**31):
+        raise RuniaHipError("boot_sel_metrics: keys and rows must be contiguous vectors of one length in 1 .. 2^31 - 1")
+    loss = _sel_vector("boot_sel_metrics", "loss", loss, n)
+    if loss.device != keys.device:
+        raise RuniaHipError("boot_sel_metrics: loss must lie on the device of the ordered table")
+    if n_boot < 1 or first_replicate < 0:
+        raise RuniaHipError("boot_sel_metrics: n_boot >= 1 and first_replicate >= 0 are required")
+    if group_of_row is not None:
+        if not (group_of_row.is_cuda and group_of_row.dtype == torch.int32 and group_of_row.is_contiguous()
+                and group_of_row.numel() == n and group_of_row.device == keys.device):
+            raise RuniaHipError("boot_sel_metrics: group_of_row must be a contiguous int32 device tensor with one entry per row")
+    out = torch.empty((n_boot, 4), dtype=torch.float64, device=keys.device)
+    launch("runia_boot_sel_metrics", keys.data_ptr(), rows.data_ptr(), loss.data_ptr(), int(loss.dtype == torch.float64), n,
+           _ptr(group_of_row), int(seed) & (2**64 - 1), first_replicate, n_boot, out.data_ptr())
+    return out
 
 
 @_device_guard()

@@ -50,3 +50,11 @@ from .selective import (  # noqa: F401
     selective_metrics_from_logits,
     selective_results_table,
 )
+from .selective_bootstrap import (  # noqa: F401
+    SelectiveBootstrapResult,
+    SelectiveComparisonResult,
+    bootstrap_selective_metrics,
+    bootstrap_selective_metrics_from_logits,
+    bootstrap_selective_table,
+    compare_selective_methods,
+)

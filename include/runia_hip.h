@@ -1212,6 +1212,47 @@ int runia_pixfeat_gather_rows(const void* features, int dtype, int64_t G, int64_
                               int32_t* row_labels, int64_t max_rows, int64_t* n_out, void* workspace, size_t workspace_bytes,
                               runia_stream_t stream);
 
+/* ---- kernel two-sample tests: MMD and energy distance with a permutation null (csrc/shift.hip) -------------------------------
+ * Two row tables X [n, D], Y [m, D] of one dtype (0 f32, 1 f16, 2 bf16), read where they lie through their row strides (in
+ * elements, >= D); pooled Z = [X; Y], N = n + m <= 2^18.  Rows are centred by the pooled column mean (f64 column sums in a fixed
+ * order, rounded to f32) unless kind is linear.
+ *   kind       0 rbf: k = sum_b exp(-d^2 / (2 sigma_b^2)) over 1 .. 8 bandwidths;  1 energy: k = -d;  2 linear: k = z_i . z_j.
+ *              d^2 = max(0, |z_i|^2 + |z_j|^2 - 2 z_i . z_j) in f32, and 0 exactly where i == j.
+ *   memberships  permutation p (p = 0: the identity, the first n rows) puts row i in the first set iff the pair (word, i), word =
+ *              component p & 3 of philox4x32_10(counter = (i, p >> 2, 0, 0x73686674), key = (seed.lo, seed.hi)), is among the n
+ *              smallest pairs in lexicographic order: exactly n members, a pure function of (seed, p, i, n, N).
+ *   sums       with K = k(Z, Z):  t_p = a_p^T K a_p,  u_p = a_p^T K 1,  S = 1^T K 1;  AA = t, AB = u - t, BB = S - 2 u + t.
+ *   estimator  0 biased: AA / n^2 + BB / m^2 - 2 AB / (n m);  1 unbiased (n, m >= 2): (AA - dA) / (n (n - 1)) + (BB - dB) / (m (m - 1))
+ *              - 2 AB / (n m), dA / dB the sums of k_ii over either side (rbf: n / m times n_bandwidths, energy: 0, linear: the
+ *              squared norms).
+ * runia_shift_perm_bits: rows first_perm .. first_perm + n_rows - 1 of the membership table as packed bits, bits[r * row_words +
+ *   (i >> 5)] bit i & 31, row_words >= ceil(N / 32); every word of a row is written, bits past N are 0.  1 <= n < N.
+ * runia_shift_perm_bits_host: the same on HOST memory through the same header code (csrc/shift_perm.hpp), no GPU touched.
+ * runia_shift_sample_rows: M = min(N, 2048), the rows of the bandwidth sample.
+ * runia_shift_pairwise_sample: out f32 [M (M - 1) / 2], the distances |z_a - z_b| (direct differences, which centring would not
+ *   change) of the sample rows floor(k N / M), k = 0 .. M - 1, upper triangle row by row.
+ * runia_shift_mmd: bandwidths is a HOST array of n_bandwidths sigmas (> 0; read for kind 0 only).  Outputs on the device: t, u,
+ *   stats f64 [1 + n_perm] (entry 0: the observed split), S f64 [1], count int64 [1] = #{p >= 1: stats[p] >= stats[0]}, p_value f64
+ *   [1] = (1 + count) / (1 + n_perm), NaN when stats[0] is NaN (any non-finite input).  The N x N kernel matrix is never
+ *   formed: Gram tiles on the f32 matrix cores are turned into kernel values in registers, split into three exact bf16 pieces and
+ *   multiplied with the 0/1 memberships on the bf16 matrix cores, at most 1024 columns (identity and ones columns included) per
+ *   launch, f32 chains of at most 2048 terms, then f64 sums in an order fixed by the shape.  No float atomics: the same bits
+ *   from call to call.
+ *   RUNIA_E_INVALID (before anything else is looked at) unless n, m >= 1, N <= 2^18, 1 <= D < 2^31, 1 <= n_perm < 2^31.
+ *   workspace: runia_shift_workspace_bytes(n, m, D, n_perm) bytes, 16-byte aligned, uninitialised (RUNIA_E_WORKSPACE if short). */
+size_t runia_shift_workspace_bytes(int64_t n, int64_t m, int64_t d, int64_t n_perm);
+int runia_shift_perm_bits(uint64_t seed, int64_t n, int64_t N, int64_t first_perm, int64_t n_rows, uint32_t* bits,
+                          int64_t row_words, runia_stream_t stream);
+int runia_shift_perm_bits_host(uint64_t seed, int64_t n, int64_t N, int64_t first_perm, int64_t n_rows, uint32_t* bits,
+                               int64_t row_words);
+int64_t runia_shift_sample_rows(int64_t N);
+int runia_shift_pairwise_sample(const void* x, int64_t n, int64_t x_stride, const void* y, int64_t m, int64_t y_stride,
+                                int64_t d, int dtype, float* out, runia_stream_t stream);
+int runia_shift_mmd(const void* x, int64_t n, int64_t x_stride, const void* y, int64_t m, int64_t y_stride, int64_t d,
+                    int dtype, int kind, const double* bandwidths, int n_bandwidths, int estimator, uint64_t seed,
+                    int64_t n_perm, double* t, double* u, double* S, double* stats, int64_t* count, double* p_value,
+                    void* workspace, size_t workspace_bytes, runia_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -364,6 +364,15 @@ _SIGNATURES = {
         c_int, [c_void_p, c_int, c_int64, c_int64, c_int64, c_int64, c_int64, c_int64, c_int64, c_int64, c_void_p, c_int,
                 c_int64, c_int64, c_void_p, c_uint64, c_int64, c_void_p, c_void_p, c_int64, c_void_p, c_void_p, c_size_t,
                 c_void_p]),
+    "runia_shift_workspace_bytes": (c_size_t, [c_int64, c_int64, c_int64, c_int64]),
+    "runia_shift_perm_bits": (c_int, [c_uint64, c_int64, c_int64, c_int64, c_int64, c_void_p, c_int64, c_void_p]),
+    "runia_shift_perm_bits_host": (c_int, [c_uint64, c_int64, c_int64, c_int64, c_int64, c_void_p, c_int64]),
+    "runia_shift_sample_rows": (c_int64, [c_int64]),
+    "runia_shift_pairwise_sample": (
+        c_int, [c_void_p, c_int64, c_int64, c_void_p, c_int64, c_int64, c_int64, c_int, c_void_p, c_void_p]),
+    "runia_shift_mmd": (
+        c_int, [c_void_p, c_int64, c_int64, c_void_p, c_int64, c_int64, c_int64, c_int, c_int, c_void_p, c_int, c_int, c_uint64,
+                c_int64, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]),
 }
 
 
@@ -2243,6 +2252,111 @@ def boot_sel_metrics(order: SelOrder, loss: torch.Tensor, n_boot: int, seed: int
     out = torch.empty((n_boot, 4), dtype=torch.float64, device=keys.device)
     launch("runia_boot_sel_metrics", keys.data_ptr(), rows.data_ptr(), loss.data_ptr(), int(loss.dtype == torch.float64), n,
            _ptr(group_of_row), int(seed) & (2**64 - 1), first_replicate, n_boot, out.data_ptr())
+    return out
+
+
+SHIFT_KERNELS = {"rbf": 0, "energy": 1, "linear": 2}     # `kind` of runia_shift_mmd
+SHIFT_ESTIMATORS = {"biased": 0, "unbiased": 1}          # `estimator` of runia_shift_mmd
+SHIFT_MAX_ROWS = 1 << 18                                 # pooled rows of one test (the row index shares a key with the word)
+SHIFT_MAX_BANDWIDTHS = 8
+
+
+class ShiftSums(NamedTuple):
+    """Outputs of :func:`shift_mmd`, all on the device: ``t``, ``u``, ``stats`` f64 ``[1 + n_perm]`` (entry 0: the observed split),
+    ``S`` f64 ``[1]``, ``count`` int64 ``[1]``, ``p_value`` f64 ``[1]``."""
+
+    t: torch.Tensor
+    u: torch.Tensor
+    S: torch.Tensor
+    stats: torch.Tensor
+    count: torch.Tensor
+    p_value: torch.Tensor
+
+
+def _shift_perm_args(n: int, N: int, first_perm: int, n_rows: int):
+    n, N, first_perm, n_rows = int(n), int(N), int(first_perm), int(n_rows)
+    if not (1 <= n < N <= SHIFT_MAX_ROWS) or first_perm < 0 or n_rows < 1:
+        raise RuniaHipError("shift_perm_bits: 1 <= n < N <= 2^18, first_perm >= 0 and n_rows >= 1 are required")
+    return n, N, first_perm, n_rows, (N + 31) // 32
+
+
+def shift_perm_bits_host(seed: int, n: int, N: int, first_perm: int, n_rows: int) -> np.ndarray:
+    """Rows ``first_perm ...`` of the membership table of the two-sample tests as packed bits, uint32 ``[n_rows, ceil(N / 32)]``
+    (``runia_shift_perm_bits_host``): plain host code over the kernel's key function, no GPU touched."""
+    n, N, first_perm, n_rows, words = _shift_perm_args(n, N, first_perm, n_rows)
+    out = np.empty((n_rows, words), dtype=np.uint32)
+    call("runia_shift_perm_bits_host", int(seed) & (2**64 - 1), n, N, first_perm, n_rows, out.ctypes.data, words)
+    return out
+
+
+def shift_perm_bits(seed: int, n: int, N: int, first_perm: int, n_rows: int) -> torch.Tensor:
+    """The same table from the membership kernel (``runia_shift_perm_bits``): device tensor int32 ``[n_rows, ceil(N / 32)]`` holding
+    the uint32 words."""
+    n, N, first_perm, n_rows, words = _shift_perm_args(n, N, first_perm, n_rows)
+    dev = require_gpu()
+    out = torch.empty((n_rows, words), dtype=torch.int32, device=dev)
+    launch("runia_shift_perm_bits", int(seed) & (2**64 - 1), n, N, first_perm, n_rows, out.data_ptr(), words)
+    return out
+
+
+def _shift_rows(name: str, x: torch.Tensor, y: torch.Tensor):
+    """Two device row tables of one dtype (f32 / f16 / bf16) and width, each with unit column stride (row views are read in place)."""
+    for t in (x, y):
+        if not (isinstance(t, torch.Tensor) and t.is_cuda and t.dim() == 2 and t.dtype in ELEM_DTYPE_CODES):
+            raise RuniaHipError(f"{name}: rows must be 2-D float32, float16 or bfloat16 device tensors")
+    if x.dtype != y.dtype or x.shape[1] != y.shape[1] or x.device != y.device:
+        raise RuniaHipError(f"{name}: the two tables must share dtype, width and device")
+    if x.shape[0] < 1 or y.shape[0] < 1 or x.shape[1] < 1 or x.shape[0] + y.shape[0] > SHIFT_MAX_ROWS:
+        raise RuniaHipError(f"{name}: n, m, D >= 1 and n + m <= 2^18 are required")
+
+    def rows_in_place(t):
+        return t if (t.stride(1) == 1 and t.stride(0) >= t.shape[1]) or t.shape[0] == 1 and t.stride(1) == 1 else t.contiguous()
+
+    return rows_in_place(x), rows_in_place(y)
+
+
+@_device_guard()
+def shift_pairwise_sample(x: torch.Tensor, y: torch.Tensor) -> torch.Tensor:
+    """Distances between the rows of the bandwidth sample of the pooled table ``[x; y]`` (``runia_shift_pairwise_sample``): the
+    upper triangle, f32 ``[M (M - 1) / 2]``, of the ``M = min(N, 2048)`` pooled rows ``floor(k N / M)``."""
+    require_gpu()
+    x, y = _shift_rows("shift_pairwise_sample", x, y)
+    m_rows = query("runia_shift_sample_rows", x.shape[0] + y.shape[0])
+    out = torch.empty((m_rows * (m_rows - 1) // 2,), dtype=torch.float32, device=x.device)
+    launch("runia_shift_pairwise_sample", x.data_ptr(), x.shape[0], max(x.stride(0), x.shape[1]), y.data_ptr(), y.shape[0],
+           max(y.stride(0), y.shape[1]), x.shape[1], ELEM_DTYPE_CODES[x.dtype], out.data_ptr())
+    return out
+
+
+@_device_guard()
+def shift_mmd(x: torch.Tensor, y: torch.Tensor, kernel: str, bandwidths, estimator: str, n_perm: int, seed: int = 0,
+              kernel_events: Optional[list] = None) -> ShiftSums:
+    """The kernel two-sample sums and statistics of ``x`` [n, D] against ``y`` [m, D] under the observed split and ``n_perm``
+    permutations (``runia_shift_mmd``) -> :class:`ShiftSums`.  ``bandwidths``: the sigmas of the rbf kernel (host numbers, 1 .. 8 of
+    them), ignored by the other kernels.  Stream-ordered, no synchronisation; the same bits from call to call.  ``kernel_events``: a
+    list that receives the event pair of the call's first fused-kernel launch (its own start / end timestamps)."""
+    require_gpu()
+    x, y = _shift_rows("shift_mmd", x, y)
+    if kernel not in SHIFT_KERNELS or estimator not in SHIFT_ESTIMATORS:
+        raise RuniaHipError(f"shift_mmd: kernel must be one of {sorted(SHIFT_KERNELS)} and estimator of {sorted(SHIFT_ESTIMATORS)}")
+    n, m, d, n_perm = x.shape[0], y.shape[0], x.shape[1], int(n_perm)
+    bw = np.ascontiguousarray(np.atleast_1d(np.asarray(bandwidths if kernel == "rbf" else [1.0], dtype=np.float64)))
+    if n_perm < 1 or bw.ndim != 1 or not (1 <= bw.size <= SHIFT_MAX_BANDWIDTHS):
+        raise RuniaHipError("shift_mmd: n_perm >= 1 and 1 .. 8 bandwidths are required")
+    p = 1 + n_perm
+    f64 = dict(dtype=torch.float64, device=x.device)
+    out = ShiftSums(torch.empty(p, **f64), torch.empty(p, **f64), torch.empty(1, **f64), torch.empty(p, **f64),
+                    torch.empty(1, dtype=torch.int64, device=x.device), torch.empty(1, **f64))
+    ws_bytes = query("runia_shift_workspace_bytes", n, m, d, n_perm)
+    ws = workspace(ws_bytes, x.device)
+    args = (x.data_ptr(), n, max(x.stride(0), d), y.data_ptr(), m, max(y.stride(0), d), d, ELEM_DTYPE_CODES[x.dtype],
+            SHIFT_KERNELS[kernel], bw.ctypes.data, int(bw.size), SHIFT_ESTIMATORS[estimator], int(seed) & (2**64 - 1), n_perm,
+            out.t.data_ptr(), out.u.data_ptr(), out.S.data_ptr(), out.stats.data_ptr(), out.count.data_ptr(), out.p_value.data_ptr(),
+            ws.data_ptr(), ws_bytes)
+    if kernel_events is not None:
+        kernel_events.append(_timed_call("runia_shift_mmd", *args))
+    else:
+        launch("runia_shift_mmd", *args)
     return out
 
 

@@ -58,3 +58,11 @@ from .selective_bootstrap import (  # noqa: F401
     bootstrap_selective_table,
     compare_selective_methods,
 )
+from .shift import (  # noqa: F401
+    ShiftDetector,
+    ShiftTestResult,
+    energy_test,
+    median_bandwidth,
+    mmd_test,
+    shift_power_table,
+)

@@ -1253,6 +1253,44 @@ int runia_shift_mmd(const void* x, int64_t n, int64_t x_stride, const void* y, i
                     int64_t n_perm, double* t, double* u, double* S, double* stats, int64_t* count, double* p_value,
                     void* workspace, size_t workspace_bytes, runia_stream_t stream);
 
+/* ---- per-pixel kNN maps from segmentation features and the k-center coreset (csrc/pixel_knn.hip) ----------------------------
+ * runia_pixknn_score: the k smallest SQUARED Euclidean distances of every pixel of G feature maps to the M rows of a bank, and
+ * the indices of those rows, ONE launch, the maps read where the model left them.
+ *   features, dtype, G, C, H, W, sn sc sh sw   as for runia_pixfeat_score (NCHW, channels_last and sliced views in place).
+ *   center     f32 [C]: subtracted from every pixel first (x~ = x - center).
+ *   bank       f32 [M, C] row-major, ALREADY centred (b~ = b - center);  bank_sq f32 [M] = |b~|^2.
+ *   outputs    contiguous, each may be NULL, at least one set:
+ *                distances     f32 (G, k, H, W)   ascending along k
+ *                indices       int32 (G, k, H, W) on equal distances the lower bank index first
+ *                kth_distance  f32 (G, H, W)      the bits of distances[:, k - 1]
+ *                mean_distance f32 (G, H, W)      (d_0 + ... + d_{k-1}) / k, summed in that order in f32
+ *              d = max(0, |x~|^2 + (|b~|^2 - 2 x~ . b~)) in f32; the products run on v_mfma_f32_32x32x2_f32 (exact f32 chains in
+ *              channel order), |x~|^2 is one fmaf chain per lane half in channel order.  A pixel whose |x~|^2 is not finite -
+ *              NaN or inf among its features - has NaN distances and index -1 in every output; no other pixel is touched by it.
+ *   A 256-thread workgroup owns 128 consecutive pixels of the flattened G * H * W axis and walks the bank in blocks of 128 rows,
+ *   32 channels at a time through LDS (the load forms of runia_pixfeat_score: the same bits on every path); the k best of a
+ *   pixel are a sorted list in registers.  No (pixels, C) table, no f32 copy of the map, no pixels x M matrix.  Fixed
+ *   summation order, no atomics: run-to-run bit identical, and a pixel's result does not depend on its position in the batch.
+ *   1 <= C <= 1024, 1 <= k <= 16, k <= M <= 2^22, G, H, W < 2^31, G * H * W < 2^31; RUNIA_E_INVALID otherwise (checked on the
+ *   host before anything else).  G == 0 or H * W == 0: 0, nothing launched.  workspace: runia_pixknn_workspace_bytes(C, M, k)
+ *   bytes - never a function of the pixels (0 today: the arguments are kept for the ABI).
+ * runia_kcenter_greedy_f32: greedy k-center (farthest-point) selection of n_pick rows of rows f32 [N, D] row-major.  Pick 0 is
+ *   row `first`; pick t + 1 is the row with the largest squared distance to its nearest picked row, the lowest index on ties.
+ *   Distances in difference form, sum_c (x_c - centre_c)^2 in f32 in a fixed order.  One launch per pick, queued back to back.
+ *   picked int32 [n_pick], radius f32 [n_pick] (the largest min-distance at the moment of each pick: radius[0] = +inf, then
+ *   non-increasing), n_picked one device int64.  Selection stops when the largest remaining distance is not positive (every
+ *   remaining row duplicates a picked one; n_pick >= N runs out the same way): the rest of picked is -1, of radius 0.
+ *   1 <= D <= 1024, 1 <= N < 2^31, 0 <= first < N, 1 <= n_pick < 2^31; RUNIA_E_INVALID otherwise or on a NULL pointer.
+ *   workspace: runia_kcenter_workspace_bytes(N, D) bytes, 16-byte aligned, uninitialised (RUNIA_E_WORKSPACE if missing or short). */
+size_t runia_pixknn_workspace_bytes(int64_t C, int64_t M, int64_t k);
+int runia_pixknn_score(const void* features, int dtype, int64_t G, int64_t C, int64_t H, int64_t W, int64_t sn, int64_t sc,
+                       int64_t sh, int64_t sw, const float* center, const float* bank, const float* bank_sq, int64_t M,
+                       int64_t k, float* distances, int32_t* indices, float* kth_distance, float* mean_distance,
+                       void* workspace, size_t workspace_bytes, runia_stream_t stream);
+size_t runia_kcenter_workspace_bytes(int64_t N, int64_t D);
+int runia_kcenter_greedy_f32(const float* rows, int64_t N, int64_t D, int64_t first, int64_t n_pick, int32_t* picked,
+                             float* radius, int64_t* n_picked, void* workspace, size_t workspace_bytes, runia_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

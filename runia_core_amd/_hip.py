@@ -373,6 +373,13 @@ _SIGNATURES = {
     "runia_shift_mmd": (
         c_int, [c_void_p, c_int64, c_int64, c_void_p, c_int64, c_int64, c_int64, c_int, c_int, c_void_p, c_int, c_int, c_uint64,
                 c_int64, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]),
+    "runia_pixknn_workspace_bytes": (c_size_t, [c_int64, c_int64, c_int64]),
+    "runia_pixknn_score": (
+        c_int, [c_void_p, c_int, c_int64, c_int64, c_int64, c_int64, c_int64, c_int64, c_int64, c_int64, c_void_p, c_void_p,
+                c_void_p, c_int64, c_int64, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]),
+    "runia_kcenter_workspace_bytes": (c_size_t, [c_int64, c_int64]),
+    "runia_kcenter_greedy_f32": (
+        c_int, [c_void_p, c_int64, c_int64, c_int64, c_int64, c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]),
 }
 
 
@@ -1780,6 +1787,57 @@ def pixfeat_gather_rows(features: torch.Tensor, labels: torch.Tensor, keep_prob:
         launch("runia_pixfeat_gather_rows", *head, rows.data_ptr(), row_labels.data_ptr(), n, n_out.data_ptr(), ws.data_ptr(),
                need)
     return rows, row_labels
+
+
+PIXKNN_OUTPUTS = ("kth_distance", "mean_distance", "distances", "indices")
+PIXKNN_MAX_CHANNELS, PIXKNN_MAX_K, PIXKNN_MAX_BANK = 1024, 16, 1 << 22  # the limits of runia_pixknn_score
+KCENTER_MAX_COLUMNS = 1024                                               # and of runia_kcenter_greedy_f32
+
+
+@_device_guard()
+def pixknn_score(features: torch.Tensor, center: torch.Tensor, bank: torch.Tensor, bank_sq: torch.Tensor, k: int,
+                 outputs=("kth_distance",)):
+    """Per-pixel kNN maps, one launch (``runia_pixknn_score``).  ``features`` (G, C, h, w) f32 / f16 / bf16 on the device, any
+    strides, read in place; ``center`` [C], ``bank`` [M, C] (already centred) and ``bank_sq`` [M] (its squared row norms) f32
+    on the device.  Returns a dict with the requested ``outputs``: ``"distances"`` f32 (G, k, h, w) ascending, ``"indices"``
+    int32 (G, k, h, w), ``"kth_distance"`` and ``"mean_distance"`` f32 (G, h, w).  Squared Euclidean distances."""
+    assert all(o in PIXKNN_OUTPUTS for o in outputs) and len(outputs) > 0, f"outputs must be among {PIXKNN_OUTPUTS}"
+    assert features.is_cuda and features.dim() == 4 and features.dtype in ELEM_DTYPE_CODES
+    g, c, h, wd = (int(v) for v in features.shape)
+    m, k = int(bank.shape[0]), int(k)
+    for t, shape in ((center, (c,)), (bank, (m, c)), (bank_sq, (m,))):
+        assert t.is_cuda and t.dtype == torch.float32 and tuple(t.shape) == shape and t.is_contiguous()
+    require_gpu()
+    dev = features.device
+    shapes = {"kth_distance": ((g, h, wd), torch.float32), "mean_distance": ((g, h, wd), torch.float32),
+              "distances": ((g, k, h, wd), torch.float32), "indices": ((g, k, h, wd), torch.int32)}
+    out = {o: torch.empty(shapes[o][0], dtype=shapes[o][1], device=dev) for o in PIXKNN_OUTPUTS if o in outputs}
+    need = query("runia_pixknn_workspace_bytes", c, m, k)
+    ws = workspace(need, dev, 0) if need else None
+    sn, sc, sh, sw = (int(v) for v in features.stride())
+    launch("runia_pixknn_score", features.data_ptr(), ELEM_DTYPE_CODES[features.dtype], g, c, h, wd, sn, sc, sh, sw,
+           center.data_ptr(), bank.data_ptr(), bank_sq.data_ptr(), m, k, _ptr(out.get("distances")), _ptr(out.get("indices")),
+           _ptr(out.get("kth_distance")), _ptr(out.get("mean_distance")), _ptr(ws), need)
+    return {o: out[o] for o in outputs}
+
+
+@_device_guard()
+def kcenter_greedy(rows: torch.Tensor, n_pick: int, first: int = 0):
+    """Greedy k-center selection (``runia_kcenter_greedy_f32``): ``rows`` f32 (N, D) contiguous on the device -> ``(picked
+    int32 [n_pick], radius f32 [n_pick], n_picked int64 [1])`` on the device, nothing read back.  One launch per pick."""
+    assert rows.is_cuda and rows.dim() == 2 and rows.dtype == torch.float32 and rows.is_contiguous()
+    n, d = (int(v) for v in rows.shape)
+    n_pick, first = int(n_pick), int(first)
+    require_gpu()
+    dev = rows.device
+    picked = torch.empty((n_pick,), dtype=torch.int32, device=dev)
+    radius = torch.empty((n_pick,), dtype=torch.float32, device=dev)
+    n_picked = torch.zeros((1,), dtype=torch.int64, device=dev)
+    need = query("runia_kcenter_workspace_bytes", n, d)
+    ws = workspace(need, dev)
+    launch("runia_kcenter_greedy_f32", rows.data_ptr(), n, d, first, n_pick, picked.data_ptr(), radius.data_ptr(),
+           n_picked.data_ptr(), ws.data_ptr(), need)
+    return picked, radius, n_picked
 
 
 # (RUNIA_CC_TILE_H, RUNIA_CC_TILE_W) of include/runia_hip.h: the tile one workgroup of the labelling kernel owns

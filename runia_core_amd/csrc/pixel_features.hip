@@ -21,6 +21,7 @@
 // The chunk is read in one of three ways, picked per launch from the strides: four neighbouring pixels of a channel plane
 // per load (NCHW), 16 neighbouring channels of a pixel per thread (channels_last; transposed on its way into Xs), or
 // element by element through the strides (crops, odd bases).  All three fill the same Xs: the results are the same bits.
+// (The view and the staging are in pixel_map.hpp, shared with pixel_knn.hip.)
 // W is lower triangular: column block jb needs the channel chunks up to its own last row only (trapezoid form, as K2').
 // The running sums of up to 32 classes live in registers; K > 32 repeats the product per group of 32 classes (the kernel
 // is laid out for K <= 32: Cityscapes 19, VOC 21).  Every sum runs in one lane in a fixed order, no atomics: results are
@@ -33,30 +34,16 @@
 #include "common.hpp"
 #include "elem.hpp"
 #include "philox.hpp"
+#include "pixel_map.hpp"
 
 namespace {
 
 typedef float f32x16 __attribute__((ext_vector_type(16)));
 
-constexpr int kTP = 128;    // pixels per workgroup
 constexpr int kTJ = 128;    // columns of z per block
-constexpr int kKCh = 32;    // channels per staged chunk
-constexpr int kWP = 34;     // pitch of Ws (nt_tile_f32.hpp's KP)
-constexpr int kXP = 132;    // pitch of Xs and of the mz block
 constexpr int kKG = 32;     // classes whose running sums a lane keeps in registers
-constexpr int kMaxC = 1024, kMaxK = 256;
+constexpr int kMaxK = 256;
 constexpr int kChunkPix = 1024;  // pixels per chunk of the gather
-
-struct MapView {  // a (G, C, h, w) map through its strides; rows that follow one another are one long row (Wr = h * w)
-  const void* x;
-  int64_t sn, sc, sh, sw, HW, Wr, P;
-  int C;
-};
-
-__device__ __forceinline__ int64_t pixel_offset(const MapView& v, int64_t p) {
-  const int64_t g = p / v.HW, q = p - g * v.HW, hh = q / v.Wr, ww = q - hh * v.Wr;
-  return g * v.sn + hh * v.sh + ww * v.sw;
-}
 
 struct ScoreArgs {
   MapView v;
@@ -66,97 +53,6 @@ struct ScoreArgs {
   int* nearest;
   float* cd;
 };
-
-// ---- staging ------------------------------------------------------------------------------------------------------------------
-// How a workgroup reads its 32-channel x 128-pixel chunk (one per launch, picked on the host from the strides):
-//   kLoadVec    w has unit stride (NCHW): four neighbouring pixels of a channel plane per 16- / 8-byte load
-//   kLoadCLast  the channels have unit stride (channels_last): 16 neighbouring channels of a pixel per thread, 16-byte loads
-//   kLoadElem   anything else (crops, odd bases): element loads through the strides
-enum { kLoadVec = 0, kLoadElem = 1, kLoadCLast = 2 };
-
-// X chunk: thread t owns the pixel group t & 31 (four neighbouring pixels) of the channel rows (t >> 5) + 8 i, i = 0 .. 3
-template <class T, bool VEC>
-__device__ __forceinline__ void load_x(const ScoreArgs& a, const int64_t (&off)[4], int nv, int k0, int tid, float (&xr)[16]) {
-  typedef typename T::elem E;
-  const E* x = static_cast<const E*>(a.v.x);
-#pragma unroll
-  for (int i = 0; i < 4; ++i) {
-    const int c = k0 + i * 8 + (tid >> 5);
-    const bool in = c < a.v.C && nv > 0;
-    const int cc = c < a.v.C ? c : a.v.C - 1;  // (every load is issued: a row past C re-reads the last plane and is masked)
-    float t[4];
-    if constexpr (VEC) {
-      const E* p = x + off[0] + (int64_t)cc * a.v.sc;
-      if (nv > 0) {
-        if constexpr (T::kBytes == 4) ld16<T>(p, t);
-        else ld8<T>(p, t);
-      } else {
-        t[0] = t[1] = t[2] = t[3] = 0.f;
-      }
-    } else {
-#pragma unroll
-      for (int j = 0; j < 4; ++j) t[j] = j < nv ? widen(T{}, x[off[j] + (int64_t)cc * a.v.sc]) : 0.f;
-    }
-#pragma unroll
-    for (int j = 0; j < 4; ++j) xr[4 * i + j] = (in && j < nv) ? t[j] : 0.f;
-  }
-}
-
-__device__ __forceinline__ void store_x(const float (&xr)[16], float (*Xs)[kXP], const float* m0s, int k0, int tid) {
-#pragma unroll
-  for (int i = 0; i < 4; ++i) {
-    const int row = i * 8 + (tid >> 5);
-    const float m = m0s[k0 + row];  // 0 past C: the padding stays 0
-    *reinterpret_cast<float4*>(&Xs[row][4 * (tid & 31)]) =
-        make_float4(xr[4 * i] - m, xr[4 * i + 1] - m, xr[4 * i + 2] - m, xr[4 * i + 3] - m);
-  }
-}
-
-// channels_last: thread t owns channels 16 (t & 1) .. + 15 of the chunk for pixel t >> 1
-template <class T>
-__device__ __forceinline__ void load_x_cl(const ScoreArgs& a, int64_t off, bool valid, int k0, int tid, float (&xr)[16]) {
-  typedef typename T::elem E;
-  const int kb = k0 + (tid & 1) * 16;
-  const int kc = kb < a.v.C ? kb : 0;  // (a half past C reads nothing)
-  const E* p = static_cast<const E*>(a.v.x) + off + kc;
-  if (valid && kb + 16 <= a.v.C) {
-#pragma unroll
-    for (int i = 0; i < 16 / T::V; ++i) ld16<T>(p + i * T::V, xr + i * T::V);
-  } else {
-#pragma unroll
-    for (int i = 0; i < 16; ++i) xr[i] = (valid && kb + i < a.v.C) ? widen(T{}, p[i]) : 0.f;
-  }
-}
-
-__device__ __forceinline__ void store_x_cl(const float (&xr)[16], float (*Xs)[kXP], const float* m0s, int k0, int tid) {
-  const int pix = tid >> 1, r0 = (tid & 1) * 16;
-#pragma unroll
-  for (int i = 0; i < 16; ++i) Xs[r0 + i][pix] = xr[i] - m0s[k0 + r0 + i];
-}
-
-// W chunk: rows j0 .. j0 + 127, columns k0 .. k0 + 31 of the row-major [C, C] matrix, zero outside it
-__device__ __forceinline__ void load_w(const float* __restrict__ W, int C, int j0, int k0, int tid, bool vec, float (&wr)[16]) {
-  const int row = tid >> 1, half = tid & 1;
-  const int j = j0 + row, kb = k0 + half * 16;
-  const float* p = W + (int64_t)j * C + kb;
-  if (j < C && vec && kb + 16 <= C) {
-#pragma unroll
-    for (int i = 0; i < 4; ++i) {
-      const float4 t = reinterpret_cast<const float4*>(p)[i];
-      wr[4 * i] = t.x; wr[4 * i + 1] = t.y; wr[4 * i + 2] = t.z; wr[4 * i + 3] = t.w;
-    }
-  } else {
-#pragma unroll
-    for (int i = 0; i < 16; ++i) wr[i] = (j < C && kb + i < C) ? p[i] : 0.f;
-  }
-}
-
-__device__ __forceinline__ void store_w(const float (&wr)[16], float (*Ws)[kWP], int tid) {
-  const int row = tid >> 1, half = tid & 1;
-#pragma unroll
-  for (int i = 0; i < 8; ++i)
-    *reinterpret_cast<float2*>(&Ws[row][half * 16 + 2 * i]) = make_float2(wr[2 * i], wr[2 * i + 1]);
-}
 
 // ---- the score kernel -----------------------------------------------------------------------------------------------------------
 template <class T, int LOAD>
@@ -175,19 +71,8 @@ __global__ __launch_bounds__(256) void pixfeat_score_kernel(ScoreArgs a) {
   for (int c = tid; c < kMaxC; c += 256) m0s[c] = c < C ? a.m0[c] : 0.f;
 
   // the four pixels (channels_last: the one pixel) this thread stages
-  int64_t off[4] = {0, 0, 0, 0};
-  int nv;
-  if constexpr (LOAD == kLoadCLast) {
-    const int64_t ps = p0 + (tid >> 1);
-    nv = ps < a.v.P ? 1 : 0;
-    off[0] = nv ? pixel_offset(a.v, ps) : 0;
-  } else {
-    const int64_t ps = p0 + 4 * (tid & 31);
-    const int64_t left = a.v.P - ps;
-    nv = left >= 4 ? 4 : (left > 0 ? (int)left : 0);
-#pragma unroll
-    for (int j = 0; j < 4; ++j) off[j] = (VEC ? j == 0 && nv > 0 : j < nv) ? pixel_offset(a.v, ps + j) : 0;
-  }
+  int64_t off[4];
+  const int nv = staged_pixels<LOAD>(a.v, p0, tid, off);
   // the pixel whose sums this lane holds
   const int64_t pm = p0 + wave * 32 + li;
   const bool mine = pm < a.v.P;
@@ -216,9 +101,9 @@ __global__ __launch_bounds__(256) void pixfeat_score_kernel(ScoreArgs a) {
         for (int r = 0; r < 16; ++r) acc[t][r] = 0.f;
       const int kend = j0 + kTJ < C ? j0 + kTJ : C;  // W[j, c] = 0 for c > j: the chunks past the block's last row are skipped
       float xr[16], wr[16];
-      if constexpr (LOAD == kLoadCLast) load_x_cl<T>(a, off[0], nv > 0, 0, tid, xr);
-      else load_x<T, VEC>(a, off, nv, 0, tid, xr);
-      load_w(a.W, C, j0, 0, tid, a.vecw != 0, wr);
+      if constexpr (LOAD == kLoadCLast) load_x_cl<T>(a.v, off[0], nv > 0, 0, tid, xr);
+      else load_x<T, VEC>(a.v, off, nv, 0, tid, xr);
+      load_w(a.W, C, C, j0, 0, tid, a.vecw != 0, wr);
       for (int k0 = 0; k0 < kend; k0 += kKCh) {
         __syncthreads();  // every wave has finished reading the previous chunk
         if constexpr (LOAD == kLoadCLast) store_x_cl(xr, Xs, m0s, k0, tid);
@@ -226,9 +111,9 @@ __global__ __launch_bounds__(256) void pixfeat_score_kernel(ScoreArgs a) {
         store_w(wr, Ws, tid);
         __syncthreads();
         if (k0 + kKCh < kend) {  // next chunk's loads fly while the matrix cores consume this one
-          if constexpr (LOAD == kLoadCLast) load_x_cl<T>(a, off[0], nv > 0, k0 + kKCh, tid, xr);
-          else load_x<T, VEC>(a, off, nv, k0 + kKCh, tid, xr);
-          load_w(a.W, C, j0, k0 + kKCh, tid, a.vecw != 0, wr);
+          if constexpr (LOAD == kLoadCLast) load_x_cl<T>(a.v, off[0], nv > 0, k0 + kKCh, tid, xr);
+          else load_x<T, VEC>(a.v, off, nv, k0 + kKCh, tid, xr);
+          load_w(a.W, C, C, j0, k0 + kKCh, tid, a.vecw != 0, wr);
         }
 #pragma unroll
         for (int s = 0; s < kKCh / 4; ++s) {
@@ -427,42 +312,6 @@ __global__ __launch_bounds__(256) void pixfeat_gather_write_kernel(GatherArgs a)
 }
 
 // ---- host side --------------------------------------------------------------------------------------------------------------------
-constexpr int64_t kLim = 0x7fffffffll;
-
-bool view_ok(int64_t G, int64_t C, int64_t H, int64_t W, int64_t sn, int64_t sc, int64_t sh, int64_t sw) {
-  return G >= 0 && H >= 0 && W >= 0 && C >= 1 && G <= kLim && H <= kLim && W <= kLim && sn >= 0 && sc >= 0 && sh >= 0 &&
-         sw >= 0 && (G == 0 || H * W == 0 || G * H * W <= (kLim << 6));
-}
-
-MapView make_view(const void* x, int64_t G, int64_t C, int64_t H, int64_t W, int64_t sn, int64_t sc, int64_t sh, int64_t sw) {
-  MapView v;
-  v.x = x;
-  v.sn = sn; v.sc = sc; v.sh = sh; v.sw = sw;
-  v.HW = H * W;
-  v.P = G * v.HW;
-  v.C = (int)C;
-  const bool flat = H == 1 || sh == W * sw;
-  v.Wr = flat ? v.HW : W;
-  if (flat) v.sh = 0;  // (hh is always 0)
-  return v;
-}
-
-// four neighbouring pixels from a multiple of four of the flat pixel axis are one aligned load
-bool view_allows_vec(const MapView& v, int64_t G, int64_t H, int elem_bytes) {
-  auto ok = [](int64_t stride, int64_t extent) { return extent <= 1 || stride % 4 == 0; };
-  const bool flat = v.Wr == v.HW;
-  return v.sw == 1 && v.Wr % 4 == 0 && (flat || ok(v.sh, H)) && ok(v.sc, v.C) && ok(v.sn, G) &&
-         reinterpret_cast<uintptr_t>(v.x) % (4 * elem_bytes) == 0;
-}
-
-// 16 neighbouring channels of a pixel are aligned 16-byte loads (T::V elements each)
-bool view_allows_clast(const MapView& v, int64_t G, int64_t H, int elems_per_16) {
-  auto ok = [&](int64_t stride, int64_t extent) { return extent <= 1 || stride % elems_per_16 == 0; };
-  const bool flat = v.Wr == v.HW;
-  return v.sc == 1 && v.C >= 16 && ok(v.sw, v.Wr) && (flat || ok(v.sh, H)) && ok(v.sn, G) &&
-         reinterpret_cast<uintptr_t>(v.x) % 16 == 0;
-}
-
 }  // namespace
 
 extern "C" size_t runia_pixfeat_workspace_bytes(int64_t C, int64_t K) {

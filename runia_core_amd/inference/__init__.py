@@ -36,6 +36,12 @@ from .pixel_features import (  # noqa: F401
     get_pixel_mahalanobis_maps,
     pixel_feature_rows,
 )
+from .pixel_knn import (  # noqa: F401
+    PixelKNN,
+    fit_pixel_knn,
+    get_pixel_knn_maps,
+    kcenter_greedy,
+)
 from .postprocessors import (  # noqa: F401
     ASH,
     DDU,

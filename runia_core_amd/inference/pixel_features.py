@@ -27,13 +27,13 @@ _DTYPES = (torch.float32, torch.float16, torch.bfloat16)
 _LABEL_DTYPES = (torch.int64, torch.int32, torch.uint8)
 
 
-def _check_outputs(outputs) -> tuple:
+def _check_outputs(outputs, maps=PIXEL_FEATURE_OUTPUTS) -> tuple:
     outputs = (outputs,) if isinstance(outputs, str) else tuple(outputs)
     if not outputs:
-        raise ValueError(f"nothing requested: outputs is empty (the maps are {PIXEL_FEATURE_OUTPUTS})")
+        raise ValueError(f"nothing requested: outputs is empty (the maps are {maps})")
     for o in outputs:
-        if o not in PIXEL_FEATURE_OUTPUTS:
-            raise ValueError(f"unknown output {o!r}: the maps are {PIXEL_FEATURE_OUTPUTS}")
+        if o not in maps:
+            raise ValueError(f"unknown output {o!r}: the maps are {maps}")
     if len(set(outputs)) != len(outputs):
         raise ValueError(f"an output is named twice in {outputs}")
     return outputs

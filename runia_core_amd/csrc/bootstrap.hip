@@ -39,6 +39,7 @@ template <typename T>
 __device__ __forceinline__ int64_t boot_key(T v, bool squash) {
   if (squash) v = (T)1 / ((T)1 + exp(-v));  // torch.sigmoid in the dtype of the scores (metrics.hip: score_key)
   uint64_t b = (uint64_t)__double_as_longlong((double)v + 0.0);  // (-0.0 and +0.0 share a key)
+  if (v != v) b = 0x7ff8000000000000ull;  // every NaN, of either sign and any payload: one key in front of +inf's (as score_key)
   b = (b >> 63) ? ~b : (b | 0x8000000000000000ull);              // ascending-sortable
   return (int64_t)(~b ^ 0x8000000000000000ull);                  // descending, as a signed number
 }

@@ -14,6 +14,9 @@
 //     all become 0.0 and tie;
 //   * curve points are float32 (tps, fps converted to f32 and divided in f32), the trapezoid terms are formed in f32.
 //     The reference then adds them in f32; here they are accumulated in f64 (differences ~1e-7, the test tolerance).
+// Settled here, where the reference is ill-defined (its non-stable sort makes every NaN a curve point of its own, in an
+// unspecified order): all NaN scores, of either sign and any payload, are ONE tie group at the top of the descending order
+// (score_key).
 #include "common.hpp"
 
 namespace {
@@ -25,7 +28,7 @@ constexpr int kTile = METRICS_TILE;  // elements per workgroup in every pass
 constexpr int kItems = kTile / 256;
 
 __device__ __forceinline__ uint64_t sortable_desc(double v) {
-  // ascending order of the key == descending order of v (NaN keys sort first, as a "largest" value)
+  // ascending order of the key == descending order of v (score_key gives every NaN one key in front of +inf's)
   uint64_t b = (uint64_t)__double_as_longlong(v);
   b = (b >> 63) ? ~b : (b | 0x8000000000000000ull);  // ascending-sortable
   return ~b;
@@ -295,9 +298,15 @@ struct MsdState {
   unsigned long long split[kMsdBuckets];  // round 6: splitter keys of the equalised buckets (msd_split_kernel)
 };
 
+// Every NaN score - either sign, any payload - takes ONE key, that of the positive quiet NaN: the smallest key in use, in
+// front of +inf.  All NaNs are one tie group at the top of the descending order (one curve point), whatever sign the
+// sigmoid hands back; by its bits a NaN with the sign bit set would sort behind -inf and NaNs of two payloads would be
+// two runs.  (The key differs from the ~0 padding of wave_sort_load, which no score can produce any more.)
+constexpr uint64_t kNanKey = 0x0007ffffffffffffull;  // sortable_desc of 0x7ff8000000000000
 template <typename T>
 __device__ __forceinline__ uint64_t score_key(T v, bool squash) {
   if (squash) v = (T)1 / ((T)1 + exp(-v));  // torch.sigmoid in the dtype of the scores
+  if (v != v) return kNanKey;
   return sortable_desc((double)v + 0.0);     // (-0.0 and +0.0 share a key: one tie group, as torchmetrics)
 }
 
@@ -388,8 +397,8 @@ __device__ __forceinline__ ProbeResult msd_reduce_probe(MsdState* st, unsigned n
 // score set in one of them).  b = (int)((largest - v) * scale) is monotone in v (a subtraction, a product with a positive
 // factor and a truncation are), so the buckets follow the key order; the keys descend with the scores and the sigmoid is
 // monotone, so the range of the squashed scores is [sigmoid(smallest), sigmoid(largest)] - two exps per workgroup instead of
-// one per score in the probe.  +inf and NaN keys at the low end of the key space go to the first bucket, -inf and NaN keys
-// at the high end to the last (the sort inside a bucket uses the whole key).
+// one per score in the probe.  The NaN key and +inf lie below every splitter and go to the first bucket, -inf to the last
+// (the sort inside a bucket uses the whole key).
 __device__ __forceinline__ double unkey(uint64_t k) {  // inverse of sortable_desc
   uint64_t b = ~k;
   b = (b >> 63) ? (b & 0x7fffffffffffffffull) : ~b;
@@ -428,7 +437,8 @@ __device__ __forceinline__ double msd_lin_pos(double raw, const MsdRange& r) {
 // the sketch: finite raw scores per linear bin - of every kSketchStride-th score once the set is large (a quarter of 2 M
 // scores still puts ~120 into an average bin; the launch is a pass over the scores with LDS atomics, 19 us -> ~7 at 2 M)
 constexpr int kSketchStride = 4;
-constexpr int64_t kSketchAll = 1 << 17;  // up to here every score is counted
+constexpr int64_t kSketchAll = 1 << 17;  // up to here every score is counted (not reachable through ood_metrics, which runs the
+                                         // sketch above 64 * kMsdBuckets = 262 144 scores only: msd_lin_hist_kernel's step is 4 there)
 // Splitter e (1 .. nb - 1) of the bucket function: the key of the raw score at which the bucket index steps from e - 1 to e -
 // squashed like every other key - made non-decreasing by a running maximum over e (so that "number of splitters <= key" is a
 // monotone function of the key whatever the rounding of the lines below).  cum / cnt: the sketch (exclusive scan of the bin

@@ -64,10 +64,6 @@ struct Front {
   double base_l[4], pl[4];  // the weighted loss likewise
 };
 
-__device__ __forceinline__ double bs_shfl_up_f64(double v, int o) {
-  return __hiloint2double(__shfl_up(__double2hiint(v), o, 64), __shfl_up(__double2loint(v), o, 64));
-}
-
 __device__ __forceinline__ double bs_load(const void* p, int is_f64, int64_t i) {
   return is_f64 ? reinterpret_cast<const double*>(p)[i] : (double)reinterpret_cast<const float*>(p)[i];
 }
@@ -113,34 +109,30 @@ __device__ __forceinline__ void bs_front(const int64_t* __restrict__ keys, const
       has_end = true;
     }
   }
-  uint32_t xw[4];
-  double xl[4];
+  // weighted loss and weight up to and with the thread; the last thread with a run end
+  struct Run { double l[4]; uint32_t w[4]; int m; } run;
 #pragma unroll
-  for (int j = 0; j < 4; ++j) { xw[j] = accw[j]; xl[j] = accl[j]; }
-  int m = has_end ? tid : -1;
+  for (int j = 0; j < 4; ++j) { run.w[j] = accw[j]; run.l[j] = accl[j]; }
+  run.m = has_end ? tid : -1;
+  run = wave_scan_incl(run, [](const Run& lower, Run own) {
 #pragma unroll
-  for (int o = 1; o < 64; o <<= 1) {
-    uint32_t yw[4];
-    double yl[4];
-#pragma unroll
-    for (int j = 0; j < 4; ++j) { yw[j] = __shfl_up(xw[j], o, 64); yl[j] = bs_shfl_up_f64(xl[j], o); }
-    const int q = __shfl_up(m, o, 64);
-    if (lane >= o) {
-#pragma unroll
-      for (int j = 0; j < 4; ++j) { xw[j] += yw[j]; xl[j] = yl[j] + xl[j]; }
-      m = max(m, q);
-    }
-  }
+    for (int j = 0; j < 4; ++j) { own.w[j] += lower.w[j]; own.l[j] = lower.l[j] + own.l[j]; }
+    own.m = max(own.m, lower.m);
+    return own;
+  });
+  const uint32_t(&xw)[4] = run.w;
+  const double(&xl)[4] = run.l;
+  const int m = run.m;
   // exclusive values of the lane
   uint32_t ew[4];
   double el[4];
 #pragma unroll
   for (int j = 0; j < 4; ++j) {
-    ew[j] = __shfl_up(xw[j], 1, 64);
-    el[j] = bs_shfl_up_f64(xl[j], 1);
+    ew[j] = lane_up(xw[j], 1);
+    el[j] = lane_up(xl[j], 1);
     if (lane == 0) { ew[j] = 0u; el[j] = 0.0; }
   }
-  int pe = __shfl_up(m, 1, 64);
+  int pe = lane_up(m, 1);
   if (lane == 0) pe = -1;
   __syncthreads();  // the previous tile's reads of `sh` are over
 #pragma unroll
@@ -286,11 +278,8 @@ __global__ __launch_bounds__(kThreads) void boot_sel_kernel(const int64_t* __res
   // the sums of the workgroup, in a fixed order
 #pragma unroll
   for (int j = 0; j < 4; ++j) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) {
-      sum_a[j] += shfl_xor_f64(sum_a[j], o);
-      sum_g[j] += shfl_xor_f64(sum_g[j], o);
-    }
+    sum_a[j] = wave_sum(sum_a[j]);
+    sum_g[j] = wave_sum(sum_g[j]);
     if (lane == 0) { sa[wave][j] = sum_a[j]; sg[wave][j] = sum_g[j]; }
   }
   __syncthreads();

@@ -137,22 +137,18 @@ __device__ __forceinline__ void boot_front(const int64_t* __restrict__ keys, con
       has_end = true;
     }
   }
-  uint32_t x[4];
+  struct Run { uint32_t x[4]; int m; } run;  // packed weights up to and with the thread; the last thread with a run end
 #pragma unroll
-  for (int j = 0; j < 4; ++j) x[j] = acc[j];
-  int m = has_end ? tid : -1;
+  for (int j = 0; j < 4; ++j) run.x[j] = acc[j];
+  run.m = has_end ? tid : -1;
+  run = wave_scan_incl(run, [](const Run& lower, Run own) {
 #pragma unroll
-  for (int o = 1; o < 64; o <<= 1) {
-    uint32_t y[4];
-#pragma unroll
-    for (int j = 0; j < 4; ++j) y[j] = __shfl_up(x[j], o, 64);
-    const int q = __shfl_up(m, o, 64);
-    if (lane >= o) {
-#pragma unroll
-      for (int j = 0; j < 4; ++j) x[j] += y[j];
-      m = max(m, q);
-    }
-  }
+    for (int j = 0; j < 4; ++j) own.x[j] += lower.x[j];
+    own.m = max(own.m, lower.m);
+    return own;
+  });
+  const uint32_t(&x)[4] = run.x;
+  const int m = run.m;
   __syncthreads();  // the previous tile's reads of `sh` are over
   if (lane == 63) {
 #pragma unroll
@@ -176,7 +172,7 @@ __device__ __forceinline__ void boot_front(const int64_t* __restrict__ keys, con
     if (w < wave) before = max(before, e);
     all = max(all, e);
   }
-  int pe = __shfl_up(m, 1, 64);
+  int pe = lane_up(m, 1);
   if (lane == 0) pe = -1;
   pe = max(pe, before);
 #pragma unroll
@@ -198,10 +194,6 @@ __device__ __forceinline__ void boot_front(const int64_t* __restrict__ keys, con
 // precision at a curve point; 1 where nothing has been counted yet (the curve's closing point, rows that all drew 0)
 __device__ __forceinline__ double boot_precision(u64 tp, u64 fp) {
   return (tp + fp == 0ull) ? 1.0 : (double)tp / (double)(tp + fp);
-}
-
-__device__ __forceinline__ u64 shfl_xor_u64(u64 v, int o) {
-  return ((u64)(unsigned)__shfl_xor((int)(unsigned)(v >> 32), o, 64) << 32) | (u64)(unsigned)__shfl_xor((int)(unsigned)v, o, 64);
 }
 
 __global__ __launch_bounds__(kThreads) void boot_replicates_kernel(const int64_t* __restrict__ keys,
@@ -277,11 +269,8 @@ __global__ __launch_bounds__(kThreads) void boot_replicates_kernel(const int64_t
   // the sums of the workgroup, in a fixed order
 #pragma unroll
   for (int j = 0; j < 4; ++j) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) {
-      roc[j] += shfl_xor_u64(roc[j], o);
-      pr[j] += shfl_xor_f64(pr[j], o);
-    }
+    roc[j] = wave_sum(roc[j]);
+    pr[j] = wave_sum(pr[j]);
     if (lane == 0) { sroc[wave][j] = roc[j]; spr[wave][j] = pr[j]; }
   }
   if (tid == 0) tstart_s = (int)ntiles;

@@ -290,17 +290,6 @@ static inline int64_t reduce_blocks(int64_t N) {
   return N > 0 ? (N + r - 1) / r : 1;
 }
 
-__device__ __forceinline__ int64_t wave_sum_i64(int64_t v) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v += __double_as_longlong(shfl_xor_f64(__longlong_as_double(v), o));  // (bits only)
-  return v;
-}
-__device__ __forceinline__ double wave_sum_f64(double v) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v += shfl_xor_f64(v, o);
-  return v;
-}
-
 // b = clamp((int)ceilf(conf * (float)n_bins) - 1, 0, n_bins - 1); a NaN goes to bin 0 (and makes its conf_sum NaN)
 __device__ __forceinline__ int conf_bin(float conf, int n_bins) {
   const float t = ceilf(conf * (float)n_bins);
@@ -354,7 +343,7 @@ __global__ __launch_bounds__(kRedThreads) void calib_partial_kernel(const int32_
         const bool mine = b == bb;
         const uint64_t members = __ballot(mine);
         const uint64_t hits = __ballot(mine && hit);
-        const double cs = wave_sum_f64(mine ? (double)c : 0.0);
+        const double cs = wave_sum(mine ? (double)c : 0.0);
         if (lane == 0) {
           w_conf[bb] += cs;
           w_cnt[bb] += __popcll(members);
@@ -364,12 +353,12 @@ __global__ __launch_bounds__(kRedThreads) void calib_partial_kernel(const int32_
       }
     }
   }
-  n_used = wave_sum_i64(n_used);
-  n_correct = wave_sum_i64(n_correct);
-  s_nll = wave_sum_f64(s_nll);
-  s_brier = wave_sum_f64(s_brier);
-  s_g = wave_sum_f64(s_g);
-  s_h = wave_sum_f64(s_h);
+  n_used = wave_sum(n_used);
+  n_correct = wave_sum(n_correct);
+  s_nll = wave_sum(s_nll);
+  s_brier = wave_sum(s_brier);
+  s_g = wave_sum(s_g);
+  s_h = wave_sum(s_h);
   if (lane == 0) {
     ired[wave][0] = n_used;
     ired[wave][1] = n_correct;

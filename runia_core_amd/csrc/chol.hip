@@ -17,13 +17,6 @@ constexpr int kCholWaves = 16;
 constexpr int kCholRows = 4;  // rows a wave works on at once (their loads overlap)
 
 template <typename T>
-__device__ __forceinline__ T wave_sum_fixed(T v) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-  return v;
-}
-
-template <typename T>
 __global__ __launch_bounds__(64 * kCholWaves) void cholesky_kernel(T* __restrict__ a, int64_t D, T jitter, int* __restrict__ info) {
   T* m = a + (int64_t)blockIdx.x * D * D;
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
@@ -47,7 +40,7 @@ __global__ __launch_bounds__(64 * kCholWaves) void cholesky_kernel(T* __restrict
       }
 #pragma unroll
       for (int r = 0; r < kCholRows; ++r) {
-        const T s = wave_sum_fixed(acc[r]);
+        const T s = wave_sum(acc[r]);
         const int64_t i = i0 + r;
         if (lane == 0 && i < D) m[i * D + j] = (m[i * D + j] + ((i == j) ? jitter : (T)0)) - s;
       }

@@ -7,6 +7,7 @@
 #include <atomic>
 
 #include "../../include/runia_hip.h"
+#include "wave.hpp"
 
 #define RUNIA_WAVE 64
 
@@ -133,36 +134,6 @@ __device__ __forceinline__ float torch_row_sum(F term, int n) {
 }
 
 __device__ __forceinline__ double kInfD() { return __builtin_inf(); }
-
-__device__ __forceinline__ float wave_max_f32(float v) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v = fmaxf(v, __shfl_xor(v, o, 64));
-  return v;
-}
-__device__ __forceinline__ float wave_sum_f32(float v) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-  return v;
-}
-// (value, index) of a row maximum, first index on ties (np.argmax); a NaN entry never wins (fmaxf drops it as well)
-constexpr int kNoIndex = 0x7fffffff;
-__device__ __forceinline__ void best_take(float& bv, int& bi, float v, int i) {
-  if (v > bv || (v == bv && i < bi)) { bv = v; bi = i; }
-}
-__device__ __forceinline__ void wave_best(float& bv, int& bi) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) {
-    const float v = __shfl_xor(bv, o, 64);
-    const int i = __shfl_xor(bi, o, 64);
-    best_take(bv, bi, v, i);
-  }
-}
-__device__ __forceinline__ double shfl_xor_f64(double v, int o) {
-  int lo = __double2loint(v), hi = __double2hiint(v);
-  lo = __shfl_xor(lo, o, 64);
-  hi = __shfl_xor(hi, o, 64);
-  return __hiloint2double(hi, lo);
-}
 
 // ---- GEN's transcendentals on the transcendental unit (v_exp_f32 / v_log_f32 are base-2 and ~1 ulp) -------------------
 // The library expf / powf cost ~20 / ~170 vector instructions each; the wave-per-row GEN kernel spent half its issue slots

@@ -189,29 +189,6 @@ __global__ __launch_bounds__(kThreads) void cc_merge_kernel(int* P, int H, int W
   report(err, err_word);
 }
 
-// ---- block scan of one int per thread (256 threads): exclusive prefix and the block total --------------------------------------
-__device__ __forceinline__ int block_excl_scan(int v, int* s_wave, int& total) {
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  int inc = v;
-#pragma unroll
-  for (int o = 1; o < 64; o <<= 1) {
-    const int u = __shfl_up(inc, o, 64);
-    if (lane >= o) inc += u;
-  }
-  __syncthreads();  // (s_wave of the previous trip has been read)
-  if (lane == 63) s_wave[wave] = inc;
-  __syncthreads();
-  int before = 0, all = 0;
-#pragma unroll
-  for (int w = 0; w < kThreads / 64; ++w) {
-    const int t = s_wave[w];
-    before += w < wave ? t : 0;
-    all += t;
-  }
-  total = all;
-  return before + inc - v;
-}
-
 // ---- 3: flatten, count the roots of every chunk -------------------------------------------------------------------------------
 __global__ __launch_bounds__(kThreads) void cc_flatten_kernel(int* P, int64_t HW, int cpi, int* __restrict__ chunk_count,
                                                               unsigned* err_word) {
@@ -232,7 +209,8 @@ __global__ __launch_bounds__(kThreads) void cc_flatten_kernel(int* P, int64_t HW
     roots += r == me;
   }
   int total;
-  block_excl_scan(roots, s_wave, total);
+  __syncthreads();
+  block_scan_excl<kThreads>(roots, s_wave, total);
   if (threadIdx.x == 0) chunk_count[blockIdx.x] = total;
   report(err, err_word);
 }
@@ -247,7 +225,8 @@ __global__ __launch_bounds__(kThreads) void cc_scan_kernel(const int* __restrict
     const int c = c0 + threadIdx.x;
     const int v = c < cpi ? chunk_count[row + c] : 0;
     int total;
-    const int ex = block_excl_scan(v, s_wave, total);
+    __syncthreads();  // (s_wave of the previous trip has been read)
+    const int ex = block_scan_excl<kThreads>(v, s_wave, total);
     if (c < cpi) chunk_base[row + c] = carry + ex;
     carry += total;
   }
@@ -265,7 +244,8 @@ __global__ __launch_bounds__(kThreads) void cc_rank_kernel(int* __restrict__ P, 
     const int64_t i = start + k * kThreads + threadIdx.x;
     const bool root = i < HW && P[base + i] == (int)(base + i);
     int total;
-    const int ex = block_excl_scan(root ? 1 : 0, s_wave, total);
+    __syncthreads();  // (s_wave of the previous trip has been read)
+    const int ex = block_scan_excl<kThreads>(root ? 1 : 0, s_wave, total);
     if (root) P[base + i] = -(running + ex + 1) - 1;
     running += total;
   }

@@ -165,8 +165,7 @@ __global__ __launch_bounds__(64 * kRowWaves) void conformal_label_wave_kernel(co
     }
     c.s0 = wave_sum_f32(c.s0);
     c.a = wave_sum_f32(c.a);
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) c.before += __shfl_xor(c.before, o, 64);
+    c.before = wave_sum(c.before);
     if (lane == 0) finish_label(M, u, score, rank, row, m, c, xy, used);
   }
 }
@@ -219,8 +218,7 @@ struct Group {
 template <int TPR>
 __device__ __forceinline__ float group_max(float v, float* red) {
   using G = Group<TPR>;
-#pragma unroll
-  for (int o = G::kWidth / 2; o > 0; o >>= 1) v = fmaxf(v, __shfl_xor(v, o, 64));
+  v = wave_reduce<G::kWidth>(v, [](float a, float b) { return fmaxf(a, b); });
   if constexpr (G::kWaves > 1) {
     if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = v;
     __syncthreads();
@@ -234,8 +232,7 @@ __device__ __forceinline__ float group_max(float v, float* red) {
 template <int TPR>
 __device__ __forceinline__ int group_sum(int v, int* red) {
   using G = Group<TPR>;
-#pragma unroll
-  for (int o = G::kWidth / 2; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
+  v = wave_sum<G::kWidth>(v);
   if constexpr (G::kWaves > 1) {
     if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = v;
     __syncthreads();
@@ -442,12 +439,9 @@ __global__ __launch_bounds__(kRedThreads) void conformal_reduce_kernel(const int
       if (hit) add_i64(class_covered + y, 1);
     }
   }
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) {
-    used += __double_as_longlong(shfl_xor_f64(__longlong_as_double(used), o));  // (bits only)
-    cov += __double_as_longlong(shfl_xor_f64(__longlong_as_double(cov), o));
-    sum += __double_as_longlong(shfl_xor_f64(__longlong_as_double(sum), o));
-  }
+  used = wave_sum(used);
+  cov = wave_sum(cov);
+  sum = wave_sum(sum);
   if ((threadIdx.x & 63) == 0 && used) {
     add_i64(out + 0, used);
     add_i64(out + 1, cov);

@@ -69,15 +69,6 @@ __device__ __forceinline__ void sweep(const char* row, int V, bool aligned, F f)
   }
 }
 
-__device__ __forceinline__ u64 shfl_xor_u64(u64 v, int o) {
-  const uint32_t lo = __shfl_xor((uint32_t)v, o, 64), hi = __shfl_xor((uint32_t)(v >> 32), o, 64);
-  return ((u64)hi << 32) | lo;
-}
-__device__ __forceinline__ u64 shfl_up_u64(u64 v, int o) {
-  const uint32_t lo = __shfl_up((uint32_t)v, o, 64), hi = __shfl_up((uint32_t)(v >> 32), o, 64);
-  return ((u64)hi << 32) | lo;
-}
-
 // The workgroup's reductions: every thread calls them, every thread gets the result; `red` is free again on return.
 struct Red {
   u64 m[kThreads / 64];
@@ -86,11 +77,8 @@ struct Red {
 };
 
 __device__ __forceinline__ void block_max_flag(float& m, int& bad, Red& red) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) {
-    m = fmaxf(m, __shfl_xor(m, o, 64));
-    bad |= __shfl_xor(bad, o, 64);
-  }
+  m = wave_max_f32(m);
+  bad = wave_or(bad);
   if ((threadIdx.x & 63) == 0) {
     red.f[threadIdx.x >> 6] = m;
     red.c[threadIdx.x >> 6] = (uint32_t)bad;
@@ -102,11 +90,8 @@ __device__ __forceinline__ void block_max_flag(float& m, int& bad, Red& red) {
 }
 
 __device__ __forceinline__ void block_sum(uint32_t& c, u64& m, Red& red) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) {
-    c += __shfl_xor(c, o, 64);
-    m += shfl_xor_u64(m, o);
-  }
+  c = wave_sum(c);
+  m = wave_sum(m);
   if ((threadIdx.x & 63) == 0) {
     red.c[threadIdx.x >> 6] = c;
     red.m[threadIdx.x >> 6] = m;
@@ -120,17 +105,8 @@ __device__ __forceinline__ void block_sum(uint32_t& c, u64& m, Red& red) {
 // (c, m) <- their sums over the threads before this one; (tc, tm) <- over all threads
 __device__ __forceinline__ void block_exclusive_scan(uint32_t& c, u64& m, uint32_t& tc, u64& tm, Red& red) {
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  uint32_t ic = c;
-  u64 im = m;
-#pragma unroll
-  for (int o = 1; o < 64; o <<= 1) {
-    const uint32_t a = __shfl_up(ic, o, 64);
-    const u64 b = shfl_up_u64(im, o);
-    if (lane >= o) {
-      ic += a;
-      im += b;
-    }
-  }
+  const uint32_t ic = wave_scan_incl(c);
+  const u64 im = wave_scan_incl(m);
   if (lane == 63) {
     red.c[wave] = ic;
     red.m[wave] = im;

@@ -90,17 +90,8 @@ __device__ __forceinline__ unsigned hist_select24(Load load, int64_t count, unsi
     unsigned ssum = 0;
 #pragma unroll
     for (int j = 0; j < 16; ++j) ssum += hb[j];
-    unsigned incl = ssum;  // inclusive prefix within the wave
-    const int lane = tid & 63;
-#pragma unroll
-    for (int o = 1; o < 64; o <<= 1) {
-      const unsigned up = __shfl_up(incl, o, 64);
-      if (lane >= o) incl += up;
-    }
-    if (lane == 63) part[tid >> 6] = incl;
-    __syncthreads();
-    unsigned before = incl - ssum;  // entries in the groups below this one
-    for (int w = 0; w < (tid >> 6); ++w) before += part[w];
+    unsigned all;
+    const unsigned before = block_scan_excl<256>(ssum, part, all);  // entries in the groups below this one
     // exactly one owner: before < rank <= before + ssum; the last group takes whatever is left (as the serial walk did)
     if ((before < rank && rank <= before + ssum && tid < 255) || (tid == 255 && before < rank)) {
       unsigned r = rank - before, b = 0;

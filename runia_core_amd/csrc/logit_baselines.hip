@@ -235,9 +235,7 @@ __global__ __launch_bounds__(256) void klm_score_kernel(const float* __restrict_
     for (int a = 0; a < 2; ++a)
 #pragma unroll
       for (int r = 0; r < 16; ++r) {
-        float v = best[a][r];
-#pragma unroll
-        for (int o = 16; o > 0; o >>= 1) v = max_nan(v, __shfl_xor(v, o, 64));
+        const float v = wave_reduce<32>(best[a][r], [](float x, float y) { return max_nan(x, y); });
         if (li == 0) red[wb][wq * 64 + a * 32 + (r & 3) + 8 * (r >> 2) + 4 * lh] = v;
       }
     __syncthreads();

@@ -59,10 +59,6 @@ __device__ __forceinline__ void merge(T& m, T& s, T& u, int& bad, const P& q) {
   u = hu + (r > (T)0 ? r * (lu + d * l1) : (T)0);
 }
 
-__device__ __forceinline__ Partial shfl_xor_partial(const Partial& p, int o) {
-  return Partial{__shfl_xor(p.m, o, 64), __shfl_xor(p.s, o, 64), __shfl_xor(p.u, o, 64), __shfl_xor(p.bad, o, 64)};
-}
-
 // ---- partial -----------------------------------------------------------------------------------------------------------
 // block = (row r = t * B + b, chunk c); lane i holds elements c*kChunk + (k*256 + i)*W + e of the row, k < kPerLane / W
 template <class T>
@@ -111,9 +107,9 @@ __global__ __launch_bounds__(kThreads) void partial_kernel(const StepDesc* __res
   }
   // fixed-order reduction: butterfly in the wave, then the four waves in order
   Partial p{m, s, u, bad};
-#pragma unroll
+#pragma unroll  // (hand-written: the butterfly runs from 1 up, wave_reduce merges from the widest step down)
   for (int o = 1; o < 64; o <<= 1) {
-    const Partial q = shfl_xor_partial(p, o);
+    const Partial q = lane_xor(p, o);
     merge(p.m, p.s, p.u, p.bad, q);
   }
   __shared__ Partial waves[kThreads / 64];
@@ -169,13 +165,10 @@ __global__ __launch_bounds__(1024) void sequence_kernel(const float* __restrict_
       sl += (double)lp;
       if (lp != -__builtin_inff()) { sv += (double)lp; nv += 1.0; }
     }
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) {
-      se += __shfl_xor(se, o, 64);
-      sl += __shfl_xor(sl, o, 64);
-      sv += __shfl_xor(sv, o, 64);
-      nv += __shfl_xor(nv, o, 64);
-    }
+    se = wave_sum(se);
+    sl = wave_sum(sl);
+    sv = wave_sum(sv);
+    nv = wave_sum(nv);
     if (lane == 0) {
       seq[b] = se / (double)T;
       seq[B + b] = -sl / (double)T;

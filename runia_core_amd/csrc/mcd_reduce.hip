@@ -89,7 +89,7 @@ __global__ __launch_bounds__(256) void mcd_seg_wave_kernel(McdArgs a, int team_l
     const typename T::elem* p = x + b * a.sb + c * a.sc + (oh * a.sth) * a.sh;
     for (int r = 0; r < nrows; ++r) acc += seg_sum<T>(p + r * a.sh, rowlen, g, team);
   }
-  for (int o = team >> 1; o; o >>= 1) acc += __shfl_xor(acc, o);
+  for (int o = team >> 1; o; o >>= 1) acc += __shfl_xor(acc, o);  // (a run-time team width: stays a loop)
   if (live && g == 0) out_row(a, b)[c * a.OH + oh] = acc / a.div;
 }
 
@@ -107,7 +107,7 @@ __global__ __launch_bounds__(1024) void mcd_plane_block_kernel(McdArgs a, int nr
   } else {  // one wave per row
     for (int r = tid >> 6; r < nrows; r += nthr >> 6) acc += seg_sum<T>(p + r * a.sh, rowlen, tid & 63, 64);
   }
-  for (int o = 32; o; o >>= 1) acc += __shfl_xor(acc, o);
+  acc = wave_sum(acc);
   if ((tid & 63) == 0) part[tid >> 6] = acc;
   __syncthreads();
   if (tid == 0) {

@@ -54,12 +54,9 @@ __device__ __forceinline__ void tile_summary_body(const uint64_t* __restrict__ k
       if (i == n - 1 || keys[i] != keys[i + 1]) { e = (int)i; ++cnt; }  // indices ascend with c
     }
   }
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) {
-    s += __shfl_xor(s, o, 64);
-    cnt += __shfl_xor(cnt, o, 64);
-    e = max(e, __shfl_xor(e, o, 64));
-  }
+  s = wave_sum(s);
+  cnt = wave_sum(cnt);
+  e = wave_max(e);
   if (lane == 0) { ssum[wave] = s; send[wave] = e; scnt[wave] = cnt; }
   __syncthreads();
   if (tid == 0) {
@@ -97,12 +94,9 @@ __device__ __forceinline__ void tile_prefix_body(const uint64_t* __restrict__ ke
     unsigned ps = 0u, pc = 0u;
     int pe = -1;
     for (unsigned t = tid; t < tile; t += 256) { ps += tile_sum[t]; pc += tile_cnt[t]; pe = max(pe, tile_end[t]); }
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) {
-      ps += __shfl_xor(ps, o, 64);
-      pc += __shfl_xor(pc, o, 64);
-      pe = max(pe, __shfl_xor(pe, o, 64));
-    }
+    ps = wave_sum(ps);
+    pc = wave_sum(pc);
+    pe = wave_max(pe);
     if (lane == 0) { wsum[wave] = ps; wcnt[wave] = pc; wend[wave] = pe; }
     __syncthreads();
     if (tid == 0) {
@@ -117,14 +111,8 @@ __device__ __forceinline__ void tile_prefix_body(const uint64_t* __restrict__ ke
     const bool valid = i < n;
     const unsigned l = valid ? lab[i] : 0u;
     const bool is_end = valid && (i == n - 1 || keys[i] != keys[i + 1]);
-    unsigned x = l;
-    int m = is_end ? (int)i : -1;
-#pragma unroll
-    for (int o = 1; o < 64; o <<= 1) {
-      const unsigned y = __shfl_up(x, o, 64);
-      const int q = __shfl_up(m, o, 64);
-      if (lane >= o) { x += y; m = max(m, q); }
-    }
+    const unsigned x = wave_scan_incl(l);
+    const int m = wave_scan_incl(is_end ? (int)i : -1, [](int a, int b) { return max(a, b); });
     const uint64_t ends = __ballot(is_end);
     const unsigned ends_before = (unsigned)__popcll(ends & ((lane == 0) ? 0ull : (~0ull >> (64 - lane))));
     if (lane == 63) { wsum[wave] = x; wend[wave] = m; wcnt[wave] = (unsigned)__popcll(ends); }
@@ -135,7 +123,7 @@ __device__ __forceinline__ void tile_prefix_body(const uint64_t* __restrict__ ke
     const unsigned cs = carry_sum, cc = carry_cnt;
     const int ce = carry_end;
     // exclusive maximum of the run-end indices before i
-    int excl = __shfl_up(m, 1, 64);
+    int excl = lane_up(m, 1);
     if (lane == 0) excl = -1;
     excl = max(max(excl, wmax), ce);
     if (valid) {
@@ -232,13 +220,9 @@ __device__ __forceinline__ void curve_terms_body(const uint64_t* __restrict__ ke
       pr += (double)((rec0 - rec) * (prec0 + prec));
     }
   }
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) {
-    roc += shfl_xor_f64(roc, o);
-    pr += shfl_xor_f64(pr, o);
-    const unsigned lo = __shfl_xor((unsigned)first, o, 64), hi = __shfl_xor((unsigned)(first >> 32), o, 64);
-    first = min(first, ((unsigned long long)hi << 32) | lo);
-  }
+  roc = wave_sum(roc);
+  pr = wave_sum(pr);
+  first = wave_reduce(first, [](unsigned long long a, unsigned long long b) { return min(a, b); });
   if (lane == 0) { sroc[wave] = roc; spr[wave] = pr; sidx[wave] = first; }
   __syncthreads();
   if (tid == 0) {
@@ -342,13 +326,8 @@ __global__ __launch_bounds__(256) void msd_probe_kernel(const T* __restrict__ in
     }
   }
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) {
-    const unsigned long long a = ((unsigned long long)__shfl_xor((unsigned)(mn >> 32), o, 64) << 32) | __shfl_xor((unsigned)mn, o, 64);
-    const unsigned long long b = ((unsigned long long)__shfl_xor((unsigned)(mx >> 32), o, 64) << 32) | __shfl_xor((unsigned)mx, o, 64);
-    mn = a < mn ? a : mn;
-    mx = b > mx ? b : mx;
-  }
+  mn = wave_reduce(mn, [](unsigned long long a, unsigned long long b) { return b < a ? b : a; });
+  mx = wave_max(mx);
   if (lane == 0) { smin[wave] = mn; smax[wave] = mx; }
   const bool any_bad = __syncthreads_or(bad);
   if (threadIdx.x == 0) {
@@ -373,14 +352,9 @@ __device__ __forceinline__ ProbeResult msd_reduce_probe(MsdState* st, unsigned n
     b = q.kmax > b ? q.kmax : b;
     bad |= q.bad;
   }
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) {
-    const unsigned long long a2 = ((unsigned long long)__shfl_xor((unsigned)(a >> 32), o, 64) << 32) | __shfl_xor((unsigned)a, o, 64);
-    const unsigned long long b2 = ((unsigned long long)__shfl_xor((unsigned)(b >> 32), o, 64) << 32) | __shfl_xor((unsigned)b, o, 64);
-    a = a2 > a ? a2 : a;
-    b = b2 > b ? b2 : b;
-    bad |= __shfl_xor(bad, o, 64);
-  }
+  a = wave_max(a);
+  b = wave_max(b);
+  bad = wave_or(bad);
   if (lane == 0) { rmin[wave] = a; rmax[wave] = b; rbad[wave] = bad; }
   __syncthreads();
   if (tid == 0) {
@@ -448,7 +422,7 @@ __device__ __forceinline__ void msd_make_splitters(const MsdRange& rg, bool squa
                                                    const unsigned* __restrict__ cnt, double buckets_per_key, int nb,
                                                    unsigned long long* __restrict__ out) {
   __shared__ unsigned long long wmax_s[4];
-  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int tid = threadIdx.x;
   const int per = (nb + 255) / 256;  // consecutive entries per thread (<= 16)
   uint64_t run = 0ull, mine[kMsdBuckets / 256];
 #pragma unroll
@@ -490,18 +464,9 @@ __device__ __forceinline__ void msd_make_splitters(const MsdRange& rg, bool squa
       mine[j] = run;
     }
   }
-  uint64_t x = run;
-#pragma unroll
-  for (int o = 1; o < 64; o <<= 1) {
-    const uint64_t y = ((uint64_t)(unsigned)__shfl_up((int)(unsigned)(x >> 32), o, 64) << 32) | (unsigned)__shfl_up((int)(unsigned)x, o, 64);
-    if (lane >= o) x = y > x ? y : x;
-  }
-  uint64_t before = ((uint64_t)(unsigned)__shfl_up((int)(unsigned)(x >> 32), 1, 64) << 32) | (unsigned)__shfl_up((int)(unsigned)x, 1, 64);
-  if (lane == 0) before = 0ull;
   __syncthreads();  // (wmax_s may still be read by a previous caller's threads)
-  if (lane == 63) wmax_s[wave] = x;
-  __syncthreads();
-  for (int w = 0; w < wave; ++w) before = wmax_s[w] > before ? wmax_s[w] : before;
+  unsigned long long all;
+  const unsigned long long before = block_scan_excl<256>((unsigned long long)run, [](unsigned long long a, unsigned long long b) { return a > b ? a : b; }, 0ull, wmax_s, all);
 #pragma unroll
   for (int j = 0; j < kMsdBuckets / 256; ++j) {
     const int e = tid * per + j;
@@ -545,30 +510,21 @@ template <typename T>
 __global__ __launch_bounds__(256) void msd_split_kernel(unsigned* __restrict__ any_outside, MsdState* st, unsigned n_probe_recs) {
   __shared__ unsigned cum_s[kMsdBuckets], cnt_s[kMsdBuckets];
   __shared__ unsigned wsum_s[4];
-  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int tid = threadIdx.x;
   const ProbeResult pr = msd_reduce_probe(st, n_probe_recs, any_outside);
   const MsdRange rg = msd_range_of(pr.nkmin, pr.kmax);
   constexpr int PER = kMsdBuckets / 256;
   unsigned v[PER], tot = 0u;
 #pragma unroll
   for (int j = 0; j < PER; ++j) { v[j] = st->lin[tid * PER + j]; tot += v[j]; }
-  unsigned x = tot;
-#pragma unroll
-  for (int o = 1; o < 64; o <<= 1) {
-    const unsigned y = __shfl_up(x, o, 64);
-    if (lane >= o) x += y;
-  }
-  if (lane == 63) wsum_s[wave] = x;
-  __syncthreads();
-  unsigned off = x - tot;
-  for (int w = 0; w < wave; ++w) off += wsum_s[w];
+  unsigned finite_total;
+  unsigned off = block_scan_excl<256>(tot, wsum_s, finite_total);
 #pragma unroll
   for (int j = 0; j < PER; ++j) {
     cum_s[tid * PER + j] = off;
     cnt_s[tid * PER + j] = v[j];
     off += v[j];
   }
-  const unsigned finite_total = wsum_s[0] + wsum_s[1] + wsum_s[2] + wsum_s[3];
   __syncthreads();
   const int e = (int)blockIdx.x * 256 + tid;
   uint64_t sk = 0ull;
@@ -606,21 +562,13 @@ __global__ __launch_bounds__(256) void msd_scatter_kernel(const uint64_t* __rest
   {
     // the exclusive scan of the bucket counts, by every workgroup for itself (16 KB of counts from L2) instead of by one
     // workgroup in a launch of its own in front of this one; workgroup 0 leaves it in st->start for the sort
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int tid = threadIdx.x;
     constexpr int PER = kMsdBuckets / 256;
     unsigned v[PER], tot = 0u;
 #pragma unroll
     for (int j = 0; j < PER; ++j) { v[j] = st->hist[tid * PER + j]; tot += v[j]; }
-    unsigned x = tot;
-#pragma unroll
-    for (int o = 1; o < 64; o <<= 1) {
-      const unsigned y = __shfl_up(x, o, 64);
-      if (lane >= o) x += y;
-    }
-    if (lane == 63) wsum[wave] = x;
-    __syncthreads();
-    unsigned off = x - tot;
-    for (int w = 0; w < wave; ++w) off += wsum[w];
+    unsigned all;
+    unsigned off = block_scan_excl<256>(tot, wsum, all);
 #pragma unroll
     for (int j = 0; j < PER; ++j) {
       first[tid * PER + j] = off;
@@ -705,9 +653,8 @@ __device__ __forceinline__ void wave_sort_network(uint64_t (&k)[PER], unsigned (
 #pragma unroll
         for (int r = 0; r < PER; ++r) {
           const uint64_t a = k[r];
-          const uint64_t o = ((uint64_t)(unsigned)__shfl_xor((int)(unsigned)(a >> 32), dl, 64) << 32) |
-                             (uint64_t)(unsigned)__shfl_xor((int)(unsigned)a, dl, 64);
-          const unsigned ol = (unsigned)__shfl_xor((int)l[r], dl, 64);
+          const uint64_t o = lane_xor(a, dl);
+          const unsigned ol = lane_xor(l[r], dl);
           const bool take = want_small ? (a > o) : (a < o);
           k[r] = take ? o : a;
           l[r] = take ? ol : l[r];
@@ -761,9 +708,7 @@ __device__ __forceinline__ unsigned long long bucket_diff_bits(const uint64_t* _
     const uint64_t k0 = k[0];
     unsigned long long d = 0ull;
     for (unsigned i = tid; i < nb; i += 256) d |= k[i] ^ k0;
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1)
-      d |= ((unsigned long long)__shfl_xor((unsigned)(d >> 32), o, 64) << 32) | __shfl_xor((unsigned)d, o, 64);
+    d = wave_or(d);
     if (lane == 0 && d) atomicOr(&diff_s, d);
   }
   __syncthreads();
@@ -785,18 +730,8 @@ __device__ __forceinline__ void bucket_radix_sort(uint64_t*& src_k, uint8_t*& sr
     for (unsigned i = tid; i < nb; i += 256) atomicAdd(&base[(unsigned)(src_k[i] >> shift) & 255u], 1u);
     __syncthreads();
     {
-      const unsigned v = base[tid];
-      unsigned x = v;
-#pragma unroll
-      for (int o = 1; o < 64; o <<= 1) {
-        const unsigned y = __shfl_up(x, o, 64);
-        if (lane >= o) x += y;
-      }
-      if (lane == 63) dsum[wave] = x;
-      __syncthreads();
-      unsigned woff = 0u;
-      for (int w = 0; w < wave; ++w) woff += dsum[w];
-      base[tid] = woff + x - v;
+      unsigned all;
+      base[tid] = block_scan_excl<256>(base[tid], dsum, all);
     }
 #pragma unroll
     for (int w = 0; w < 4; ++w) wcnt[w][tid] = 0u;
@@ -909,13 +844,9 @@ __global__ __launch_bounds__(256) void curve_terms_finalize_kernel(const uint64_
     pr += __hip_atomic_load(&parts[b].pr_sum, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
     first = min(first, __hip_atomic_load(&parts[b].fpr95_idx, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT));
   }
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) {
-    roc += shfl_xor_f64(roc, o);
-    pr += shfl_xor_f64(pr, o);
-    const unsigned lo = __shfl_xor((unsigned)first, o, 64), hi = __shfl_xor((unsigned)(first >> 32), o, 64);
-    first = min(first, ((unsigned long long)hi << 32) | lo);
-  }
+  roc = wave_sum(roc);
+  pr = wave_sum(pr);
+  first = wave_reduce(first, [](unsigned long long a, unsigned long long b) { return min(a, b); });
   if (lane == 0) { sroc[wave] = roc; spr[wave] = pr; sidx[wave] = first; }
   __syncthreads();
   if (tid == 0) {
@@ -959,7 +890,6 @@ __global__ __launch_bounds__(256) void msd_keys_split_kernel(const T* __restrict
   for (int b = tid; b < kMsdBuckets; b += 256) lh[b] = 0u;
   if (equalise) {  // (uniform) the splitters of the equalised buckets (msd_split_kernel), made non-decreasing by a running maximum
     __shared__ unsigned long long wmax_l[4];
-    const int lane = tid & 63, wave = tid >> 6;
     constexpr int PER = kMsdBuckets / 256;
     uint64_t mine[PER], run = 0ull;
 #pragma unroll
@@ -968,17 +898,8 @@ __global__ __launch_bounds__(256) void msd_keys_split_kernel(const T* __restrict
       run = v > run ? v : run;
       mine[j] = run;
     }
-    uint64_t x = run;
-#pragma unroll
-    for (int o = 1; o < 64; o <<= 1) {
-      const uint64_t y = ((uint64_t)(unsigned)__shfl_up((int)(unsigned)(x >> 32), o, 64) << 32) | (unsigned)__shfl_up((int)(unsigned)x, o, 64);
-      if (lane >= o) x = y > x ? y : x;
-    }
-    uint64_t before = ((uint64_t)(unsigned)__shfl_up((int)(unsigned)(x >> 32), 1, 64) << 32) | (unsigned)__shfl_up((int)(unsigned)x, 1, 64);
-    if (lane == 0) before = 0ull;
-    if (lane == 63) wmax_l[wave] = x;
-    __syncthreads();
-    for (int w = 0; w < wave; ++w) before = wmax_l[w] > before ? wmax_l[w] : before;
+    unsigned long long all;
+    const unsigned long long before = block_scan_excl<256>((unsigned long long)run, [](unsigned long long a, unsigned long long b) { return a > b ? a : b; }, 0ull, wmax_l, all);
 #pragma unroll
     for (int j = 0; j < PER; ++j) split[tid * PER + j] = mine[j] > before ? mine[j] : before;
   } else {         // raw-linear buckets, nbk of them over the range of the finite scores
@@ -1059,15 +980,9 @@ __device__ __forceinline__ void wave_bucket_curve(const uint64_t* __restrict__ k
   unsigned tp[PER], s = 0u;
 #pragma unroll
   for (int r = 0; r < PER; ++r) { s += l[r]; tp[r] = s; }
-  unsigned x = s;
-#pragma unroll
-  for (int o = 1; o < 64; o <<= 1) {
-    const unsigned y = __shfl_up(x, o, 64);
-    if (lane >= o) x += y;
-  }
-  const unsigned off = x - s;
+  const unsigned off = wave_scan_incl(s) - s;
   // run ends: the key differs from the next one; the bucket's last key always ends a run
-  const uint64_t next0 = ((uint64_t)(unsigned)__shfl_down((int)(unsigned)(k[0] >> 32), 1, 64) << 32) | (unsigned)__shfl_down((int)(unsigned)k[0], 1, 64);
+  const uint64_t next0 = lane_down(k[0], 1);
   bool end[PER];
   uint64_t pm[PER], run = 0ull;  // (element + 1) << 32 | positives at it, of the last run end before element r of this lane
 #pragma unroll
@@ -1079,13 +994,7 @@ __device__ __forceinline__ void wave_bucket_curve(const uint64_t* __restrict__ k
     const uint64_t packed = ((uint64_t)(e + 1u) << 32) | (uint64_t)(off + tp[r]);
     run = end[r] ? packed : run;  // indices rise with r: the latest run end is the maximum
   }
-  uint64_t m = run;
-#pragma unroll
-  for (int o = 1; o < 64; o <<= 1) {
-    const uint64_t y = ((uint64_t)(unsigned)__shfl_up((int)(unsigned)(m >> 32), o, 64) << 32) | (unsigned)__shfl_up((int)(unsigned)m, o, 64);
-    if (lane >= o) m = y > m ? y : m;
-  }
-  uint64_t carry = ((uint64_t)(unsigned)__shfl_up((int)(unsigned)(m >> 32), 1, 64) << 32) | (unsigned)__shfl_up((int)(unsigned)m, 1, 64);
+  uint64_t carry = lane_up(wave_scan_incl(run, [](uint64_t a, uint64_t b) { return a > b ? a : b; }), 1);
   if (lane == 0) carry = 0ull;
 #pragma unroll
   for (int r = 0; r < PER; ++r) {
@@ -1125,8 +1034,7 @@ __global__ __launch_bounds__(256) void msd_sort_curve_kernel(uint64_t* __restric
   {
     unsigned q = 0u;
     for (int c = tid; c < b0; c += 256) q += (unsigned)(st->cursor64[c] >> 32);
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) q += __shfl_xor(q, o, 64);
+    q = wave_sum(q);
     if (lane == 0) psum[wave] = q;
     __syncthreads();
     before_pos = psum[0] + psum[1] + psum[2] + psum[3];
@@ -1175,16 +1083,8 @@ __global__ __launch_bounds__(256) void msd_sort_curve_kernel(uint64_t* __restric
       uint64_t pmj[4], run = 0ull;
 #pragma unroll
       for (int j = 0; j < 4; ++j) { ssum += ll[j]; tpj[j] = ssum; }
-      unsigned x = ssum;
-#pragma unroll
-      for (int o = 1; o < 64; o <<= 1) {
-        const unsigned y = __shfl_up(x, o, 64);
-        if (lane >= o) x += y;
-      }
-      if (lane == 63) dsum[wave] = x;
-      __syncthreads();
-      unsigned off = x - ssum + carry_tp_s;
-      for (int w = 0; w < wave; ++w) off += dsum[w];
+      unsigned all_tp;
+      const unsigned off = block_scan_excl<256>(ssum, dsum, all_tp) + carry_tp_s;
 #pragma unroll
       for (int j = 0; j < 4; ++j) {
         const unsigned e = e0 + j;
@@ -1192,18 +1092,9 @@ __global__ __launch_bounds__(256) void msd_sort_curve_kernel(uint64_t* __restric
         pmj[j] = run;
         run = endj[j] ? (((uint64_t)(e + 1u) << 32) | (uint64_t)(off + tpj[j])) : run;
       }
-      uint64_t m = run;
-#pragma unroll
-      for (int o = 1; o < 64; o <<= 1) {
-        const uint64_t y = ((uint64_t)(unsigned)__shfl_up((int)(unsigned)(m >> 32), o, 64) << 32) | (unsigned)__shfl_up((int)(unsigned)m, o, 64);
-        if (lane >= o) m = y > m ? y : m;
-      }
-      uint64_t carry = ((uint64_t)(unsigned)__shfl_up((int)(unsigned)(m >> 32), 1, 64) << 32) | (unsigned)__shfl_up((int)(unsigned)m, 1, 64);
-      if (lane == 0) carry = 0ull;
-      if (lane == 63) wprev[wave] = m;
-      __syncthreads();
+      unsigned long long all_prev;  // the chunk's last run end
+      unsigned long long carry = block_scan_excl<256>((unsigned long long)run, [](unsigned long long a, unsigned long long b) { return a > b ? a : b; }, 0ull, wprev, all_prev);
       carry = carry > carry_prev_s ? carry : carry_prev_s;
-      for (int w = 0; w < wave; ++w) carry = wprev[w] > carry ? wprev[w] : carry;
 #pragma unroll
       for (int j = 0; j < 4; ++j) {
         if (!endj[j]) continue;
@@ -1220,8 +1111,7 @@ __global__ __launch_bounds__(256) void msd_sort_curve_kernel(uint64_t* __restric
       __syncthreads();
       if (tid == 255) {
         carry_tp_s = off + ssum;
-        const uint64_t mm = m > carry ? m : carry;
-        carry_prev_s = mm;
+        carry_prev_s = all_prev > carry ? all_prev : carry;
       }
       __syncthreads();
     }
@@ -1231,12 +1121,12 @@ __global__ __launch_bounds__(256) void msd_sort_curve_kernel(uint64_t* __restric
     double roc = acc.roc, prs = acc.pr;
     unsigned long long fi = acc.first_idx;
     unsigned ffp = acc.first_fp;
+    roc = wave_sum(roc);
+    prs = wave_sum(prs);
 #pragma unroll
-    for (int o = 32; o > 0; o >>= 1) {
-      roc += shfl_xor_f64(roc, o);
-      prs += shfl_xor_f64(prs, o);
-      const unsigned long long oi = ((unsigned long long)__shfl_xor((unsigned)(fi >> 32), o, 64) << 32) | __shfl_xor((unsigned)fi, o, 64);
-      const unsigned of = __shfl_xor(ffp, o, 64);
+    for (int o = 32; o > 0; o >>= 1) {  // (the smallest index and the count that goes with it)
+      const unsigned long long oi = lane_xor(fi, o);
+      const unsigned of = lane_xor(ffp, o);
       if (oi < fi) { fi = oi; ffp = of; }
     }
     __syncthreads();
@@ -1276,12 +1166,12 @@ __global__ __launch_bounds__(256) void msd_sort_curve_kernel(uint64_t* __restric
     const unsigned of = __hip_atomic_load(&parts[g].first_fp, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
     if (oi < fi) { fi = oi; ffp = of; }
   }
+  roc = wave_sum(roc);
+  prs = wave_sum(prs);
 #pragma unroll
   for (int o = 32; o > 0; o >>= 1) {
-    roc += shfl_xor_f64(roc, o);
-    prs += shfl_xor_f64(prs, o);
-    const unsigned long long oi = ((unsigned long long)__shfl_xor((unsigned)(fi >> 32), o, 64) << 32) | __shfl_xor((unsigned)fi, o, 64);
-    const unsigned of = __shfl_xor(ffp, o, 64);
+    const unsigned long long oi = lane_xor(fi, o);
+    const unsigned of = lane_xor(ffp, o);
     if (oi < fi) { fi = oi; ffp = of; }
   }
   if (lane == 0) { sroc[wave] = roc; spr[wave] = prs; sidx[wave] = fi; sfp[wave] = ffp; }

@@ -313,25 +313,7 @@ struct I3 {
   int a, b, c;
 };
 
-// inclusive block scan of three int counters; returns the block total in *tot
-__device__ I3 block_scan3(I3 v, I3* tot, I3* sh) {
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-#pragma unroll
-  for (int o = 1; o < 64; o <<= 1) {
-    const int x = __shfl_up(v.a, o, 64), y = __shfl_up(v.b, o, 64), z = __shfl_up(v.c, o, 64);
-    if (lane >= o) v.a += x, v.b += y, v.c += z;
-  }
-  if (lane == 63) sh[wave] = v;
-  __syncthreads();
-  I3 pre = {0, 0, 0};
-  for (int w = 0; w < wave; ++w) pre.a += sh[w].a, pre.b += sh[w].b, pre.c += sh[w].c;
-  I3 t = {0, 0, 0};
-  for (int w = 0; w < kCurveThreads / 64; ++w) t.a += sh[w].a, t.b += sh[w].b, t.c += sh[w].c;
-  *tot = t;
-  __syncthreads();
-  v.a += pre.a, v.b += pre.b, v.c += pre.c;
-  return v;
-}
+__device__ __forceinline__ I3 operator+(I3 x, I3 y) { return I3{x.a + y.a, x.b + y.b, x.c + y.c}; }
 
 // inclusive suffix max within the block (thread order reversed)
 __device__ double block_suffix_max(double v, double* sh) {
@@ -399,9 +381,9 @@ __global__ void __launch_bounds__(kCurveThreads) curves_kernel(
       v.c = (f >> 2) & 1;
     }
     I3 tot;
-    I3 s = block_scan3(v, &tot, sh3);
-    s.a += carry.a, s.b += carry.b, s.c += carry.c;
-    carry.a += tot.a, carry.b += tot.b, carry.c += tot.c;
+    const I3 s = carry + block_scan_excl<kCurveThreads>(v, [](I3 x, I3 y) { return x + y; }, I3{0, 0, 0}, sh3, tot) + v;
+    __syncthreads();  // (sh3 is free for the next trip)
+    carry = carry + tot;
     if (r < nd) {
       const double tp = (double)s.a, fp = (double)s.b;
       const double rec = npos[c] > 0 ? tp / np_ : tp;

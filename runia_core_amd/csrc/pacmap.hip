@@ -340,10 +340,10 @@ __global__ void __launch_bounds__(kStepThreads) pacmap_step_kernel(
       for (int c = 0; c < CM; ++c) g[c] = fmaf(w, dy[c], g[c]);
     }
   }
-#pragma unroll
+#pragma unroll  // (hand-written: the butterfly runs from 1 up, wave_reduce adds from the widest step down)
   for (int o = 1; o < kStepLanes; o <<= 1)
 #pragma unroll
-    for (int c = 0; c < CM; ++c) g[c] += __shfl_xor(g[c], o, 64);
+    for (int c = 0; c < CM; ++c) g[c] += lane_xor(g[c], o);
   if (!live || sub >= nc) return;
   // lane `sub` updates component `sub` (registers are indexed statically)
   float gc = 0.f, yc = 0.f;

@@ -221,27 +221,6 @@ __device__ __forceinline__ int kept_label(const GatherArgs& a, int64_t p) {
   return runia_philox::to_uniform(b.x) < a.keep_prob[l] ? (int)l : -1;
 }
 
-// exclusive scan of one int per thread over the 256 threads, in thread order; total in `total`
-__device__ __forceinline__ int block_scan_256(int v, int* wsum, int& total) {
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  int s = v;
-#pragma unroll
-  for (int o = 1; o < 64; o <<= 1) {
-    const int t = __shfl_up(s, o, 64);
-    if (lane >= o) s += t;
-  }
-  if (lane == 63) wsum[wave] = s;
-  __syncthreads();
-  int base = 0;
-  total = 0;
-#pragma unroll
-  for (int w = 0; w < 4; ++w) {
-    if (w < wave) base += wsum[w];
-    total += wsum[w];
-  }
-  return base + s - v;
-}
-
 __global__ __launch_bounds__(256) void pixfeat_gather_count_kernel(GatherArgs a) {
   __shared__ int wsum[4];
   const int64_t p = (int64_t)blockIdx.x * kChunkPix + 4 * threadIdx.x;
@@ -249,7 +228,7 @@ __global__ __launch_bounds__(256) void pixfeat_gather_count_kernel(GatherArgs a)
 #pragma unroll
   for (int j = 0; j < 4; ++j) n += kept_label(a, p + j) >= 0;
   int total;
-  block_scan_256(n, wsum, total);
+  block_scan_excl<256>(n, wsum, total);
   if (threadIdx.x == 0) a.offsets[blockIdx.x] = total;
 }
 
@@ -290,7 +269,7 @@ __global__ __launch_bounds__(256) void pixfeat_gather_write_kernel(GatherArgs a)
     n += lab[j] >= 0;
   }
   int total;
-  int at = block_scan_256(n, wsum, total);
+  int at = block_scan_excl<256>(n, wsum, total);
 #pragma unroll
   for (int j = 0; j < 4; ++j) {
     if (lab[j] >= 0) {

@@ -373,13 +373,9 @@ __global__ __launch_bounds__(1024) void pixel_map_reduce_kernel(const float* __r
       ++cnt;
     }
   }
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) {
-    sum += shfl_xor_f64(sum, o);
-    m = fmaxf(m, __shfl_xor(m, o, 64));
-    const int lo = __shfl_xor((int)(cnt & 0xffffffffll), o, 64), hi = __shfl_xor((int)(cnt >> 32), o, 64);
-    cnt += ((long long)hi << 32) | (unsigned)lo;
-  }
+  sum = wave_sum(sum);
+  m = wave_max_f32(m);
+  cnt = wave_sum(cnt);
   if ((threadIdx.x & 63) == 0) {
     s_sum[threadIdx.x >> 6] = sum;
     s_max[threadIdx.x >> 6] = m;

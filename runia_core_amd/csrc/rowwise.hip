@@ -296,8 +296,7 @@ __global__ __launch_bounds__(64 * kRowWaves) void ash_s_kernel(const float* __re
       int gt = 0;
 #pragma unroll
       for (int t = 0; t < NV; ++t) gt += (key[t] > thr);
-#pragma unroll
-      for (int o = 32; o > 0; o >>= 1) gt += __shfl_xor(gt, o, 64);
+      gt = wave_sum(gt);
       int ties_left = k - gt;  // how many elements equal to the threshold are kept (index order)
 #pragma unroll
       for (int t = 0; t < NV; ++t) {
@@ -451,9 +450,9 @@ __global__ __launch_bounds__(64 * kRowWaves) void gen_kernel(const float* __rest
         const unsigned lowk = ok[t] ? key[t] : 0xffffffffu;
         kmin = lowk < kmin ? lowk : kmin;
       }
-#pragma unroll
+#pragma unroll  // (max and min in one butterfly: as two wave_reduce calls gen_kernel<64, false> takes one more register)
       for (int o = 32; o > 0; o >>= 1) {
-        const unsigned a = (unsigned)__shfl_xor((int)kmax, o, 64), b = (unsigned)__shfl_xor((int)kmin, o, 64);
+        const unsigned a = lane_xor(kmax, o), b = lane_xor(kmin, o);
         kmax = a > kmax ? a : kmax;
         kmin = b < kmin ? b : kmin;
       }

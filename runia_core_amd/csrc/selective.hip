@@ -87,10 +87,6 @@ struct TileCarry {  // pass 2 -> pass 3
 };
 static_assert(sizeof(TileSum) == 64 && sizeof(TileCarry) == 48, "workspace layout");
 
-__device__ __forceinline__ double shfl_up_f64(double v, int o) {
-  return __hiloint2double(__shfl_up(__double2hiint(v), o, 64), __shfl_up(__double2loint(v), o, 64));
-}
-
 struct SelShared {
   double wl[kSelWaves], ws[kSelWaves];
   int wcnt[kSelWaves], wlast[kSelWaves], wfirst[kSelWaves];
@@ -109,18 +105,18 @@ __device__ __forceinline__ void sel_block_scan(double al, double as, int cnt, in
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   double xl = al, xs = as;
   int xc = cnt, xm = last, xf = first;
-#pragma unroll
+#pragma unroll  // (hand-written: a forward scan of four fields paired with the backward scan of xf)
   for (int d = 1; d < 64; d <<= 1) {
-    const double yl = shfl_up_f64(xl, d), ys = shfl_up_f64(xs, d);
-    const int yc = __shfl_up(xc, d, 64), ym = __shfl_up(xm, d, 64), yf = __shfl_down(xf, d, 64);
+    const double yl = lane_up(xl, d), ys = lane_up(xs, d);
+    const int yc = lane_up(xc, d), ym = lane_up(xm, d), yf = lane_down(xf, d);
     if (lane >= d) { xl = yl + xl; xs = ys + xs; xc += yc; xm = max(xm, ym); }
     if (lane + d < 64) xf = min(xf, yf);
   }
   if (lane == 63) { sh.wl[wave] = xl; sh.ws[wave] = xs; sh.wcnt[wave] = xc; sh.wlast[wave] = xm; }
   if (lane == 0) sh.wfirst[wave] = xf;
   // exclusive values of the lane
-  double el = shfl_up_f64(xl, 1), es = shfl_up_f64(xs, 1);
-  int ec = __shfl_up(xc, 1, 64), em = __shfl_up(xm, 1, 64), ef = __shfl_down(xf, 1, 64);
+  double el = lane_up(xl, 1), es = lane_up(xs, 1);
+  int ec = lane_up(xc, 1), em = lane_up(xm, 1), ef = lane_down(xf, 1);
   if (lane == 0) { el = 0.0; es = 0.0; ec = 0; em = -1; }
   if (lane == 63) ef = kNoEnd;
   __syncthreads();
@@ -367,11 +363,8 @@ __global__ __launch_bounds__(kSelThreads) void sel_final_kernel(const int64_t* _
       }
     }
   }
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) {
-    sum_a += shfl_xor_f64(sum_a, o);
-    sum_g += shfl_xor_f64(sum_g, o);
-  }
+  sum_a = wave_sum(sum_a);
+  sum_g = wave_sum(sum_g);
   if (lane == 0) { wa[wave] = sum_a; wg[wave] = sum_g; }
   __syncthreads();
   if (tid == 0) {
@@ -432,8 +425,7 @@ __global__ __launch_bounds__(256) void sel_best_kernel(const int32_t* __restrict
 #pragma unroll
       for (int c = 0; c < kQItems; ++c)
         if (e[c] > 0.0 && l[c] <= rj * e[c]) b = (int)e[c];  // (run ends ascend with c)
-#pragma unroll
-      for (int o = 32; o > 0; o >>= 1) b = max(b, __shfl_xor(b, o, 64));
+      b = wave_max(b);
       if (lane == 0 && b > 0) atomicMax(&sbest[j], b);
     }
   }

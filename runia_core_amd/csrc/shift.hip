@@ -410,11 +410,8 @@ __global__ __launch_bounds__(256) void shift_fused_kernel(FusedArgs a) {
       const int c = (wave * NT + t) * 32 + (r & 3) + 8 * (r >> 2) + 4 * lh;
       const bool in = (member_word(a, c, it) >> li) & 1u;
       float tv = in ? q[t][r] : 0.f, uv = in ? ri : 0.f;
-#pragma unroll
-      for (int o = 16; o > 0; o >>= 1) {  // (the 32 lanes of a half)
-        tv += __shfl_xor(tv, o, 64);
-        uv += __shfl_xor(uv, o, 64);
-      }
+      tv = wave_sum<32>(tv);  // (the 32 lanes of a half)
+      uv = wave_sum<32>(uv);
       if (li == 0) {
         a.part_t[ent + c] = tv;
         a.part_u[ent + c] = uv;

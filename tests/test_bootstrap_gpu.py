@@ -103,6 +103,17 @@ def test_three_values_runs_span_tiles():
     cases.assert_replicates_match(run(a, b, 5, seed=9), cases.replicates(a, b, 5, seed=9), "three values")
 
 
+@pytest.mark.parametrize("n", [T - 1, T, T + 1])
+def test_three_values_runs_at_the_tile_edge(n):
+    """One tile less a row, one tile, one tile and a row: with three distinct scores a run of equal keys lies across the end of
+    the first tile (where there is one), so the last run end in front of a thread comes from another wave or tile."""
+    n_ind, n_ood = cases.split_2_to_1(n)
+    g = np.random.default_rng(n)
+    a = g.choice([0.25, 0.5, 0.75], size=n_ind, p=[0.2, 0.3, 0.5])
+    b = g.choice([0.25, 0.5, 0.75], size=n_ood, p=[0.5, 0.3, 0.2])
+    cases.assert_replicates_match(run(a, b, 5, seed=9), cases.replicates(a, b, 5, seed=9), f"three values, n={n}")
+
+
 def test_all_scores_equal():
     n_ind, n_ood = cases.split_2_to_1(3 * T + 5)
     got = run(np.full(n_ind, 0.5), np.full(n_ood, 0.5), 5, seed=2)

@@ -1,5 +1,5 @@
 """Connected-component labelling and the component-level metrics on the GPU, against ``scipy.ndimage.label`` and the float64
-restatement of ``component_cases``.  Every shape is a few tiles at most."""
+restatement of ``component_cases``.  Every shape is a few tiles at most, but for one that needs two trips of the count scan."""
 import numpy as np
 import pytest
 import torch
@@ -35,6 +35,19 @@ def test_labels_equal_scipy_exactly(h, w):
         for i, name in enumerate(names):
             assert got_counts[i] == ref_counts[i], (name, connectivity)
             assert np.array_equal(got[i], ref[i]), (name, connectivity)
+
+
+def test_more_chunks_per_image_than_one_trip_of_the_count_scan():
+    """513 x 513 pixels are 258 flat chunks of 1 024: the per-image scan of the chunks' root counts takes two trips of 256 with a
+    carry, every wave of its workgroup holds counts, and the last chunk is partial."""
+    h = w = 513
+    rng = np.random.default_rng(11)
+    masks = np.stack([rng.random((h, w)) < 0.45, rng.random((h, w)) < 0.05])
+    for connectivity in (4, 8):
+        ref, ref_counts = cc.label_stack(masks, connectivity)
+        labels, counts = label_components(_dev(masks), connectivity)
+        assert np.array_equal(counts.cpu().numpy(), ref_counts), connectivity
+        assert np.array_equal(labels.cpu().numpy(), ref), connectivity
 
 
 def test_three_by_three_tiles_patterns_are_one_component():

@@ -170,7 +170,7 @@ def _expected_rows(x, lab, k):
     return rows[valid], lab.reshape(-1)[valid].astype(np.int32), int((~valid).sum())
 
 
-@pytest.mark.parametrize("hw", ((1, 1023), (32, 32), (25, 41)), ids=lambda s: str(s[0] * s[1]))
+@pytest.mark.parametrize("hw", ((1, 1023), (32, 32), (25, 41), (1, 500), (1, 512)), ids=lambda s: str(s[0] * s[1]))
 @pytest.mark.parametrize("dt", (torch.float32, torch.float16, torch.bfloat16), ids=("f32", "f16", "bf16"))
 def test_gather_keeps_all_or_none_in_pixel_order(hw, dt):
     k = 5

@@ -1253,6 +1253,33 @@ int runia_shift_mmd(const void* x, int64_t n, int64_t x_stride, const void* y, i
                     int64_t n_perm, double* t, double* u, double* S, double* stats, int64_t* count, double* p_value,
                     void* workspace, size_t workspace_bytes, runia_stream_t stream);
 
+/* ---- per-feature Kolmogorov-Smirnov statistics with a permutation null (csrc/ks_perm.hip) -----------------------------------
+ * Two row tables X [n, D], Y [m, D] of one dtype (0 f32, 1 f16, 2 bf16), read where they lie through their row strides (in
+ * elements, >= D); pooled Z = [X; Y], N = n + m <= runia_ks_max_rows().
+ *   statistic  for column d and permutation p: walk the pooled values of the column in ascending order, v = 0, v += m for a member
+ *              of the first set of p and v -= n otherwise; T[p, d] = max |v| over the LAST positions of the runs of equal values.
+ *              An exact integer <= n m; the two-sample KS statistic is T / (n m).
+ *   order      values compare as numbers: f16 / bf16 widened exactly, -0 == +0, +-inf ordinary extreme values.  A column that holds
+ *              a NaN is invalid: valid[d] = 0 and T[:, d] = -1; otherwise valid[d] = 1.
+ *   memberships  those of runia_shift_perm_bits with the same (seed, n, N): p = 0 the identity (rows i < n), exactly n members.
+ * runia_ks_max_rows: the largest pooled N of one call (16384: one column's (key, row) pairs are sorted in 128 KiB of LDS; n m <=
+ *   2^26, so the walk's counters are 32-bit).
+ * runia_ks_columns_per_pass: the columns ordered and walked per pass, min(4096, 64 MiB / (4 ceil(N / 64) 64)) >= 1024: the row
+ *   orders of a pass take at most 64 MiB of the workspace whatever D is.  0 for an invalid shape.
+ * runia_ks_workspace_bytes: the orders of one pass (bounded, above) plus the membership bits twice (as rows of permutations and
+ *   as rows of pooled rows), which are NOT bounded: about N / 4 bytes per permutation, so the workspace grows linearly in n_perm -
+ *   4 MB at N = 16384, n_perm = 999, 4 GiB at N = 16384, n_perm = 2^20 - 1.  0 for invalid shapes.
+ * runia_ks_perm_table: table int64 [1 + n_perm, D] and valid int32 [D] on the device.  Integer work only: the same bits from call
+ *   to call.  RUNIA_E_INVALID (before anything is dereferenced or launched) unless n, m >= 1, N <= runia_ks_max_rows(),
+ *   1 <= D < 2^31, 0 <= n_perm < 2^20, dtype in 0 .. 2, strides >= D and no NULL pointer.
+ *   workspace: runia_ks_workspace_bytes(n, m, D, n_perm) bytes, 16-byte aligned, uninitialised (RUNIA_E_WORKSPACE if short). */
+int64_t runia_ks_max_rows(void);
+int64_t runia_ks_columns_per_pass(int64_t n, int64_t m, int64_t n_perm);
+size_t runia_ks_workspace_bytes(int64_t n, int64_t m, int64_t d, int64_t n_perm);
+int runia_ks_perm_table(const void* x, int64_t n, int64_t x_stride, const void* y, int64_t m, int64_t y_stride, int64_t d,
+                        int dtype, uint64_t seed, int64_t n_perm, int64_t* table, int32_t* valid, void* workspace,
+                        size_t workspace_bytes, runia_stream_t stream);
+
 /* ---- per-pixel kNN maps from segmentation features and the k-center coreset (csrc/pixel_knn.hip) ----------------------------
  * runia_pixknn_score: the k smallest SQUARED Euclidean distances of every pixel of G feature maps to the M rows of a bank, and
  * the indices of those rows, ONE launch, the maps read where the model left them.

@@ -373,6 +373,12 @@ _SIGNATURES = {
     "runia_shift_mmd": (
         c_int, [c_void_p, c_int64, c_int64, c_void_p, c_int64, c_int64, c_int64, c_int, c_int, c_void_p, c_int, c_int, c_uint64,
                 c_int64, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]),
+    "runia_ks_max_rows": (c_int64, []),
+    "runia_ks_columns_per_pass": (c_int64, [c_int64, c_int64, c_int64]),
+    "runia_ks_workspace_bytes": (c_size_t, [c_int64, c_int64, c_int64, c_int64]),
+    "runia_ks_perm_table": (
+        c_int, [c_void_p, c_int64, c_int64, c_void_p, c_int64, c_int64, c_int64, c_int, c_uint64, c_int64, c_void_p, c_void_p,
+                c_void_p, c_size_t, c_void_p]),
     "runia_pixknn_workspace_bytes": (c_size_t, [c_int64, c_int64, c_int64]),
     "runia_pixknn_score": (
         c_int, [c_void_p, c_int, c_int64, c_int64, c_int64, c_int64, c_int64, c_int64, c_int64, c_int64, c_void_p, c_void_p,
@@ -2416,6 +2422,40 @@ def shift_mmd(x: torch.Tensor, y: torch.Tensor, kernel: str, bandwidths, estimat
     else:
         launch("runia_shift_mmd", *args)
     return out
+
+
+KS_MAX_PERM = (1 << 20) - 1                              # permutations of one runia_ks_perm_table call
+
+
+def ks_max_rows() -> int:
+    """The largest pooled ``n + m`` of one :func:`ks_perm_table` call (``runia_ks_max_rows``); needs no GPU."""
+    return query("runia_ks_max_rows")
+
+
+@_device_guard()
+def ks_perm_table(x: torch.Tensor, y: torch.Tensor, n_perm: int, seed: int = 0, kernel_events: Optional[list] = None):
+    """The integer Kolmogorov-Smirnov table of ``x`` [n, D] against ``y`` [m, D] (``runia_ks_perm_table``) -> ``(table, valid)``:
+    ``table`` int64 ``[1 + n_perm, D]``, row 0 the observed split and row p the permutation p of :func:`shift_perm_bits`, each
+    entry ``n m`` times the two-sample KS statistic of that column (``-1`` in a column that holds a NaN); ``valid`` int32 ``[D]``.
+    Rows are read in place as in :func:`shift_mmd`.  Stream-ordered, no synchronisation; the same bits from call to call.
+    ``kernel_events`` is a measurement hook for ``tools/ablate/run_shift_ks.py``, not part of the scoring interface: a list that
+    receives the event pair of the call's first walk-kernel launch (its own start / end timestamps)."""
+    require_gpu()
+    x, y = _shift_rows("ks_perm_table", x, y)
+    n, m, d, n_perm = x.shape[0], y.shape[0], x.shape[1], int(n_perm)
+    if n + m > ks_max_rows() or not (0 <= n_perm <= KS_MAX_PERM):
+        raise RuniaHipError(f"ks_perm_table: n + m <= {ks_max_rows()} and 0 <= n_perm < 2^20 are required")
+    table = torch.empty((1 + n_perm, d), dtype=torch.int64, device=x.device)
+    valid = torch.empty((d,), dtype=torch.int32, device=x.device)
+    ws_bytes = query("runia_ks_workspace_bytes", n, m, d, n_perm)
+    ws = workspace(ws_bytes, x.device)
+    args = (x.data_ptr(), n, max(x.stride(0), d), y.data_ptr(), m, max(y.stride(0), d), d, ELEM_DTYPE_CODES[x.dtype],
+            int(seed) & (2**64 - 1), n_perm, table.data_ptr(), valid.data_ptr(), ws.data_ptr(), ws_bytes)
+    if kernel_events is not None:
+        kernel_events.append(_timed_call("runia_ks_perm_table", *args))
+    else:
+        launch("runia_ks_perm_table", *args)
+    return table, valid
 
 
 @_device_guard()

@@ -66,3 +66,11 @@ from .shift import (  # noqa: F401
     mmd_test,
     shift_power_table,
 )
+from .shift_univariate import (  # noqa: F401
+    MaxTAdjustment,
+    UnivariateShiftDetector,
+    UnivariateShiftResult,
+    ks_asymptotic_p,
+    ks_test,
+    maxt_adjust,
+)

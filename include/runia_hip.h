@@ -322,6 +322,26 @@ int runia_mc_entropy_f32(const float* x, const float* rand, int64_t rand_image_s
                          float* z_out, double* zero_fill, void* workspace, size_t workspace_bytes, int64_t N,
                          int C, int H, int W, int n_mc, double drop_prob, int block_size, int k, double min_dist,
                          runia_stream_t stream);
+/* The product case of runia_mc_entropy_f32 as ONE launch, without the keep-flag launch and its per-image table: 4x4 maps,
+ * n_mc == 16, k == 5, explicit draws, drop_prob > 0, no z_out (runia_mc_entropy_lut_supported; anything else: the entry
+ * points above).  What the keep-flag launch derives from a drop layer's 16 seed bits depends on (H, W, block_size) alone, so
+ * it is a table over all 65 536 seed words, built once on the HOST: runia_mc_flag_lut_fill writes
+ * runia_mc_flag_lut_bytes(H, W, block_size) bytes (0: geometry not supported) of records of 20 dwords - the 16 keep flags
+ * (2^-a or 0, in the kernel's operand order), zh, zl as the keep-flag table holds them (a fully dropped layer: zh = NaN,
+ * flags 0), a sort word (class << 27 | record byte offset; class = (m - 1) / 2, 8 for a fully dropped layer) and the odd
+ * part m of the mask sum (0 for a fully dropped layer) - followed by zero records up to the largest byte offset a sort word
+ * can carry (2^23), so that the kernel's reads stay inside lut_bytes whatever a caller's table holds.  host_out: 4-byte aligned (RUNIA_E_INVALID if NULL, misaligned or the
+ * geometry is not supported; RUNIA_E_WORKSPACE if `bytes` is short).
+ * runia_mc_entropy_lut_f32: `lut` = a DEVICE copy of exactly those bytes for the same block_size (lut_bytes short or lut NULL:
+ * RUNIA_E_WORKSPACE); x 16-byte aligned; rand [N, 16, 4, 4] with rand_image_stride >= 0 elements between images; h, zero_fill
+ * as runia_mc_entropy_f32.  Each wave forms its image's seed bits from the draws with four ballots and reads its operands from
+ * the table through the scalar cache.  h is bit-identical to runia_mc_entropy_f32 on the same arguments. */
+size_t runia_mc_flag_lut_bytes(int H, int W, int block_size);
+int runia_mc_flag_lut_fill(void* host_out, size_t bytes, int H, int W, int block_size);
+int runia_mc_entropy_lut_supported(int H, int W, int n_mc, int k, int block_size);
+int runia_mc_entropy_lut_f32(const float* x, const float* rand, int64_t rand_image_stride, const void* lut,
+                             size_t lut_bytes, double* h, double* zero_fill, int64_t N, int C, int H, int W, int n_mc,
+                             double drop_prob, int block_size, int k, double min_dist, runia_stream_t stream);
 /* Throughput mode of the sampler: the DropBlock draws are not read from memory but made
  * inside the keep-flag launch by a counter generator - Philox4x32-10 keyed by `seed`; draw i (= layer*H*W + position)
  * of image g is component (i/64)&3 of philox(counter = (g.lo, g.hi, i%64 + 64*(i/256), 0)), u = (bits >> 8) * 2^-24.

@@ -120,6 +120,14 @@ _SIGNATURES = {
         [c_void_p, c_void_p, c_int64, c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, c_int64, c_int, c_int, c_int,
          c_int, c_double, c_int, c_int, c_double, c_void_p],
     ),
+    "runia_mc_flag_lut_bytes": (c_size_t, [c_int, c_int, c_int]),
+    "runia_mc_flag_lut_fill": (c_int, [c_void_p, c_size_t, c_int, c_int, c_int]),
+    "runia_mc_entropy_lut_supported": (c_int, [c_int, c_int, c_int, c_int, c_int]),
+    "runia_mc_entropy_lut_f32": (
+        c_int,
+        [c_void_p, c_void_p, c_int64, c_void_p, c_size_t, c_void_p, c_void_p, c_int64, c_int, c_int, c_int, c_int, c_double,
+         c_int, c_int, c_double, c_void_p],
+    ),
     "runia_mc_draws_f32": (c_int, [c_void_p, c_int64, c_int, c_int, c_int, c_uint64, c_int64, c_void_p]),
     "runia_mc_mask_table_counter_f32": (
         c_int,
@@ -1447,6 +1455,40 @@ def mc_mask_table(rand: Union[torch.Tensor, CounterDraws, None], n: int, h: int,
     return out
 
 
+_FLAG_LUTS: dict = {}  # (device index, H, W, block_size) -> device copy of the geometry table
+_FLAG_LUTS_LOCK = threading.Lock()
+
+
+def mc_flag_lut_host(h: int, w: int, block_size: int) -> np.ndarray:
+    """The geometry table of ``runia_mc_flag_lut_fill`` as a [records, 20] uint32 array (no GPU needed): row ``key`` < 65 536 is
+    the record of seed word ``key``, the rows behind them are zero padding (see ``runia_hip.h``)."""
+    nbytes = query("runia_mc_flag_lut_bytes", int(h), int(w), int(block_size))
+    if nbytes == 0:
+        raise RuniaHipError(f"no keep-flag geometry table for {h}x{w} maps, block_size {block_size}")
+    host = np.empty(nbytes // 4, dtype=np.uint32)
+    call("runia_mc_flag_lut_fill", host.ctypes.data, nbytes, int(h), int(w), int(block_size))
+    return host.reshape(-1, 20)
+
+
+def _flag_lut(device: torch.device, h: int, w: int, block_size: int) -> torch.Tensor:
+    """One device copy of the geometry table per (device, H, W, block_size): uploaded once, and the device synchronised once
+    after the upload, because later launches that read it may come from any of the pipeline's streams."""
+    key = (device.index, int(h), int(w), int(block_size))
+    lut = _FLAG_LUTS.get(key)
+    if lut is None:
+        with _FLAG_LUTS_LOCK:
+            lut = _FLAG_LUTS.get(key)
+            if lut is None:
+                lut = torch.from_numpy(mc_flag_lut_host(h, w, block_size).view(np.int32)).to(device)
+                torch.cuda.synchronize(device)
+                _FLAG_LUTS[key] = lut
+    return lut
+
+
+def mc_entropy_lut_supported(h: int, w: int, n_mc: int, k: int, block_size: int) -> bool:
+    return bool(query("runia_mc_entropy_lut_supported", int(h), int(w), int(n_mc), int(k), int(block_size)))
+
+
 @_device_guard()
 def mc_entropy(x: torch.Tensor, rand: Union[torch.Tensor, CounterDraws, None], n_mc: int, drop_prob: float, block_size: int, k: int,
                min_dist: float = 1e-5, want_samples: bool = False, out: Optional[torch.Tensor] = None,
@@ -1457,7 +1499,10 @@ def mc_entropy(x: torch.Tensor, rand: Union[torch.Tensor, CounterDraws, None], n
     (the kernel's own start / end timestamps; the keep-flag table launch before it is left out) are appended - bench.py
     times the dominant kernel with it.
     ``zero_fill``: optional [N] f64 tensor cleared by the launch (the accumulator of ``proj_sq_accumulate``).
-    ``table``: the batch's keep-flag table built earlier by :func:`mc_mask_table` (``rand`` is then ignored)."""
+    ``table``: the batch's keep-flag table built earlier by :func:`mc_mask_table` (``rand`` is then ignored).
+    The product case - 4x4 maps, 16 drop layers, k = 5, ``rand`` a tensor, ``drop_prob > 0``, no samples, no ``table`` - is ONE
+    launch that reads the draws itself (``runia_mc_entropy_lut_f32``; ``config.k1_flag_table``), with or without
+    ``kernel_events``; everything else is the keep-flag table launch + the launch from that table.  Same bits either way."""
     lib = load_library()
     require_gpu()
     assert x.is_cuda and x.dtype == torch.float32 and x.dim() == 4
@@ -1488,6 +1533,20 @@ def mc_entropy(x: torch.Tensor, rand: Union[torch.Tensor, CounterDraws, None], n
     z = torch.empty((n * n_mc, c), dtype=torch.float32, device=x.device) if want_samples else None
     if zero_fill is not None:
         assert zero_fill.is_cuda and zero_fill.dtype == torch.float64 and zero_fill.shape == (n,) and zero_fill.is_contiguous()
+    if (_config.k1_flag_table and rand is not None and not want_samples and drop_prob > 0 and x.data_ptr() % 16 == 0
+            and mc_entropy_lut_supported(hh, ww, n_mc, k, block_size)):
+        # the product case: one launch from the draws and the geometry table (no keep-flag launch, no per-image table)
+        lut = _flag_lut(x.device, hh, ww, block_size)
+        lut_bytes = lut.numel() * 4
+        for done, m in _image_slices(n):
+            args = (x.data_ptr() + done * c * hh * ww * 4, rand.data_ptr() + done * stride * 4, stride, lut.data_ptr(), lut_bytes,
+                    h.data_ptr() + done * c * 8, None if zero_fill is None else zero_fill.data_ptr() + done * 8, m, c, hh, ww,
+                    n_mc, float(drop_prob), int(block_size), int(k), float(min_dist))
+            if kernel_events is not None:
+                kernel_events.append(_timed_call("runia_mc_entropy_lut_f32", *args))
+            else:
+                launch("runia_mc_entropy_lut_f32", *args)
+        return h
     ws_bytes = int(lib.runia_mc_entropy_workspace_bytes(min(65535, n), hh, ww, n_mc))
     ws = torch.empty(max(ws_bytes, 16), dtype=torch.uint8, device=x.device)  # stream-ordered: reused per slice
     if counter is not None:

@@ -44,3 +44,8 @@ md_triangular = True
 # exact covariance's null space and sits up to ~1.5e-5 (relative) from the reference's float32 one on tests/golden/ref_f4.npz -
 # INTEGRATION.md, "Known divergences".
 vim_device_fit = False
+
+# Sampler + entropy of the product case (4x4 maps, 16 drop layers, k = 5, explicit draws, drop_prob > 0, no sample copy): one
+# launch that reads the draws itself and takes each drop layer's keep flags from a table over all 65 536 seed words, built once
+# per (device, H, W, block_size) - no keep-flag launch, no per-image table.  Same bits.  False: always the two launches.
+k1_flag_table = True

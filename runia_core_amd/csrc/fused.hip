@@ -4,7 +4,9 @@
 //
 //   K0  mc_mask      DropBlock draws (N,n_mc,H,W) -> per-image keep-flag table (the DropBlock2D masks of
 //                    feature_extraction/abstract_classes.py:91-96 as 0/1 floats, drop layers sorted by mask sum).
-//                    Bit arithmetic on one 64-bit word per drop layer; ~9 us per 10 000 images.
+//                    Bit arithmetic on one 64-bit word per drop layer; ~9 us per 10 000 images.  Not launched in the
+//                    product case (4x4, 16 drop layers, explicit draws): there K1 reads the draws itself and looks the
+//                    layers' flags up in a geometry table (mc_entropy_lut_kernel) - two launches per batch.
 //   K1  mc_entropy   hooked latent maps (N,C,H,W) + table -> per-dimension entropies H (N,C) f64
 //                    = MCSamplerModule.forward (feature_extraction/abstract_classes.py:81-101) fused with
 //                      the per-dimension loop of get_dl_h_z (evaluation/entropy.py:77-82).  One thread owns
@@ -232,6 +234,77 @@ __global__ __launch_bounds__(64 * kMaskBitsWaves) void mc_mask_bits_kernel(const
   store_out<K0_NT_STORE>(out + n_mc * (HW + 1) + rank, zl);
 }
 
+// ---- geometry table: what K0 derives from a layer's seed bits, for every seed word -------------------------------------
+// Between the ballot and the table record K0 computes a pure function of (H, W, block_size): neither the data nor gamma
+// enters.  For maps of 16 positions there are 65 536 seed words, so the function is a table built once on the host:
+// record `key` = the 16 keep flags (2^-a or 0, mask_slot order), zh, zl - exactly K0's record of a layer whose seed word is
+// `key` - and in the padding a sort word and the odd part m (0: the layer drops the whole map).
+//   sort word = class << 27 | key * 80: class = (m - 1) / 2, 8 for a fully dropped layer; the kernel ORs the layer index
+//   in at bit 23, so that an ascending sort is K0's order (by m, dead layers last, ties by layer) and the low 23 bits are
+//   the record's byte offset.  With gamma = 0.125 99 % of the layers have at most 5 seeds: 6 885 records, 550 KB.
+constexpr int kLutRecDwords = 20, kLutSortDword = 18, kLutOddDword = 19;
+constexpr int kLutLayerShift = 23, kLutClassShift = 27;
+constexpr unsigned kLutOffsetMask = (1u << kLutLayerShift) - 1u;
+constexpr size_t kLutKeys = 65536;
+static_assert((kLutKeys - 1) * kLutRecDwords * 4 <= kLutOffsetMask, "a record's byte offset fits below the layer index");
+// The table is padded with zero records up to the largest offset the mask lets through: whatever the words a caller's
+// table holds, the kernel's reads stay inside the lut_bytes the entry point has checked.
+constexpr size_t kLutRecords = (kLutOffsetMask + 1) / (kLutRecDwords * 4) + 2;
+static_assert(kLutRecords * kLutRecDwords * 4 >= kLutOffsetMask + 1 + kLutRecDwords * 4, "every masked offset reads inside the table");
+
+void flag_lut_fill_4x4(uint32_t* out, int block_size) {
+  constexpr int HT = 4, WT = 4, HW = 16;
+  const int pad = block_size / 2;
+  for (size_t i = kLutKeys * kLutRecDwords; i < kLutRecords * kLutRecDwords; ++i) out[i] = 0u;
+  for (unsigned key = 0; key < kLutKeys; ++key) {
+    unsigned keep = 0;
+    for (int y = 0; y < HT; ++y)
+      for (int xw = 0; xw < WT; ++xw) {
+        bool dropped = false;  // a seed inside the block window of (y, x), as keep_of of K0
+        for (int yy = 0; yy < HT; ++yy)
+          for (int xx = 0; xx < WT; ++xx)
+            if (((key >> (yy * WT + xx)) & 1u) && yy - y >= -pad && yy - y < block_size - pad && xx - xw >= -pad &&
+                xx - xw < block_size - pad)
+              dropped = true;
+        if (!dropped) keep |= 1u << (y * WT + xw);
+      }
+    const int cnt = __builtin_popcount(keep);
+    const int a = cnt ? __builtin_ctz((unsigned)cnt) : 0;  // layer_consts on the host
+    const int m = cnt >> a;
+    const uint32_t flag = (uint32_t)(127 - a) << 23;  // 2^-a
+    uint32_t* rec = out + (size_t)key * kLutRecDwords;
+    for (int slot = 0; slot < HW; ++slot) rec[slot] = ((keep >> slot_position<HT, WT>(slot)) & 1u) ? flag : 0u;
+    rec[HW] = cnt ? runia_div::kDivHiC[(m - 1) >> 1] : 0x7fc00000u;  // NaN: 0 * numel / 0 upstream
+    rec[HW + 1] = cnt ? runia_div::kDivLoC[(m - 1) >> 1] : 0u;
+    const unsigned cls = cnt ? (unsigned)(m - 1) >> 1 : 8u;
+    rec[kLutSortDword] = (cls << kLutClassShift) | (key * (unsigned)(kLutRecDwords * 4));
+    rec[kLutOddDword] = (uint32_t)m;
+  }
+}
+
+// Ascending sort of 16 wave-uniform words (Batcher's odd-even merge sort, 63 compare-exchanges): s_min_u32 + s_max_u32 each,
+// no vector instruction.
+__device__ __forceinline__ void sort16_uniform(unsigned (&v)[16]) {
+#pragma unroll
+  for (int p = 1; p < 16; p <<= 1) {
+#pragma unroll
+    for (int k = p; k >= 1; k >>= 1) {
+#pragma unroll
+      for (int j = k % p; j + k < 16; j += 2 * k) {
+#pragma unroll
+        for (int i = 0; i < k; ++i) {
+          if (i + j + k < 16 && (i + j) / (2 * p) == (i + j + k) / (2 * p)) {
+            const unsigned lo = v[i + j] < v[i + j + k] ? v[i + j] : v[i + j + k];
+            const unsigned hi = v[i + j] < v[i + j + k] ? v[i + j + k] : v[i + j];
+            v[i + j] = lo;
+            v[i + j + k] = hi;
+          }
+        }
+      }
+    }
+  }
+}
+
 // ------------------------------------------------------------------------------------------
 // K1: latent map -> MC samples -> entropy.   one workgroup = (image, block of kK1Block channels); no LDS, no barrier.
 // The mask table is wave-uniform: it arrives through the scalar cache (s_load) and enters the arithmetic as
@@ -351,17 +424,43 @@ __device__ __forceinline__ void roi_load_map(float (&u)[HT * WT], const RoiSourc
 #endif
 // ZOUT: the launch also writes the MC samples to z_out (the sampler-only entry point and the tests); the product launch
 // passes no z_out and takes the instantiation without the stores, whose drop layers are then free of branches on it.
-template <int HT, int WT, int NP, int K, bool FULL, bool ENTROPY, int ROI_G, bool ZOUT>
+// LUT: `table` is the geometry table (flag_lut_fill_4x4 above) and the launch reads the draws itself: no K0, no per-image table.
+//   A wave forms its image's seed bits with four ballots (the draws as K0 reads them, bit i = layer * HW + position), takes
+//   each layer's 16-bit seed word as the key of its table record, and orders the 16 layers as K0 does - by the odd part of the
+//   mask sum, then by layer - with a sorting network over the records' sort words on the scalar unit.  Everything after that
+//   is the table form; only the address of a layer's operands differs.
+template <int HT, int WT, int NP, int K, bool FULL, bool ENTROPY, int ROI_G, bool ZOUT, bool LUT = false>
 __device__ __forceinline__ void mc_entropy_item(const float* __restrict__ x, const float* __restrict__ table,
                                                 double* __restrict__ h, float* __restrict__ z_out,
                                                 double* __restrict__ zero_fill, int64_t N, int C, int n_mc_rt,
-                                                double min_dist, double const_term, double inv_n, int64_t img, int c) {
+                                                double min_dist, double const_term, double inv_n, int64_t img, int c,
+                                                const float* __restrict__ rnd = nullptr, int64_t rand_stride = 0,
+                                                float gamma = 0.f) {
   constexpr int HW = HT * WT;
   constexpr bool PAIRS = (HT % 2 == 0);
   const int n_mc = FULL ? NP : n_mc_rt;
   if (img >= N) return;
+  // the ballots come before any lane leaves: a wave with fewer than 64 live channels still needs all 64 draws of a word
+  unsigned long long seedw[LUT ? NP * HW / 64 : 1];
+  if constexpr (LUT) {
+    static_assert(!LUT || (HW == 16 && NP == 16 && FULL && !ZOUT && ROI_G == 0), "the geometry table is for 4x4 x 16 layers");
+    const float* r = rnd + img * rand_stride + (threadIdx.x & 63);
+#pragma unroll
+    for (int t = 0; t < NP * HW / 64; ++t) seedw[t] = __ballot(r[64 * t] < gamma);
+  }
   if (zero_fill && c == 0) zero_fill[img] = 0.0;  // the accumulator of the score launch that follows (optional)
   if (c >= C) return;
+  typedef const __attribute__((address_space(4))) unsigned* lut_ptr;  // constant address space: scalar loads
+  const lut_ptr lut = (lut_ptr) reinterpret_cast<const unsigned*>(table);
+  unsigned sv[LUT ? NP : 1];  // LUT: the layers' sort words (class, layer, byte offset of the record), ascending
+  if constexpr (LUT) {
+#pragma unroll
+    for (int s = 0; s < NP; ++s) {
+      const unsigned key = (unsigned)(seedw[s >> 2] >> (16 * (s & 3))) & 0xffffu;
+      sv[s] = lut[key * kLutRecDwords + kLutSortDword] | ((unsigned)s << kLutLayerShift);
+    }
+    sort16_uniform(sv);
+  }
   const float* mk = table + img * (int64_t)(n_mc * (HW + 2));  // wave-uniform
   const float* zhs = mk + n_mc * HW;
   const float* zls = zhs + n_mc;
@@ -439,11 +538,19 @@ __device__ __forceinline__ void mc_entropy_item(const float* __restrict__ x, con
     const float* zls_t = zls + (FULL ? s0 : 0);
 #pragma unroll
     for (int g = 0; g < G; ++g) {
-      const int sc = FULL ? g : ((s0 + g < n_mc) ? s0 + g : n_mc - 1);
-      dg[g] = zhs_t[sc];
-      rg[g] = zls_t[sc];
+      if constexpr (LUT) {  // this trip's layers are sv[0 .. G-1]: constant indices, the array moves down after the trip
+        const lut_ptr rec = lut + (sv[g] & kLutOffsetMask) / 4u;
+        dg[g] = __uint_as_float(rec[HW]);
+        rg[g] = __uint_as_float(rec[HW + 1]);
 #pragma unroll
-      for (int p = 0; p < HW; ++p) mg[g][p] = mk_t[sc * HW + p];
+        for (int p = 0; p < HW; ++p) mg[g][p] = __uint_as_float(rec[p]);
+      } else {
+        const int sc = FULL ? g : ((s0 + g < n_mc) ? s0 + g : n_mc - 1);
+        dg[g] = zhs_t[sc];
+        rg[g] = zls_t[sc];
+#pragma unroll
+        for (int p = 0; p < HW; ++p) mg[g][p] = mk_t[sc * HW + p];
+      }
     }
 #pragma unroll
     for (int g = 0; g < G; ++g) {
@@ -519,6 +626,10 @@ __device__ __forceinline__ void mc_entropy_item(const float* __restrict__ x, con
     for (int i = NP - 1; i >= G; --i) z[i] = z[i - G];
 #pragma unroll
     for (int g = 0; g < G; ++g) z[g] = znew[g];
+    if constexpr (LUT) {
+#pragma unroll
+      for (int g = 0; g + G < NP; ++g) sv[g] = sv[g + G];
+    }
   }
   if constexpr (ENTROPY) {
     // A NaN sample - a fully dropped map (0*numel/0 upstream), a NaN or infinite activation - makes the entropy NaN
@@ -548,6 +659,7 @@ __global__ __launch_bounds__(kK1Block) void mc_entropy_kernel(const float* __res
   // XCD-aware order: consecutive workgroup ids go round-robin over the 8 XCDs (each with its own L2), so the
   // channel blocks of one image are given ids that are congruent mod 8 - the image's keep-flag table is then
   // fetched into ONE L2 (with the plain (block, image) grid up to 4 XCDs fetched it: +35 MB per 10 000 images).
+  // (The product launch, mc_entropy_lut_kernel below, has no per-image table: the same order keeps the image's draws there.)
   const unsigned chunks = (unsigned)(C + kK1Block - 1) / kK1Block;
   const unsigned slot = blockIdx.x >> 3;
   const int c = (int)(slot % chunks) * kK1Block + threadIdx.x;
@@ -556,6 +668,29 @@ __global__ __launch_bounds__(kK1Block) void mc_entropy_kernel(const float* __res
     const int64_t img = ((int64_t)(slot / chunks) * K1_IMGS + rep) * 8 + (blockIdx.x & 7);
     mc_entropy_item<HT, WT, NP, K, FULL, ENTROPY, ROI_G, ZOUT>(x, table, h, z_out, zero_fill, N, C, n_mc_rt, min_dist,
                                                               const_term, inv_n, img, c);
+  }
+}
+
+// K1 from the draws and the geometry table (no K0 launch): the workgroup order of mc_entropy_kernel, which here keeps an
+// image's 1 KB of draws in one L2 - each of the image's waves reads them and derives the same operands on its own.
+// (six waves per SIMD as the table form: left alone the register allocator took 87 vector registers here, for the same code
+// behind the drop layers that takes 75 there)
+template <int HT, int WT, int NP, int K>
+__attribute__((amdgpu_waves_per_eu(6, 8)))
+__global__ __launch_bounds__(kK1Block) void mc_entropy_lut_kernel(const float* __restrict__ x,
+                                                              const float* __restrict__ rnd, int64_t rand_stride,
+                                                              const float* __restrict__ lut, float gamma,
+                                                              double* __restrict__ h, double* __restrict__ zero_fill,
+                                                              int64_t N, int C, double min_dist, double const_term,
+                                                              double inv_n) {
+  const unsigned chunks = (unsigned)(C + kK1Block - 1) / kK1Block;
+  const unsigned slot = blockIdx.x >> 3;
+  const int c = (int)(slot % chunks) * kK1Block + threadIdx.x;
+#pragma unroll 1
+  for (int rep = 0; rep < K1_IMGS; ++rep) {
+    const int64_t img = ((int64_t)(slot / chunks) * K1_IMGS + rep) * 8 + (blockIdx.x & 7);
+    mc_entropy_item<HT, WT, NP, K, true, true, 0, false, true>(x, lut, h, nullptr, zero_fill, N, C, NP, min_dist, const_term,
+                                                               inv_n, img, c, rnd, rand_stride, gamma);
   }
 }
 
@@ -1236,6 +1371,42 @@ extern "C" int runia_mc_entropy_f32(const float* x, const float* rnd, int64_t ra
     return rc;
   return runia_mc_entropy_from_table_f32(x, workspace, workspace_bytes, h, z_out, zero_fill, N, C, H, W, n_mc, k,
                                          min_dist, stream);
+}
+
+// ---- the product launch without K0: draws + geometry table -> entropies ------------------------------------------------
+extern "C" size_t runia_mc_flag_lut_bytes(int H, int W, int block_size) {
+  if (H != 4 || W != 4 || block_size < 1) return 0;
+  return kLutRecords * kLutRecDwords * sizeof(uint32_t);
+}
+
+extern "C" int runia_mc_flag_lut_fill(void* host_out, size_t bytes, int H, int W, int block_size) {
+  const size_t need = runia_mc_flag_lut_bytes(H, W, block_size);
+  if (need == 0 || !host_out || (((uintptr_t)host_out) & 3) != 0) return RUNIA_E_INVALID;
+  if (bytes < need) return RUNIA_E_WORKSPACE;
+  flag_lut_fill_4x4(reinterpret_cast<uint32_t*>(host_out), block_size);
+  return RUNIA_OK;
+}
+
+extern "C" int runia_mc_entropy_lut_supported(int H, int W, int n_mc, int k, int block_size) {
+  return H == 4 && W == 4 && n_mc == 16 && k == 5 && block_size >= 1;
+}
+
+extern "C" int runia_mc_entropy_lut_f32(const float* x, const float* rnd, int64_t rand_image_stride, const void* lut,
+                                        size_t lut_bytes, double* h, double* zero_fill, int64_t N, int C, int H, int W,
+                                        int n_mc, double drop_prob, int block_size, int k, double min_dist,
+                                        runia_stream_t stream) {
+  if (N < 0 || C <= 0 || rand_image_stride < 0 || !runia_mc_entropy_lut_supported(H, W, n_mc, k, block_size))
+    return RUNIA_E_INVALID;
+  if (!(drop_prob > 0.0)) return RUNIA_E_INVALID;  // no drop layers: the identity table of runia_mc_entropy_f32
+  if (N == 0) return RUNIA_OK;
+  if (!x || !rnd || !h || N > 65535 || (((uintptr_t)x) & 15) != 0) return RUNIA_E_INVALID;
+  if (!lut || (((uintptr_t)lut) & 3) != 0 || lut_bytes < runia_mc_flag_lut_bytes(H, W, block_size)) return RUNIA_E_WORKSPACE;
+  const float gamma = (float)(drop_prob / (double)(block_size * block_size));
+  const double ct = digamma_diff(n_mc, k), inv_n = 1.0 / (double)n_mc;
+  const unsigned grid = (unsigned)((((N + 7) / 8 + K1_IMGS - 1) / K1_IMGS) * 8 * ((C + kK1Block - 1) / kK1Block));
+  RUNIA_LAUNCH_TIMED((mc_entropy_lut_kernel<4, 4, 16, 5>), grid, kK1Block, 0, as_stream(stream), x, rnd, rand_image_stride,
+                     reinterpret_cast<const float*>(lut), gamma, h, zero_fill, N, C, min_dist, ct, inv_n);
+  return runia_check_launch();
 }
 
 // ---- ROI source (config 4): roi_align folded into K1's load ------------------------------------------------------------

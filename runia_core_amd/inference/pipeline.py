@@ -132,7 +132,8 @@ class LaREMPipeline:
     def entropy_from_latents(self, latents: Tensor, rand: Optional[Tensor], kernel_events: Optional[list] = None,
                              zero_fill: Optional[Tensor] = None, prepared: Optional[PreparedDraws] = None) -> Tensor:
         """Sampler + per-dimension entropy without materialising the MC samples when the map shape is supported
-        (``runia_mc_entropy_f32``: keep-flag table launch + sampler/entropy launch), else the two unfused kernels.
+        (``runia_mc_entropy_f32``: keep-flag table launch + sampler/entropy launch; 4x4 maps with 16 drop layers and explicit
+        draws: the one launch of ``runia_mc_entropy_lut_f32``, same bits), else the two unfused kernels.
         ``prepared``: the batch's table from :meth:`prepare_draws` (``rand`` is then not read)."""
         n, _, h, w = latents.shape
         if prepared is not None:

@@ -2,6 +2,7 @@
 """Static instruction statistics of the kernels in one .hip file (no GPU needed).
 
     python tools/isa_stats.py runia_core_amd/csrc/fused.hip [name-filter]
+    python tools/isa_stats.py runia_core_amd/csrc/fused.hip mc_entropy    # K1: the table forms and mc_entropy_lut_kernel
 
 Compiles the file to gfx950 assembly with the Makefile's flags and prints, per kernel: vector / scalar instruction
 counts, v_readlane + v_writelane (scalar registers spilled to vector lanes), MFMA count, VGPRs, SGPRs, scratch bytes,

@@ -1427,6 +1427,14 @@ def _timed_call(name: str, *args):
     return e0, e1
 
 
+def _launch_with_events(kernel_events: Optional[list], name: str, *args) -> None:
+    """``launch(name, *args)``; given a list, the call runs under :func:`_timed_call` and its event pair is appended."""
+    if kernel_events is not None:
+        kernel_events.append(_timed_call(name, *args))
+    else:
+        launch(name, *args)
+
+
 def mc_entropy_supported(h: int, w: int, n_mc: int, k: int) -> bool:
     return bool(query("runia_mc_entropy_supported", int(h), int(w), int(n_mc), int(k)))
 
@@ -1508,44 +1516,29 @@ def mc_entropy(x: torch.Tensor, rand: Union[torch.Tensor, CounterDraws, None], n
     assert x.is_cuda and x.dtype == torch.float32 and x.dim() == 4
     x = x.contiguous()
     n, c, hh, ww = x.shape
-    if table is not None:
-        h = torch.empty((n, c), dtype=torch.float64, device=x.device) if out is None else out
-        assert h.is_cuda and h.dtype == torch.float64 and h.shape == (n, c) and h.is_contiguous()
-        z = torch.empty((n * n_mc, c), dtype=torch.float32, device=x.device) if want_samples else None
-        ws_bytes = int(lib.runia_mc_entropy_workspace_bytes(n, hh, ww, n_mc))
-        assert table.is_cuda and table.numel() >= ws_bytes and n <= 65535
-        if zero_fill is not None:
-            assert zero_fill.is_cuda and zero_fill.dtype == torch.float64 and zero_fill.shape == (n,) and zero_fill.is_contiguous()
-        args = (x.data_ptr(), table.data_ptr(), ws_bytes, h.data_ptr(), _ptr(z), _ptr(zero_fill), n, c, hh, ww, n_mc, int(k),
-                float(min_dist))
-        if kernel_events is not None:
-            kernel_events.append(_timed_call("runia_mc_entropy_from_table_f32", *args))
-        else:
-            launch("runia_mc_entropy_from_table_f32", *args)
-        return (h, z) if want_samples else h
-    counter = rand if isinstance(rand, CounterDraws) else None
-    rand, stride = _draws(None if counter is not None else rand, n, n_mc, hh, ww)
-    if out is None:
-        h = torch.empty((n, c), dtype=torch.float64, device=x.device)
-    else:
-        assert out.is_cuda and out.dtype == torch.float64 and out.shape == (n, c) and out.is_contiguous()
-        h = out
+    h = torch.empty((n, c), dtype=torch.float64, device=x.device) if out is None else out
+    assert h.is_cuda and h.dtype == torch.float64 and h.shape == (n, c) and h.is_contiguous()
     z = torch.empty((n * n_mc, c), dtype=torch.float32, device=x.device) if want_samples else None
     if zero_fill is not None:
         assert zero_fill.is_cuda and zero_fill.dtype == torch.float64 and zero_fill.shape == (n,) and zero_fill.is_contiguous()
+    if table is not None:
+        ws_bytes = int(lib.runia_mc_entropy_workspace_bytes(n, hh, ww, n_mc))
+        assert table.is_cuda and table.numel() >= ws_bytes and n <= 65535
+        _launch_with_events(kernel_events, "runia_mc_entropy_from_table_f32", x.data_ptr(), table.data_ptr(), ws_bytes,
+                            h.data_ptr(), _ptr(z), _ptr(zero_fill), n, c, hh, ww, n_mc, int(k), float(min_dist))
+        return (h, z) if want_samples else h
+    counter = rand if isinstance(rand, CounterDraws) else None
+    rand, stride = _draws(None if counter is not None else rand, n, n_mc, hh, ww)
     if (_config.k1_flag_table and rand is not None and not want_samples and drop_prob > 0 and x.data_ptr() % 16 == 0
             and mc_entropy_lut_supported(hh, ww, n_mc, k, block_size)):
         # the product case: one launch from the draws and the geometry table (no keep-flag launch, no per-image table)
         lut = _flag_lut(x.device, hh, ww, block_size)
         lut_bytes = lut.numel() * 4
         for done, m in _image_slices(n):
-            args = (x.data_ptr() + done * c * hh * ww * 4, rand.data_ptr() + done * stride * 4, stride, lut.data_ptr(), lut_bytes,
-                    h.data_ptr() + done * c * 8, None if zero_fill is None else zero_fill.data_ptr() + done * 8, m, c, hh, ww,
-                    n_mc, float(drop_prob), int(block_size), int(k), float(min_dist))
-            if kernel_events is not None:
-                kernel_events.append(_timed_call("runia_mc_entropy_lut_f32", *args))
-            else:
-                launch("runia_mc_entropy_lut_f32", *args)
+            _launch_with_events(kernel_events, "runia_mc_entropy_lut_f32", x.data_ptr() + done * c * hh * ww * 4,
+                                rand.data_ptr() + done * stride * 4, stride, lut.data_ptr(), lut_bytes, h.data_ptr() + done * c * 8,
+                                None if zero_fill is None else zero_fill.data_ptr() + done * 8, m, c, hh, ww, n_mc,
+                                float(drop_prob), int(block_size), int(k), float(min_dist))
         return h
     ws_bytes = int(lib.runia_mc_entropy_workspace_bytes(min(65535, n), hh, ww, n_mc))
     ws = torch.empty(max(ws_bytes, 16), dtype=torch.uint8, device=x.device)  # stream-ordered: reused per slice
@@ -1563,8 +1556,8 @@ def mc_entropy(x: torch.Tensor, rand: Union[torch.Tensor, CounterDraws, None], n
             else:
                 launch("runia_mc_mask_table_f32", rp, stride, ws.data_ptr(), ws_bytes, m, hh, ww, n_mc, float(drop_prob),
                        int(block_size))
-            kernel_events.append(_timed_call("runia_mc_entropy_from_table_f32", xp, ws.data_ptr(), ws_bytes, hp, zp, zf, m, c, hh,
-                                             ww, n_mc, int(k), float(min_dist)))
+            _launch_with_events(kernel_events, "runia_mc_entropy_from_table_f32", xp, ws.data_ptr(), ws_bytes, hp, zp, zf, m, c,
+                                hh, ww, n_mc, int(k), float(min_dist))
         elif counter is not None:
             launch("runia_mc_entropy_counter_f32", xp, seed, int(counter.first_image) + done, hp, zp, zf, ws.data_ptr(), ws_bytes,
                    m, c, hh, ww, n_mc, float(drop_prob), int(block_size), int(k), float(min_dist), redraw)

@@ -612,12 +612,6 @@ int next_pow2(int n) {
   return p;
 }
 
-double digamma_diff(int n, int k) {  // psi(n) - psi(k) = sum_{j=k}^{n-1} 1/j for integers
-  double s = 0.0;
-  for (int j = n - 1; j >= k; --j) s += 1.0 / (double)j;
-  return s;
-}
-
 template <int NP, int K>
 void launch_per_dim(const float* z, double* h, int64_t N, int n, int64_t D, double min_dist, double ct,
                     double inv_n, hipStream_t s) {

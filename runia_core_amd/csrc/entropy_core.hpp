@@ -1,4 +1,4 @@
-// Register-level core of the 1-D Kozachenko-Leonenko entropy (shared by entropy.hip and fused.hip):
+// Register-level core of the 1-D Kozachenko-Leonenko entropy (shared by entropy.hip and mc_sampler.hip):
 // a sorting network over NP floats and the k-th-nearest-neighbour window scan in f64.
 #pragma once
 #include "common.hpp"
@@ -6,6 +6,12 @@
 namespace runia_entropy {
 
 constexpr double kInf = __builtin_inf();
+
+inline double digamma_diff(int n, int k) {  // psi(n) - psi(k) = sum_{j=k}^{n-1} 1/j for integers (host)
+  double s = 0.0;
+  for (int j = n - 1; j >= k; --j) s += 1.0 / (double)j;
+  return s;
+}
 
 // One compare-exchange = v_min_f32 + v_max_f32.  Written as instructions because fminf/fmaxf make the
 // compiler canonicalise every operand it cannot prove quiet (72 extra `v_max_f32 v, v, v` per 16-sort).

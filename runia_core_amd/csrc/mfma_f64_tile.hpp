@@ -1,4 +1,4 @@
-// Shared pieces of the f64 matrix-core kernels (gemm_f64.hip, fused.hip).
+// Shared pieces of the f64 matrix-core kernels (gemm_f64.hip, proj_sq.hip).
 //
 // Packed weights.  A constant right-hand matrix B [K, n] is stored in MFMA fragment order:
 //   packed[((s2*NT + ct)*64 + lane)*2 + h] = B[8*s2 + 4*h + (lane>>4)][16*ct + (lane&15)]

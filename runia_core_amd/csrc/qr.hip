@@ -1,4 +1,4 @@
-// Setup-time helper of the folded LaREM score (fused.hip, K2'): the score -|| M h + c ||^2 does not change under an orthogonal
+// Setup-time helper of the folded LaREM score (proj_sq.hip, K2'): the score -|| M h + c ||^2 does not change under an orthogonal
 // Q applied from the left, so M [r, D] (r <= D) is replaced once per fitted state by the upper-trapezoidal R = Q M
 // (R[j][k] = 0 for k < j) and c by Q c; K2' then skips the k range in which a column tile of R^T holds only zeros.
 // Householder reflections on the augmented [M | c] - not the Cholesky factor of M^T M, which squares the condition number

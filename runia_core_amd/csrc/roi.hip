@@ -7,6 +7,7 @@
 //   samples further than one pixel outside the map contribute 0, coordinates are clamped to the map.
 // Output [K, C, PH, PW] f32 = the (N, C, H, W) input of the sampler kernels (runia_mc_entropy_f32 for 2x2/4x4/7x7/8x8).
 #include "common.hpp"
+#include "roi_source.hpp"
 
 namespace {
 
@@ -60,7 +61,7 @@ __global__ __launch_bounds__(256) void roi_align_kernel(const float* __restrict_
   }
 }
 
-// ---- roi_align folded into the sampler's load (fused.hip, roi_load_map) ---------------------------------------------------
+// ---- roi_align folded into the sampler's load (mc_sampler.hip, roi_load_map) ---------------------------------------------------
 // The feature map in NHWC, so that the 64 channels of a wave read one bilinear tap as one contiguous run.
 __global__ __launch_bounds__(256) void nchw_to_nhwc_kernel(const float* __restrict__ in, float* __restrict__ out, int C,
                                                             int64_t HW) {
@@ -84,24 +85,14 @@ __global__ __launch_bounds__(256) void nchw_to_nhwc_kernel(const float* __restri
   }
 }
 
-// mirrors RoiSource of fused.hip
-struct RoiSourceHost {
-  const float* quads;
-  const unsigned* table;
-  int64_t image_bytes;
-  int C;
-  int roi_dwords;
-};
-static_assert(sizeof(RoiSourceHost) <= 64, "the source description fits the head of the table");
-
 // One thread per sample row or sample column of a ROI (PH * G rows, then PW * G columns).  The coordinates, the validity
 // test, the clamping and the weights are those of `bilinear` / roi_align_kernel above, expression for expression (they are
 // separable: y and x never meet before the four products).
-__global__ __launch_bounds__(256) void roi_sample_table_kernel(RoiSourceHost src, const float* __restrict__ boxes,
+__global__ __launch_bounds__(256) void roi_sample_table_kernel(RoiSource src, const float* __restrict__ boxes,
                                                                 const int* __restrict__ batch_idx, unsigned* __restrict__ tab,
                                                                 int64_t K, int64_t B, int C, int H, int W, int PH, int PW,
                                                                 float spatial_scale, int G, int aligned) {
-  if (blockIdx.x == 0 && threadIdx.x == 0) *reinterpret_cast<RoiSourceHost*>(tab) = src;
+  if (blockIdx.x == 0 && threadIdx.x == 0) *reinterpret_cast<RoiSource*>(tab) = src;
   unsigned* roi_tab = tab + 16;  // 64 bytes of RoiSource in front
   const int nrows = PH * G, ncols = PW * G, per_roi = nrows + ncols, roi_dwords = 8 + 4 * per_roi;
   const int64_t total = K * per_roi;
@@ -164,8 +155,8 @@ int runia_roi_sample_table(const float* feat_nhwc, const float* boxes, const int
                            hipStream_t s) {
   if (table_bytes < runia_roi_sample_table_bytes(K, PH, PW, G) || PH * G > 32 || PW * G > 32) return RUNIA_E_WORKSPACE;
   if ((int64_t)H * W * C * 4 >= (int64_t)1 << 30) return RUNIA_E_INVALID;  // (offsets of outside samples: row + column + channel stay below 2^32)
-  RoiSourceHost src;
-  src.quads = feat_nhwc;
+  RoiSource src;
+  src.nhwc = feat_nhwc;
   src.table = reinterpret_cast<const unsigned*>(table) + 16;
   src.image_bytes = (int64_t)H * W * C * 4;
   src.C = C;

@@ -1,5 +1,5 @@
 // Balanced order of the 32-row blocks of an upper-trapezoidal R [r, D] (runia_qr_trapezoid_f64) over the 32-column groups
-// of its packed transpose: ONE rule for the setup code that permutes the rows (qr.hip) and for K2' (fused.hip), which
+// of its packed transpose: ONE rule for the setup code that permutes the rows (qr.hip) and for K2' (proj_sq.hip), which
 // takes every group's first live chunk from it.
 //
 // Block b of R (rows 32 b .. 32 b + 31) is zero for k < 32 b, so the column group that holds it may skip b chunks of 32.

@@ -1,6 +1,6 @@
 #!/bin/bash
 # Whole library with one source file recompiled under extra -D flags (the other objects are the shipped ones):
-#   tools/ablate/build_lib_variant.sh fused.hip k2w1 -DK2_WAVES=1   ->  runia_core_amd/librunia_k2w1.so
+#   tools/ablate/build_lib_variant.sh proj_sq.hip k2w1 -DK2_WAVES=1   ->  runia_core_amd/librunia_k2w1.so
 # The variant travels to the GPU box with the snapshot; select it with RUNIA_LIB=$PWD/runia_core_amd/librunia_<tag>.so
 set -e
 cd "$(dirname "$0")/../../runia_core_amd/csrc"

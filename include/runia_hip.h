@@ -138,6 +138,25 @@ int runia_kl_entropy_joint_f32(const float* z, double* h_mvn, int64_t N, int n_m
  * kernel covers 5 <= n_mc <= 32 with k = 5 (n_mc <= 8 also k = 4) on rows of whole 16-byte (n_mc <= 16) / 8-byte vectors;
  * runia_kl_entropy_both_fused tells (1 / 0); other shapes run the two kernels one after the other inside the same call. */
 int runia_kl_entropy_both_fused(int n_mc, int64_t D, int k);
+/* Which kernel runia_kl_entropy_joint_f32 / runia_kl_entropy_per_dim_f32 launch for a shape (host-only; the two entry points
+ * choose through these very functions, so the answer is the dispatch).  byte_offset: the operands' distance from a 16-byte
+ * boundary - z & 15 for the joint call, (z | h) & 15 for the per-dimension one.  RUNIA_E_INVALID for arguments the entry points
+ * refuse (n_mc outside 2 .. 64, D <= 0, k outside 1 .. n_mc - 1) and for byte_offset < 0.
+ *   joint          LDS: any shape (n_mc > 32, rows that are not whole aligned vectors);  REG8 / REG16 / REG32: the register form
+ *                  with room for 8 / 16 / 32 samples (n_mc <= 8 / 16 / 32; rows of whole 16- / 16- / 8-byte aligned vectors);
+ *                  PAIR16: the pair-group form (9 <= n_mc <= 16, even D, 8-byte aligned rows).
+ *   per dimension  GENERIC: the insertion-sort kernel for any k;  RUNIA_KL_PER_DIM_REG(NP, K, VEC) = 100 NP + 10 K + VEC: the
+ *                  register kernel with room for NP = 4 .. 64 samples (the power of two >= n_mc), K = k compiled in and
+ *                  VEC = 4 (float4 loads: NP <= 16, D % 4 == 0, byte_offset % 16 == 0) or 1 adjacent dims per thread. */
+#define RUNIA_KL_JOINT_LDS 0
+#define RUNIA_KL_JOINT_REG8 1
+#define RUNIA_KL_JOINT_REG16 2
+#define RUNIA_KL_JOINT_REG32 3
+#define RUNIA_KL_JOINT_PAIR16 4
+#define RUNIA_KL_PER_DIM_GENERIC 0
+#define RUNIA_KL_PER_DIM_REG(np, k, vec) (100 * (np) + 10 * (k) + (vec))
+int runia_kl_entropy_joint_form(int n_mc, int64_t D, int byte_offset);
+int runia_kl_entropy_per_dim_form(int n_mc, int k, int64_t D, int byte_offset);
 int runia_kl_entropy_both_f32(const float* z, double* h_mvn, double* h, int64_t N, int n_mc, int64_t D, int k,
                               double min_dist, runia_stream_t stream);
 

@@ -47,6 +47,8 @@ _SIGNATURES = {
     "runia_kl_entropy_per_dim_f32": (c_int, [c_void_p, c_void_p, c_int64, c_int, c_int64, c_int, c_double, c_void_p]),
     "runia_kl_entropy_joint_f32": (c_int, [c_void_p, c_void_p, c_int64, c_int, c_int64, c_int, c_double, c_void_p]),
     "runia_kl_entropy_both_fused": (c_int, [c_int, c_int64, c_int]),
+    "runia_kl_entropy_joint_form": (c_int, [c_int, c_int64, c_int]),
+    "runia_kl_entropy_per_dim_form": (c_int, [c_int, c_int, c_int64, c_int]),
     "runia_kl_entropy_both_f32": (c_int, [c_void_p, c_void_p, c_void_p, c_int64, c_int, c_int64, c_int, c_double, c_void_p]),
     "runia_packed_weights_bytes": (c_size_t, [c_int64, c_int64]),
     "runia_pack_weights_f64": (c_int, [c_void_p, c_int64, c_int64, c_int64, c_void_p, c_void_p]),

@@ -19,6 +19,18 @@ namespace {
 
 using namespace runia_entropy;
 
+// NaN probe of one column (samples, then +inf pads): a sum is NaN iff a term is - as long as the finite terms cannot add up
+// to -inf, which would meet the +inf pads of a short column as NaN.  Hence the factor 2^-8: at most 64 samples of at most
+// 3.4e38 / 256 stay inside the f32 range (samples of +-3e38 gave NaN entropies for n_mc = 2, 3, 5, ... before).  One
+// multiply-add per sample, as the plain sum was one add.
+template <int NP>
+__device__ __forceinline__ bool column_has_nan(const float (&v)[NP]) {
+  float probe = v[0] * 0x1p-8f;
+#pragma unroll
+  for (int t = 1; t < NP; ++t) probe = fmaf(v[t], 0x1p-8f, probe);
+  return probe != probe;
+}
+
 // VEC adjacent dims per thread (VEC = 4 -> float4 loads, VEC = 1 -> scalar)
 template <int NP, int K, int VEC>
 __global__ __launch_bounds__(256) void entropy_per_dim_kernel(const float* __restrict__ z,
@@ -49,14 +61,11 @@ __global__ __launch_bounds__(256) void entropy_per_dim_kernel(const float* __res
     double out[VEC];
 #pragma unroll
     for (int q = 0; q < VEC; ++q) {
-      // a NaN sample makes the reference's entropy NaN; the min/max sort would drop it, so it is caught first (a sum is
-      // NaN iff a term is: the +inf pads of a short column cannot cancel finite samples)
-      float probe = v[q][0];
-#pragma unroll
-      for (int t = 1; t < NP; ++t) probe += v[q][t];
+      // a NaN sample makes the reference's entropy NaN; the min/max sort would drop it, so it is caught first
+      const bool has_nan = column_has_nan<NP>(v[q]);
       sort_asc<NP>(v[q]);
       out[q] = const_term + inv_n * column_log_sum<NP, K>(v[q], n, min_dist);
-      if (probe != probe) out[q] = NAN;
+      if (has_nan) out[q] = NAN;
     }
     double* dst = h + img * D + c * VEC;
     if constexpr (VEC == 4) {
@@ -367,12 +376,10 @@ __global__ __launch_bounds__(256) void entropy_joint_reg_kernel(const float* __r
             float col[NP];
 #pragma unroll
             for (int s = 0; s < NP; ++s) col[s] = (s < n) ? raw[s][q] : INFINITY;
-            float probe = col[0];  // NaN sample -> NaN entropy, as entropy_per_dim_kernel
-#pragma unroll
-            for (int t = 1; t < NP; ++t) probe += col[t];
+            const bool has_nan = column_has_nan<NP>(col);  // NaN sample -> NaN entropy, as entropy_per_dim_kernel
             sort_asc<NP>(col);
             out[q] = const_term + inv_n * column_log_sum<NP, K1D>(col, n, min_dist);
-            if (probe != probe) out[q] = NAN;
+            if (has_nan) out[q] = NAN;
           }
           double* dst = h_dim + img * D + dd;
 #pragma unroll
@@ -612,10 +619,10 @@ int next_pow2(int n) {
   return p;
 }
 
+// vec: the float4 variant, as runia_kl_entropy_per_dim_form decided it
 template <int NP, int K>
 void launch_per_dim(const float* z, double* h, int64_t N, int n, int64_t D, double min_dist, double ct,
-                    double inv_n, hipStream_t s) {
-  const bool vec = (NP <= 16) && ((D & 3) == 0) && ((((uintptr_t)z) & 15) == 0) && ((((uintptr_t)h) & 15) == 0);
+                    double inv_n, bool vec, hipStream_t s) {
   if constexpr (NP <= 16) {
     if (vec) {
       entropy_per_dim_kernel<NP, K, 4><<<runia_stream_grid(N * (D / 4), 256), 256, 0, s>>>(
@@ -629,6 +636,32 @@ void launch_per_dim(const float* z, double* h, int64_t N, int n, int64_t D, doub
 
 }  // namespace
 
+// ---- which kernel a shape takes: host-only queries, and the dispatch itself (the two entry points below switch on them) ----
+// byte_offset: the operands' distance from a 16-byte boundary ((z | h) & 15 for the per-dimension call, z & 15 for the joint one).
+extern "C" int runia_kl_entropy_per_dim_form(int n_mc, int k, int64_t D, int byte_offset) {
+  if (D <= 0 || n_mc < 2 || n_mc > 64 || k < 1 || k >= n_mc || byte_offset < 0) return RUNIA_E_INVALID;
+  const int np = next_pow2(n_mc);
+  // register kernels exist for K = 1 .. 3 at NP = 4, K = 4, 5 at NP = 8 and K = 5 from NP = 16 on
+  const bool reg = (np == 4) || (np == 8 && (k == 4 || k == 5)) || (np >= 16 && k == 5);
+  if (!reg) return RUNIA_KL_PER_DIM_GENERIC;
+  const bool vec = (np <= 16) && ((D & 3) == 0) && ((byte_offset & 15) == 0);
+  return RUNIA_KL_PER_DIM_REG(np, k, vec ? 4 : 1);
+}
+
+#ifndef JOINT_PAIR16
+#define JOINT_PAIR16 1
+#endif
+extern "C" int runia_kl_entropy_joint_form(int n_mc, int64_t D, int byte_offset) {
+  if (D <= 0 || n_mc < 2 || n_mc > 64 || byte_offset < 0) return RUNIA_E_INVALID;
+  if (JOINT_PAIR16 && n_mc > 8 && n_mc <= 16 && (D & 1) == 0 && (byte_offset & 7) == 0)  // pair-group form (round 6)
+    return RUNIA_KL_JOINT_PAIR16;
+  // register form: rows of whole, aligned vectors (the LDS form takes everything else)
+  const int vec = n_mc <= 8 ? 4 : (n_mc <= 16 ? JOINT_VEC16 : 2);
+  if (n_mc <= 32 && D % vec == 0 && byte_offset % (4 * vec) == 0)
+    return n_mc <= 8 ? RUNIA_KL_JOINT_REG8 : (n_mc <= 16 ? RUNIA_KL_JOINT_REG16 : RUNIA_KL_JOINT_REG32);
+  return RUNIA_KL_JOINT_LDS;
+}
+
 extern "C" int runia_kl_entropy_per_dim_f32(const float* z, double* h, int64_t N, int n_mc, int64_t D, int k,
                                             double min_dist, runia_stream_t stream) {
   if (N < 0 || D <= 0 || n_mc < 2 || n_mc > 64 || k < 1 || k >= n_mc || (N > 0 && (!z || !h)))
@@ -637,20 +670,22 @@ extern "C" int runia_kl_entropy_per_dim_f32(const float* z, double* h, int64_t N
   hipStream_t s = as_stream(stream);
   const double ct = digamma_diff(n_mc, k);
   const double inv_n = 1.0 / (double)n_mc;
-  const int np = next_pow2(n_mc);
-  bool done = true;
-  if (np == 4 && k == 1) launch_per_dim<4, 1>(z, h, N, n_mc, D, min_dist, ct, inv_n, s);
-  else if (np == 4 && k == 2) launch_per_dim<4, 2>(z, h, N, n_mc, D, min_dist, ct, inv_n, s);
-  else if (np == 4 && k == 3) launch_per_dim<4, 3>(z, h, N, n_mc, D, min_dist, ct, inv_n, s);
-  else if (np == 8 && k == 4) launch_per_dim<8, 4>(z, h, N, n_mc, D, min_dist, ct, inv_n, s);
-  else if (np == 8 && k == 5) launch_per_dim<8, 5>(z, h, N, n_mc, D, min_dist, ct, inv_n, s);
-  else if (np == 16 && k == 5) launch_per_dim<16, 5>(z, h, N, n_mc, D, min_dist, ct, inv_n, s);
-  else if (np == 32 && k == 5) launch_per_dim<32, 5>(z, h, N, n_mc, D, min_dist, ct, inv_n, s);
-  else if (np == 64 && k == 5) launch_per_dim<64, 5>(z, h, N, n_mc, D, min_dist, ct, inv_n, s);
-  else done = false;
-  if (!done)
-    entropy_per_dim_generic_kernel<<<runia_stream_grid(N * D, 64), 64, 0, s>>>(z, h, N, n_mc, D, k, min_dist,
-                                                                               ct, inv_n);
+  const int form = runia_kl_entropy_per_dim_form(n_mc, k, D, (int)((((uintptr_t)z) | ((uintptr_t)h)) & 15));
+  const bool vec = form % 10 == 4;
+  switch (form / 10) {  // NP * 10 + K of RUNIA_KL_PER_DIM_REG
+    case 41: launch_per_dim<4, 1>(z, h, N, n_mc, D, min_dist, ct, inv_n, vec, s); break;
+    case 42: launch_per_dim<4, 2>(z, h, N, n_mc, D, min_dist, ct, inv_n, vec, s); break;
+    case 43: launch_per_dim<4, 3>(z, h, N, n_mc, D, min_dist, ct, inv_n, vec, s); break;
+    case 84: launch_per_dim<8, 4>(z, h, N, n_mc, D, min_dist, ct, inv_n, vec, s); break;
+    case 85: launch_per_dim<8, 5>(z, h, N, n_mc, D, min_dist, ct, inv_n, vec, s); break;
+    case 165: launch_per_dim<16, 5>(z, h, N, n_mc, D, min_dist, ct, inv_n, vec, s); break;
+    case 325: launch_per_dim<32, 5>(z, h, N, n_mc, D, min_dist, ct, inv_n, vec, s); break;
+    case 645: launch_per_dim<64, 5>(z, h, N, n_mc, D, min_dist, ct, inv_n, vec, s); break;
+    default:
+      if (form != RUNIA_KL_PER_DIM_GENERIC) return RUNIA_E_INVALID;
+      entropy_per_dim_generic_kernel<<<runia_stream_grid(N * D, 64), 64, 0, s>>>(z, h, N, n_mc, D, k, min_dist,
+                                                                                 ct, inv_n);
+  }
   return runia_check_launch();
 }
 
@@ -662,26 +697,22 @@ extern "C" int runia_kl_entropy_joint_f32(const float* z, double* h_mvn, int64_t
   const double ct = digamma_diff(n_mc, k);
   const double d_over_n = (double)D / (double)n_mc;
   hipStream_t s = as_stream(stream);
-#ifndef JOINT_PAIR16
-#define JOINT_PAIR16 1
-#endif
-  if (JOINT_PAIR16 && n_mc > 8 && n_mc <= 16 && (D & 1) == 0 && (((uintptr_t)z) & 7) == 0) {  // pair-group form (round 6)
+  const int form = runia_kl_entropy_joint_form(n_mc, D, (int)(((uintptr_t)z) & 15));
+  if (form == RUNIA_KL_JOINT_PAIR16) {
     entropy_joint_pair16_kernel<<<(unsigned)(N < 0x7fffffffll ? N : 0x7fffffffll), 64, 0, s>>>(z, h_mvn, N, n_mc, D, k, min_dist, ct, d_over_n);
     return runia_check_launch();
   }
-  {
-    // register form: rows of whole, aligned vectors (the LDS form below takes everything else)
-    const int vec = n_mc <= 8 ? 4 : (n_mc <= 16 ? JOINT_VEC16 : 2);
-    if (n_mc <= 32 && D % vec == 0 && ((uintptr_t)z) % (4 * vec) == 0) {
-      const int64_t lanes = (D / vec + 63) / 64 * 64;
-      const unsigned threads = (unsigned)(lanes < 256 ? lanes : 256);
-      const unsigned grid = (unsigned)(N < 0x7fffffffll ? N : 0x7fffffffll);
-      if (n_mc <= 8) entropy_joint_reg_kernel<8><<<grid, threads, 0, s>>>(z, h_mvn, N, n_mc, D, k, min_dist, ct, d_over_n);
-      else if (n_mc <= 16) entropy_joint_reg_kernel<16><<<grid, threads, 0, s>>>(z, h_mvn, N, n_mc, D, k, min_dist, ct, d_over_n);
-      else entropy_joint_reg_kernel<32><<<grid, threads, 0, s>>>(z, h_mvn, N, n_mc, D, k, min_dist, ct, d_over_n);
-      return runia_check_launch();
-    }
+  if (form == RUNIA_KL_JOINT_REG8 || form == RUNIA_KL_JOINT_REG16 || form == RUNIA_KL_JOINT_REG32) {
+    const int vec = form == RUNIA_KL_JOINT_REG8 ? 4 : (form == RUNIA_KL_JOINT_REG16 ? JOINT_VEC16 : 2);
+    const int64_t lanes = (D / vec + 63) / 64 * 64;
+    const unsigned threads = (unsigned)(lanes < 256 ? lanes : 256);
+    const unsigned grid = (unsigned)(N < 0x7fffffffll ? N : 0x7fffffffll);
+    if (form == RUNIA_KL_JOINT_REG8) entropy_joint_reg_kernel<8><<<grid, threads, 0, s>>>(z, h_mvn, N, n_mc, D, k, min_dist, ct, d_over_n);
+    else if (form == RUNIA_KL_JOINT_REG16) entropy_joint_reg_kernel<16><<<grid, threads, 0, s>>>(z, h_mvn, N, n_mc, D, k, min_dist, ct, d_over_n);
+    else entropy_joint_reg_kernel<32><<<grid, threads, 0, s>>>(z, h_mvn, N, n_mc, D, k, min_dist, ct, d_over_n);
+    return runia_check_launch();
   }
+  if (form != RUNIA_KL_JOINT_LDS) return RUNIA_E_INVALID;
   const size_t lds = ((size_t)n_mc * (kJointChunk + 2) + (size_t)n_mc * (n_mc + 1)) * sizeof(double);  // <= 99 KB
   static std::atomic<uint64_t> lds_ok{0};
   if (runia_allow_dynamic_lds(reinterpret_cast<const void*>(entropy_joint_kernel), 100 * 1024, lds_ok) != RUNIA_OK)

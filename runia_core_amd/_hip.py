@@ -9,8 +9,9 @@ from __future__ import annotations
 import contextlib
 import ctypes
 import os
+import re
 import threading
-from ctypes import c_char_p, c_double, c_float, c_int, c_int64, c_size_t, c_uint64, c_void_p
+from ctypes import c_char_p, c_double, c_float, c_int, c_int64, c_size_t, c_uint32, c_uint64, c_void_p
 from typing import NamedTuple, Optional, Tuple, Union
 
 import numpy as np
@@ -21,386 +22,77 @@ from . import config as _config
 _LIB_PATH = os.path.join(os.path.dirname(os.path.abspath(__file__)), "librunia_hip.so")
 _lib: Optional[ctypes.CDLL] = None
 
-# name -> (restype, argtypes); mirrors include/runia_hip.h one to one
-_SIGNATURES = {
-    "runia_abi_version": (c_int, []),
-    "runia_error_string": (c_char_p, [c_int]),
-    "runia_device_count": (c_int, []),
-    "runia_clock_probe": (c_int, [c_void_p, c_int, c_void_p]),
-    "runia_time_next_launch": (c_int, [c_void_p, c_void_p]),
-    "runia_mc_stack_f32": (
-        c_int,
-        [c_void_p, c_void_p, c_int64, c_void_p, c_int64, c_int, c_int, c_int, c_int, c_double, c_int, c_void_p],
-    ),
-    "runia_mc_drop_flat_f32": (
-        c_int,
-        [c_void_p, c_void_p, c_int64, c_void_p, c_int64, c_int, c_int, c_int, c_int, c_double, c_int, c_void_p],
-    ),
-    "runia_map_reduce_f32": (c_int, [c_void_p, c_void_p, c_int64, c_int, c_int, c_int, c_void_p]),
-    "runia_mcd_reduce_rows": (
-        c_int,
-        [c_void_p, c_int, c_int64, c_int64, c_int64, c_int64, c_int64, c_int64, c_int64, c_int64, c_int, c_int, c_int,
-         c_int, c_void_p, c_int64, c_int64, c_int64, c_int64, c_void_p],
-    ),
-    "runia_ragged_rows": (
-        c_int, [c_void_p, c_void_p, c_int64, c_int64, c_int64, c_int, c_int, c_void_p, c_int64, c_void_p, c_void_p]),
-    "runia_kl_entropy_per_dim_f32": (c_int, [c_void_p, c_void_p, c_int64, c_int, c_int64, c_int, c_double, c_void_p]),
-    "runia_kl_entropy_joint_f32": (c_int, [c_void_p, c_void_p, c_int64, c_int, c_int64, c_int, c_double, c_void_p]),
-    "runia_kl_entropy_both_fused": (c_int, [c_int, c_int64, c_int]),
-    "runia_kl_entropy_joint_form": (c_int, [c_int, c_int64, c_int]),
-    "runia_kl_entropy_per_dim_form": (c_int, [c_int, c_int, c_int64, c_int]),
-    "runia_kl_entropy_both_f32": (c_int, [c_void_p, c_void_p, c_void_p, c_int64, c_int, c_int64, c_int, c_double, c_void_p]),
-    "runia_packed_weights_bytes": (c_size_t, [c_int64, c_int64]),
-    "runia_pack_weights_f64": (c_int, [c_void_p, c_int64, c_int64, c_int64, c_void_p, c_void_p]),
-    "runia_pca_transform_f64": (
-        c_int,
-        [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_int64, c_int64, c_int, c_void_p],
-    ),
-    "runia_pca_transform_f32in": (
-        c_int,
-        [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_int64, c_int64, c_int, c_void_p],
-    ),
-    "runia_md_score_f64": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_int64, c_void_p]),
-    "runia_md_score_f32": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_int64, c_void_p]),
-    "runia_md_score_f32x_f64mean": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_int64, c_void_p]),
-    "runia_md_score_tril_f64": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, c_int64, c_int64, c_void_p]),
-    "runia_md_score_tril_f32": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, c_int64, c_int64, c_void_p]),
-    "runia_md_score_tril_f32x_f64mean": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, c_int64, c_int64, c_void_p]),
-    "runia_md_score_workspace_bytes": (c_size_t, [c_int64, c_int64]),
-    "runia_md_score_ws_f64": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, c_int64, c_int64, c_void_p]),
-    "runia_md_score_ws_f32": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, c_int64, c_int64, c_void_p]),
-    "runia_md_score_ws_f32x_f64mean": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, c_int64, c_int64, c_void_p]),
-    "runia_mahalanobis_workspace_bytes": (c_size_t, [c_int64, c_int64]),
-    "runia_mahalanobis_workspace_bytes_classes": (c_size_t, [c_int64, c_int64, c_int]),
-    "runia_mahalanobis_score_f32": (
-        c_int,
-        [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, c_int64, c_int64, c_int, c_void_p],
-    ),
-    "runia_mahalanobis_score_f64": (
-        c_int,
-        [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, c_int64, c_int64, c_int, c_void_p],
-    ),
-    "runia_row_lse_msp_f32": (c_int, [c_void_p, c_void_p, c_void_p, c_int64, c_int64, c_void_p]),
-    "runia_l2_normalize_f32": (c_int, [c_void_p, c_void_p, c_int64, c_int64, c_void_p]),
-    "runia_kde_score_kernel_f64": (c_int, [c_void_p, c_void_p, c_void_p, c_int64, c_int64, c_int64, c_double, c_int, c_void_p]),
-    "runia_knn_workspace_bytes": (c_size_t, [c_int64, c_int64, c_int64, c_int]),
-    "runia_knn_piece_products": (c_int, [c_int64, c_int64, c_int64]),
-    "runia_knn_bank_state_bytes": (c_size_t, [c_int64, c_int64]),
-    "runia_knn_prepare_bank_f32": (c_int, [c_void_p, c_void_p, c_size_t, c_int64, c_int64, c_void_p]),
-    "runia_knn_prepared_workspace_bytes": (c_size_t, [c_int64, c_int64, c_int64, c_int]),
-    "runia_knn_kth_prepared_f32": (c_int, [c_void_p, c_void_p, c_void_p, c_size_t, c_void_p, c_void_p, c_size_t, c_int64, c_int64,
-                                           c_int64, c_int, c_void_p]),
-    "runia_knn_kth_f32": (
-        c_int,
-        [c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, c_int64, c_int64, c_int64, c_int, c_void_p],
-    ),
-    "runia_kde_score_f64": (c_int, [c_void_p, c_void_p, c_void_p, c_int64, c_int64, c_int64, c_double, c_void_p]),
-    "runia_row_sqnorm_f64": (c_int, [c_void_p, c_void_p, c_int64, c_int64, c_void_p]),
-    "runia_kde_workspace_bytes": (c_size_t, [c_int64, c_int64]),
-    "runia_kde_score_packed_f64": (
-        c_int,
-        [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, c_int64, c_int64, c_int64, c_double, c_void_p],
-    ),
-    "runia_mc_entropy_supported": (c_int, [c_int, c_int, c_int, c_int]),
-    "runia_mc_entropy_workspace_bytes": (c_size_t, [c_int64, c_int, c_int, c_int]),
-    "runia_mc_mask_table_f32": (
-        c_int,
-        [c_void_p, c_int64, c_void_p, c_size_t, c_int64, c_int, c_int, c_int, c_double, c_int, c_void_p],
-    ),
-    "runia_mc_stack_table_f32": (
-        c_int,
-        [c_void_p, c_void_p, c_int64, c_void_p, c_void_p, c_size_t, c_int64, c_int, c_int, c_int, c_int, c_double, c_int,
-         c_void_p],
-    ),
-    "runia_mc_entropy_from_table_f32": (
-        c_int,
-        [c_void_p, c_void_p, c_size_t, c_void_p, c_void_p, c_void_p, c_int64, c_int, c_int, c_int, c_int, c_int,
-         c_double, c_void_p],
-    ),
-    "runia_mc_entropy_f32": (
-        c_int,
-        [c_void_p, c_void_p, c_int64, c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, c_int64, c_int, c_int, c_int,
-         c_int, c_double, c_int, c_int, c_double, c_void_p],
-    ),
-    "runia_mc_flag_lut_bytes": (c_size_t, [c_int, c_int, c_int]),
-    "runia_mc_flag_lut_fill": (c_int, [c_void_p, c_size_t, c_int, c_int, c_int]),
-    "runia_mc_entropy_lut_supported": (c_int, [c_int, c_int, c_int, c_int, c_int]),
-    "runia_mc_entropy_lut_f32": (
-        c_int,
-        [c_void_p, c_void_p, c_int64, c_void_p, c_size_t, c_void_p, c_void_p, c_int64, c_int, c_int, c_int, c_int, c_double,
-         c_int, c_int, c_double, c_void_p],
-    ),
-    "runia_mc_draws_f32": (c_int, [c_void_p, c_int64, c_int, c_int, c_int, c_uint64, c_int64, c_void_p]),
-    "runia_mc_mask_table_counter_f32": (
-        c_int,
-        [c_uint64, c_int64, c_void_p, c_size_t, c_int64, c_int, c_int, c_int, c_double, c_int, c_int, c_void_p],
-    ),
-    "runia_mc_entropy_counter_f32": (
-        c_int,
-        [c_void_p, c_uint64, c_int64, c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, c_int64, c_int, c_int, c_int,
-         c_int, c_double, c_int, c_int, c_double, c_int, c_void_p],
-    ),
-    "runia_select_hist_f32": (c_int, [c_void_p, c_void_p, c_int64, ctypes.c_uint32, ctypes.c_uint32, c_int, c_void_p]),
-    "runia_cholesky_f32": (c_int, [c_void_p, c_void_p, c_int64, c_int64, c_double, c_void_p]),
-    "runia_cholesky_f64": (c_int, [c_void_p, c_void_p, c_int64, c_int64, c_double, c_void_p]),
-    "runia_gmm_log_prob_workspace_bytes": (c_size_t, [c_int64, c_int64, c_int]),
-    "runia_gmm_log_prob_f32": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, c_int64,
-                                       c_int64, c_int, c_void_p]),
-    "runia_ood_metrics_workspace_bytes": (c_size_t, [c_int64]),
-    "runia_ood_metrics_f64": (c_int, [c_void_p, c_int64, c_void_p, c_int64, c_void_p, c_void_p, c_size_t, c_void_p]),
-    "runia_ood_metrics_f32": (c_int, [c_void_p, c_int64, c_void_p, c_int64, c_void_p, c_void_p, c_size_t, c_void_p]),
-    "runia_ood_clf_curve_f64": (
-        c_int, [c_void_p, c_int64, c_void_p, c_int64, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]),
-    "runia_ood_clf_curve_f32": (
-        c_int, [c_void_p, c_int64, c_void_p, c_int64, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]),
-    "runia_eigh_workspace_bytes": (c_size_t, [c_int64]),
-    "runia_eigh_init_f64": (c_int, [c_void_p, c_void_p, c_int64, c_void_p, c_size_t, c_void_p]),
-    "runia_eigh_sweep_f64": (c_int, [c_void_p, c_void_p, c_int64, c_void_p, c_size_t, c_void_p, c_void_p]),
-    "runia_eigh_block_padded": (c_int64, [c_int64]),
-    "runia_eigh_block_workspace_bytes": (c_size_t, [c_int64]),
-    "runia_eigh_block_init_f64": (c_int, [c_void_p, c_void_p, c_int64, c_void_p, c_size_t, c_void_p]),
-    "runia_eigh_block_sweep_f64": (c_int, [c_void_p, c_void_p, c_int64, c_void_p, c_size_t, c_void_p, c_void_p]),
-    "runia_matmul_f64": (c_int, [c_void_p, c_void_p, c_void_p, c_int64, c_int64, c_int64, c_int, c_void_p]),
-    "runia_p2p_buffer_bytes": (c_size_t, [c_int, c_size_t]),
-    "runia_p2p_alloc": (c_int, [c_int, c_size_t, ctypes.POINTER(c_void_p)]),
-    "runia_p2p_free": (c_int, [c_void_p]),
-    "runia_p2p_export": (c_int, [c_void_p, c_void_p]),
-    "runia_p2p_open": (c_int, [c_void_p, ctypes.POINTER(c_void_p)]),
-    "runia_p2p_close": (c_int, [c_void_p]),
-    "runia_p2p_all_gather": (
-        c_int, [c_void_p, c_size_t, c_void_p, ctypes.POINTER(c_void_p), c_int, c_int, c_size_t, c_uint64, c_int, c_void_p]),
-    "runia_p2p_status": (c_int, [c_void_p, ctypes.POINTER(c_int)]),
-    "runia_p2p_debug": (c_int, [c_int]),
-    "runia_centred_gram_f32": (c_int, [c_void_p, c_void_p, c_int64, c_int64, c_double, c_void_p]),
-    "runia_roi_align_f32": (
-        c_int,
-        [c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_int64, c_int, c_int, c_int, c_int, c_int, c_double, c_int, c_int,
-         c_void_p],
-    ),
-    "runia_nchw_to_nhwc_f32": (c_int, [c_void_p, c_void_p, c_int64, c_int, c_int64, c_void_p]),
-    "runia_roi_mc_entropy_supported": (c_int, [c_int, c_int, c_int, c_int, c_int]),
-    "runia_roi_mc_entropy_workspace_bytes": (c_size_t, [c_int64, c_int, c_int, c_int, c_int]),
-    "runia_roi_mc_entropy_f32": (
-        c_int,
-        [c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_void_p, c_void_p, c_void_p, c_size_t, c_int64, c_int64, c_int, c_int,
-         c_int, c_int, c_int, c_double, c_int, c_int, c_int, c_double, c_int, c_int, c_double, c_void_p],
-    ),
-    "runia_roi_means_f32": (
-        c_int,
-        [c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_int64, c_int64, c_int64, c_int, c_int, c_int, c_int, c_int,
-         c_double, c_int, c_int, c_void_p],
-    ),
-    "runia_linear_f32": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_int64, c_int64, c_float, c_void_p]),
-    "runia_ash_s_f32": (c_int, [c_void_p, c_void_p, c_int64, c_int64, c_int, c_void_p]),
-    "runia_gen_score_f32": (c_int, [c_void_p, c_void_p, c_int64, c_int64, c_int, c_double, c_void_p]),
-    "runia_gen_entropy_f32": (c_int, [c_void_p, c_void_p, c_int64, c_int64, c_int, c_double, c_void_p]),
-    "runia_mcd_uncertainty_f32": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_int, c_int64, c_void_p]),
-    "runia_ash_s_rows_f32": (c_int, [c_void_p, c_void_p, c_void_p, c_int64, c_int64, c_int, c_int, c_void_p]),
-    "runia_tril_inverse_f64": (c_int, [c_void_p, c_void_p, c_int64, c_int64, c_void_p]),
-    "runia_proj_norm_f32": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_int64, c_int64, c_void_p]),
-    "runia_proj_norm_f64": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_int64, c_int64, c_void_p]),
-    "runia_proj_sq_workspace_bytes": (c_size_t, [c_int64]),
-    "runia_proj_sq_accumulate_f64": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_int64, c_int64, c_void_p]),
-    "runia_proj_sq_accumulate_trap_f64": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_int64, c_int64, c_void_p]),
-    "runia_proj_sq_accumulate_btrap_f64": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_int64, c_int64, c_void_p]),
-    "runia_qr_trapezoid_f64": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_int64, c_void_p]),
-    "runia_trap_balance_order": (c_int, [c_void_p, c_int64]),
-    "runia_trap_balance_rows_f64": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_int64, c_void_p]),
-    "runia_proj_sq_score_btrap_f64": (
-        c_int,
-        [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, c_int64, c_int64, c_int64, c_void_p],
-    ),
-    "runia_proj_sq_score_f64": (
-        c_int,
-        [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, c_int64, c_int64, c_int64, c_void_p],
-    ),
-    "runia_proj_sq_score_trap_f64": (
-        c_int,
-        [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, c_int64, c_int64, c_int64, c_void_p],
-    ),
-    "runia_covariance_workspace_bytes": (c_size_t, [c_int64, c_int64]),
-    "runia_covariance_f64": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, c_int64, c_int64, c_void_p]),
-    "runia_covariance_f32in": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, c_int64, c_int64, c_void_p]),
-    "runia_rauq_workspace_bytes": (c_size_t, [c_int64, c_int64, c_int64, c_int64, c_int64, c_int]),
-    "runia_rauq_gather": (c_int, [c_void_p, c_int, c_int64, c_int64, c_int64, c_int, c_void_p, c_void_p]),
-    "runia_rauq_score": (
-        c_int,
-        [c_void_p, c_int64, c_int64, c_int64, c_int, c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p],
-    ),
-    "runia_rauq_rollout_rows": (
-        c_int, [c_void_p, c_int, c_int64, c_int64, c_int64, c_int64, c_void_p, c_void_p, c_size_t, c_void_p]),
-    "runia_rauq_rollout_att": (
-        c_int,
-        [c_void_p, c_int, c_int64, c_int64, c_int64, c_int64, c_int, c_int, c_int64, c_void_p, c_void_p, c_size_t, c_void_p],
-    ),
-    "runia_rauqb_workspace_bytes": (c_size_t, [c_int64, c_int64, c_int64, c_int64, c_int64, c_int]),
-    "runia_rauqb_gather": (c_int, [c_void_p, c_void_p, c_int, c_int64, c_int64, c_int64, c_int64, c_int, c_void_p, c_void_p]),
-    "runia_rauqb_score": (
-        c_int,
-        [c_void_p, c_void_p, c_int64, c_int64, c_int64, c_int64, c_int, c_int, c_void_p, c_int64, c_void_p, c_int, c_void_p,
-         c_void_p, c_size_t, c_void_p],
-    ),
-    "runia_rauqb_rollout_rows": (
-        c_int, [c_void_p, c_void_p, c_int, c_int64, c_int64, c_int64, c_int64, c_int64, c_void_p, c_void_p, c_size_t, c_void_p]),
-    "runia_rauqb_rollout_att": (
-        c_int,
-        [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int64, c_int64, c_int64, c_int64, c_int64, c_int, c_void_p,
-         c_void_p, c_size_t, c_void_p],
-    ),
-    "runia_logit_stats_workspace_bytes": (c_size_t, [c_int64, c_int64, c_int64]),
-    "runia_logit_stats": (
-        c_int,
-        [c_void_p, c_int, c_int64, c_int64, c_int64, c_void_p, c_int64, c_int, c_void_p, c_void_p, c_void_p, c_void_p,
-         c_void_p, c_size_t, c_void_p],
-    ),
-    "runia_eigen_score_batch": (c_int, [c_void_p, c_int, c_int64, c_int64, c_int64, c_int64, c_double, c_void_p, c_void_p]),
-    "runia_pca_md_score_f64": (
-        c_int,
-        [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_int64, c_int64,
-         c_void_p],
-    ),
-    "runia_osod_quantize": (
-        c_int, [c_void_p, c_int, c_int64, c_int, ctypes.c_uint32, c_int, c_void_p, c_void_p, c_int, c_void_p, c_void_p]),
-    "runia_osod_sort_workspace_bytes": (c_size_t, [c_int64, c_int]),
-    "runia_osod_bucket_sort": (c_int, [c_void_p, c_int64, c_int, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]),
-    "runia_osod_overlaps": (
-        c_int, [c_void_p, c_void_p, c_void_p, c_int64, c_void_p, c_void_p, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p]),
-    "runia_osod_match_workspace_bytes": (c_size_t, [c_int, c_int64]),
-    "runia_osod_match": (
-        c_int,
-        [c_void_p, c_int64, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_void_p,
-         c_double, c_void_p, c_void_p, c_void_p, c_int64, c_double, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p],
-    ),
-    "runia_osod_gtu_keys": (c_int, [c_void_p, c_void_p, c_int64, c_int, c_void_p, c_void_p]),
-    "runia_osod_gather_f64": (c_int, [c_void_p, c_int64, c_void_p, c_void_p, c_int64, c_void_p, c_void_p]),
-    "runia_osod_curves_workspace_bytes": (c_size_t, [c_int64]),
-    "runia_osod_curves": (
-        c_int,
-        [c_void_p, c_void_p, c_void_p, c_int64, c_int, c_int, c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_void_p,
-         c_void_p, c_void_p, c_size_t, c_void_p],
-    ),
-    "runia_yolo_candidates_workspace_bytes": (c_size_t, [c_int64]),
-    "runia_yolo_candidates_f32": (
-        c_int,
-        [c_void_p, c_int64, c_int, c_int, c_float, c_void_p, c_int, c_float, c_void_p, c_void_p, c_void_p, c_void_p,
-         c_void_p, c_void_p, c_size_t, c_void_p],
-    ),
-    "runia_nms_keys_f32": (c_int, [c_void_p, c_int64, c_void_p, c_void_p]),
-    "runia_nms_sort_keys": (c_int, [c_void_p, c_int64, c_void_p]),
-    "runia_nms_workspace_bytes": (c_size_t, [c_int64]),
-    "runia_nms_sorted_f32": (
-        c_int, [c_void_p, c_void_p, c_int64, c_float, c_int64, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]),
-    "runia_pacmap_knn_f32": (c_int, [c_void_p, c_int64, c_void_p, c_int64, c_int64, c_int, c_int, c_void_p, c_void_p, c_void_p]),
-    "runia_pacmap_pairs_workspace_bytes": (c_size_t, [c_int64]),
-    "runia_pacmap_pairs": (
-        c_int,
-        [c_void_p, c_int64, c_void_p, c_int64, c_int64, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_uint64, c_int,
-         c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p],
-    ),
-    "runia_pixel_maps_workspace_bytes": (c_size_t, [c_int64, c_int64, c_int64, c_int64, c_int, c_int]),
-    "runia_pixel_uncertainty_maps": (
-        c_int,
-        [c_void_p, c_int, c_int, c_int64, c_int, c_int64, c_int64, c_int64, c_int64, c_int64, c_int64, c_int64, c_void_p,
-         c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p],
-    ),
-    "runia_pixel_map_reduce_f32": (c_int, [c_void_p, c_void_p, c_int64, c_int64, c_void_p, c_void_p, c_void_p, c_void_p]),
-    "runia_pacmap_phase_weights": (c_int, [c_int, c_void_p]),
-    "runia_pacmap_step_f32": (
-        c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_int, c_int, c_float, c_void_p]),
-    "runia_row_logit_stats_f32": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_int64, c_void_p]),
-    "runia_klm_score_f32": (
-        c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_int64, c_int64, c_void_p]),
-    "runia_fdbd_score_f32": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_int64, c_void_p]),
-    "runia_row_dist_f32": (c_int, [c_void_p, c_void_p, c_void_p, c_int64, c_int64, c_void_p]),
-    "runia_calib_rows": (
-        c_int, [c_void_p, c_int, c_void_p, c_int, c_int, c_int64, c_float, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
-                c_void_p, c_int64, c_int64, c_void_p]),
-    "runia_calib_reduce_workspace_bytes": (c_size_t, [c_int64, c_int]),
-    "runia_calib_reduce_f32": (
-        c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int64, c_int64, c_int,
-                c_void_p, c_void_p, c_size_t, c_void_p]),
-    "runia_conformal_max_classes": (c_int, []),
-    "runia_conformal_label_scores": (
-        c_int, [c_void_p, c_int, c_int64, c_void_p, c_int, c_int, c_int64, c_void_p, c_int, c_float, c_float, c_int, c_void_p,
-                c_void_p, c_int64, c_int64, c_void_p]),
-    "runia_conformal_sets": (
-        c_int, [c_void_p, c_int, c_int64, c_void_p, c_int, c_int, c_int64, c_void_p, c_int, c_float, c_float, c_int, c_float,
-                c_void_p, c_void_p, c_void_p, c_int64, c_int64, c_void_p]),
-    "runia_conformal_record_slots": (c_int64, [c_int64]),
-    "runia_conformal_reduce": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_int64, c_int64, c_int64, c_void_p, c_void_p]),
-    "runia_conformal_sets_wide": (
-        c_int, [c_void_p, c_int, c_int64, c_int64, c_int64, c_void_p, c_int, c_int64, c_int, c_int64, c_void_p, c_int, c_float,
-                c_float, c_int, c_float, c_void_p, c_void_p, c_void_p, c_void_p]),
-    "runia_boot_tile_rows": (c_int, []),
-    "runia_boot_keys_f32": (c_int, [c_void_p, c_int64, c_void_p, c_int64, c_void_p, c_void_p, c_void_p]),
-    "runia_boot_keys_f64": (c_int, [c_void_p, c_int64, c_void_p, c_int64, c_void_p, c_void_p, c_void_p]),
-    "runia_boot_workspace_bytes": (c_size_t, [c_int64, c_int64]),
-    "runia_boot_metrics": (
-        c_int, [c_void_p, c_void_p, c_int64, c_int64, c_void_p, c_uint64, c_int64, c_int64, c_void_p, c_void_p, c_size_t,
-                c_void_p]),
-    "runia_boot_weight_of_word_host": (c_int, [ctypes.c_uint32]),
-    "runia_boot_weights_host": (c_int, [c_uint64, c_int64, c_int64, c_void_p, c_int64, c_void_p]),
-    "runia_cc_tile_h": (c_int, []),
-    "runia_cc_tile_w": (c_int, []),
-    "runia_cc_label_workspace_bytes": (c_size_t, [c_int64, c_int64, c_int64]),
-    "runia_cc_label": (
-        c_int, [c_void_p, c_void_p, c_void_p, c_int64, c_int, c_void_p, c_int64, c_int64, c_int64, c_int, c_void_p, c_void_p,
-                c_void_p, c_size_t, c_void_p]),
-    "runia_cc_overlap": (
-        c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_int64, c_int64, c_int64, c_int64, c_void_p, c_void_p,
-                c_void_p, c_void_p, c_void_p, c_int64, c_void_p, c_int, c_void_p]),
-    "runia_cc_relabel": (c_int, [c_void_p, c_void_p, c_void_p, c_int64, c_int64, c_int64, c_void_p]),
-    "runia_sel_tile_rows": (c_int, []),
-    "runia_sel_keys_f32": (c_int, [c_void_p, c_int64, c_void_p, c_void_p, c_void_p]),
-    "runia_sel_keys_f64": (c_int, [c_void_p, c_int64, c_void_p, c_void_p, c_void_p]),
-    "runia_sel_key_of_f64_host": (c_int64, [c_double]),
-    "runia_sel_workspace_bytes": (c_size_t, [c_int64]),
-    "runia_sel_curve": (
-        c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int64, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_size_t,
-                c_void_p]),
-    "runia_sel_query": (
-        c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_void_p, c_int, c_void_p, c_int, c_int, c_void_p, c_void_p,
-                c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]),
-    "runia_boot_sel_tile_rows": (c_int, []),
-    "runia_boot_sel_metrics": (
-        c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int64, c_void_p, c_uint64, c_int64, c_int64, c_void_p, c_void_p]),
-    "runia_pixfeat_workspace_bytes": (c_size_t, [c_int64, c_int64]),
-    "runia_pixfeat_score": (
-        c_int, [c_void_p, c_int, c_int64, c_int64, c_int64, c_int64, c_int64, c_int64, c_int64, c_int64, c_void_p, c_void_p,
-                c_void_p, c_int64, c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]),
-    "runia_pixfeat_label_hist": (c_int, [c_void_p, c_int, c_int64, c_int64, c_int64, c_void_p, c_void_p, c_void_p]),
-    "runia_pixfeat_gather_workspace_bytes": (c_size_t, [c_int64]),
-    "runia_pixfeat_gather_rows": (
-        c_int, [c_void_p, c_int, c_int64, c_int64, c_int64, c_int64, c_int64, c_int64, c_int64, c_int64, c_void_p, c_int,
-                c_int64, c_int64, c_void_p, c_uint64, c_int64, c_void_p, c_void_p, c_int64, c_void_p, c_void_p, c_size_t,
-                c_void_p]),
-    "runia_shift_workspace_bytes": (c_size_t, [c_int64, c_int64, c_int64, c_int64]),
-    "runia_shift_perm_bits": (c_int, [c_uint64, c_int64, c_int64, c_int64, c_int64, c_void_p, c_int64, c_void_p]),
-    "runia_shift_perm_bits_host": (c_int, [c_uint64, c_int64, c_int64, c_int64, c_int64, c_void_p, c_int64]),
-    "runia_shift_sample_rows": (c_int64, [c_int64]),
-    "runia_shift_pairwise_sample": (
-        c_int, [c_void_p, c_int64, c_int64, c_void_p, c_int64, c_int64, c_int64, c_int, c_void_p, c_void_p]),
-    "runia_shift_mmd": (
-        c_int, [c_void_p, c_int64, c_int64, c_void_p, c_int64, c_int64, c_int64, c_int, c_int, c_void_p, c_int, c_int, c_uint64,
-                c_int64, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]),
-    "runia_ks_max_rows": (c_int64, []),
-    "runia_ks_columns_per_pass": (c_int64, [c_int64, c_int64, c_int64]),
-    "runia_ks_workspace_bytes": (c_size_t, [c_int64, c_int64, c_int64, c_int64]),
-    "runia_ks_perm_table": (
-        c_int, [c_void_p, c_int64, c_int64, c_void_p, c_int64, c_int64, c_int64, c_int, c_uint64, c_int64, c_void_p, c_void_p,
-                c_void_p, c_size_t, c_void_p]),
-    "runia_pixknn_workspace_bytes": (c_size_t, [c_int64, c_int64, c_int64]),
-    "runia_pixknn_score": (
-        c_int, [c_void_p, c_int, c_int64, c_int64, c_int64, c_int64, c_int64, c_int64, c_int64, c_int64, c_void_p, c_void_p,
-                c_void_p, c_int64, c_int64, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]),
-    "runia_kcenter_workspace_bytes": (c_size_t, [c_int64, c_int64]),
-    "runia_kcenter_greedy_f32": (
-        c_int, [c_void_p, c_int64, c_int64, c_int64, c_int64, c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]),
-}
+_HEADER_PATH = os.path.join(os.path.dirname(os.path.abspath(__file__)), os.pardir, "include", "runia_hip.h")
 
 
 class RuniaHipError(RuntimeError):
     pass
+
+
+# value types of the C ABI; every parameter declared with `*` or `[]` is an address (c_void_p)
+_C_TYPES = {"void": None, "int": c_int, "int64_t": c_int64, "size_t": c_size_t, "uint64_t": c_uint64, "uint32_t": c_uint32,
+            "unsigned": c_uint32, "double": c_double, "float": c_float, "runia_stream_t": c_void_p}
+# host out-parameters: the only entries whose ctypes type says more than the header (name -> {parameter index: type})
+_HOST_OUT_PARAMS = {
+    "runia_p2p_alloc": {2: ctypes.POINTER(c_void_p)},
+    "runia_p2p_open": {1: ctypes.POINTER(c_void_p)},
+    "runia_p2p_all_gather": {3: ctypes.POINTER(c_void_p)},
+    "runia_p2p_status": {1: ctypes.POINTER(c_int)},
+}
+
+
+def _c_type(decl: str, symbol: str, result: bool = False):
+    """ctypes type of one parameter declaration (``const float* x``, ``int64_t N``, ``double w[4]``) or of a return type."""
+    words = [w for w in re.sub(r"[*\[\]]", " ", decl).split() if w != "const"]
+    if "*" in decl or "[" in decl:
+        if not result:
+            return c_void_p
+        if words == ["char"]:
+            return c_char_p
+    elif words and words[0] in _C_TYPES and len(words) <= (1 if result else 2):
+        return _C_TYPES[words[0]]
+    raise RuniaHipError(f"include/runia_hip.h: {symbol}: no ctypes type for {decl.strip()!r}")
+
+
+def _macro_int(body: str) -> int:
+    """Value of an integer macro body: ``n``, ``(-n)`` or ``(a << b)``; anything else raises ValueError."""
+    m = re.fullmatch(r"\(?\s*(-?\d+)\s*(?:<<\s*(\d+)\s*)?\)?", body.strip())
+    if not m or body.count("(") != body.count(")"):
+        raise ValueError(f"not an integer macro body: {body!r}")
+    return int(m.group(1)) << int(m.group(2) or 0)
+
+
+def _parse_header(text: str):
+    """``(signatures, macros)`` of a C header text: ``name -> (restype, [argtypes])`` for every ``ret runia_*(args);`` and
+    ``name -> int`` for every ``#define RUNIA_*`` whose body is an integer.  A type outside ``_C_TYPES`` raises."""
+    text = re.sub(r"/\*.*?\*/|//[^\n]*", " ", text, flags=re.S)
+    macros = {}
+    for name, body in re.findall(r"^[ \t]*#[ \t]*define[ \t]+(RUNIA_\w+)(.*)$", text, flags=re.M):
+        try:
+            macros[name] = _macro_int(body)
+        except ValueError:  # include guard, function-like macros
+            pass
+    signatures = {}
+    for ret, name, params in re.findall(r"([\w \t\n*]+?)\b(runia_\w+)\s*\(([^()]*)\)\s*;", re.sub(r"^[ \t]*#.*$", "", text, flags=re.M)):
+        params = [] if params.strip() in ("", "void") else params.split(",")
+        signatures[name] = (_c_type(ret, name, result=True), [_c_type(p, name) for p in params])
+    for name, fixed in _HOST_OUT_PARAMS.items():
+        for i, t in fixed.items():
+            if name in signatures:
+                signatures[name][1][i] = t
+    return signatures, macros
+
+
+def _read_header():
+    try:
+        with open(_HEADER_PATH) as f:
+            return _parse_header(f.read())
+    except OSError as e:
+        raise RuniaHipError(f"cannot read the C ABI header {os.path.normpath(_HEADER_PATH)}: {e}") from e
+
+
+# name -> (restype, argtypes) of every entry point, and the integer RUNIA_* macros: both read from include/runia_hip.h
+_SIGNATURES, _HEADER_MACROS = _read_header()
 
 
 class CounterDraws(NamedTuple):
@@ -773,7 +465,7 @@ def map_reduce(x: torch.Tensor, h: int, w: int, mode: str) -> torch.Tensor:
     return out
 
 
-_MCD_MODES = {"fullmean": 0, "mean": 1, "avgpool": 2, "copy": 3}
+_MCD_MODES = {m: _HEADER_MACROS["RUNIA_MCD_" + m.upper()] for m in ("fullmean", "mean", "avgpool", "copy")}
 
 
 def mcd_row_width(shape, mode: str, avg_pooling_parameters=None) -> int:
@@ -829,7 +521,7 @@ def mcd_reduce_rows(x: torch.Tensor, table: torch.Tensor, mode: str, row0: int =
     return table
 
 
-_RAGGED_MODES = {"copy": 0, "log_eps": 1}
+_RAGGED_MODES = {m: _HEADER_MACROS["RUNIA_RAGGED_" + m.upper()] for m in ("copy", "log_eps")}
 
 
 @_device_guard()
@@ -1901,7 +1593,7 @@ def kcenter_greedy(rows: torch.Tensor, n_pick: int, first: int = 0):
 
 
 # (RUNIA_CC_TILE_H, RUNIA_CC_TILE_W) of include/runia_hip.h: the tile one workgroup of the labelling kernel owns
-CC_TILE = (32, 32)
+CC_TILE = (_HEADER_MACROS["RUNIA_CC_TILE_H"], _HEADER_MACROS["RUNIA_CC_TILE_W"])
 CC_MAX_PIXELS = (1 << 31) - 1  # N * H * W of one labelling call (parents are int32)
 
 
@@ -2695,7 +2387,7 @@ def roi_mc_entropy(x_nhwc: torch.Tensor, boxes: torch.Tensor, output_size, spati
     return (h, z) if return_samples else h
 
 
-ROI_MEANS_MAX_HW = 2048  # RUNIA_ROI_MEANS_MAX_HW: H + W of one feature map (the per-axis weights live in LDS)
+ROI_MEANS_MAX_HW = _HEADER_MACROS["RUNIA_ROI_MEANS_MAX_HW"]  # H + W of one feature map (the per-axis weights live in LDS)
 
 
 def roi_means_supported(x_nhwc_shape) -> bool:
@@ -2851,9 +2543,9 @@ def cholesky(a: torch.Tensor, jitter: float = 0.0):
     return m.reshape(a.shape), info
 
 
-NMS_SORT_MAX = 4096  # RUNIA_NMS_SORT_MAX: keys one workgroup sorts in LDS (longer lists: torch.sort of the same keys)
-NMS_MAX_BOXES = 65536  # RUNIA_NMS_MAX_BOXES: boxes one greedy walk takes (its removed bitmap lives in LDS)
-YOLO_MAX_ANCHORS = 1 << 22  # RUNIA_YOLO_MAX_ANCHORS
+NMS_SORT_MAX = _HEADER_MACROS["RUNIA_NMS_SORT_MAX"]  # keys one workgroup sorts in LDS (longer lists: torch.sort of the same keys)
+NMS_MAX_BOXES = _HEADER_MACROS["RUNIA_NMS_MAX_BOXES"]  # boxes one greedy walk takes (its removed bitmap lives in LDS)
+YOLO_MAX_ANCHORS = _HEADER_MACROS["RUNIA_YOLO_MAX_ANCHORS"]
 
 
 def nms_workspace_bytes(m: int) -> int:
@@ -2936,11 +2628,11 @@ def yolo_candidates(pred: torch.Tensor, nc: int, conf_thres: float, classes=None
     return boxes, scores, anchor, cls, count
 
 
-PACMAP_MAX_K = 192  # RUNIA_PACMAP_MAX_K: neighbour candidates per row of the kNN graph
-PACMAP_MAX_MN = 128  # RUNIA_PACMAP_MAX_MN
-PACMAP_MAX_FP = 256  # RUNIA_PACMAP_MAX_FP
-PACMAP_MAX_COMPONENTS = 16  # RUNIA_PACMAP_MAX_COMPONENTS
-PACMAP_KIND_NB, PACMAP_KIND_MN, PACMAP_KIND_FP = 0, 1, 2  # RUNIA_PACMAP_KIND_*: bits 30-31 of a grouped pair entry
+PACMAP_MAX_K = _HEADER_MACROS["RUNIA_PACMAP_MAX_K"]  # neighbour candidates per row of the kNN graph
+PACMAP_MAX_MN = _HEADER_MACROS["RUNIA_PACMAP_MAX_MN"]
+PACMAP_MAX_FP = _HEADER_MACROS["RUNIA_PACMAP_MAX_FP"]
+PACMAP_MAX_COMPONENTS = _HEADER_MACROS["RUNIA_PACMAP_MAX_COMPONENTS"]
+PACMAP_KIND_NB, PACMAP_KIND_MN, PACMAP_KIND_FP = (_HEADER_MACROS["RUNIA_PACMAP_KIND_" + k] for k in ("NB", "MN", "FP"))  # bits 30-31 of a grouped pair entry
 
 
 @_device_guard()

@@ -373,9 +373,11 @@ extern "C" int runia_boot_keys_f64(const double* ind_scores, int64_t n_ind, cons
   return boot_keys<double>(ind_scores, n_ind, ood_scores, n_ood, keys, any_outside, stream);
 }
 
+// one record per tile and workgroup (a workgroup = four replicates)
+static size_t boot_records_bytes(int64_t quads, int64_t n) { return (size_t)quads * (size_t)boot_tiles(n) * sizeof(TileRec); }
 extern "C" size_t runia_boot_workspace_bytes(int64_t n, int64_t n_boot) {
   if (n <= 0 || n_boot <= 0) return 0;
-  return (size_t)boot_max_quads(n_boot) * (size_t)boot_tiles(n) * sizeof(TileRec);
+  return boot_records_bytes(boot_max_quads(n_boot), n);
 }
 
 extern "C" int runia_boot_metrics(const int64_t* sorted_keys, const int32_t* sorted_rows, int64_t n, int64_t n_ind,
@@ -387,8 +389,7 @@ extern "C" int runia_boot_metrics(const int64_t* sorted_keys, const int32_t* sor
   if (n_boot < 1 || first_replicate < 0 || n_boot > (1ll << 31) || first_replicate > (1ll << 31) - n_boot) return RUNIA_E_INVALID;
   if (!sorted_keys || !sorted_rows || !out) return RUNIA_E_INVALID;
   const int64_t q0 = first_replicate >> 2, q1 = (first_replicate + n_boot - 1) >> 2, ntiles = boot_tiles(n);
-  const size_t need = (size_t)(q1 - q0 + 1) * (size_t)ntiles * sizeof(TileRec);
-  if (!workspace || workspace_bytes < need || (((uintptr_t)workspace) & 7) != 0) return RUNIA_E_WORKSPACE;
+  if (ws_refused(workspace, workspace_bytes, boot_records_bytes(q1 - q0 + 1, n), 8)) return RUNIA_E_WORKSPACE;
   boot_replicates_kernel<<<(unsigned)(q1 - q0 + 1), kThreads, 0, as_stream(stream)>>>(
       sorted_keys, sorted_rows, group_of_row, n, n_ind, seed, first_replicate, n_boot, (uint32_t)q0, out,
       reinterpret_cast<TileRec*>(workspace), ntiles);

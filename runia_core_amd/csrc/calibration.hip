@@ -441,7 +441,7 @@ extern "C" int runia_calib_reduce_f32(const int32_t* pred, const float* conf, co
   const size_t rec_bytes = (size_t)(kHead + 3 * n_bins) * sizeof(double);
   if (N == 0) return hipMemsetAsync(out, 0, rec_bytes, s) == hipSuccess ? RUNIA_OK : RUNIA_E_LAUNCH;
   if (!labels || (n_bins > 0 && !conf)) return RUNIA_E_INVALID;
-  if (!workspace || workspace_bytes < runia_calib_reduce_workspace_bytes(N, n_bins)) return RUNIA_E_WORKSPACE;
+  if (ws_refused(workspace, workspace_bytes, runia_calib_reduce_workspace_bytes(N, n_bins), 1)) return RUNIA_E_WORKSPACE;
   const Labels L = {labels, labels_i64 != 0, has_ignore != 0, ignore_index};
   const int64_t blocks = reduce_blocks(N);
   const size_t shmem = (size_t)kRedWaves * 3 * n_bins * sizeof(double);

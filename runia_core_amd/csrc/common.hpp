@@ -8,6 +8,7 @@
 
 #include "../../include/runia_hip.h"
 #include "wave.hpp"
+#include "workspace.hpp"
 
 #define RUNIA_WAVE 64
 

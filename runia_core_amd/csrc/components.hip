@@ -367,9 +367,18 @@ int64_t chunks_per_image(int64_t HW) { return (HW + kChunk - 1) / kChunk; }
 extern "C" int runia_cc_tile_h(void) { return TH; }
 extern "C" int runia_cc_tile_w(void) { return TW; }
 
+struct CcPlan { unsigned* err_word; int *chunk_count, *chunk_base; };  // error word (16-byte slot) | [N][chunks] x 2
+static CcPlan cc_plan(WsWalk& w, int64_t N, int64_t HW) {
+  const size_t chunks = (size_t)N * (size_t)chunks_per_image(HW);
+  CcPlan p;
+  p.err_word = w.take<unsigned>(1, 16);
+  p.chunk_count = w.take<int>(chunks);
+  p.chunk_base = w.take<int>(chunks);
+  return p;
+}
 extern "C" size_t runia_cc_label_workspace_bytes(int64_t N, int64_t H, int64_t W) {
   if (N <= 0 || H <= 0 || W <= 0) return 0;
-  return 16 + 2 * (size_t)N * (size_t)chunks_per_image(H * W) * sizeof(int);
+  return ws_bytes([&](WsWalk& w) { cc_plan(w, N, H * W); });
 }
 
 extern "C" int runia_cc_label(const uint8_t* mask, const float* score, const float* thresholds, int64_t T, int less,
@@ -383,13 +392,13 @@ extern "C" int runia_cc_label(const uint8_t* mask, const float* score, const flo
   if (N == 0 || HW == 0) return RUNIA_OK;
   if (HW > lim || N > lim / HW) return RUNIA_E_INVALID;  // parents are int32
   if (!labels || !counts || (score && !thresholds)) return RUNIA_E_INVALID;
-  const size_t need = runia_cc_label_workspace_bytes(N, H, W);
-  if (!workspace || workspace_bytes < need || reinterpret_cast<uintptr_t>(workspace) % 16) return RUNIA_E_WORKSPACE;
+  WsWalk w(workspace);
+  const CcPlan plan = cc_plan(w, N, HW);
+  if (ws_refused(workspace, workspace_bytes, w.used(), 16)) return RUNIA_E_WORKSPACE;
   hipStream_t s = as_stream(stream);
-  unsigned* err_word = static_cast<unsigned*>(workspace);
+  unsigned* err_word = plan.err_word;
   const int cpi = (int)chunks_per_image(HW);
-  int* chunk_count = reinterpret_cast<int*>(static_cast<char*>(workspace) + 16);
-  int* chunk_base = chunk_count + N * cpi;
+  int *chunk_count = plan.chunk_count, *chunk_base = plan.chunk_base;
   if (hipMemsetAsync(err_word, 0, 16, s) != hipSuccess) return RUNIA_E_LAUNCH;
   const int ntx = (int)((W + TW - 1) / TW), nty = (int)((H + TH - 1) / TH), conn8 = connectivity == 8;
   CcSource src{mask, score, thresholds, valid, score ? G : N, less != 0};

@@ -261,16 +261,28 @@ int64_t splits_for(int64_t N, int64_t D) {
   return best;
 }
 
+struct Plan {
+  int64_t splits, mean_blocks;
+  double *part, *mpart;  // [splits][D][D] partial Gram matrices | [mean_blocks][D] partial column sums
+};
+Plan make_plan(WsWalk& w, int64_t N, int64_t D) {
+  Plan p;
+  p.splits = splits_for(N, D);
+  p.mean_blocks = (N + 255) / 256 < 256 ? (N + 255) / 256 : 256;
+  p.part = w.take<double>(p.splits * D * D);
+  p.mpart = w.take<double>(p.mean_blocks * D);
+  return p;
+}
+
 template <typename T>
 int covariance_impl(const T* x, double* mean, double* cov, void* workspace, size_t workspace_bytes, int64_t N,
                     int64_t D, runia_stream_t stream) {
   if (N <= 0 || D <= 0 || !x || !mean || !cov) return RUNIA_E_INVALID;
-  const int64_t splits = splits_for(N, D);
-  const int64_t mean_blocks = (N + 255) / 256 < 256 ? (N + 255) / 256 : 256;
-  const size_t need = (size_t)(splits * D * D + mean_blocks * D) * sizeof(double);
-  if (!workspace || workspace_bytes < need) return RUNIA_E_WORKSPACE;
-  double* part = reinterpret_cast<double*>(workspace);
-  double* mpart = part + splits * D * D;
+  WsWalk w(workspace);
+  const Plan plan = make_plan(w, N, D);
+  if (ws_refused(workspace, workspace_bytes, w.used(), 1)) return RUNIA_E_WORKSPACE;
+  const int64_t splits = plan.splits, mean_blocks = plan.mean_blocks;
+  double *part = plan.part, *mpart = plan.mpart;
   hipStream_t s = as_stream(stream);
   const int64_t rows_per_block = (N + mean_blocks - 1) / mean_blocks;
   col_sum_kernel<T><<<dim3((unsigned)((D + 255) / 256), (unsigned)mean_blocks), 256, 0, s>>>(x, mpart, N, D, rows_per_block);
@@ -296,8 +308,7 @@ int covariance_impl(const T* x, double* mean, double* cov, void* workspace, size
 
 extern "C" size_t runia_covariance_workspace_bytes(int64_t N, int64_t D) {
   if (N <= 0 || D <= 0) return 0;
-  const int64_t mean_blocks = (N + 255) / 256 < 256 ? (N + 255) / 256 : 256;
-  return (size_t)(splits_for(N, D) * D * D + mean_blocks * D) * sizeof(double);
+  return ws_bytes([&](WsWalk& w) { make_plan(w, N, D); });
 }
 
 extern "C" int runia_covariance_f64(const double* x, double* mean, double* cov, void* workspace,

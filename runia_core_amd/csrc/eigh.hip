@@ -176,19 +176,26 @@ __global__ __launch_bounds__(256) void centred_gram_kernel(const float* __restri
 
 }  // namespace
 
+struct EighPlan { double* anorm; Rot* rot; };  // norm + counter (64-byte slot) | rotations of one step
+static EighPlan eigh_plan(WsWalk& w, int64_t n) {
+  EighPlan p;
+  p.anorm = w.take<double>(1, 64);
+  p.rot = w.take<Rot>(((n + 1) & ~1ll) / 2);
+  return p;
+}
+
 extern "C" size_t runia_eigh_workspace_bytes(int64_t n) {
   if (n <= 0) return 0;
-  const int64_t m = (n + 1) & ~1ll;
-  return (size_t)(m / 2) * sizeof(Rot) + 64;  // rotations of one step + norm + counter
+  return ws_bytes([&](WsWalk& w) { eigh_plan(w, n); });
 }
 
 // V = I and the matrix norm; call once before the sweeps.
 extern "C" int runia_eigh_init_f64(const double* A, double* V, int64_t n, void* workspace, size_t workspace_bytes,
                                    runia_stream_t stream) {
   if (n <= 0 || n > 32768 || !A || !V) return RUNIA_E_INVALID;
-  if (!workspace || workspace_bytes < runia_eigh_workspace_bytes(n) || (((uintptr_t)workspace) & 15) != 0)
-    return RUNIA_E_WORKSPACE;
-  double* anorm = reinterpret_cast<double*>(workspace);
+  WsWalk w(workspace);
+  double* anorm = eigh_plan(w, n).anorm;
+  if (ws_refused(workspace, workspace_bytes, w.used(), 16)) return RUNIA_E_WORKSPACE;
   eigh_init_kernel<<<1, 256, 0, as_stream(stream)>>>(A, V, (int)n, anorm);
   return runia_check_launch();
 }
@@ -198,12 +205,13 @@ extern "C" int runia_eigh_init_f64(const double* A, double* V, int64_t n, void* 
 extern "C" int runia_eigh_sweep_f64(double* A, double* V, int64_t n, void* workspace, size_t workspace_bytes,
                                     unsigned* rotations, runia_stream_t stream) {
   if (n <= 0 || n > 32768 || !A || !V || !rotations) return RUNIA_E_INVALID;
-  if (!workspace || workspace_bytes < runia_eigh_workspace_bytes(n) || (((uintptr_t)workspace) & 15) != 0)
-    return RUNIA_E_WORKSPACE;
+  WsWalk w(workspace);
+  const EighPlan plan = eigh_plan(w, n);
+  if (ws_refused(workspace, workspace_bytes, w.used(), 16)) return RUNIA_E_WORKSPACE;
   if (n == 1) return RUNIA_OK;
   const int m = (int)((n + 1) & ~1ll);
-  double* anorm = reinterpret_cast<double*>(workspace);
-  Rot* rot = reinterpret_cast<Rot*>(reinterpret_cast<char*>(workspace) + 64);
+  double* anorm = plan.anorm;
+  Rot* rot = plan.rot;
   hipStream_t s = as_stream(stream);
   const int half = m / 2;
   for (int t = 0; t < m - 1; ++t) {

@@ -314,20 +314,27 @@ extern "C" int64_t runia_eigh_block_padded(int64_t n) {
   return ((nb + 1) & ~1ll) * BS;
 }
 
+struct BlockPlan { double *anorm, *R; };  // norm (runia_eigh_init_f64's 64-byte slot) | one R per block pair
+static BlockPlan block_plan(WsWalk& w, int64_t n) {
+  BlockPlan p;
+  p.anorm = w.take<double>(1, 64);
+  p.R = w.take<double>((size_t)(runia_eigh_block_padded(n) / (2 * BS)) * SB * SB);
+  return p;
+}
+
 extern "C" size_t runia_eigh_block_workspace_bytes(int64_t n) {
   if (n <= 0) return 0;
-  const int64_t np = runia_eigh_block_padded(n) / (2 * BS);
-  return 64 + (size_t)np * SB * SB * sizeof(double);  // norm (runia_eigh_init_f64's slot) + one R per block pair
+  return ws_bytes([&](WsWalk& w) { block_plan(w, n); });
 }
 
 // V = I (N x N) and the Frobenius norm of the padded A into the workspace; call once before the sweeps.
 extern "C" int runia_eigh_block_init_f64(const double* A, double* V, int64_t N, void* workspace, size_t workspace_bytes,
                                          runia_stream_t stream) {
   if (N <= 0 || N > 32768 || N % (2 * BS) != 0 || !A || !V) return RUNIA_E_INVALID;
-  if (!workspace || workspace_bytes < runia_eigh_block_workspace_bytes(N) || (((uintptr_t)workspace) & 15) != 0)
-    return RUNIA_E_WORKSPACE;
-  double* anorm = reinterpret_cast<double*>(workspace);
-  double* partial = reinterpret_cast<double*>(reinterpret_cast<char*>(workspace) + 64);  // the R buffer, not yet in use
+  WsWalk w(workspace);
+  const BlockPlan plan = block_plan(w, N);
+  if (ws_refused(workspace, workspace_bytes, w.used(), 16)) return RUNIA_E_WORKSPACE;
+  double *anorm = plan.anorm, *partial = plan.R;  // the R buffer, not yet in use
   const int64_t total = N * N;
   const int grid = (int)((total / 256 < 1024) ? (total / 256 > 0 ? total / 256 : 1) : 1024);  // <= 4096 doubles of R
   hipStream_t s = as_stream(stream);
@@ -342,11 +349,12 @@ extern "C" int runia_eigh_block_init_f64(const double* A, double* V, int64_t N, 
 extern "C" int runia_eigh_block_sweep_f64(double* A, double* V, int64_t N, void* workspace, size_t workspace_bytes,
                                           unsigned* rotations, runia_stream_t stream) {
   if (N <= 0 || N > 32768 || N % (2 * BS) != 0 || !A || !V || !rotations) return RUNIA_E_INVALID;
-  if (!workspace || workspace_bytes < runia_eigh_block_workspace_bytes(N) || (((uintptr_t)workspace) & 15) != 0)
-    return RUNIA_E_WORKSPACE;
+  WsWalk w(workspace);
+  const BlockPlan plan = block_plan(w, N);
+  if (ws_refused(workspace, workspace_bytes, w.used(), 16)) return RUNIA_E_WORKSPACE;
   const int nb = (int)(N / BS), np = nb / 2;
-  const double* anorm = reinterpret_cast<const double*>(workspace);
-  double* Rg = reinterpret_cast<double*>(reinterpret_cast<char*>(workspace) + 64);
+  const double* anorm = plan.anorm;
+  double* Rg = plan.R;
   hipStream_t s = as_stream(stream);
   const size_t lds = (size_t)3 * SB * UP * sizeof(double);  // 101 376 bytes
   const size_t lds_s = (size_t)(2 * SB * SP + 64) * sizeof(double) + 528 * sizeof(unsigned short) + 64;  // 68 192 bytes

@@ -1037,9 +1037,7 @@ __global__ __launch_bounds__(256) void kde_replay_kernel(const double* __restric
 
 // query norms, + the values of the column-split launch when the batch has fewer 16-row tiles than the chip has compute units
 static bool kde_split_wanted(int64_t N, int64_t M) { return (N + 15) / 16 < runia_cu_count() && n_padded(M) / BN > 1; }
-static size_t kde_split_bytes(int64_t rows, int64_t M) {
-  return (size_t)(((rows + 15) / 16) * (n_padded(M) / BN) * 256 * 16) * sizeof(double);
-}
+static size_t kde_split_values(int64_t rows, int64_t M) { return (size_t)(((rows + 15) / 16) * (n_padded(M) / BN) * 256 * 16); }
 // Large batches: the rows behind the whole rounds of 32-row tiles (launch_gemm_nct) go through the same column split - units
 // of 1/(2 * blocks) of a 32-row tile instead of a last round on part of the chip (100 000 x 256 against 4 000 rows: 3 125
 // tiles on 512 resident workgroups = 6.1 rounds; 4.40 -> 3.97 ms).  0 = no such rows.
@@ -1050,12 +1048,16 @@ static int64_t kde_last_round_rows(int64_t N, int64_t M) {
   const int64_t head = gemm_whole_round_rows<double, EPI_KDE, double, 4>(g);
   return head > 0 ? N - head : 0;
 }
+struct KdePlan { double *qn, *vals; };  // |x|^2 of the rows (256-byte slot) | values of the column-split rows
+static KdePlan kde_plan(WsWalk& w, int64_t N, int64_t M) {
+  KdePlan p;
+  p.qn = w.take<double>(N, 256);
+  p.vals = w.take<double>(kde_split_values(kde_split_wanted(N, M) ? N : kde_last_round_rows(N, M), M));
+  return p;
+}
 extern "C" size_t runia_kde_workspace_bytes(int64_t N, int64_t M) {
   if (N <= 0 || M <= 0) return 0;
-  size_t bytes = (((size_t)N * sizeof(double)) + 255) / 256 * 256;
-  if (kde_split_wanted(N, M)) bytes += kde_split_bytes(N, M);
-  else bytes += kde_split_bytes(kde_last_round_rows(N, M), M);
-  return bytes;
+  return ws_bytes([&](WsWalk& w) { kde_plan(w, N, M); });
 }
 
 extern "C" int runia_kde_score_packed_f64(const double* packed_train_t, const double* train_sqnorm, const double* x,
@@ -1064,8 +1066,11 @@ extern "C" int runia_kde_score_packed_f64(const double* packed_train_t, const do
   if (M <= 0 || N < 0 || D <= 0 || !(bandwidth > 0.0)) return RUNIA_E_INVALID;
   if (N == 0) return RUNIA_OK;
   if (!packed_train_t || !train_sqnorm || !x || !score) return RUNIA_E_INVALID;
-  if (!workspace || workspace_bytes < (size_t)N * sizeof(double)) return RUNIA_E_WORKSPACE;
-  double* qn = reinterpret_cast<double*>(workspace);
+  if (ws_refused(workspace, workspace_bytes, (size_t)N * sizeof(double), 1)) return RUNIA_E_WORKSPACE;  // (|x|^2 alone: the one launch)
+  WsWalk w(workspace);
+  const KdePlan plan = kde_plan(w, N, M);
+  const bool split_room = workspace_bytes >= w.used();
+  double* qn = plan.qn;
   if (int rc = runia_row_sqnorm_f64(x, qn, N, D, stream)) return rc;
   GemmArgs g{};
   g.x = x; g.ldx = D; g.packed = packed_train_t; g.N = N; g.K = D; g.n = M;
@@ -1077,15 +1082,15 @@ extern "C" int runia_kde_score_packed_f64(const double* packed_train_t, const do
   // compute unit (8 rows against 10 000 x 256: 0.6 ms).  With the workspace runia_kde_workspace_bytes asks for, the
   // 256-column blocks of a tile go to separate workgroups, which store their values, and a second launch replays the
   // online logsumexp over them in block order with the fused kernel's own update and merges: the same bits.
-  if (kde_split_wanted(N, M) && workspace_bytes >= runia_kde_workspace_bytes(N, M)) {
+  if (kde_split_wanted(N, M) && split_room) {
     hipStream_t s = as_stream(stream);
     const int64_t tiles = (N + 15) / 16, nb = n_padded(M) / BN;
-    g.kde_vals = reinterpret_cast<double*>(reinterpret_cast<char*>(workspace) + (((size_t)N * sizeof(double)) + 255) / 256 * 256);
+    g.kde_vals = plan.vals;
     gemm_rows_kernel<double, double, EPI_KDE, 1, 4><<<(unsigned)(tiles * nb), 256, 0, s>>>(g);
     kde_replay_kernel<<<(unsigned)tiles, 256, 0, s>>>(g.kde_vals, g.rown, score, N, nb, g.addc);
     return runia_check_launch();
   }
-  if (const int64_t rest = kde_last_round_rows(N, M); rest > 0 && workspace_bytes >= runia_kde_workspace_bytes(N, M)) {
+  if (const int64_t rest = kde_last_round_rows(N, M); rest > 0 && split_room) {
     hipStream_t s = as_stream(stream);
     const int64_t head = N - rest, tiles = (rest + 15) / 16, nb = n_padded(M) / BN;
     if (tiles * nb <= 0x7fffffff) {
@@ -1093,7 +1098,7 @@ extern "C" int runia_kde_score_packed_f64(const double* packed_train_t, const do
       h.N = head;
       gemm_rows_kernel<double, double, EPI_KDE, 2, 4><<<(unsigned)(head / BM), 256, 0, s>>>(h);
       GemmArgs t = gemm_rows_from<double>(g, head, 1);
-      t.kde_vals = reinterpret_cast<double*>(reinterpret_cast<char*>(workspace) + (((size_t)N * sizeof(double)) + 255) / 256 * 256);
+      t.kde_vals = plan.vals;
       gemm_rows_kernel<double, double, EPI_KDE, 1, 4><<<(unsigned)(tiles * nb), 256, 0, s>>>(t);
       kde_replay_kernel<<<(unsigned)tiles, 256, 0, s>>>(t.kde_vals, t.rown, t.out, rest, nb, g.addc);
       return runia_check_launch();
@@ -1111,14 +1116,20 @@ extern "C" size_t runia_mahalanobis_workspace_bytes(int64_t N, int64_t D) {
 
 // Workspace that also lets C > 16 classes take the matrix-core form of the class terms (below): the packed class means,
 // qc, and G and S = G M^T for a chunk of rows.  (With only runia_mahalanobis_workspace_bytes the class loop runs.)
-static size_t maha_class_carve_bytes(int64_t D, int C) {
-  return (size_t)packed_elems(D, C) * sizeof(double) + (((size_t)C * sizeof(double) + 255) / 256) * 256;
+struct MahaClassPlan { double *packed_mt, *qc, *G; };  // G (and S behind it): D + C values per row, as many rows as fit
+static MahaClassPlan maha_class_plan(WsWalk& w, int64_t D, int C) {
+  MahaClassPlan p;
+  p.packed_mt = w.take<double>(packed_elems(D, C));
+  p.qc = w.take<double>(C, 256);
+  p.G = w.take<double>(0);
+  return p;
 }
 extern "C" size_t runia_mahalanobis_workspace_bytes_classes(int64_t N, int64_t D, int C) {
   if (N <= 0 || D <= 0 || C <= 0) return 0;
   if (C <= kMahaMaxClasses) return runia_mahalanobis_workspace_bytes(N, D);
-  const int64_t rows = N < 65536 ? N : 65536;
-  return maha_class_carve_bytes(D, C) + (size_t)rows * (size_t)(D + C) * sizeof(double);
+  WsWalk w;
+  maha_class_plan(w, D, C);
+  return w.used() + (size_t)(N < 65536 ? N : 65536) * (size_t)(D + C) * sizeof(double);
 }
 
 // Finish of the column-split Mahalanobis launch: per (row, class) the blocks' partial sums of each wave in block order
@@ -1196,13 +1207,13 @@ static int maha_impl(const TX* x, const TX* class_mean, const double* packed_p, 
     return launch_gemm<TX, EPI_MAHA>(g, s);
   }
   if (!workspace) return RUNIA_E_WORKSPACE;
-  const size_t carve = maha_class_carve_bytes(D, C);
-  if ((((uintptr_t)workspace) & 15) == 0 && workspace_bytes >= carve + (size_t)(D + C) * sizeof(double)) {
+  WsWalk w(workspace);
+  const MahaClassPlan plan = maha_class_plan(w, D, C);
+  const size_t carve = w.used(), row_bytes = (size_t)(D + C) * sizeof(double);
+  if (!ws_refused(workspace, workspace_bytes, carve + row_bytes, 16)) {
     // class terms on the matrix cores: S = G M^T ranks the classes, the f32-diff formula finishes the candidates
-    double* packed_mt = reinterpret_cast<double*>(workspace);
-    double* qc = packed_mt + packed_elems(D, C);
-    double* G = reinterpret_cast<double*>(reinterpret_cast<char*>(workspace) + carve);
-    const int64_t cap_rows = (int64_t)((workspace_bytes - carve) / ((size_t)(D + C) * sizeof(double)));
+    double *packed_mt = plan.packed_mt, *qc = plan.qc, *G = plan.G;
+    const int64_t cap_rows = (int64_t)((workspace_bytes - carve) / row_bytes);
     const int64_t total = packed_elems(D, C);
     pack_class_means_kernel<TX><<<runia_stream_grid(total, 256), 256, 0, s>>>(class_mean, D, C, packed_mt,
                                                                                n_padded(C) / 16, total);

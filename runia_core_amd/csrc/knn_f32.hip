@@ -749,7 +749,6 @@ static int64_t knn_chunk_rows(int64_t N, int64_t M) {
   if (qc > by_size) qc = by_size < 256 ? (N < 256 ? N : 256) : by_size;
   return qc;
 }
-static size_t knn16_head_bytes(int64_t qc, int64_t M) { return (knn_f32_words(qc, M) * sizeof(float) + 255) / 256 * 256; }
 
 // Sample rows of the candidate filter (0 = the dense form): the expected number of bank rows at or below a row's
 // threshold is k * M / S, with a spread of ~ sqrt(k) * M / S; S is the multiple of 256 that puts the mean at 0.6 of a
@@ -757,33 +756,37 @@ static size_t knn16_head_bytes(int64_t qc, int64_t M) { return (knn_f32_words(qc
 // quarter of the bank or more (large k), or for a call of a few hundred queries.
 static int64_t knn16_sample_rows(int64_t N, int64_t M, int k) {
   if (!KNN16_FILTER || N < KNN16_FILTER_MIN_ROWS) return 0;
-  int64_t S = ((int64_t)k * M * 10 / (6 * kListCap) + 255) / 256 * 256;
+  int64_t S = (int64_t)round_up((size_t)((int64_t)k * M * 10 / (6 * kListCap)), 256);
   if (S < 1024) S = 1024;
-  if (S < 4 * (int64_t)k) S = (4 * (int64_t)k + 255) / 256 * 256;
+  if (S < 4 * (int64_t)k) S = (int64_t)round_up(4 * (size_t)k, 256);
   return (4 * S <= M) ? S : 0;
 }
 
-static size_t align256(size_t b) { return (b + 255) / 256 * 256; }
-// Workspace of one call of the bf16 kernel after the head (dense rows, |q|^2, |b|^2, max |b|^2) and outside the pieces:
+// Workspace of one call of the bf16 kernel after the head (dense rows, |q|^2, |b|^2, max |b|^2) and outside the pieces, in
+// 256-byte slots:
 //   bn_p [Mpad] (not for a prepared bank: the state holds it) | samp [qc, S] | thr [qc] | counts [qc] | ov_list [qc] |
 //   n_ov [64] | lists [qc, kListCap] x 8 B | pieces of the overflowed rows [dense rows, padded] | their |q|^2 | |q|^2 [qc]
 struct Knn16Filter {
-  size_t bn_p, samp, thr, counts, ov_list, n_ov, lists, ov_planes, ov_qn, qn, end;
+  float *bn_p, *samp, *thr;
+  unsigned* counts;
+  int *ov_list, *n_ov;
+  uint2* lists;
+  uint16_t* ov_planes;
+  float *ov_qn, *qn;
 };
-static Knn16Filter knn16_filter_layout(size_t at, int64_t qc, int64_t dense_rows, int64_t M, int64_t D, int64_t S, bool own_bn_p) {
+static Knn16Filter knn16_filter_plan(WsWalk& w, int64_t qc, int64_t dense_rows, int64_t M, int64_t D, int64_t S, bool own_bn_p) {
   Knn16Filter f;
   const size_t on = S > 0 ? 1 : 0;  // (the dense form keeps only bn_p and |q|^2)
-  f.bn_p = at;       at += own_bn_p ? align256((size_t)runia_knn16_padded_rows(M) * 4) : 0;
-  f.samp = at;       at += align256((size_t)(qc * S) * 4) * on;
-  f.thr = at;        at += align256((size_t)qc * 4) * on;
-  f.counts = at;     at += align256((size_t)qc * 4) * on;
-  f.ov_list = at;    at += align256((size_t)qc * 4) * on;
-  f.n_ov = at;       at += 256 * on;
-  f.lists = at;      at += align256((size_t)qc * kListCap * 8) * on;
-  f.ov_planes = at;  at += S ? runia_knn16_plane_bytes(dense_rows, D) : 0;
-  f.ov_qn = at;      at += align256((size_t)runia_knn16_padded_rows(dense_rows) * 4) * on;
-  f.qn = at;         at += align256((size_t)qc * 4);  // |q|^2 of the chunk
-  f.end = at;
+  f.bn_p = w.take<float>(own_bn_p ? runia_knn16_padded_rows(M) : 0, 256);
+  f.samp = w.take<float>(qc * S * on, 256);
+  f.thr = w.take<float>(qc * on, 256);
+  f.counts = w.take<unsigned>(qc * on, 256);
+  f.ov_list = w.take<int>(qc * on, 256);
+  f.n_ov = w.take<int>(on, 256);
+  f.lists = w.take<uint2>(qc * kListCap * on, 256);
+  f.ov_planes = w.take<uint16_t>(S ? runia_knn16_plane_bytes(dense_rows, D) / sizeof(uint16_t) : 0);
+  f.ov_qn = w.take<float>(runia_knn16_padded_rows(dense_rows) * on, 256);
+  f.qn = w.take<float>(qc, 256);  // |q|^2 of the chunk
   return f;
 }
 // Query rows per pass of the bf16 kernel.  Dense form: the f32 kernel's chunk.  With the candidate filter no Q x M matrix
@@ -813,14 +816,34 @@ static int64_t knn16_dense_rows(int64_t qc, int64_t M, int64_t S) {
   return dr;
 }
 
+// The whole workspace of a bf16 call: the head (plain call: dense rows, |q|^2, |b|^2, max |b|^2 as the f32 kernel lays them
+// out; prepared bank: the dense rows) in a 256-byte slot | the filter's regions | the bank's pieces (plain call) | the chunk's
+struct Knn16Plan {
+  int64_t S, qc, dense_rows;
+  float* head;
+  Knn16Filter f;
+  uint16_t *bank_planes, *q_planes;
+};
+static Knn16Plan knn16_plan(WsWalk& w, int64_t N, int64_t M, int64_t D, int k, bool prepared) {
+  Knn16Plan p;
+  p.S = knn16_sample_rows(N, M, k);
+  p.qc = knn16_chunk_rows(N, M, p.S);
+  p.dense_rows = knn16_dense_rows(p.qc, M, p.S);
+  p.head = w.take<float>(prepared ? (size_t)(p.dense_rows * M) : knn_f32_words(p.dense_rows, M), 256);
+  p.f = knn16_filter_plan(w, p.qc, p.dense_rows, M, D, p.S, !prepared);
+  p.bank_planes = w.take<uint16_t>(prepared ? 0 : runia_knn16_plane_bytes(M, D) / sizeof(uint16_t));
+  p.q_planes = w.take<uint16_t>(runia_knn16_plane_bytes(p.qc, D) / sizeof(uint16_t));
+  return p;
+}
+
 extern "C" size_t runia_knn_workspace_bytes(int64_t N, int64_t M, int64_t D, int k) {
   if (N <= 0 || M <= 0) return 0;
   // + the bf16 pieces of the bank and of one chunk of queries when the bf16 kernel will be taken; the entry point works
   // with whatever it is given (>= 1 row of distances), but takes the bf16 kernel only with at least this much
   if (knn16_wanted(N, M, D)) {
-    const int64_t S = knn16_sample_rows(N, M, k), qc = knn16_chunk_rows(N, M, S), dr = knn16_dense_rows(qc, M, S);
-    const Knn16Filter f = knn16_filter_layout(knn16_head_bytes(dr, M), qc, dr, M, D, S, true);
-    return f.end + runia_knn16_plane_bytes(M, D) + runia_knn16_plane_bytes(qc, D);
+    WsWalk w;
+    knn16_plan(w, N, M, D, k, false);
+    return w.used();
   }
   return knn_f32_words(knn_chunk_rows(N, M), M) * sizeof(float);
 }
@@ -832,7 +855,6 @@ struct Knn16Run {            // (use16 only)
   uint16_t* q_planes;
   const float* bn_p;         // |b|^2 in piece order
   int64_t S, dense_rows;
-  char* ws;                  // base of the workspace `f` is laid out in
   Knn16Filter f;
 };
 static int knn_scan(const float* q, const float* bank, float* score, float* dist, float* qn, const float* bn,
@@ -849,14 +871,12 @@ static int knn_scan(const float* q, const float* bank, float* score, float* dist
     if (now16 && r16->S > 0) {  // candidate filter: no Q x M matrix
       const int64_t S = r16->S;
       const float rel = runia_knn16_refine_rel(D);
-      float* samp = reinterpret_cast<float*>(r16->ws + r16->f.samp);
-      float* thr = reinterpret_cast<float*>(r16->ws + r16->f.thr);
-      unsigned* counts = reinterpret_cast<unsigned*>(r16->ws + r16->f.counts);
-      int* ov_list = reinterpret_cast<int*>(r16->ws + r16->f.ov_list);
-      int* n_ov = reinterpret_cast<int*>(r16->ws + r16->f.n_ov);
-      void* lists = r16->ws + r16->f.lists;
-      uint16_t* ov_planes = reinterpret_cast<uint16_t*>(r16->ws + r16->f.ov_planes);
-      float* ov_qn = reinterpret_cast<float*>(r16->ws + r16->f.ov_qn);
+      const Knn16Filter& f = r16->f;
+      float *samp = f.samp, *thr = f.thr, *ov_qn = f.ov_qn;
+      unsigned* counts = f.counts;
+      int *ov_list = f.ov_list, *n_ov = f.n_ov;
+      uint2* lists = f.lists;
+      uint16_t* ov_planes = f.ov_planes;
       rc = runia_knn16_split(q + r0 * D, r16->q_planes, rows, D, s);
       if (rc == RUNIA_OK) rc = runia_knn16_dist(r16->q_planes, r16->bank_planes, qn, r16->bn_p, samp, rows, S, D, qpad, Mpad, nullptr, 0, s);
       if (rc != RUNIA_OK) return rc;
@@ -865,7 +885,7 @@ static int knn_scan(const float* q, const float* bank, float* score, float* dist
       rc = runia_knn16_filter(r16->q_planes, r16->bank_planes + S * Dp2, qn, r16->bn_p + S, thr, counts, lists, kListCap,
                               (int)S, rows, M - S, D, qpad, Mpad - S, s);
       if (rc != RUNIA_OK) return rc;
-      kth_select_lists_kernel<<<sel_grid, 256, 0, s>>>(samp, (int)S, reinterpret_cast<const uint2*>(lists), counts, thr,
+      kth_select_lists_kernel<<<sel_grid, 256, 0, s>>>(samp, (int)S, lists, counts, thr,
                                                        q + r0 * D, bank, qn, bn_max, score + r0, ov_list, n_ov, rows, D, k, rel, pm);
       // the rows that overflowed (none, as a rule: the launches below then end at their first instruction)
       const int64_t dr = r16->dense_rows;
@@ -938,25 +958,24 @@ extern "C" int runia_knn_kth_f32(const float* q, const float* bank, float* score
   if (qc > kQueryChunk) qc = kQueryChunk;
   // bf16 candidate distances exactly when the caller hands over the workspace runia_knn_workspace_bytes asks for (a
   // smaller one - e.g. the f32 kernel's (chunk * M + chunk + M + 4) floats - keeps the f32 kernel: the caller's switch)
-  const bool use16 = knn16_wanted(N, M, D) && workspace_bytes >= runia_knn_workspace_bytes(N, M, D, k);
+  bool use16 = knn16_wanted(N, M, D);
   Knn16Run r16{};
   int64_t dense_rows = qc;
   if (use16) {
-    r16.S = knn16_sample_rows(N, M, k);
-    qc = knn16_chunk_rows(N, M, r16.S);
-    r16.dense_rows = dense_rows = knn16_dense_rows(qc, M, r16.S);
-    r16.ws = reinterpret_cast<char*>(workspace);
-    r16.f = knn16_filter_layout(knn16_head_bytes(dense_rows, M), qc, dense_rows, M, D, r16.S, true);
-    uint16_t* planes = reinterpret_cast<uint16_t*>(r16.ws + r16.f.end);
-    r16.bank_planes = planes;
-    r16.q_planes = planes + runia_knn16_plane_bytes(M, D) / sizeof(uint16_t);
-    r16.bn_p = reinterpret_cast<const float*>(r16.ws + r16.f.bn_p);
+    WsWalk w(workspace);
+    const Knn16Plan p = knn16_plan(w, N, M, D, k, false);
+    use16 = workspace_bytes >= w.used();
+    if (use16) {
+      qc = p.qc;
+      dense_rows = p.dense_rows;
+      r16 = Knn16Run{p.bank_planes, p.q_planes, p.f.bn_p, p.S, p.dense_rows, p.f};
+    }
   }
   float* dist = reinterpret_cast<float*>(workspace);
   float* qn = dist + dense_rows * M;  // (bf16 kernel: the head keeps `dense_rows` slots; the chunk's |q|^2 have their own block)
   float* bn = qn + dense_rows;
   unsigned* bn_max = reinterpret_cast<unsigned*>(bn + M);
-  if (use16) qn = reinterpret_cast<float*>(r16.ws + r16.f.qn);
+  if (use16) qn = r16.f.qn;
   if (hipMemsetAsync(bn_max, 0, sizeof(unsigned), s) != hipSuccess) return RUNIA_E_LAUNCH;
   if (knn_small_fits(N, M, D) && qc >= N) {  // a handful of queries: one pass over the bank, exact distances
     const int rc_small = knn_small_path(q, bank, score, dist, qn, bn_max, bn_max, N, M, D, k, s);
@@ -984,28 +1003,36 @@ static bool knn16_prepared_wanted(int64_t N, int64_t M, int64_t D) {
   return knn16_bank_ok(M, D) && N >= KNN16_MIN_ROWS_PREPARED && N * M >= ((int64_t)1 << 29) / D &&
          (M * D >= ((int64_t)1 << 23) || N >= 1000);  // (tools/ablate/run_knn_prepared.py: small banks stay on the f32 kernel)
 }
-static size_t knn_state_head_bytes(int64_t M) { return (((size_t)M + 1) * sizeof(float) + 255) / 256 * 256; }
-static size_t knn_state_bnp_bytes(int64_t M) { return align256((size_t)runia_knn16_padded_rows(M) * sizeof(float)); }
+// |b|^2 and their maximum (256-byte slot) | with the pieces: |b|^2 in piece order (256-byte slot) | the bf16 pieces
+struct KnnBankState { float *bn, *bn_p; uint16_t* planes; };
+static KnnBankState knn_state_plan(WsWalk& w, int64_t M, int64_t D, bool pieces) {
+  KnnBankState st;
+  st.bn = w.take<float>(M + 1, 256);
+  st.bn_p = w.take<float>(pieces ? runia_knn16_padded_rows(M) : 0, 256);
+  st.planes = w.take<uint16_t>(pieces ? runia_knn16_plane_bytes(M, D) / sizeof(uint16_t) : 0);
+  return st;
+}
+static size_t knn_state_bytes(int64_t M, int64_t D, bool pieces) {
+  return ws_bytes([&](WsWalk& w) { knn_state_plan(w, M, D, pieces); });
+}
 extern "C" size_t runia_knn_bank_state_bytes(int64_t M, int64_t D) {
   if (M <= 0 || D <= 0) return 0;
-  return knn_state_head_bytes(M) + (knn16_bank_ok(M, D) ? knn_state_bnp_bytes(M) + runia_knn16_plane_bytes(M, D) : 0);
+  return knn_state_bytes(M, D, knn16_bank_ok(M, D));
 }
 extern "C" int runia_knn_prepare_bank_f32(const float* bank, void* state, size_t state_bytes, int64_t M, int64_t D,
                                           runia_stream_t stream) {
   if (M <= 0 || D <= 0 || !bank || !state) return RUNIA_E_INVALID;
-  if ((((uintptr_t)state) & 15) != 0 || state_bytes < knn_state_head_bytes(M)) return RUNIA_E_WORKSPACE;
+  if (ws_refused(state, state_bytes, knn_state_bytes(M, D, false), 16)) return RUNIA_E_WORKSPACE;
   hipStream_t s = as_stream(stream);
-  float* bn = reinterpret_cast<float*>(state);
+  WsWalk w(state);
+  const KnnBankState st = knn_state_plan(w, M, D, knn16_bank_ok(M, D));
+  float* bn = st.bn;
   unsigned* bn_max = reinterpret_cast<unsigned*>(bn + M);
   if (hipMemsetAsync(bn_max, 0, sizeof(unsigned), s) != hipSuccess) return RUNIA_E_LAUNCH;
   row_sqnorm_kernel<<<runia_rows_grid(M), 64 * kRowWaves, 0, s>>>(bank, bn, M, D, bn_max);
   int rc = runia_check_launch();
   if (rc != RUNIA_OK) return rc;
-  if (knn16_bank_ok(M, D) && state_bytes >= runia_knn_bank_state_bytes(M, D)) {
-    char* st = reinterpret_cast<char*>(state);
-    rc = runia_knn16_split_bank(bank, reinterpret_cast<uint16_t*>(st + knn_state_head_bytes(M) + knn_state_bnp_bytes(M)), bn,
-                                reinterpret_cast<float*>(st + knn_state_head_bytes(M)), M, D, s);
-  }
+  if (knn16_bank_ok(M, D) && state_bytes >= w.used()) rc = runia_knn16_split_bank(bank, st.planes, bn, st.bn_p, M, D, s);
   return rc;
 }
 // workspace of a call against a prepared bank: the dense rows, |q|^2 and (bf16 kernel) the filter's buffers and the chunk's pieces
@@ -1013,11 +1040,9 @@ extern "C" size_t runia_knn_prepared_workspace_bytes(int64_t N, int64_t M, int64
   if (N <= 0 || M <= 0) return 0;
   if (!knn16_prepared_wanted(N, M, D)) {
     const int64_t qc = knn_chunk_rows(N, M);
-    return align256((size_t)(qc * M + qc) * sizeof(float));
+    return round_up((size_t)(qc * M + qc) * sizeof(float), 256);
   }
-  const int64_t S = knn16_sample_rows(N, M, k), qc = knn16_chunk_rows(N, M, S), dr = knn16_dense_rows(qc, M, S);
-  const Knn16Filter f = knn16_filter_layout(align256((size_t)(dr * M) * sizeof(float)), qc, dr, M, D, S, false);
-  return f.end + runia_knn16_plane_bytes(qc, D);
+  return ws_bytes([&](WsWalk& w) { knn16_plan(w, N, M, D, k, true); });
 }
 extern "C" int runia_knn_kth_prepared_f32(const float* q, const float* bank, const void* state, size_t state_bytes,
                                           float* score, void* workspace, size_t workspace_bytes, int64_t N, int64_t M,
@@ -1025,21 +1050,28 @@ extern "C" int runia_knn_kth_prepared_f32(const float* q, const float* bank, con
   if (N < 0 || M <= 0 || D <= 0 || k < 1) return RUNIA_E_INVALID;
   if (N == 0) return RUNIA_OK;
   if (!q || !score || !bank || !state) return RUNIA_E_INVALID;
-  if (state_bytes < knn_state_head_bytes(M)) return RUNIA_E_WORKSPACE;
+  if (state_bytes < knn_state_bytes(M, D, false)) return RUNIA_E_WORKSPACE;
   hipStream_t s = as_stream(stream);
   if (k > M) {
     fill_kernel<<<runia_stream_grid(N, 256), 256, 0, s>>>(score, N, -kFltMax);
     return runia_check_launch();
   }
   if (!workspace || workspace_bytes < (size_t)(M + 1) * sizeof(float)) return RUNIA_E_WORKSPACE;
-  const float* bn = reinterpret_cast<const float*>(state);
+  WsWalk sw(const_cast<void*>(state));
+  const KnnBankState st = knn_state_plan(sw, M, D, knn16_bank_ok(M, D));
+  const float* bn = st.bn;
   const unsigned* bn_max = reinterpret_cast<const unsigned*>(bn + M);  // max |b|^2 of the prepared bank: never written by a scoring call
   // the bf16 kernel when the state holds the pieces and the workspace is the one asked for; else the f32 kernel with as
   // many query rows per pass as the workspace holds
-  const bool use16 = knn16_prepared_wanted(N, M, D) && state_bytes >= runia_knn_bank_state_bytes(M, D) &&
-                     workspace_bytes >= runia_knn_prepared_workspace_bytes(N, M, D, k);
-  const int64_t S16 = use16 ? knn16_sample_rows(N, M, k) : 0;
-  int64_t qc = use16 ? knn16_chunk_rows(N, M, S16) : (int64_t)(workspace_bytes / sizeof(float) / (size_t)(M + 1));
+  bool use16 = knn16_prepared_wanted(N, M, D) && state_bytes >= sw.used();
+  Knn16Run r16{};
+  if (use16) {
+    WsWalk w(workspace);
+    const Knn16Plan p = knn16_plan(w, N, M, D, k, true);
+    use16 = workspace_bytes >= w.used();
+    if (use16) r16 = Knn16Run{st.planes, p.q_planes, st.bn_p, p.S, p.dense_rows, p.f};
+  }
+  int64_t qc = use16 ? knn16_chunk_rows(N, M, r16.S) : (int64_t)(workspace_bytes / sizeof(float) / (size_t)(M + 1));
   if (qc < 1) return RUNIA_E_WORKSPACE;
   if (qc > N) qc = N;
   if (!use16 && qc > kQueryChunk) qc = kQueryChunk;
@@ -1049,17 +1081,6 @@ extern "C" int runia_knn_kth_prepared_f32(const float* q, const float* bank, con
     const int rc_small = knn_small_path(q, bank, score, dist, qn, bn_max, nullptr, N, M, D, k, s);
     if (rc_small <= 0) return rc_small;
   }
-  Knn16Run r16{};
-  if (use16) {
-    const char* st = reinterpret_cast<const char*>(state);
-    r16.S = S16;
-    r16.dense_rows = knn16_dense_rows(qc, M, r16.S);
-    r16.ws = reinterpret_cast<char*>(workspace);
-    r16.f = knn16_filter_layout(align256((size_t)(r16.dense_rows * M) * sizeof(float)), qc, r16.dense_rows, M, D, r16.S, false);
-    r16.bn_p = reinterpret_cast<const float*>(st + knn_state_head_bytes(M));
-    r16.bank_planes = reinterpret_cast<const uint16_t*>(st + knn_state_head_bytes(M) + knn_state_bnp_bytes(M));
-    qn = reinterpret_cast<float*>(r16.ws + r16.f.qn);
-    r16.q_planes = reinterpret_cast<uint16_t*>(r16.ws + r16.f.end);
-  }
+  if (use16) qn = r16.f.qn;
   return knn_scan(q, bank, score, dist, qn, bn, bn_max, use16 ? &r16 : nullptr, qc, N, M, D, k, s, 1);
 }

@@ -164,12 +164,10 @@ __global__ __launch_bounds__(kTile) void ks_walk_kernel(const uint32_t* __restri
 }
 
 // ---- host side --------------------------------------------------------------------------------------------------------------------
-int64_t round_up(int64_t v, int64_t q) { return (v + q - 1) / q * q; }
-
 struct Plan {
   int64_t N, P, row_words, pw, ord_stride, cols;
   int np2, threads;
-  size_t off_bits, off_memT, off_order, total;
+  uint32_t *bits, *memT, *order;  // the regions of the workspace (256-byte slots)
 };
 
 bool shape_ok(int64_t n, int64_t m, int64_t n_perm) {
@@ -181,7 +179,7 @@ int64_t columns_per_pass(int64_t n, int64_t m) {
   return std::max<int64_t>(1, std::min<int64_t>(kMaxCols, (int64_t)kOrderBudget / per_col));
 }
 
-bool make_plan(int64_t n, int64_t m, int64_t d, int64_t n_perm, Plan& pl) {
+bool make_plan(WsWalk& w, int64_t n, int64_t m, int64_t d, int64_t n_perm, Plan& pl) {
   if (!shape_ok(n, m, n_perm) || d < 1 || d >= (1ll << 31)) return false;
   pl.N = n + m;
   pl.P = 1 + n_perm;
@@ -192,12 +190,9 @@ bool make_plan(int64_t n, int64_t m, int64_t d, int64_t n_perm, Plan& pl) {
   pl.np2 = 2;
   while (pl.np2 < pl.N) pl.np2 *= 2;
   pl.threads = pl.np2 >= 2048 ? 1024 : 256;
-  size_t o = 0;
-  auto take = [&](size_t bytes) { const size_t at = o; o += (bytes + 255) / 256 * 256; return at; };
-  pl.off_bits = take((size_t)pl.P * (size_t)pl.row_words * 4);
-  pl.off_memT = take((size_t)pl.N * (size_t)pl.pw * 4);
-  pl.off_order = take((size_t)pl.cols * (size_t)pl.ord_stride * 4);
-  pl.total = o;
+  pl.bits = w.take<uint32_t>((size_t)pl.P * (size_t)pl.row_words, 256);
+  pl.memT = w.take<uint32_t>((size_t)pl.N * (size_t)pl.pw, 256);
+  pl.order = w.take<uint32_t>((size_t)pl.cols * (size_t)pl.ord_stride, 256);
   return true;
 }
 
@@ -218,23 +213,22 @@ extern "C" int64_t runia_ks_columns_per_pass(int64_t n, int64_t m, int64_t n_per
 }
 
 extern "C" size_t runia_ks_workspace_bytes(int64_t n, int64_t m, int64_t d, int64_t n_perm) {
+  WsWalk w;
   Plan pl;
-  return make_plan(n, m, d, n_perm, pl) ? pl.total : 0;
+  return make_plan(w, n, m, d, n_perm, pl) ? w.used() : 0;
 }
 
 extern "C" int runia_ks_perm_table(const void* x, int64_t n, int64_t x_stride, const void* y, int64_t m, int64_t y_stride, int64_t d,
                                    int dtype, uint64_t seed, int64_t n_perm, int64_t* table, int32_t* valid, void* workspace,
                                    size_t workspace_bytes, runia_stream_t stream) {
+  WsWalk w(workspace);
   Plan pl;
-  if (!make_plan(n, m, d, n_perm, pl)) return RUNIA_E_INVALID;
+  if (!make_plan(w, n, m, d, n_perm, pl)) return RUNIA_E_INVALID;
   if (!elem_dtype_ok(dtype) || x_stride < d || y_stride < d) return RUNIA_E_INVALID;
   if (!x || !y || !table || !valid) return RUNIA_E_INVALID;
-  if (!workspace || workspace_bytes < pl.total || (((uintptr_t)workspace) & 15) != 0) return RUNIA_E_WORKSPACE;
+  if (ws_refused(workspace, workspace_bytes, w.used(), 16)) return RUNIA_E_WORKSPACE;
   hipStream_t s = as_stream(stream);
-  char* ws = reinterpret_cast<char*>(workspace);
-  uint32_t* bits = reinterpret_cast<uint32_t*>(ws + pl.off_bits);
-  uint32_t* memT = reinterpret_cast<uint32_t*>(ws + pl.off_memT);
-  uint32_t* order = reinterpret_cast<uint32_t*>(ws + pl.off_order);
+  uint32_t *bits = pl.bits, *memT = pl.memT, *order = pl.order;
   const Cols c{x, y, n, pl.N, x_stride, y_stride};
 
   if (int rc = runia_shift_perm_bits(seed, n, pl.N, 0, pl.P, bits, pl.row_words, stream)) return rc;

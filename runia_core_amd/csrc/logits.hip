@@ -208,7 +208,7 @@ extern "C" int runia_logit_stats(const void* table, int dtype, int64_t n_steps, 
   if (log_prob && (!tokens || (B > 1 && token_stride < n_steps))) return RUNIA_E_INVALID;
   if (seq && (!log_prob || !entropy)) return RUNIA_E_INVALID;
   const size_t need = runia_logit_stats_workspace_bytes(n_steps, B, V);
-  if (!workspace || workspace_bytes < need || (reinterpret_cast<uintptr_t>(workspace) & 15) != 0) return RUNIA_E_WORKSPACE;
+  if (ws_refused(workspace, workspace_bytes, need, 16)) return RUNIA_E_WORKSPACE;
   const int nc = (int)n_chunks(V);
   const int64_t rows = B * n_steps;
   const StepDesc* tab = reinterpret_cast<const StepDesc*>(table);

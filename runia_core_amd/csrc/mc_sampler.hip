@@ -807,8 +807,8 @@ static int mc_args_ok(int64_t N, int C, int H, int W, int n_mc, int block_size, 
                       const void* ws = nullptr, size_t ws_bytes = 0) {
   if (N < 0 || N > kMaxImages || C <= 0 || H <= 0 || W <= 0 || n_mc < 2 || n_mc > kMaxMC || block_size < 1 || k < 1 || k >= n_mc)
     return RUNIA_E_INVALID;
-  const bool ws_ok = ws && ws_bytes >= runia_mc_entropy_workspace_bytes(N, H, W, n_mc) && (((uintptr_t)ws) & 15) == 0;
-  return (N > 0 && has_ws && !ws_ok) ? RUNIA_E_WORKSPACE : RUNIA_OK;
+  const bool refused = ws_refused(ws, ws_bytes, runia_mc_entropy_workspace_bytes(N, H, W, n_mc), 16);
+  return (N > 0 && has_ws && refused) ? RUNIA_E_WORKSPACE : RUNIA_OK;
 }
 
 // (2) The operands of a K1 launch on N > 0 maps: input and output, a shape with a kernel, and x on 16 bytes where a map is
@@ -926,7 +926,7 @@ extern "C" int runia_mc_entropy_lut_f32(const float* x, const float* rnd, int64_
   if (int rc = mc_args_ok(N, C, H, W, n_mc, block_size, k)) return rc;
   if (N == 0) return RUNIA_OK;
   if (!rnd || !k1_operands_ok(x, h, H, W, n_mc, k)) return RUNIA_E_INVALID;
-  if (!lut || (((uintptr_t)lut) & 3) != 0 || lut_bytes < runia_mc_flag_lut_bytes(H, W, block_size)) return RUNIA_E_WORKSPACE;
+  if (ws_refused(lut, lut_bytes, runia_mc_flag_lut_bytes(H, W, block_size), 4)) return RUNIA_E_WORKSPACE;
   const float gamma = (float)(drop_prob / (double)(block_size * block_size));
   const double ct = digamma_diff(n_mc, k), inv_n = 1.0 / (double)n_mc;
   RUNIA_LAUNCH_TIMED((mc_entropy_lut_kernel<4, 4, 16, 5>), k1_grid(N, C), kK1Block, 0, as_stream(stream), x, rnd,
@@ -935,10 +935,17 @@ extern "C" int runia_mc_entropy_lut_f32(const float* x, const float* rnd, int64_
 }
 
 // ---- ROI source (config 4): roi_align folded into K1's load ------------------------------------------------------------
+struct RoiMcPlan { float* masks; size_t masks_bytes; char* tab; };  // the ROIs' keep-flag table (256-byte slot) | their sample table
+static RoiMcPlan roi_mc_plan(WsWalk& w, int64_t K, int PH, int PW, int n_mc, int sampling_ratio) {
+  RoiMcPlan p;
+  p.masks = w.take<float>(runia_mc_entropy_workspace_bytes(K, PH, PW, n_mc) / sizeof(float), 256);
+  p.masks_bytes = w.used();
+  p.tab = w.take<char>(runia_roi_sample_table_bytes(K, PH, PW, sampling_ratio));
+  return p;
+}
 extern "C" size_t runia_roi_mc_entropy_workspace_bytes(int64_t K, int PH, int PW, int n_mc, int sampling_ratio) {
   if (K <= 0 || sampling_ratio < 1) return 0;
-  const size_t masks = (runia_mc_entropy_workspace_bytes(K, PH, PW, n_mc) + 255) / 256 * 256;
-  return masks + runia_roi_sample_table_bytes(K, PH, PW, sampling_ratio);
+  return ws_bytes([&](WsWalk& w) { roi_mc_plan(w, K, PH, PW, n_mc, sampling_ratio); });
 }
 extern "C" int runia_roi_mc_entropy_f32(const float* feat_nhwc, const float* boxes, const int* batch_idx, const float* rnd,
                                         int64_t rand_image_stride, double* h, float* z_out, void* workspace,
@@ -952,18 +959,18 @@ extern "C" int runia_roi_mc_entropy_f32(const float* feat_nhwc, const float* box
   if (!runia_roi_mc_entropy_supported(PH, PW, n_mc, k, sampling_ratio)) return RUNIA_E_INVALID;
   if ((int64_t)H * W * C * 4 >= ((int64_t)1 << 30)) return RUNIA_E_INVALID;  // one image's map behind a 32-bit buffer (RUNIA_ROI_FUSED_MAX_IMAGE_BYTES)
   if (drop_prob != 0.0 && !rnd) return RUNIA_E_INVALID;
-  if (!workspace || (((uintptr_t)workspace) & 15) != 0 ||
-      workspace_bytes < runia_roi_mc_entropy_workspace_bytes(K, PH, PW, n_mc, sampling_ratio))
-    return RUNIA_E_WORKSPACE;
-  const size_t masks = (runia_mc_entropy_workspace_bytes(K, PH, PW, n_mc) + 255) / 256 * 256;
+  WsWalk w(workspace);
+  const RoiMcPlan plan = roi_mc_plan(w, K, PH, PW, n_mc, sampling_ratio);
+  if (ws_refused(workspace, workspace_bytes, w.used(), 16)) return RUNIA_E_WORKSPACE;
+  const size_t masks = plan.masks_bytes;
   if (int rc = runia_mc_mask_table_f32(rnd, rand_image_stride, workspace, masks, K, PH, PW, n_mc, drop_prob, block_size, stream))
     return rc;
-  char* tab = reinterpret_cast<char*>(workspace) + masks;
+  char* tab = plan.tab;
   hipStream_t s = as_stream(stream);
   if (int rc = runia_roi_sample_table(feat_nhwc, boxes, batch_idx, tab, workspace_bytes - masks, K, B, C, H, W, PH, PW,
                                       spatial_scale, sampling_ratio, aligned, s))
     return rc;
-  const float* table = reinterpret_cast<const float*>(workspace);
+  const float* table = plan.masks;
   const float* src = reinterpret_cast<const float*>(tab);  // the RoiSource at the head of the sample table
   const double ct = digamma_diff(n_mc, k), inv_n = 1.0 / (double)n_mc;
   if (!roi_mc_for_shape(PH, PW, n_mc, k, sampling_ratio, [&](auto hh, auto ww, auto np, auto kk, auto gg, auto full) {

@@ -1198,33 +1198,37 @@ __global__ __launch_bounds__(256) void msd_sort_curve_kernel(uint64_t* __restric
 // digit counters by 256 threads is serial over the predecessors, up to G - 1 of them when G tiles start together.  A
 // dependent launch costs ~7.5 us.  Not kept; what did shorten the step is fewer passes over the keys (above).
 
-size_t align256(size_t v) { return (v + 255) & ~(size_t)255; }
-
-struct Layout {
-  size_t keys_a, keys_b, lab_a, lab_b, tps, prev_end, tile_sum, tile_end, tile_cnt, flag, msd, parts, bucket_of, parts2, total;
+// The regions of the caller's workspace (256-byte slots; the base must be 256-byte aligned)
+struct Plan {
+  uint64_t* keys[2];
+  uint8_t* labs[2];
+  unsigned *tps, *tile_sum, *tile_cnt, *flag;
+  int *prev_end, *tile_end;
+  MsdState* msd;
+  MetricsAccum* parts;  // per-workgroup records of the curve-term launch (written before read)
+  uint16_t* bucket_of;  // bucket of every key (key launch -> scatter)
+  FusedPart* parts2;    // per-workgroup records of the fused sort + curve launch
   unsigned nblocks;
 };
 
-Layout make_layout(int64_t n) {
-  Layout L;
-  L.nblocks = (unsigned)((n + kTile - 1) / kTile);
-  size_t o = 0;
-  L.keys_a = o; o += align256((size_t)n * 8);
-  L.keys_b = o; o += align256((size_t)n * 8);
-  L.lab_a = o; o += align256((size_t)n);
-  L.lab_b = o; o += align256((size_t)n);
-  L.tps = o; o += align256((size_t)n * 4);
-  L.prev_end = o; o += align256((size_t)n * 4);
-  L.tile_sum = o; o += align256((size_t)L.nblocks * 4);
-  L.tile_end = o; o += align256((size_t)L.nblocks * 4);
-  L.tile_cnt = o; o += align256((size_t)L.nblocks * 4);
-  L.flag = o; o += 256;
-  L.msd = o; o += align256(sizeof(MsdState));
-  L.parts = o; o += align256(kCurveBlocks * sizeof(MetricsAccum));  // per-workgroup records of the curve-term launch (written before read)
-  L.bucket_of = o; o += align256((size_t)n * 2);                     // bucket of every key (key launch -> scatter)
-  L.parts2 = o; o += align256((size_t)(kMsdBuckets / 4) * sizeof(FusedPart));  // per-workgroup records of the fused sort + curve launch
-  L.total = o;
-  return L;
+Plan make_plan(WsWalk& w, int64_t n) {
+  Plan p;
+  p.nblocks = (unsigned)((n + kTile - 1) / kTile);
+  p.keys[0] = w.take<uint64_t>(n, 256);
+  p.keys[1] = w.take<uint64_t>(n, 256);
+  p.labs[0] = w.take<uint8_t>(n, 256);
+  p.labs[1] = w.take<uint8_t>(n, 256);
+  p.tps = w.take<unsigned>(n, 256);
+  p.prev_end = w.take<int>(n, 256);
+  p.tile_sum = w.take<unsigned>(p.nblocks, 256);
+  p.tile_end = w.take<int>(p.nblocks, 256);
+  p.tile_cnt = w.take<unsigned>(p.nblocks, 256);
+  p.flag = w.take<unsigned>(1, 256);
+  p.msd = w.take<MsdState>(1, 256);
+  p.parts = w.take<MetricsAccum>(kCurveBlocks, 256);
+  p.bucket_of = w.take<uint16_t>(n, 256);
+  p.parts2 = w.take<FusedPart>(kMsdBuckets / 4, 256);
+  return p;
 }
 
 template <typename T>
@@ -1234,31 +1238,21 @@ int ood_metrics(const T* ind, int64_t n_ind, const T* ood, int64_t n_ood, double
   if (!ind || !ood || !out3) return RUNIA_E_INVALID;
   if ((tps_out || fps_out || n_points) && !(tps_out && fps_out && n_points)) return RUNIA_E_INVALID;
   const int64_t n = n_ind + n_ood;
-  const Layout L = make_layout(n);
-  if (!workspace || workspace_bytes < L.total || (((uintptr_t)workspace) & 255) != 0) return RUNIA_E_WORKSPACE;
-  char* w = reinterpret_cast<char*>(workspace);
-  uint64_t* keys[2] = {reinterpret_cast<uint64_t*>(w + L.keys_a), reinterpret_cast<uint64_t*>(w + L.keys_b)};
-  uint8_t* labs[2] = {reinterpret_cast<uint8_t*>(w + L.lab_a), reinterpret_cast<uint8_t*>(w + L.lab_b)};
-  unsigned* tps = reinterpret_cast<unsigned*>(w + L.tps);
-  int* prev_end = reinterpret_cast<int*>(w + L.prev_end);
-  unsigned* tile_sum = reinterpret_cast<unsigned*>(w + L.tile_sum);
-  int* tile_end = reinterpret_cast<int*>(w + L.tile_end);
-  unsigned* tile_cnt = reinterpret_cast<unsigned*>(w + L.tile_cnt);
-  unsigned* flag = reinterpret_cast<unsigned*>(w + L.flag);
-  MsdState* st = reinterpret_cast<MsdState*>(w + L.msd);
-  uint16_t* bucket_of = reinterpret_cast<uint16_t*>(w + L.bucket_of);
+  WsWalk walk(workspace);
+  const Plan L = make_plan(walk, n);
+  if (ws_refused(workspace, workspace_bytes, walk.used(), 256)) return RUNIA_E_WORKSPACE;
   hipStream_t s = as_stream(stream);
   // nothing cleared beforehand (MsdState)
   const unsigned sgrid = runia_stream_grid(n, 256);
   const unsigned pgrid = sgrid < kProbeBlocks ? sgrid : kProbeBlocks;
-  msd_probe_kernel<T><<<pgrid, 256, 0, s>>>(ind, n_ind, ood, n_ood, st);
+  msd_probe_kernel<T><<<pgrid, 256, 0, s>>>(ind, n_ind, ood, n_ood, L.msd);
   // Small sets (<= 64 keys per bucket on average) skip the sketch: a raw-linear bin of a bell-shaped set holds a few times
   // the mean, far below the wave sort's 1 024, and the launch would cost them 10 us of their 80
   const int equalise = n > (int64_t)64 * kMsdBuckets;
   if (equalise) {
     const int64_t sketch_n = (n > kSketchAll) ? (n + kSketchStride - 1) / kSketchStride : n;
-    msd_lin_hist_kernel<T><<<(unsigned)((sketch_n + kScatTileHist - 1) / kScatTileHist), 256, 0, s>>>(ind, n_ind, ood, n_ood, flag, st, pgrid);
-    msd_split_kernel<T><<<kMsdBuckets / 256, 256, 0, s>>>(flag, st, pgrid);
+    msd_lin_hist_kernel<T><<<(unsigned)((sketch_n + kScatTileHist - 1) / kScatTileHist), 256, 0, s>>>(ind, n_ind, ood, n_ood, L.flag, L.msd, pgrid);
+    msd_split_kernel<T><<<kMsdBuckets / 256, 256, 0, s>>>(L.flag, L.msd, pgrid);
   }
   // Front half of both forms (round 6): keys + buckets by splitter keys, scatter.  Buckets: 4 096 (equalised by the sketch) for
   // large sets; for small ones raw-linear bins, ~64 keys each - every (tile, bucket) pair costs the scatter an atomic and every
@@ -1269,27 +1263,27 @@ int ood_metrics(const T* ind, int64_t n_ind, const T* ood, int64_t n_ood, double
     while (nbk < kMsdBuckets && (int64_t)nbk * 64 < n) nbk <<= 1;
   }
   if (n <= 65536) {  // small sets: smaller tiles, more workgroups (the two launches are latency-bound there)
-    msd_keys_split_kernel<T, 4><<<(unsigned)((n + 1023) / 1024), 256, 0, s>>>(ind, n_ind, ood, n_ood, flag, st, pgrid, keys[0], labs[0], bucket_of, equalise, nbk);
-    msd_scatter_kernel<8><<<(unsigned)((n + 2047) / 2048), 256, 0, s>>>(keys[0], labs[0], keys[1], labs[1], n, bucket_of, st);
+    msd_keys_split_kernel<T, 4><<<(unsigned)((n + 1023) / 1024), 256, 0, s>>>(ind, n_ind, ood, n_ood, L.flag, L.msd, pgrid, L.keys[0], L.labs[0], L.bucket_of, equalise, nbk);
+    msd_scatter_kernel<8><<<(unsigned)((n + 2047) / 2048), 256, 0, s>>>(L.keys[0], L.labs[0], L.keys[1], L.labs[1], n, L.bucket_of, L.msd);
   } else if (n <= 524288) {  // mid-sized sets: 16 keys per thread in the scatter (200 000 scores: 85 -> 73 us; 2 M: 230 -> 240)
-    msd_keys_split_kernel<T><<<L.nblocks, 256, 0, s>>>(ind, n_ind, ood, n_ood, flag, st, pgrid, keys[0], labs[0], bucket_of, equalise, nbk);
-    msd_scatter_kernel<16><<<(unsigned)((n + 4095) / 4096), 256, 0, s>>>(keys[0], labs[0], keys[1], labs[1], n, bucket_of, st);
+    msd_keys_split_kernel<T><<<L.nblocks, 256, 0, s>>>(ind, n_ind, ood, n_ood, L.flag, L.msd, pgrid, L.keys[0], L.labs[0], L.bucket_of, equalise, nbk);
+    msd_scatter_kernel<16><<<(unsigned)((n + 4095) / 4096), 256, 0, s>>>(L.keys[0], L.labs[0], L.keys[1], L.labs[1], n, L.bucket_of, L.msd);
   } else {
-    msd_keys_split_kernel<T><<<L.nblocks, 256, 0, s>>>(ind, n_ind, ood, n_ood, flag, st, pgrid, keys[0], labs[0], bucket_of, equalise, nbk);
-    msd_scatter_kernel<kScatItems><<<(unsigned)((n + kScatTile - 1) / kScatTile), 256, 0, s>>>(keys[0], labs[0], keys[1], labs[1], n, bucket_of, st);
+    msd_keys_split_kernel<T><<<L.nblocks, 256, 0, s>>>(ind, n_ind, ood, n_ood, L.flag, L.msd, pgrid, L.keys[0], L.labs[0], L.bucket_of, equalise, nbk);
+    msd_scatter_kernel<kScatItems><<<(unsigned)((n + kScatTile - 1) / kScatTile), 256, 0, s>>>(L.keys[0], L.labs[0], L.keys[1], L.labs[1], n, L.bucket_of, L.msd);
   }
   if (!tps_out) {  // the three scalars alone: bucket sort + curve terms + finalise in ONE launch (six launches, four without the sketch)
-    msd_sort_curve_kernel<<<(unsigned)(nbk / 4), 256, 0, s>>>(keys[1], labs[1], keys[0], labs[0], st,
-                                                              reinterpret_cast<FusedPart*>(w + L.parts2), (float)n_ind, (float)n_ood, out3);
+    msd_sort_curve_kernel<<<(unsigned)(nbk / 4), 256, 0, s>>>(L.keys[1], L.labs[1], L.keys[0], L.labs[0], L.msd,
+                                                              L.parts2, (float)n_ind, (float)n_ood, out3);
     return runia_check_launch();
   }
   // the curve API: every run's cumulative counts have to land in memory - bucket sort, tile summary, tile prefix, terms
-  msd_bucket_sort_kernel<<<kMsdBuckets / 4, 256, 0, s>>>(keys[1], labs[1], keys[0], labs[0], st);  // (four buckets per workgroup)
-  tile_summary_kernel<<<L.nblocks, 256, 0, s>>>(keys[1], labs[1], n, tile_sum, tile_end, tile_cnt);
-  tile_prefix_raw_kernel<<<L.nblocks, 256, 0, s>>>(keys[1], labs[1], n, tile_sum, tile_end, tile_cnt, tps, prev_end, tps_out,
+  msd_bucket_sort_kernel<<<kMsdBuckets / 4, 256, 0, s>>>(L.keys[1], L.labs[1], L.keys[0], L.labs[0], L.msd);  // (four buckets per workgroup)
+  tile_summary_kernel<<<L.nblocks, 256, 0, s>>>(L.keys[1], L.labs[1], n, L.tile_sum, L.tile_end, L.tile_cnt);
+  tile_prefix_raw_kernel<<<L.nblocks, 256, 0, s>>>(L.keys[1], L.labs[1], n, L.tile_sum, L.tile_end, L.tile_cnt, L.tps, L.prev_end, tps_out,
                                                    fps_out, n_points);
   curve_terms_finalize_kernel<<<(sgrid < kCurveBlocks ? sgrid : kCurveBlocks), 256, 0, s>>>(
-      keys[1], n, tps, prev_end, reinterpret_cast<MetricsAccum*>(w + L.parts), st, out3);
+      L.keys[1], n, L.tps, L.prev_end, L.parts, L.msd, out3);
   return runia_check_launch();
 }
 
@@ -1297,7 +1291,7 @@ int ood_metrics(const T* ind, int64_t n_ind, const T* ood, int64_t n_ood, double
 
 extern "C" size_t runia_ood_metrics_workspace_bytes(int64_t n_total) {
   if (n_total <= 0) return 0;
-  return make_layout(n_total).total;
+  return ws_bytes([&](WsWalk& w) { make_plan(w, n_total); });
 }
 
 extern "C" int runia_ood_metrics_f64(const double* ind_scores, int64_t n_ind, const double* ood_scores, int64_t n_ood,

@@ -237,10 +237,18 @@ __global__ void __launch_bounds__(kWalkThreads) nms_walk_kernel(const uint64_t* 
 
 }  // namespace
 
+struct CandPlan { int* cls; float* score; int* counts; int64_t blocks; };  // best class and score per anchor | count per workgroup
+static CandPlan cand_plan(WsWalk& w, int64_t A) {
+  CandPlan p;
+  p.blocks = (A + kCandThreads - 1) / kCandThreads;
+  p.cls = w.take<int>(A);
+  p.score = w.take<float>(A);
+  p.counts = w.take<int>(p.blocks);
+  return p;
+}
 extern "C" size_t runia_yolo_candidates_workspace_bytes(int64_t A) {
   if (A <= 0) return 0;
-  const int64_t blocks = (A + kCandThreads - 1) / kCandThreads;
-  return (size_t)(A * 4 + A * 4 + blocks * 4);
+  return ws_bytes([&](WsWalk& w) { cand_plan(w, A); });
 }
 
 extern "C" int runia_yolo_candidates_f32(const float* pred, int64_t A, int nc, int nm, float conf_thres,
@@ -250,11 +258,12 @@ extern "C" int runia_yolo_candidates_f32(const float* pred, int64_t A, int nc, i
   if (!pred || !cand_boxes || !cand_scores || !cand_anchor || !cand_cls || !count || A <= 0 || A > RUNIA_YOLO_MAX_ANCHORS || nc < 1 ||
       nm < 0 || n_classes < 0 || (n_classes > 0 && !classes))
     return RUNIA_E_INVALID;
-  if (!workspace || workspace_bytes < runia_yolo_candidates_workspace_bytes(A)) return RUNIA_E_WORKSPACE;
-  const int64_t blocks = (A + kCandThreads - 1) / kCandThreads;
-  int* cls_ws = reinterpret_cast<int*>(workspace);
-  float* score_ws = reinterpret_cast<float*>(cls_ws + A);
-  int* counts = reinterpret_cast<int*>(score_ws + A);
+  WsWalk w(workspace);
+  const CandPlan plan = cand_plan(w, A);
+  if (ws_refused(workspace, workspace_bytes, w.used(), 1)) return RUNIA_E_WORKSPACE;
+  const int64_t blocks = plan.blocks;
+  int *cls_ws = plan.cls, *counts = plan.counts;
+  float* score_ws = plan.score;
   hipStream_t s = as_stream(stream);
   hipLaunchKernelGGL(yolo_best_class_kernel, dim3((unsigned)blocks), dim3(kCandThreads), 0, s, pred, A, nc, conf_thres,
                      n_classes > 0 ? classes : nullptr, n_classes, cls_ws, score_ws, counts);
@@ -290,7 +299,7 @@ extern "C" int runia_nms_sorted_f32(const float* boxes, const int64_t* sorted_ke
                                     runia_stream_t stream) {
   if (m < 0 || m > RUNIA_NMS_MAX_BOXES || max_det < 0 || !count || (m > 0 && (!boxes || !sorted_keys || !keep)))
     return RUNIA_E_INVALID;
-  if (m > 0 && (!workspace || workspace_bytes < runia_nms_workspace_bytes(m))) return RUNIA_E_WORKSPACE;
+  if (m > 0 && ws_refused(workspace, workspace_bytes, runia_nms_workspace_bytes(m), 1)) return RUNIA_E_WORKSPACE;
   hipStream_t s = as_stream(stream);
   const int nb = (int)((m + RUNIA_WAVE - 1) / RUNIA_WAVE);
   uint64_t* mask = reinterpret_cast<uint64_t*>(workspace);

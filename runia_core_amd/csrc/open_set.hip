@@ -533,7 +533,7 @@ extern "C" int runia_osod_quantize(const void* x, int dtype, int64_t n, int peri
 extern "C" size_t runia_osod_sort_workspace_bytes(int64_t n, int nb) {
   if (n < 0 || n > 0x7fffffffll || nb < 1 || nb > kMaxBuckets) return 0;
   const int64_t e = (int64_t)nb * sort_chunks(n > 0 ? n : 1);
-  return (size_t)((e * 4 + 15) / 16 * 16);
+  return round_up((size_t)e * 4, 16);
 }
 
 extern "C" int runia_osod_bucket_sort(const int32_t* keys, int64_t n, int nb, int32_t* perm, int64_t* bucket_start,
@@ -541,7 +541,7 @@ extern "C" int runia_osod_bucket_sort(const int32_t* keys, int64_t n, int nb, in
   if (n < 0 || n > 0x7fffffffll || nb < 1 || nb > kMaxBuckets || !bucket_start || (n > 0 && (!keys || !perm)))
     return RUNIA_E_INVALID;
   const size_t need = runia_osod_sort_workspace_bytes(n, nb);
-  if (!workspace || workspace_bytes < need) return RUNIA_E_WORKSPACE;
+  if (ws_refused(workspace, workspace_bytes, need, 1)) return RUNIA_E_WORKSPACE;
   const hipStream_t st = as_stream(stream);
   const int nch = (int)sort_chunks(n > 0 ? n : 1);
   int32_t* counts = reinterpret_cast<int32_t*>(workspace);
@@ -565,7 +565,7 @@ extern "C" int runia_osod_overlaps(const double* boxes, const int32_t* det_img, 
 
 extern "C" size_t runia_osod_match_workspace_bytes(int n_methods, int64_t n_slots) {
   if (n_methods < 1 || n_slots < 0) return 0;
-  return (size_t)(((int64_t)n_methods * (n_slots > 0 ? n_slots : 1) * 4 + 15) / 16 * 16);
+  return round_up((size_t)((int64_t)n_methods * (n_slots > 0 ? n_slots : 1)) * 4, 16);
 }
 
 extern "C" int runia_osod_match(const int32_t* perm, int64_t n, int n_methods, int n_classes, const int32_t* label,
@@ -581,7 +581,7 @@ extern "C" int runia_osod_match(const int32_t* perm, int64_t n, int n_methods, i
   if (!perm || !label || !det_img || !ov || !jpos || !group_of_class || !gstart || !cbase || !key || !flags) return RUNIA_E_INVALID;
   if (!open_set && (!mscore || !thr)) return RUNIA_E_INVALID;
   const size_t need = runia_osod_match_workspace_bytes(n_methods, n_slots);
-  if (!workspace || workspace_bytes < need) return RUNIA_E_WORKSPACE;
+  if (ws_refused(workspace, workspace_bytes, need, 1)) return RUNIA_E_WORKSPACE;
   const hipStream_t st = as_stream(stream);
   int32_t* minpos = reinterpret_cast<int32_t*>(workspace);
   if (hipMemsetAsync(minpos, 0x7f, need, st) != hipSuccess) return RUNIA_E_LAUNCH;
@@ -626,7 +626,7 @@ extern "C" int runia_osod_curves(const int32_t* part, const int64_t* bucket_star
   if (!bucket_start || !npos || !summary || (n > 0 && (!part || !flags))) return RUNIA_E_INVALID;
   if (rec && (!prec || !tpfp || !fpos)) return RUNIA_E_INVALID;
   const size_t need = runia_osod_curves_workspace_bytes(rows);
-  if (!workspace || workspace_bytes < need) return RUNIA_E_WORKSPACE;
+  if (ws_refused(workspace, workspace_bytes, need, 1)) return RUNIA_E_WORKSPACE;
   double* ws = reinterpret_cast<double*>(workspace);
   const int segs = n_methods * (n_classes + 1);
   const hipStream_t st = as_stream(stream);

@@ -386,7 +386,7 @@ extern "C" int runia_pacmap_pairs(const float* x, int64_t R, const float* bank, 
       (R > 0 && n_mn > 0 && !pair_mn) || (R > 0 && n_fp > 0 && !pair_fp))
     return RUNIA_E_INVALID;
   if (R == 0) return RUNIA_OK;
-  if (!transform && (!workspace || workspace_bytes < runia_pacmap_pairs_workspace_bytes(R))) return RUNIA_E_WORKSPACE;
+  if (!transform && ws_refused(workspace, workspace_bytes, runia_pacmap_pairs_workspace_bytes(R), 1)) return RUNIA_E_WORKSPACE;
   hipStream_t s = as_stream(stream);
   float* sig = reinterpret_cast<float*>(workspace);
   if (!transform)

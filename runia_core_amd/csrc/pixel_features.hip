@@ -362,7 +362,7 @@ extern "C" int runia_pixfeat_gather_rows(const void* features, int dtype, int64_
   if (P == 0) return hipMemsetAsync(n_out, 0, sizeof(int64_t), s) == hipSuccess ? RUNIA_OK : RUNIA_E_LAUNCH;
   if (!features || !labels) return RUNIA_E_INVALID;
   const size_t need = runia_pixfeat_gather_workspace_bytes(P);
-  if (!workspace || workspace_bytes < need || reinterpret_cast<uintptr_t>(workspace) % 8) return RUNIA_E_WORKSPACE;
+  if (ws_refused(workspace, workspace_bytes, need, 8)) return RUNIA_E_WORKSPACE;
   GatherArgs a;
   a.v = make_view(features, G, C, H, W, sn, sc, sh, sw);
   a.lab_code = label_dtype;

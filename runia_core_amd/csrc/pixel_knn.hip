@@ -320,7 +320,14 @@ __global__ __launch_bounds__(256) void kcenter_tail_kernel(int* __restrict__ pic
   }
 }
 
-size_t kc_min_dist_bytes(int64_t N) { return ((size_t)N * sizeof(float) + 15) & ~(size_t)15; }
+struct KcPlan { float* min_dist; KcBest* best[2]; };  // [N] (16-byte slot) | two sets of per-workgroup records
+KcPlan kc_plan(WsWalk& w, int64_t N) {
+  KcPlan p;
+  p.min_dist = w.take<float>(N, 16);
+  p.best[0] = w.take<KcBest>(kKcBlocks);
+  p.best[1] = w.take<KcBest>(kKcBlocks);
+  return p;
+}
 
 }  // namespace
 
@@ -365,7 +372,7 @@ extern "C" int runia_pixknn_score(const void* features, int dtype, int64_t G, in
 
 extern "C" size_t runia_kcenter_workspace_bytes(int64_t N, int64_t D) {
   if (N < 1 || N > kLim || D < 1 || D > kKcMaxD) return 0;
-  return kc_min_dist_bytes(N) + 2 * kKcBlocks * sizeof(KcBest);
+  return ws_bytes([&](WsWalk& w) { kc_plan(w, N); });
 }
 
 extern "C" int runia_kcenter_greedy_f32(const float* rows, int64_t N, int64_t D, int64_t first, int64_t n_pick,
@@ -374,18 +381,17 @@ extern "C" int runia_kcenter_greedy_f32(const float* rows, int64_t N, int64_t D,
   if (N < 1 || N > kLim || D < 1 || D > kKcMaxD || first < 0 || first >= N || n_pick < 1 || n_pick > kLim || !rows || !picked ||
       !radius || !n_picked)
     return RUNIA_E_INVALID;
-  if (!workspace || workspace_bytes < runia_kcenter_workspace_bytes(N, D) || reinterpret_cast<uintptr_t>(workspace) % 16)
-    return RUNIA_E_WORKSPACE;
+  WsWalk w(workspace);
+  const KcPlan plan = kc_plan(w, N);
+  if (ws_refused(workspace, workspace_bytes, w.used(), 16)) return RUNIA_E_WORKSPACE;
   KcArgs a;
   a.rows = rows;
   a.N = N;
   a.D = (int)D;
   a.first = (int)first;
   a.vec = (D % 4 == 0 && reinterpret_cast<uintptr_t>(rows) % 16 == 0) ? 1 : 0;
-  a.min_dist = static_cast<float*>(workspace);
-  KcBest* best[2];
-  best[0] = reinterpret_cast<KcBest*>(static_cast<char*>(workspace) + kc_min_dist_bytes(N));
-  best[1] = best[0] + kKcBlocks;
+  a.min_dist = plan.min_dist;
+  KcBest* const* best = plan.best;
   a.picked = picked;
   a.radius = radius;
   a.n_picked = n_picked;

@@ -427,7 +427,7 @@ extern "C" int runia_pixel_uncertainty_maps(const void* const* table, int single
   if (G * H * W > (lim << 8) || n_mc > (1 << 20)) return RUNIA_E_INVALID;
   if (!table || (!pred_h && !mi && !msp && !energy && !max_logit && !label && !mean_probs)) return RUNIA_E_INVALID;
   const size_t need = runia_pixel_maps_workspace_bytes(G, C, H, W, n_mc, max_logit != nullptr);
-  if (need && (!workspace || workspace_bytes < need || reinterpret_cast<uintptr_t>(workspace) % 4)) return RUNIA_E_WORKSPACE;
+  if (need && ws_refused(workspace, workspace_bytes, need, 4)) return RUNIA_E_WORKSPACE;
   PixArgs a;
   a.ptrs = table;
   a.sn = sn; a.sc = sc; a.sh = sh; a.sw = sw;

@@ -432,58 +432,41 @@ __global__ __launch_bounds__(256) void chain_final_kernel(int T, int n, int mean
 }
 
 // ---- workspace layout --------------------------------------------------------------------------------------------------
-static size_t al(size_t b) { return (b + 255) & ~(size_t)255; }
-
-struct Layout {
-  size_t series, unc, rsum, diag, sub, v0, v1, p0, p1, row_tab, row_rsum, total;
+struct Plan {
+  float *rsum, *diag, *sub, *series, *unc, *row_rsum;
+  double *v[2], *p[2];
+  MapDesc* row_tab;
   int64_t nb;
 };
 
-static Layout layout(int64_t L, int64_t n_gen, int64_t in, int64_t n, int64_t chain_rows, int n_alpha) {
-  Layout o{};
-  const int64_t T = in > 0 ? in + n_gen : 0;
-  const int64_t N = n_gen > n ? n_gen : n;
-  o.nb = T > 0 ? (T + kChainRows - 1) / kChainRows : 0;
-  size_t at = 0;  // the rollout regions first: their offsets depend on (L, T) only
-  o.rsum = at;   at += al((size_t)(L * T) * 4);
-  o.diag = at;   at += al((size_t)(L * T) * 4);
-  o.sub = at;    at += al((size_t)(L * T) * 4);
-  o.series = at; at += al((size_t)(L * N) * 4);
-  o.unc = at;    at += al((size_t)(L * n_alpha) * 4);
-  const int64_t k = T > 0 ? chain_rows : 0;
-  o.v0 = at;     at += al((size_t)(k * T) * 8);
-  o.v1 = at;     at += al((size_t)(k * T) * 8);
-  o.p0 = at;     at += al((size_t)(k * o.nb * T) * 8);
-  o.p1 = at;     at += al((size_t)(k * o.nb * T) * 8);
-  o.total = at;
-  return o;
-}
-
-// batched calls: the row-pass regions hold [B][L][T] (T = input_length + n_gen), series [B][L][n_gen], unc [B][L][n_alpha];
+// 256-byte slots on a 16-byte aligned base.  One generation: B = 1 and a series of max(n_gen, n) floats per layer.
+// Batched calls: the row-pass regions hold [B][L][T] (T = input_length + n_gen), series [B][L][n_gen], unc [B][L][n_alpha];
 // the chain regions (and the chained row's own map table and rsum) are sized for the largest row and reused row after row
-static Layout layout_batch(int64_t B, int64_t L, int64_t n_gen, int64_t in, int64_t chain_rows, int n_alpha) {
-  Layout o{};
+static Plan plan(WsWalk& w, int64_t B, int64_t L, int64_t n_gen, int64_t series_n, int64_t in, int64_t chain_rows, int n_alpha,
+                 bool batched) {
+  Plan o{};
   const int64_t T = in > 0 ? in + n_gen : 0;
   o.nb = T > 0 ? (T + kChainRows - 1) / kChainRows : 0;
-  size_t at = 0;
-  o.rsum = at;   at += al((size_t)(B * L * T) * 4);
-  o.diag = at;   at += al((size_t)(B * L * T) * 4);
-  o.sub = at;    at += al((size_t)(B * L * T) * 4);
-  o.series = at; at += al((size_t)(B * L * n_gen) * 4);
-  o.unc = at;    at += al((size_t)(B * L * n_alpha) * 4);
+  // the rollout regions first: their offsets depend on (B, L, T) only
+  o.rsum = w.take<float>(B * L * T, 256);
+  o.diag = w.take<float>(B * L * T, 256);
+  o.sub = w.take<float>(B * L * T, 256);
+  o.series = w.take<float>(B * L * series_n, 256);
+  o.unc = w.take<float>(B * L * n_alpha, 256);
   const int64_t k = T > 0 ? chain_rows : 0;
-  o.v0 = at;     at += al((size_t)(k * T) * 8);
-  o.v1 = at;     at += al((size_t)(k * T) * 8);
-  o.p0 = at;     at += al((size_t)(k * o.nb * T) * 8);
-  o.p1 = at;     at += al((size_t)(k * o.nb * T) * 8);
-  o.row_tab = at; at += al((size_t)(k > 0 ? n_gen * L : 0) * sizeof(MapDesc));
-  o.row_rsum = at; at += al((size_t)(k > 0 ? L * T : 0) * 4);
-  o.total = at;
+  o.v[0] = w.take<double>(k * T, 256);
+  o.v[1] = w.take<double>(k * T, 256);
+  o.p[0] = w.take<double>(k * o.nb * T, 256);
+  o.p[1] = w.take<double>(k * o.nb * T, 256);
+  o.row_tab = w.take<MapDesc>(batched && k > 0 ? n_gen * L : 0, 256);
+  o.row_rsum = w.take<float>(batched && k > 0 ? L * T : 0, 256);
   return o;
 }
-
-static bool bad_ws(const void* ws, size_t bytes, size_t need) {
-  return !ws || bytes < need || (((uintptr_t)ws) & 15) != 0;
+static Plan plan_one(WsWalk& w, int64_t L, int64_t n_gen, int64_t in, int64_t n, int64_t chain_rows, int n_alpha) {
+  return plan(w, 1, L, n_gen, n_gen > n ? n_gen : n, in, chain_rows, n_alpha, false);
+}
+static Plan plan_batch(WsWalk& w, int64_t B, int64_t L, int64_t n_gen, int64_t in, int64_t chain_rows, int n_alpha) {
+  return plan(w, B, L, n_gen, n_gen, in, chain_rows, n_alpha, true);
 }
 
 constexpr int64_t kMaxDim = 1 << 20;
@@ -496,7 +479,7 @@ static bool dims_ok(int64_t n_gen, int64_t L, int64_t H) {
 extern "C" size_t runia_rauq_workspace_bytes(int64_t L, int64_t n_gen, int64_t input_length, int64_t n, int64_t chain_rows,
                                              int n_alpha) {
   if (L < 1 || n_gen < 1 || input_length < 0 || n < 0 || chain_rows < 0 || n_alpha < 0) return 0;
-  return layout(L, n_gen, input_length, n, chain_rows, n_alpha).total;
+  return ws_bytes([&](WsWalk& w) { plan_one(w, L, n_gen, input_length, n, chain_rows, n_alpha); });
 }
 
 extern "C" int runia_rauq_gather(const void* table, int dtype, int64_t n_gen, int64_t L, int64_t H, int token_agg, float* w,
@@ -521,12 +504,12 @@ extern "C" int runia_rauq_score(const float* att, int64_t L, int64_t H, int64_t 
       L < 1 || L > 4096 || H < 1 || H > 4096 || (head_mode == 2 && (L != 1 || H != 1)))
     return RUNIA_E_INVALID;
   // the layout's series region holds L * max(n_gen, n) floats: N of them per layer
-  const Layout o = layout(L, N, 0, 0, 0, n_alpha);
-  if (bad_ws(workspace, workspace_bytes, o.total)) return RUNIA_E_WORKSPACE;
-  char* ws = reinterpret_cast<char*>(workspace);
+  WsWalk w(workspace);
+  const Plan o = plan_one(w, L, N, 0, 0, 0, n_alpha);
+  if (ws_refused(workspace, workspace_bytes, w.used(), 16)) return RUNIA_E_WORKSPACE;
   score_kernel<<<1, 256, 0, as_stream(stream)>>>(att, (int)L, (int)H, (int)N, head_mode, log_probs, alphas, n_alpha, scores,
-                                                 head_mode == 0 ? heads : nullptr, reinterpret_cast<float*>(ws + o.series),
-                                                 reinterpret_cast<float*>(ws + o.unc));
+                                                 head_mode == 0 ? heads : nullptr, o.series,
+                                                 o.unc);
   return runia_check_launch();
 }
 
@@ -536,16 +519,16 @@ extern "C" int runia_rauq_rollout_rows(const void* table, int dtype, int64_t n_g
   if (!table || !upper_flag || !elem_dtype_ok(dtype) || !dims_ok(n_gen, L, H) || n_gen < 2 || input_length < 1 ||
       input_length + n_gen > kMaxDim)
     return RUNIA_E_INVALID;
-  const Layout o = layout(L, n_gen, input_length, 0, 0, 1);
-  if (bad_ws(workspace, workspace_bytes, o.total)) return RUNIA_E_WORKSPACE;
-  char* ws = reinterpret_cast<char*>(workspace);
+  WsWalk w(workspace);
+  const Plan o = plan_one(w, L, n_gen, input_length, 0, 0, 1);
+  if (ws_refused(workspace, workspace_bytes, w.used(), 16)) return RUNIA_E_WORKSPACE;
   const int T = (int)(input_length + n_gen);
   if (hipMemsetAsync(upper_flag, 0, sizeof(int), as_stream(stream)) != hipSuccess) return RUNIA_E_LAUNCH;
   const MapDesc* tab = reinterpret_cast<const MapDesc*>(table);
   return dispatch_elem(dtype, [&](auto et) {
     rows_kernel<decltype(et)><<<dim3((unsigned)T, (unsigned)L), 256, 0, as_stream(stream)>>>(
-        tab, (int)L, (int)H, (int)input_length, T, reinterpret_cast<float*>(ws + o.rsum),
-        reinterpret_cast<float*>(ws + o.diag), reinterpret_cast<float*>(ws + o.sub), upper_flag);
+        tab, (int)L, (int)H, (int)input_length, T, o.rsum,
+        o.diag, o.sub, upper_flag);
     return runia_check_launch();
   });
 }
@@ -560,21 +543,20 @@ extern "C" int runia_rauq_rollout_att(const void* table, int dtype, int64_t n_ge
   const int64_t T = input_length + n_gen;
   if ((token_agg == 0 && n > T - 1) || (token_agg == 1 && n > T)) return RUNIA_E_INVALID;
   const int64_t k = route == 0 ? 0 : (token_agg ? 1 : n);
-  const Layout o = layout(L, n_gen, input_length, n, k, 1);
-  if (bad_ws(workspace, workspace_bytes, o.total)) return RUNIA_E_WORKSPACE;
+  WsWalk w(workspace);
+  const Plan o = plan_one(w, L, n_gen, input_length, n, k, 1);
+  if (ws_refused(workspace, workspace_bytes, w.used(), 16)) return RUNIA_E_WORKSPACE;
   if (k > 65535) return RUNIA_E_INVALID;
-  char* ws = reinterpret_cast<char*>(workspace);
-  const float* rsum = reinterpret_cast<const float*>(ws + o.rsum);
+  const float* rsum = o.rsum;
   const unsigned out_grid = (unsigned)((n + 255) / 256);
   hipStream_t s = as_stream(stream);
   if (route == 0) {
-    one_pass_kernel<<<out_grid, 256, 0, s>>>(reinterpret_cast<const float*>(ws + o.diag),
-                                             reinterpret_cast<const float*>(ws + o.sub), (int)L, (int)T, (int)n, att);
+    one_pass_kernel<<<out_grid, 256, 0, s>>>(o.diag,
+                                             o.sub, (int)L, (int)T, (int)n, att);
     return runia_check_launch();
   }
   const MapDesc* tab = reinterpret_cast<const MapDesc*>(table);
-  double* v[2] = {reinterpret_cast<double*>(ws + o.v0), reinterpret_cast<double*>(ws + o.v1)};
-  double* p[2] = {reinterpret_cast<double*>(ws + o.p0), reinterpret_cast<double*>(ws + o.p1)};
+  double* const *v = o.v, *const *p = o.p;
   const dim3 grid((unsigned)((T + kChainCols - 1) / kChainCols), (unsigned)o.nb, (unsigned)k);
   int cur = 0;
   int rc = RUNIA_OK;
@@ -601,7 +583,7 @@ constexpr int64_t kMaxBatch = 65535;  // grid y / z
 extern "C" size_t runia_rauqb_workspace_bytes(int64_t B, int64_t L, int64_t n_gen, int64_t input_length, int64_t chain_rows,
                                               int n_alpha) {
   if (B < 1 || B > kMaxBatch || L < 1 || n_gen < 1 || input_length < 0 || chain_rows < 0 || n_alpha < 0) return 0;
-  return layout_batch(B, L, n_gen, input_length, chain_rows, n_alpha).total;
+  return ws_bytes([&](WsWalk& w) { plan_batch(w, B, L, n_gen, input_length, chain_rows, n_alpha); });
 }
 
 extern "C" int runia_rauqb_gather(const void* table, const void* rows, int dtype, int64_t B, int64_t n_gen, int64_t L,
@@ -631,12 +613,12 @@ extern "C" int runia_rauqb_score(const float* att, const void* rows, int64_t B, 
       head_mode < 0 || head_mode > 2 || (token_agg != 0 && token_agg != 1) || L < 1 || L > 4096 || H < 1 || H > 4096 ||
       (head_mode == 2 && (L != 1 || H != 1)) || lp_stride < 1)
     return RUNIA_E_INVALID;
-  const Layout o = layout_batch(B, L, N, 0, 0, n_alpha);
-  if (bad_ws(workspace, workspace_bytes, o.total)) return RUNIA_E_WORKSPACE;
-  char* ws = reinterpret_cast<char*>(workspace);
+  WsWalk w(workspace);
+  const Plan o = plan_batch(w, B, L, N, 0, 0, n_alpha);
+  if (ws_refused(workspace, workspace_bytes, w.used(), 16)) return RUNIA_E_WORKSPACE;
   score_batch_kernel<<<(unsigned)B, 256, 0, as_stream(stream)>>>(
       att, reinterpret_cast<const RowInfo*>(rows), N, (int)L, (int)H, head_mode, token_agg, log_probs, lp_stride, alphas,
-      n_alpha, scores, reinterpret_cast<float*>(ws + o.series), reinterpret_cast<float*>(ws + o.unc));
+      n_alpha, scores, o.series, o.unc);
   return runia_check_launch();
 }
 
@@ -646,16 +628,16 @@ extern "C" int runia_rauqb_rollout_rows(const void* table, const void* rows, int
   if (!table || !rows || !upper_flags || !elem_dtype_ok(dtype) || B < 1 || B > kMaxBatch || !dims_ok(n_gen, L, H) ||
       n_gen < 2 || input_length < 1 || input_length + n_gen > kMaxDim)
     return RUNIA_E_INVALID;
-  const Layout o = layout_batch(B, L, n_gen, input_length, 0, 1);
-  if (bad_ws(workspace, workspace_bytes, o.total)) return RUNIA_E_WORKSPACE;
-  char* ws = reinterpret_cast<char*>(workspace);
+  WsWalk w(workspace);
+  const Plan o = plan_batch(w, B, L, n_gen, input_length, 0, 1);
+  if (ws_refused(workspace, workspace_bytes, w.used(), 16)) return RUNIA_E_WORKSPACE;
   const int T = (int)(input_length + n_gen);
   if (hipMemsetAsync(upper_flags, 0, sizeof(int) * (size_t)B, as_stream(stream)) != hipSuccess) return RUNIA_E_LAUNCH;
   const BMapDesc* tab = reinterpret_cast<const BMapDesc*>(table);
   return dispatch_elem(dtype, [&](auto et) {
     rows_batch_kernel<decltype(et)><<<dim3((unsigned)T, (unsigned)L, (unsigned)B), 256, 0, as_stream(stream)>>>(
         tab, reinterpret_cast<const RowInfo*>(rows), (int)L, (int)H, (int)input_length, T,
-        reinterpret_cast<float*>(ws + o.rsum), reinterpret_cast<float*>(ws + o.diag), reinterpret_cast<float*>(ws + o.sub),
+        o.rsum, o.diag, o.sub,
         upper_flags);
     return runia_check_launch();
   });
@@ -677,30 +659,29 @@ extern "C" int runia_rauqb_rollout_att(const void* table, const void* rows, cons
     if (n >= 2 && (token_agg || host_upper[b])) k = std::max(k, token_agg ? (int64_t)1 : n);
   }
   if (k > 65535) return RUNIA_E_INVALID;
-  const Layout o = layout_batch(B, L, n_gen, input_length, k, 1);
-  if (bad_ws(workspace, workspace_bytes, o.total)) return RUNIA_E_WORKSPACE;
-  char* ws = reinterpret_cast<char*>(workspace);
+  WsWalk w(workspace);
+  const Plan o = plan_batch(w, B, L, n_gen, input_length, k, 1);
+  if (ws_refused(workspace, workspace_bytes, w.used(), 16)) return RUNIA_E_WORKSPACE;
   hipStream_t s = as_stream(stream);
   const int64_t T = input_length + n_gen;
-  const float* rsum = reinterpret_cast<const float*>(ws + o.rsum);
+  const float* rsum = o.rsum;
   if (!token_agg) {  // route 0 for every row with a clear flag, in one launch
     one_pass_batch_kernel<<<dim3((unsigned)((n_gen + 255) / 256), (unsigned)B), 256, 0, s>>>(
-        reinterpret_cast<const float*>(ws + o.diag), reinterpret_cast<const float*>(ws + o.sub),
+        o.diag, o.sub,
         reinterpret_cast<const RowInfo*>(rows), upper_flags, (int)L, (int)input_length, (int)T, n_gen, att);
     const int rc = runia_check_launch();
     if (rc != RUNIA_OK) return rc;
   }
   const BMapDesc* tab = reinterpret_cast<const BMapDesc*>(table);
-  double* v[2] = {reinterpret_cast<double*>(ws + o.v0), reinterpret_cast<double*>(ws + o.v1)};
-  double* p[2] = {reinterpret_cast<double*>(ws + o.p0), reinterpret_cast<double*>(ws + o.p1)};
+  double* const *v = o.v, *const *p = o.p;
   for (int64_t b = 0; b < B; ++b) {  // the chains, row after row, in the one workspace
     const int64_t pad = host_rows[2 * b], n = host_rows[2 * b + 1];
     if (n < 2 || !(token_agg || host_upper[b])) continue;
     const int route = host_upper[b] ? 2 : 1;
     const int64_t in_b = input_length - pad, T_b = in_b + n, nb = (T_b + kChainRows - 1) / kChainRows;
     const dim3 grid((unsigned)((T_b + kChainCols - 1) / kChainCols), (unsigned)nb, (unsigned)(token_agg ? 1 : n));
-    MapDesc* row_tab = reinterpret_cast<MapDesc*>(ws + o.row_tab);
-    float* row_rsum = reinterpret_cast<float*>(ws + o.row_rsum);
+    MapDesc* row_tab = o.row_tab;
+    float* row_rsum = o.row_rsum;
     const int64_t prep = std::max(n * L, L * T_b);
     int rc = dispatch_elem(dtype, [&](auto et) {
       chain_row_kernel<decltype(et)><<<(unsigned)((prep + 255) / 256), 256, 0, s>>>(

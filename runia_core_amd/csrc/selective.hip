@@ -395,7 +395,7 @@ __global__ __launch_bounds__(kSelThreads) void sel_finish_kernel(const double* _
 }
 
 int64_t sel_tiles(int64_t n) { return (n + kSelTile - 1) / kSelTile; }
-constexpr size_t kBestBytes = 256;  // runia_sel_query's 64 run ends, at the front of the workspace
+constexpr size_t kBestBytes = 256;  // slot of runia_sel_query's 64 run ends
 
 // ---- queries --------------------------------------------------------------------------------------------------------------
 constexpr int kQItems = 8;
@@ -502,10 +502,27 @@ extern "C" int runia_sel_keys_f64(const double* conf, int64_t n, int64_t* keys, 
 
 extern "C" int64_t runia_sel_key_of_f64_host(double conf) { return sel_key(conf); }
 
+struct SelPlan {
+  int* best;  // runia_sel_query's 64 run ends, at the front of the workspace
+  double* gl;
+  TileSum* sums;
+  TileCarry* carry;
+  double* partial;
+};
+static SelPlan sel_plan(WsWalk& w, int64_t n) {
+  const size_t t = (size_t)sel_tiles(n);
+  SelPlan p;
+  p.best = w.take<int>(64, kBestBytes);
+  p.gl = w.take<double>(n);
+  p.sums = w.take<TileSum>(t);
+  p.carry = w.take<TileCarry>(t);
+  p.partial = w.take<double>(2 * t);
+  return p;
+}
+
 extern "C" size_t runia_sel_workspace_bytes(int64_t n) {
   if (n < 1 || n >= (1ll << 31)) return 0;
-  const size_t t = (size_t)sel_tiles(n);
-  return kBestBytes + (size_t)n * sizeof(double) + t * (sizeof(TileSum) + sizeof(TileCarry) + 2 * sizeof(double));
+  return ws_bytes([&](WsWalk& w) { sel_plan(w, n); });
 }
 
 extern "C" int runia_sel_curve(const int64_t* sorted_keys, const int32_t* sorted_rows, const void* loss, int loss_f64, int64_t n,
@@ -515,13 +532,13 @@ extern "C" int runia_sel_curve(const int64_t* sorted_keys, const int32_t* sorted
   if (!sorted_keys || !sorted_rows || !loss || !record) return RUNIA_E_INVALID;
   if ((run_end != nullptr) != (cum_loss != nullptr) || (run_end != nullptr) != (cum_conf != nullptr)) return RUNIA_E_INVALID;
   if (run_end && !n_points) return RUNIA_E_INVALID;
-  if (!workspace || workspace_bytes < runia_sel_workspace_bytes(n) || (((uintptr_t)workspace) & 7) != 0) return RUNIA_E_WORKSPACE;
+  WsWalk w(workspace);
+  const SelPlan plan = sel_plan(w, n);
+  if (ws_refused(workspace, workspace_bytes, w.used(), 8)) return RUNIA_E_WORKSPACE;
   const int64_t ntiles = sel_tiles(n);
-  char* w = reinterpret_cast<char*>(workspace) + kBestBytes;
-  double* gl = reinterpret_cast<double*>(w);
-  TileSum* sums = reinterpret_cast<TileSum*>(gl + n);
-  TileCarry* carry = reinterpret_cast<TileCarry*>(sums + ntiles);
-  double* partial = reinterpret_cast<double*>(carry + ntiles);
+  double *gl = plan.gl, *partial = plan.partial;
+  TileSum* sums = plan.sums;
+  TileCarry* carry = plan.carry;
   hipStream_t s = as_stream(stream);
   sel_summary_kernel<<<(unsigned)ntiles, kSelThreads, 0, s>>>(sorted_keys, sorted_rows, loss, loss_f64, n, gl, sums);
   sel_tiles_kernel<<<1, kSelThreads, 0, s>>>(sums, carry, ntiles, n, record, n_points);
@@ -540,7 +557,7 @@ extern "C" int runia_sel_query(const int32_t* run_end, const double* cum_loss, c
   if (!run_end || !cum_loss || !cum_conf || !n_points) return RUNIA_E_INVALID;
   if ((n_targets && (!targets || !risk_at || !coverage_at)) || (n_risks && (!risks || !coverage_at_risk)) || (n_bins && !bins))
     return RUNIA_E_INVALID;
-  if (!workspace || workspace_bytes < kBestBytes || (((uintptr_t)workspace) & 7) != 0) return RUNIA_E_WORKSPACE;
+  if (ws_refused(workspace, workspace_bytes, kBestBytes, 8)) return RUNIA_E_WORKSPACE;
   hipStream_t s = as_stream(stream);
   int* best = reinterpret_cast<int*>(workspace);
   if (n_risks) {

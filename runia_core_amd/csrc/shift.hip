@@ -522,15 +522,17 @@ __global__ __launch_bounds__(256) void shift_pairwise_kernel(Rows r, int64_t M, 
 }
 
 // ---- host side ----------------------------------------------------------------------------------------------------------------
-int64_t round_up(int64_t v, int64_t q) { return (v + q - 1) / q * q; }
-
 struct Plan {
   int64_t N, Npad, row_words, P, nit, seg_len, nit_batch;
   int nseg, nsegm, NT, cstride, chunk_cols;
-  size_t off_mean, off_norms, off_colpart, off_su, off_diag, off_bits, off_part_t, off_part_u, off_table, total;
+  // the regions of the workspace (256-byte slots)
+  float *mean, *norms, *part_t, *part_u;
+  double *colpart, *su, *diag;
+  uint32_t* bits;
+  uint4* table;
 };
 
-bool make_plan(int64_t n, int64_t m, int64_t d, int64_t n_perm, Plan& pl) {
+bool make_plan(WsWalk& w, int64_t n, int64_t m, int64_t d, int64_t n_perm, Plan& pl) {
   if (n < 1 || m < 1 || d < 1 || d >= (1ll << 31) || n_perm < 1 || n_perm >= (1ll << 31)) return false;
   if (n + m > runia_shift::kMaxRows) return false;
   pl.N = n + m;
@@ -548,21 +550,18 @@ bool make_plan(int64_t n, int64_t m, int64_t d, int64_t n_perm, Plan& pl) {
   while (pl.NT * 128 < pl.chunk_cols + 1) pl.NT *= 2;
   pl.cstride = pl.NT * 128;
   pl.nit_batch = std::max<int64_t>(1, std::min<int64_t>(pl.nit, (int64_t)(kPartBudget / 8) / ((int64_t)pl.nseg * pl.cstride)));
-  size_t o = 0;
-  auto take = [&](size_t bytes) { const size_t at = o; o += (bytes + 255) / 256 * 256; return at; };
-  pl.off_mean = take((size_t)d * 4);
-  pl.off_norms = take((size_t)pl.Npad * 4);
-  pl.off_colpart = take((size_t)pl.nsegm * (size_t)d * 8);
-  pl.off_su = take(16);
-  pl.off_diag = take((size_t)(pl.P + 1) * 8);
-  pl.off_bits = take((size_t)pl.P * (size_t)pl.row_words * 4);
-  const size_t part = (size_t)pl.nit_batch * (size_t)pl.nseg * (size_t)pl.cstride * 4;
-  pl.off_part_t = take(part);
-  pl.off_part_u = take(part);
+  pl.mean = w.take<float>(d, 256);
+  pl.norms = w.take<float>(pl.Npad, 256);
+  pl.colpart = w.take<double>((size_t)pl.nsegm * (size_t)d, 256);
+  pl.su = w.take<double>(2, 256);
+  pl.diag = w.take<double>(pl.P + 1, 256);
+  pl.bits = w.take<uint32_t>((size_t)pl.P * (size_t)pl.row_words, 256);
+  const size_t part = (size_t)pl.nit_batch * (size_t)pl.nseg * (size_t)pl.cstride;
+  pl.part_t = w.take<float>(part, 256);
+  pl.part_u = w.take<float>(part, 256);
 #if SHIFT_MEMBER_TABLE
-  pl.off_table = take((size_t)pl.row_words * (size_t)pl.cstride * 64);
+  pl.table = w.take<uint4>((size_t)pl.row_words * (size_t)pl.cstride * 4, 256);
 #endif
-  pl.total = o;
   return true;
 }
 
@@ -580,8 +579,9 @@ void launch_fused(const FusedArgs& fa, dim3 grid, hipStream_t s) {
 }  // namespace
 
 extern "C" size_t runia_shift_workspace_bytes(int64_t n, int64_t m, int64_t d, int64_t n_perm) {
+  WsWalk w;
   Plan pl;
-  return make_plan(n, m, d, n_perm, pl) ? pl.total : 0;
+  return make_plan(w, n, m, d, n_perm, pl) ? w.used() : 0;
 }
 
 extern "C" int runia_shift_perm_bits(uint64_t seed, int64_t n, int64_t N, int64_t first_perm, int64_t n_rows, uint32_t* bits,
@@ -652,8 +652,9 @@ extern "C" int runia_shift_mmd(const void* x, int64_t n, int64_t x_stride, const
                                int dtype, int kind, const double* bandwidths, int n_bandwidths, int estimator, uint64_t seed,
                                int64_t n_perm, double* t, double* u, double* S, double* stats, int64_t* count, double* p_value,
                                void* workspace, size_t workspace_bytes, runia_stream_t stream) {
+  WsWalk w(workspace);
   Plan pl;
-  if (!make_plan(n, m, d, n_perm, pl)) return RUNIA_E_INVALID;
+  if (!make_plan(w, n, m, d, n_perm, pl)) return RUNIA_E_INVALID;
   if (!elem_dtype_ok(dtype) || kind < kRbf || kind > kLinear || (estimator != kBiased && estimator != kUnbiased)) return RUNIA_E_INVALID;
   if (estimator == kUnbiased && (n < 2 || m < 2)) return RUNIA_E_INVALID;
   if (x_stride < d || y_stride < d) return RUNIA_E_INVALID;
@@ -663,17 +664,11 @@ extern "C" int runia_shift_mmd(const void* x, int64_t n, int64_t x_stride, const
       if (bandwidths[b] <= 0.0) return RUNIA_E_INVALID;  // (a NaN bandwidth passes: non-finite rows give NaN results)
   }
   if (!x || !y || !t || !u || !S || !stats || !count || !p_value) return RUNIA_E_INVALID;
-  if (!workspace || workspace_bytes < pl.total || (((uintptr_t)workspace) & 15) != 0) return RUNIA_E_WORKSPACE;
+  if (ws_refused(workspace, workspace_bytes, w.used(), 16)) return RUNIA_E_WORKSPACE;
   hipStream_t s = as_stream(stream);
-  char* ws = reinterpret_cast<char*>(workspace);
-  float* mean = reinterpret_cast<float*>(ws + pl.off_mean);
-  float* norms = reinterpret_cast<float*>(ws + pl.off_norms);
-  double* colpart = reinterpret_cast<double*>(ws + pl.off_colpart);
-  double* su = reinterpret_cast<double*>(ws + pl.off_su);
-  double* diag = reinterpret_cast<double*>(ws + pl.off_diag);
-  uint32_t* bits = reinterpret_cast<uint32_t*>(ws + pl.off_bits);
-  float* part_t = reinterpret_cast<float*>(ws + pl.off_part_t);
-  float* part_u = reinterpret_cast<float*>(ws + pl.off_part_u);
+  float *mean = pl.mean, *norms = pl.norms, *part_t = pl.part_t, *part_u = pl.part_u;
+  double *colpart = pl.colpart, *su = pl.su, *diag = pl.diag;
+  uint32_t* bits = pl.bits;
   const Rows r{x, y, n, pl.N, d, x_stride, y_stride};
 
   shift_perm_bits_kernel<<<(unsigned)pl.P, 256, 0, s>>>(seed, (uint32_t)n, (uint32_t)pl.N, 0u, bits, pl.row_words);
@@ -699,9 +694,9 @@ extern "C" int runia_shift_mmd(const void* x, int64_t n, int64_t x_stride, const
     fa.p0 = p0;
     fa.ncols = (int)std::min<int64_t>(pl.chunk_cols, pl.P - p0);
 #if SHIFT_MEMBER_TABLE
-    fa.table = reinterpret_cast<const uint4*>(ws + pl.off_table);
+    fa.table = pl.table;
     shift_member_table_kernel<<<runia_stream_grid(pl.row_words * pl.cstride, 256), 256, 0, s>>>(
-        fa, reinterpret_cast<uint4*>(ws + pl.off_table));
+        fa, pl.table);
 #endif
     for (int64_t it0 = 0; it0 < pl.nit; it0 += pl.nit_batch) {
       const int64_t nb = std::min<int64_t>(pl.nit_batch, pl.nit - it0);

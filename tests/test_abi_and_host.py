@@ -1,6 +1,7 @@
 """CPU-only checks: the C-ABI library loads and exports every symbol the header declares;
 host-side logic of the drop-in classes (registry, flags, error texts, thresholds, fitted state);
 no compute call is made (there is no GPU here and no CPU fallback)."""
+import ctypes
 import os
 import re
 import subprocess
@@ -56,6 +57,51 @@ def test_library_exports_every_header_symbol():
     assert lib.runia_packed_weights_bytes(20, 10) == (32 + 32) * 256 * 8
 
 
+_I, _L, _Z, _P = ctypes.c_int, ctypes.c_int64, ctypes.c_size_t, ctypes.c_void_p
+
+
+@pytest.mark.parametrize("c_type, name, signature", [
+    ("const char* return, int", "runia_error_string", (ctypes.c_char_p, [_I])),
+    ("size_t return, int64_t", "runia_packed_weights_bytes", (_Z, [_L, _L])),
+    ("int64_t return, double", "runia_sel_key_of_f64_host", (_L, [ctypes.c_double])),
+    ("uint64_t* out4, runia_stream_t", "runia_clock_probe", (_I, [_P, _I, _P])),
+    ("size_t", "runia_p2p_buffer_bytes", (_Z, [_I, _Z])),
+    ("uint64_t", "runia_mc_draws_f32", (_I, [_P, _L, _I, _I, _I, ctypes.c_uint64, _L, _P])),
+    ("unsigned", "runia_select_hist_f32", (_I, [_P, _P, _L, ctypes.c_uint32, ctypes.c_uint32, _I, _P])),
+    ("float", "runia_linear_f32", (_I, [_P, _P, _P, _P, _L, _L, _L, ctypes.c_float, _P])),
+    ("host out-parameter", "runia_p2p_status", (_I, [_P, ctypes.POINTER(_I)])),
+    ("host out-parameter", "runia_p2p_all_gather",
+     (_I, [_P, _Z, _P, ctypes.POINTER(_P), _I, _I, _Z, ctypes.c_uint64, _I, _P])),
+])
+def test_signature_table_is_read_from_the_header(c_type, name, signature):
+    assert _hip._SIGNATURES[name] == signature, c_type
+
+
+def test_header_parser_types_and_refusals():
+    sigs, macros = _hip._parse_header(
+        "/* int runia_gone(int); */\n#define RUNIA_A (1 << 3)\n#define RUNIA_B (-7)\n#define RUNIA_F(x) (2 * (x))\n"
+        "int runia_x(const double w[4], uint32_t m,\n            runia_stream_t s);\nsize_t runia_y(void);\n")
+    assert sigs == {"runia_x": (_I, [_P, ctypes.c_uint32, _P]), "runia_y": (_Z, [])}
+    assert macros == {"RUNIA_A": 8, "RUNIA_B": -7}
+    # a type the table does not know is never bound silently: the error names the symbol
+    for text in ("int runia_x(long n);", "long runia_x(int n);", "int* runia_x(int n);", "int runia_x(unsigned long n);"):
+        with pytest.raises(_hip.RuniaHipError, match="runia_x"):
+            _hip._parse_header(text)
+    m = _hip._HEADER_MACROS
+    assert (m["RUNIA_NMS_SORT_MAX"], m["RUNIA_NMS_MAX_BOXES"], m["RUNIA_YOLO_MAX_ANCHORS"]) == (4096, 65536, 1 << 22)
+    assert (_hip.NMS_SORT_MAX, _hip.NMS_MAX_BOXES, _hip.YOLO_MAX_ANCHORS) == (4096, 65536, 1 << 22)
+    assert m["RUNIA_E_WORKSPACE"] == -4 and "RUNIA_KL_PER_DIM_REG" not in m and "RUNIA_HIP_H" not in m
+    for body in ("(100 * (np) + 10 * (k) + (vec))", "", "1.5", "(1 << 2", "RUNIA_OK", "__import__('os')"):
+        with pytest.raises(ValueError):
+            _hip._macro_int(body)
+
+
+def test_missing_header_names_its_path(monkeypatch):
+    monkeypatch.setattr(_hip, "_HEADER_PATH", os.path.join(ROOT, "include", "no_such_header.h"))
+    with pytest.raises(_hip.RuniaHipError, match="no_such_header.h"):
+        _hip._read_header()
+
+
 @pytest.mark.skipif(not no_gpu, reason="CPU-only behaviour")
 def test_fused_sampler_shape_query_needs_no_gpu():
     """runia_mc_entropy_supported is a pure host query: the shapes the fused sampler + entropy covers, and k < n_mc."""
@@ -67,6 +113,112 @@ def test_fused_sampler_shape_query_needs_no_gpu():
     assert lib.runia_mc_entropy_supported(5, 5, 16, 5) == 0 and lib.runia_mc_entropy_supported(4, 4, 16, 3) == 0
     assert lib.runia_mc_entropy_workspace_bytes(10, 4, 4, 16) == 10 * (16 * 18) * 4
     assert lib.runia_proj_sq_workspace_bytes(100) == 1600
+
+
+# Every size query of the C ABI on a small grid, recorded from the library before the workspace layouts moved to
+# csrc/workspace.hpp: zero, negative and unit arguments, an ordinary shape, and each side of every branch a formula has (the
+# column split of md / kde at (N + 15) / 16 against the compute units, the bf16 kNN kernel and its candidate filter on and
+# off, one and several covariance slices, rauq with and without rollout and chain rows, the shift test below and above one
+# launch's 1 024 columns).  The rows that depend on the compute-unit count assume 256, which the MI355X has and which
+# runia_cu_count() falls back to without a device.
+_Q = (1 << 31)
+SIZES = {
+    "runia_boot_workspace_bytes": [((0, 5), 0), ((5, 0), 0), ((-1, 5), 0), ((1, 1), 128), ((1000, 3), 128), ((1000, 4), 128),
+        ((1000, 5), 192), ((1000, 200), 3264), ((100000, 1000), 401600)],
+    "runia_calib_reduce_workspace_bytes": [((-1, 15), 0), ((10000, -1), 0), ((10000, 100000), 0), ((0, 15), 408), ((1, 1), 72),
+        ((10000, 15), 2040), ((10000, 0), 240), ((5000000, 15), 398616)],
+    "runia_cc_label_workspace_bytes": [((0, 64, 64), 0), ((1, 0, 5), 0), ((1, 5, -1), 0), ((1, 1, 1), 24), ((2, 64, 64), 80),
+        ((2, 100, 37), 80), ((3, 512, 512), 6160)],
+    "runia_covariance_workspace_bytes": [((0, 5), 0), ((5, 0), 0), ((-1, 5), 0), ((1, 1), 16), ((100, 8), 576),
+        ((256, 2048), 33570816), ((257, 2048), 67141632), ((1000, 64), 133120), ((50000, 2048), 506527744),
+        ((50000, 64), 2164736), ((100000, 256), 33554432), ((65280, 16), 161664), ((65281, 16), 161792),
+        ((5000, 4096), 2282356736)],
+    "runia_eigh_block_workspace_bytes": [((0,), 0), ((-1,), 0), ((1,), 32832), ((32,), 32832), ((64,), 32832), ((65,), 65600),
+        ((1000,), 524352)],
+    "runia_eigh_workspace_bytes": [((0,), 0), ((-1,), 0), ((1,), 80), ((2,), 80), ((3,), 96), ((64,), 576), ((1001,), 8080)],
+    "runia_gmm_log_prob_workspace_bytes": [((0, 64, 10), 0), ((100, 0, 10), 0), ((100, 64, -1), 0), ((1, 1, 1), 8),
+        ((100, 64, 10), 8000), ((100, 65, 10), 8000)],
+    "runia_kcenter_workspace_bytes": [((0, 5), 0), ((1000, 0), 0), ((1000, 100000), 0), ((1, 1), 16400), ((3, 64), 16400),
+        ((1000, 64), 20384), ((1001, 64), 20400)],
+    "runia_kde_workspace_bytes": [((0, 5), 0), ((-1, 5), 0), ((5, 0), 0), ((1, 1), 256), ((100, 10000), 9176064),
+        ((100, 256), 1024), ((100, 257), 459776), ((4080, 1000), 33456128), ((4081, 1000), 32768), ((32736, 1000), 261888),
+        ((32768, 1000), 262144), ((32800, 1000), 524544), ((100000, 4000), 56374528), ((100000, 256), 800000)],
+    "runia_knn_bank_state_bytes": [((0, 5), 0), ((5, 0), 0), ((-1, 5), 0), ((1, 1), 256), ((100, 32), 512), ((4095, 64), 16384),
+        ((4096, 64), 1081600), ((50000, 2048), 411442688), ((4096, 1), 16640), ((4096, 2), 557312)],
+    "runia_knn_prepared_workspace_bytes": [((0, 100, 32, 5), 0), ((10, -1, 32, 5), 0), ((1, 1, 1, 1), 256),
+        ((12, 50000, 2048, 5), 2400256), ((13, 50000, 2048, 5), 4697600), ((16, 50000, 2048, 5), 5297408),
+        ((1023, 50000, 2048, 50), 212992768), ((1024, 50000, 2048, 50), 246763776), ((999, 20000, 64, 5), 79924224),
+        ((1000, 20000, 64, 5), 80266240), ((9000, 1000000, 64, 5), 2441615616)],
+    "runia_knn_workspace_bytes": [((0, 100, 32, 5), 0), ((-1, 100, 32, 5), 0), ((10, 0, 32, 5), 0), ((1, 1, 1, 1), 28),
+        ((10, 100, 32, 5), 4456), ((511, 50000, 2048, 5), 102402060), ((512, 50000, 2048, 5), 518041088),
+        ((1023, 50000, 2048, 50), 624439552), ((1024, 50000, 2048, 50), 658210560), ((1024, 4096, 2048, 50), 88138240),
+        ((1024, 4095, 2048, 50), 16793612), ((10000, 50000, 4, 50), 1893569280), ((10000, 50000, 1, 50), 1638632784),
+        ((65536, 50000, 128, 300), 2751143680), ((20000, 50000, 128, 2000), 1668750848), ((9000, 1000000, 64, 5), 2705667840),
+        ((100, 1000000, 64, 5), 404000416)],
+    "runia_ks_workspace_bytes": [((0, 1, 1, 0), 0), ((1, 1, 0, 0), 0), ((1, 1, 1, -1), 0), ((1, 1, 1, 0), 768),
+        ((100, 100, 16, 99), 25600), ((500, 700, 64, 999), 616960), ((100, 100, 5000, 99), 4203520),
+        ((3000, 3000, 10, 99), 507904), ((9000, 9000, 3, 9), 0)],
+    "runia_logit_stats_workspace_bytes": [((0, 1, 100), 0), ((5, 0, 100), 0), ((5, 2, 0), 0), ((-1, 2, 100), 0), ((1, 1, 1), 16),
+        ((5, 2, 32000), 1280), ((5, 2, 1024), 160), ((5, 2, 1025), 160), ((100, 8, 151936), 486400)],
+    "runia_mahalanobis_workspace_bytes": [((0, 5), 0), ((-1, 5), 0), ((5, 0), 0), ((1, 1), 8), ((100, 64), 51200),
+        ((65536, 8), 4194304), ((65537, 8), 4194304)],
+    "runia_mahalanobis_workspace_bytes_classes": [((0, 5, 3), 0), ((100, 64, 0), 0), ((100, 64, -1), 0), ((1, 1, 1), 8),
+        ((100, 64, 16), 51200), ((100, 64, 17), 261664), ((100, 64, 100), 328832), ((70000, 32, 20), 27394304)],
+    "runia_mc_entropy_workspace_bytes": [((0, 4, 4, 16), 0), ((-1, 4, 4, 16), 0), ((10, 0, 4, 16), 0), ((10, 4, 4, 0), 0),
+        ((1, 1, 1, 1), 12), ((10, 4, 4, 16), 11520), ((65535, 8, 8, 32), 553639680)],
+    "runia_mc_flag_lut_bytes": [((4, 4, 2), 8388720), ((4, 4, 0), 0), ((4, 4, -1), 0), ((5, 5, 2), 0), ((4, 4, 1), 8388720)],
+    "runia_md_score_workspace_bytes": [((0, 512), 0), ((-1, 512), 0), ((1, 1), 0), ((1, 512), 65536), ((100, 512), 458752),
+        ((100, 256), 0), ((100, 257), 458752), ((4080, 512), 16711680), ((4081, 512), 0), ((5000, 2048), 0)],
+    "runia_nms_workspace_bytes": [((0,), 0), ((-1,), 0), ((1,), 8), ((64,), 512), ((65,), 1040), ((1000,), 128000)],
+    "runia_ood_metrics_workspace_bytes": [((0,), 0), ((-1,), 0), ((1,), 169984), ((1000,), 196864), ((4096,), 282880),
+        ((4097,), 284672), ((100000,), 2968832), ((2000000,), 56173824)],
+    "runia_osod_curves_workspace_bytes": [((-1,), 0), ((0,), 16), ((1,), 16), ((1000,), 16000), ((_Q,), 0)],
+    "runia_osod_match_workspace_bytes": [((0, 5), 0), ((1, -1), 0), ((1, 0), 16), ((1, 1), 16), ((3, 100), 1200),
+        ((3, 101), 1216)],
+    "runia_osod_sort_workspace_bytes": [((-1, 1), 0), ((1000, 0), 0), ((0, 1), 16), ((1, 1), 16), ((5, 3), 16),
+        ((1000, 81), 336), ((100000, 200), 20000), ((_Q, 4), 0)],
+    "runia_p2p_buffer_bytes": [((0, 0), 0), ((1, 1), 4608), ((2, 1000), 8192), ((8, 1048576), 16781312)],
+    "runia_packed_weights_bytes": [((0, 0), 0), ((-1, 5), 0), ((1, 1), 131072), ((512, 256), 1114112), ((20, 10), 131072),
+        ((33, 257), 393216)],
+    "runia_pacmap_pairs_workspace_bytes": [((0,), 0), ((-1,), 0), ((1,), 4), ((1000,), 4000)],
+    "runia_pixel_maps_workspace_bytes": [((0, 19, 64, 64, 8, 0), 0), ((2, 19, 64, 64, 0, 0), 0), ((2, 0, 64, 64, 8, 0), 0),
+        ((1, 1, 1, 1, 1, 0), 0), ((2, 19, 64, 64, 8, 0), 0), ((2, 19, 64, 64, 8, 1), 0), ((2, 150, 64, 64, 8, 0), 0),
+        ((2, 150, 64, 64, 30, 0), 2949120), ((2, 150, 64, 64, 30, 1), 2949120), ((2, 1000, 8, 8, 100, 1), 153600),
+        ((2, 1000, 8, 8, 100, 0), 153600), ((2, 19, 33, 17, 100, 1), 1346400)],
+    "runia_pixfeat_gather_workspace_bytes": [((0,), 0), ((-1,), 0), ((1,), 8), ((4096,), 32), ((100000,), 784)],
+    "runia_pixfeat_workspace_bytes": [((0, 0), 0), ((-1, 1), 0), ((64, 19), 0)],
+    "runia_pixknn_workspace_bytes": [((0, 0, 0), 0), ((64, 1000, 5), 0)],
+    "runia_proj_sq_workspace_bytes": [((0,), 0), ((-1,), 0), ((1,), 16), ((100,), 1600)],
+    "runia_rauq_workspace_bytes": [((0, 10, 0, 0, 0, 3), 0), ((4, 0, 0, 0, 0, 3), 0), ((4, 10, -1, 0, 0, 3), 0),
+        ((4, 10, 0, 0, 0, -1), 0), ((1, 1, 0, 0, 0, 0), 256), ((1, 1, 0, 0, 0, 1), 512), ((4, 10, 0, 0, 0, 3), 512),
+        ((4, 10, 20, 0, 0, 1), 2048), ((4, 10, 20, 9, 9, 1), 24064), ((4, 10, 20, 30, 1, 1), 4864), ((4, 10, 0, 5, 5, 1), 512),
+        ((32, 100, 300, 99, 99, 1), 32480512), ((32, 100, 156, 256, 1, 1), 266496)],
+    "runia_rauqb_workspace_bytes": [((0, 4, 10, 0, 0, 3), 0), ((65536, 4, 10, 0, 0, 3), 0), ((3, 0, 10, 0, 0, 3), 0),
+        ((3, 4, 10, 0, -1, 3), 0), ((1, 1, 1, 0, 0, 0), 256), ((1, 1, 1, 0, 0, 1), 512), ((3, 4, 10, 0, 0, 3), 768),
+        ((3, 4, 10, 20, 0, 1), 5376), ((3, 4, 10, 20, 9, 1), 29952), ((3, 4, 10, 20, 1, 1), 10496), ((3, 4, 10, 0, 5, 1), 768),
+        ((8, 32, 100, 300, 99, 1), 33850880)],
+    "runia_roi_mc_entropy_workspace_bytes": [((0, 7, 7, 16, 2), 0), ((-1, 7, 7, 16, 2), 0), ((10, 7, 7, 16, 0), 0),
+        ((10, 7, 7, 16, -1), 0), ((1, 7, 7, 16, 2), 3872), ((10, 7, 7, 16, 1), 35392), ((100, 4, 4, 32, 2), 259264),
+        ((10, 0, 7, 16, 2), 2624), ((10, 7, 7, 0, 2), 4864)],
+    "runia_sel_workspace_bytes": [((0,), 0), ((-1,), 0), ((_Q,), 0), ((1,), 392), ((1000,), 8384), ((5000,), 40640),
+        ((100000,), 806528)],
+    "runia_shift_workspace_bytes": [((0, 1, 1, 1), 0), ((1, 0, 1, 1), 0), ((1, 1, 0, 1), 0), ((1, 1, 1, 0), 0),
+        ((-1, 1, 1, 1), 0), ((1, 1, 1, 1), 2816), ((100, 100, 16, 99), 21248), ((100, 100, 16, 1021), 158208),
+        ((100, 100, 16, 1022), 158208), ((100, 100, 16, 1023), 158464), ((100, 100, 16, 5000), 317696),
+        ((500, 700, 64, 199), 837120), ((20000, 20000, 8, 99), 26266880)],
+    "runia_yolo_candidates_workspace_bytes": [((0,), 0), ((-1,), 0), ((1,), 12), ((255,), 2044), ((256,), 2052), ((257,), 2064),
+        ((8400,), 67332)],
+}
+
+
+@pytest.mark.parametrize("name", sorted(SIZES))
+def test_size_queries_keep_their_values(name):
+    fn = getattr(_hip.load_library(), name)
+    assert [(args, int(fn(*args))) for args, _ in SIZES[name]] == SIZES[name]
+
+
+def test_size_table_covers_every_size_query():
+    assert sorted(SIZES) == sorted(n for n, (res, _) in _hip._SIGNATURES.items() if res is ctypes.c_size_t)
 
 
 def test_argument_checks_come_before_any_launch():
@@ -96,6 +248,96 @@ def test_argument_checks_come_before_any_launch():
     # kNN
     assert lib.runia_knn_kth_f32(P, P, P, None, 0, 10, 100, 32, 5, None) == WORKSPACE
     assert lib.runia_error_string(WORKSPACE) and lib.runia_error_string(INVALID)
+    # every entry point that refuses a workspace: none, one byte short, and a base off its alignment rule by half
+    for name, args, need, align, *codes in _workspace_refusals():
+        if not isinstance(need, int):
+            need = int(getattr(lib, need[0])(*need[1]))
+        assert need > 0, name
+        null_code, misaligned_code = codes or (WORKSPACE, WORKSPACE)
+        call = lambda ws, nbytes: getattr(lib, name)(*[ws if a is WS else nbytes if a is NB else a for a in args])  # noqa: E731
+        assert call(None, need) == null_code, name
+        assert call(P, need - 1) == WORKSPACE, name
+        if align > 1:
+            assert call(P + align // 2, need) == misaligned_code, name
+
+
+WS, NB = object(), object()  # where a row's workspace pointer and byte count go
+_HOST_ROWS = np.array([[0, 10], [2, 5], [0, 1]], dtype=np.int64)  # runia_rauqb_rollout_att reads (padding, tokens) per row on the host
+_HOST_UPPER = np.array([1, 0, 0], dtype=np.int32)                   # row 0 chains its 10 tokens
+
+
+def _workspace_refusals():
+    """(entry point, arguments, bytes needed: a number or (size query, its arguments), base alignment[, code without a
+    buffer, code off alignment]).  Pointers are fake (P): every call made from a row is refused before a launch.  The entry
+    points that pick a slower path instead of refusing (runia_md_score_ws_* / _tril_*, runia_kde_score_packed_f64,
+    runia_mahalanobis_score_*, runia_knn_kth*) have no row: with N > 0 they would launch."""
+    P, N, INVALID, WORKSPACE = 4096, None, -1, -4
+    mc = ("runia_mc_entropy_workspace_bytes", (10, 4, 4, 16))
+    om = ("runia_ood_metrics_workspace_bytes", (1000,))
+    hr, hu = _HOST_ROWS.ctypes.data, _HOST_UPPER.ctypes.data
+    return [
+        ("runia_mc_mask_table_f32", (P, 256, WS, NB, 10, 4, 4, 16, 0.5, 2, N), mc, 16),
+        ("runia_mc_stack_table_f32", (P, P, 256, P, WS, NB, 10, 8, 4, 4, 16, 0.5, 2, N), mc, 16),
+        ("runia_mc_entropy_from_table_f32", (P, WS, NB, P, N, N, 10, 8, 4, 4, 16, 5, 1e-5, N), mc, 16),
+        ("runia_mc_entropy_f32", (P, P, 256, P, N, N, WS, NB, 10, 8, 4, 4, 16, 0.5, 2, 5, 1e-5, N), mc, 16),
+        ("runia_mc_mask_table_counter_f32", (7, 0, WS, NB, 10, 4, 4, 16, 0.5, 2, 0, N), mc, 16),
+        ("runia_mc_entropy_counter_f32", (P, 7, 0, P, N, N, WS, NB, 10, 8, 4, 4, 16, 0.5, 2, 5, 1e-5, 0, N), mc, 16),
+        ("runia_mc_entropy_lut_f32", (P, P, 256, WS, NB, P, N, 10, 8, 4, 4, 16, 0.5, 2, 5, 1e-5, N),
+         ("runia_mc_flag_lut_bytes", (4, 4, 2)), 4),
+        ("runia_mc_flag_lut_fill", (WS, NB, 4, 4, 2), ("runia_mc_flag_lut_bytes", (4, 4, 2)), 4, INVALID, INVALID),
+        ("runia_roi_mc_entropy_f32", (P, P, N, P, 256, P, N, WS, NB, 10, 1, 8, 32, 32, 7, 7, 0.25, 2, 1, 16, 0.5, 2, 5, 1e-5, N),
+         ("runia_roi_mc_entropy_workspace_bytes", (10, 7, 7, 16, 2)), 16),
+        ("runia_ood_metrics_f64", (P, 500, P, 500, P, WS, NB, N), om, 256),
+        ("runia_ood_metrics_f32", (P, 500, P, 500, P, WS, NB, N), om, 256),
+        ("runia_ood_clf_curve_f64", (P, 500, P, 500, P, P, P, P, WS, NB, N), om, 256),
+        ("runia_ood_clf_curve_f32", (P, 500, P, 500, P, P, P, P, WS, NB, N), om, 256),
+        ("runia_eigh_init_f64", (P, P, 64, WS, NB, N), ("runia_eigh_workspace_bytes", (64,)), 16),
+        ("runia_eigh_sweep_f64", (P, P, 64, WS, NB, P, N), ("runia_eigh_workspace_bytes", (64,)), 16),
+        ("runia_eigh_block_init_f64", (P, P, 128, WS, NB, N), ("runia_eigh_block_workspace_bytes", (128,)), 16),
+        ("runia_eigh_block_sweep_f64", (P, P, 128, WS, NB, P, N), ("runia_eigh_block_workspace_bytes", (128,)), 16),
+        ("runia_covariance_f64", (P, P, P, WS, NB, 1000, 64, N), ("runia_covariance_workspace_bytes", (1000, 64)), 1),
+        ("runia_covariance_f32in", (P, P, P, WS, NB, 1000, 64, N), ("runia_covariance_workspace_bytes", (1000, 64)), 1),
+        ("runia_knn_prepare_bank_f32", (P, WS, NB, 100, 32, N), ("runia_knn_bank_state_bytes", (100, 32)), 16, INVALID, WORKSPACE),
+        ("runia_gmm_log_prob_f32", (P, P, P, P, P, N, WS, NB, 1, 64, 10, N),
+         ("runia_gmm_log_prob_workspace_bytes", (1, 64, 10)), 8, INVALID, INVALID),
+        ("runia_rauq_score", (P, 4, 8, 10, 0, P, P, 3, P, P, WS, NB, N), ("runia_rauq_workspace_bytes", (4, 10, 0, 0, 0, 3)), 16),
+        ("runia_rauq_rollout_rows", (P, 0, 10, 4, 8, 20, P, WS, NB, N), ("runia_rauq_workspace_bytes", (4, 10, 20, 0, 0, 1)), 16),
+        ("runia_rauq_rollout_att", (P, 0, 10, 4, 8, 20, 0, 2, 9, P, WS, NB, N),
+         ("runia_rauq_workspace_bytes", (4, 10, 20, 9, 9, 1)), 16),
+        ("runia_rauqb_score", (P, P, 3, 4, 8, 10, 0, 0, P, 10, P, 3, P, WS, NB, N),
+         ("runia_rauqb_workspace_bytes", (3, 4, 10, 0, 0, 3)), 16),
+        ("runia_rauqb_rollout_rows", (P, P, 0, 3, 10, 4, 8, 20, P, WS, NB, N),
+         ("runia_rauqb_workspace_bytes", (3, 4, 10, 20, 0, 1)), 16),
+        ("runia_rauqb_rollout_att", (P, P, hr, P, hu, 0, 3, 10, 4, 8, 20, 0, P, WS, NB, N),
+         ("runia_rauqb_workspace_bytes", (3, 4, 10, 20, 10, 1)), 16),
+        ("runia_logit_stats", (P, 0, 5, 2, 32000, P, 5, 1, P, P, P, P, WS, NB, N),
+         ("runia_logit_stats_workspace_bytes", (5, 2, 32000)), 16),
+        ("runia_osod_bucket_sort", (P, 1000, 81, P, P, WS, NB, N), ("runia_osod_sort_workspace_bytes", (1000, 81)), 1),
+        ("runia_osod_match", (P, 100, 3, 5, P, P, P, P, P, P, 0, 5, P, 0.0, P, P, P, 100, 0.5, P, P, WS, NB, N),
+         ("runia_osod_match_workspace_bytes", (3, 100)), 1),
+        ("runia_osod_curves", (P, P, P, 100, 3, 5, P, 0, P, N, N, N, N, WS, NB, N), ("runia_osod_curves_workspace_bytes", (300,)), 1),
+        ("runia_yolo_candidates_f32", (P, 8400, 80, 0, 0.25, N, 0, 7680.0, P, P, P, P, P, WS, NB, N),
+         ("runia_yolo_candidates_workspace_bytes", (8400,)), 1),
+        ("runia_nms_sorted_f32", (P, P, 1000, 0.5, 300, P, P, WS, NB, N), ("runia_nms_workspace_bytes", (1000,)), 1),
+        ("runia_pacmap_pairs", (P, 1000, P, 1000, 16, P, P, 60, 10, 5, 20, 1, 0, P, P, P, WS, NB, N),
+         ("runia_pacmap_pairs_workspace_bytes", (1000,)), 1),
+        ("runia_pixel_uncertainty_maps", (P, 0, 0, 2, 30, 150, 64, 64, 150 * 4096, 4096, 64, 1, P, N, N, N, N, N, N, WS, NB, N),
+         ("runia_pixel_maps_workspace_bytes", (2, 150, 64, 64, 30, 0)), 4),
+        ("runia_calib_reduce_f32", (P, P, P, P, N, N, P, 1, 0, -100, 10000, 15, P, WS, NB, N),
+         ("runia_calib_reduce_workspace_bytes", (10000, 15)), 1),
+        # replicates 3 .. 200 touch 51 groups of four, the most 198 replicates can: what the size query counts
+        ("runia_boot_metrics", (P, P, 1000, 500, N, 1, 3, 198, P, WS, NB, N), ("runia_boot_workspace_bytes", (1000, 198)), 8),
+        ("runia_cc_label", (P, N, N, 1, 0, N, 2, 64, 64, 4, P, P, WS, NB, N), ("runia_cc_label_workspace_bytes", (2, 64, 64)), 16),
+        ("runia_sel_curve", (P, P, P, 0, 1000, P, N, N, N, N, WS, NB, N), ("runia_sel_workspace_bytes", (1000,)), 8),
+        ("runia_sel_query", (P, P, P, P, 1000, P, 2, P, 2, 0, P, P, P, N, WS, NB, N), 256, 8),
+        ("runia_pixfeat_gather_rows", (P, 0, 2, 16, 8, 8, 1024, 64, 8, 1, P, 0, 5, -1, P, 1, 0, N, N, 0, P, WS, NB, N),
+         ("runia_pixfeat_gather_workspace_bytes", (128,)), 8),
+        ("runia_shift_mmd", (P, 100, 16, P, 100, 16, 16, 0, 2, N, 0, 0, 1, 99, P, P, P, P, P, P, WS, NB, N),
+         ("runia_shift_workspace_bytes", (100, 100, 16, 99)), 16),
+        ("runia_ks_perm_table", (P, 100, 16, P, 100, 16, 16, 0, 1, 99, P, P, WS, NB, N),
+         ("runia_ks_workspace_bytes", (100, 100, 16, 99)), 16),
+        ("runia_kcenter_greedy_f32", (P, 1000, 64, 0, 10, P, P, P, WS, NB, N), ("runia_kcenter_workspace_bytes", (1000, 64)), 16),
+    ]
 
 
 def test_product_path_fails_loudly_without_gpu(monkeypatch):

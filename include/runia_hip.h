@@ -1357,6 +1357,54 @@ size_t runia_kcenter_workspace_bytes(int64_t N, int64_t D);
 int runia_kcenter_greedy_f32(const float* rows, int64_t N, int64_t D, int64_t first, int64_t n_pick, int32_t* picked,
                              float* radius, int64_t* n_picked, void* workspace, size_t workspace_bytes, runia_stream_t stream);
 
+/* ---- Calibration of a segmentation head (pixel_calibration.hip; evaluation/pixel_calibration.py) --------------- *
+ * runia_pixel_calib_accumulate: ONE pass over logits (G, C, H, W), read in place through the element strides sn, sc, sh, sw
+ *   (`dtype` 0 f32, 1 f16, 2 bf16, widened exactly, f32 arithmetic) at the temperature 1 / beta (0 < beta < inf), against
+ *   labels (G, H, W) contiguous (`label_dtype` 0 int64, 1 int32, 2 uint8).  The row of a pixel is x = logits[g, :, i, j]; its
+ *   pred, conf, nll, brier, g and h are those of runia_calib_rows (the same arithmetic, csrc/calib_core.hpp).  A pixel is
+ *   USED when 0 <= y < C and not (has_ignore and y == ignore_index); a pixel whose label is outside [0, C) and is not the
+ *   ignore value is BAD: counted, not scored.  The call ADDS into `record` (the caller zeroes it once; int64 / f64 slots of 8
+ *   bytes, 8-byte aligned), whose layout depends on C and n_bins alone:
+ *     [0] n_used  [1] n_correct  [2] n_bad (int64)   [3] sum nll  [4] sum brier  [5] sum g  [6] sum h (f64)   [7] reserved
+ *     RUNIA_PIXCAL_HEAD_SLOTS = 8 ..      count[n_bins]  correct[n_bins] (int64)  conf_sum[n_bins] (f64)      top-label table
+ *     8 + 3 n_bins ..                     support[C]  predicted[C]  hit[C] (int64)                            per-class counters
+ *     8 + 3 n_bins + 3 C ..               cw_count[C][n_bins]  cw_pos[C][n_bins] (int64)  cw_conf_sum[C][n_bins] (f64)
+ *   over the used pixels: bin b = clamp((int)ceilf(conf * (float)n_bins) - 1, 0, n_bins - 1) of the top-label table (f32
+ *   arithmetic); support[k] pixels labelled k, predicted[k] pixels with pred == k, hit[k] both; for every class k the
+ *   probability p_k = e_k / S0 enters bin b(p_k) of row k of the class-wise table, cw_pos counting the entries with y == k.
+ *   A used pixel with a NaN logit (or without a finite one) counts in n_used, with pred the first maximum among its non-NaN
+ *   logits (0 without one) - so in n_correct, support, predicted and hit like any other - and in bin 0 of every table row it
+ *   enters, whose conf_sum it makes NaN, as it makes the four float sums (the rule of runia_calib_reduce_f32 for a NaN row).
+ *   mode: RUNIA_PIXCAL_MODE_HEAD      the head only (n_bins must be 0): what a Newton iteration of the temperature fit reads
+ *         RUNIA_PIXCAL_MODE_TOP       the head, the top-label table and the per-class counters (1 <= n_bins <= 512)
+ *         RUNIA_PIXCAL_MODE_CLASSWISE all of it; C * n_bins <= RUNIA_PIXCAL_MAX_CLASSWISE (4096)
+ *   conf_map f32 / pred_map int32 (G, H, W) contiguous, either may be NULL: conf and pred of EVERY pixel, whatever its label.
+ *   record may be NULL when a map is asked for (labels are then not read).
+ *   Load forms, picked from the strides: four neighbouring pixels of a class plane per lane and load when w has unit stride,
+ *   every other stride and the base are multiples of four elements and the row (rows that follow one another, sh == W * sw,
+ *   count as one) is a multiple of four pixels; a pixel per lane over its contiguous classes when sc == 1 (channels_last); a
+ *   pixel per lane through the strides otherwise.  C <= 24 keeps a pixel's logits in registers (one read); wider heads walk
+ *   the class planes twice, three times with the class-wise table.
+ *   Counts by integer atomics; the conf sums as integer multiples of 2^-30 (each confidence rounded to the nearest one); the
+ *   four float sums in f64 in a fixed order (per-workgroup partials, one ordered pass): the same calls give the same bits.
+ *   1 <= C <= RUNIA_PIXCAL_MAX_CLASSES (1024), G, H, W < 2^31, G * H * W <= 2^34, strides >= 0; RUNIA_E_INVALID otherwise,
+ *   before anything is launched.  G == 0 or H * W == 0: 0, nothing launched, the record untouched.
+ *   workspace: runia_pixel_calib_workspace_bytes(G, C, H, W, n_bins, mode) bytes (0 for sizes the call refuses or has nothing
+ *   to do for), 8-byte aligned, uninitialised (RUNIA_E_WORKSPACE if missing or short).  (The query returns int64_t: its values
+ *   are pinned on a grid of their own in tests/test_pixel_calibration_host.py.) */
+#define RUNIA_PIXCAL_HEAD_SLOTS 8
+#define RUNIA_PIXCAL_MAX_BINS 512
+#define RUNIA_PIXCAL_MAX_CLASSES 1024
+#define RUNIA_PIXCAL_MAX_CLASSWISE 4096
+#define RUNIA_PIXCAL_MODE_HEAD 0
+#define RUNIA_PIXCAL_MODE_TOP 1
+#define RUNIA_PIXCAL_MODE_CLASSWISE 2
+int64_t runia_pixel_calib_workspace_bytes(int64_t G, int64_t C, int64_t H, int64_t W, int n_bins, int mode);
+int runia_pixel_calib_accumulate(const void* logits, int dtype, int64_t G, int64_t C, int64_t H, int64_t W, int64_t sn,
+                                 int64_t sc, int64_t sh, int64_t sw, const void* labels, int label_dtype, int has_ignore,
+                                 int64_t ignore_index, float beta, int n_bins, int mode, void* record, float* conf_map,
+                                 int32_t* pred_map, void* workspace, size_t workspace_bytes, runia_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

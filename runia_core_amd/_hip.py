@@ -842,6 +842,78 @@ def calibration_record(record: np.ndarray, n_bins: int) -> dict:
             "conf_sum": f[6 + 2 * n_bins:6 + 3 * n_bins].copy()}
 
 
+PIXCAL_MODES = {m: _HEADER_MACROS["RUNIA_PIXCAL_MODE_" + m.upper()] for m in ("head", "top", "classwise")}
+PIXCAL_HEAD_SLOTS = _HEADER_MACROS["RUNIA_PIXCAL_HEAD_SLOTS"]
+PIXCAL_MAX_BINS = _HEADER_MACROS["RUNIA_PIXCAL_MAX_BINS"]
+PIXCAL_MAX_CLASSES = _HEADER_MACROS["RUNIA_PIXCAL_MAX_CLASSES"]
+PIXCAL_MAX_CLASSWISE = _HEADER_MACROS["RUNIA_PIXCAL_MAX_CLASSWISE"]  # C * n_bins of the class-wise table
+PIXCAL_MAX_PIXELS = 1 << 34
+# label dtype of the (G, H, W) masks -> the `label_dtype` code of runia_pixel_calib_accumulate
+PIXCAL_LABEL_CODES = {torch.int64: 0, torch.int32: 1, torch.uint8: 2}
+
+
+def pixel_calibration_record_slots(c: int, n_bins: int, classwise: bool) -> int:
+    """8-byte slots of the record of ``runia_pixel_calib_accumulate`` for ``c`` classes and ``n_bins`` bins."""
+    return PIXCAL_HEAD_SLOTS + 3 * n_bins + 3 * c + (3 * c * n_bins if classwise else 0)
+
+
+@_device_guard()
+def pixel_calibration_accumulate(logits: torch.Tensor, labels: Optional[torch.Tensor], record: Optional[torch.Tensor],
+                                 beta: float = 1.0, n_bins: int = 15, mode: str = "top", ignore_index: Optional[int] = None,
+                                 conf_map: Optional[torch.Tensor] = None, pred_map: Optional[torch.Tensor] = None) -> None:
+    """One pass over ``logits`` (G, C, H, W) (f32 / f16 / bf16 on the device, any strides, read in place) against ``labels``
+    (G, H, W) int64 / int32 / uint8 that ADDS into ``record`` (int64 device tensor the caller zeroed, at least
+    ``pixel_calibration_record_slots`` long; ``pixel_calibration_record`` splits a host copy) - ``runia_pixel_calib_accumulate``.
+    ``mode``: ``"head"`` (``n_bins`` is not used), ``"top"`` or ``"classwise"``.  ``conf_map`` f32 / ``pred_map`` int32
+    (G, H, W) contiguous are filled for every pixel when given.  Stream-ordered; nothing is read back."""
+    assert logits.is_cuda and logits.dim() == 4 and logits.dtype in ELEM_DTYPE_CODES, \
+        f"logits: a (G, C, H, W) device tensor of float32, float16 or bfloat16, got {tuple(logits.shape)} {logits.dtype}"
+    assert mode in PIXCAL_MODES, f"mode must be one of {tuple(PIXCAL_MODES)}"
+    g, c, h, w = (int(v) for v in logits.shape)
+    n_bins = 0 if mode == "head" else int(n_bins)
+    assert record is not None or conf_map is not None or pred_map is not None
+    if record is not None:
+        assert labels is not None and labels.is_cuda and labels.dtype in PIXCAL_LABEL_CODES and tuple(labels.shape) == (g, h, w), \
+            f"labels: a (G, H, W) device tensor of int64, int32 or uint8 matching the logits, got {labels.dtype}"
+        labels = labels.contiguous()
+        need = PIXCAL_HEAD_SLOTS if mode == "head" else pixel_calibration_record_slots(c, n_bins, mode == "classwise")
+        assert record.is_cuda and record.dtype == torch.int64 and record.is_contiguous() and record.numel() >= need
+    for t, dt in ((conf_map, torch.float32), (pred_map, torch.int32)):
+        assert t is None or (t.is_cuda and t.dtype == dt and tuple(t.shape) == (g, h, w) and t.is_contiguous())
+    require_gpu()
+    if g == 0 or h * w == 0:
+        return
+    ws_bytes = query("runia_pixel_calib_workspace_bytes", g, c, h, w, n_bins, PIXCAL_MODES[mode])
+    ws = workspace(ws_bytes, logits.device)
+    sn, sc, sh, sw = (int(v) for v in logits.stride())
+    launch("runia_pixel_calib_accumulate", logits.data_ptr(), ELEM_DTYPE_CODES[logits.dtype], g, c, h, w, sn, sc, sh, sw,
+           _ptr(labels) if record is not None else None, PIXCAL_LABEL_CODES[labels.dtype] if record is not None else 0,
+           int(ignore_index is not None), 0 if ignore_index is None else int(ignore_index), float(beta), n_bins,
+           PIXCAL_MODES[mode], _ptr(record), _ptr(conf_map), _ptr(pred_map), ws.data_ptr(), ws_bytes)
+
+
+def pixel_calibration_record(record: np.ndarray, c: int, n_bins: int, classwise: bool) -> dict:
+    """A host copy of the record of ``pixel_calibration_accumulate`` -> its named parts (ints, float64 and int64 arrays).
+    ``n_bins = 0``: the head alone."""
+    record = np.ascontiguousarray(record, dtype=np.int64)
+    f = record.view(np.float64)
+    out = {"n_used": int(record[0]), "n_correct": int(record[1]), "n_bad": int(record[2]), "nll": float(f[3]),
+           "brier": float(f[4]), "g": float(f[5]), "h": float(f[6])}
+    if n_bins == 0:
+        return out
+    o = PIXCAL_HEAD_SLOTS
+    out.update(count=record[o:o + n_bins].copy(), correct=record[o + n_bins:o + 2 * n_bins].copy(),
+               conf_sum=f[o + 2 * n_bins:o + 3 * n_bins].copy())
+    o += 3 * n_bins
+    out.update(support=record[o:o + c].copy(), predicted=record[o + c:o + 2 * c].copy(), hit=record[o + 2 * c:o + 3 * c].copy())
+    o += 3 * c
+    if classwise:
+        e = c * n_bins
+        out.update(cw_count=record[o:o + e].reshape(c, n_bins).copy(), cw_pos=record[o + e:o + 2 * e].reshape(c, n_bins).copy(),
+                   cw_conf_sum=f[o + 2 * e:o + 3 * e].reshape(c, n_bins).copy())
+    return out
+
+
 CONFORMAL_METHODS = {"lac": 0, "aps": 1, "raps": 2}  # `method` of the runia_conformal_* entry points
 
 

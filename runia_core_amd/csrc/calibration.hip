@@ -4,16 +4,16 @@
 //                           first and second derivative of the nll in beta (the Newton step of the temperature fit)
 //   runia_calib_reduce_f32: the per-row table -> n_used, n_correct, the four f64 sums and the reliability table, in a fixed order
 //                           (per-workgroup partials, then one ordered pass; integer counts, no floating-point atomics)
+// The arithmetic of a row lives in calib_core.hpp (shared with pixel_calibration.hip).
 // With m the row maximum, d_k = x_k - m and e_k = exp(beta d_k), a row is the four sums
 //   S0 = sum e_k   S1 = sum e_k d_k   S2 = sum e_k d_k^2   Q = sum e_k^2          (p_k = e_k / S0)
 // and the label's d_y:  conf = 1 / S0,  nll = log S0 - beta d_y,  brier = Q / S0^2 - 2 p_y + 1,  g = S1 / S0 - d_y,
 // h = max(0, S2 / S0 - (S1 / S0)^2).  A class at -inf adds nothing; a NaN logit makes the row's outputs NaN.
 #include "common.hpp"
 #include "elem.hpp"
+#include "calib_core.hpp"
 
 namespace {
-
-struct Sums { float s0, s1, s2, q; };
 
 struct Labels {
   const void* p;   // int32 or int64 [N]; NULL: no labels (pred and conf only)
@@ -39,48 +39,15 @@ __device__ __forceinline__ int row_class(const Labels& L, int64_t row, int64_t C
   return used ? (int)y : 0;
 }
 
-__device__ __forceinline__ void term(float x, float m, float beta, Sums& a) {
-  const float d = x - m;
-  const float e = (x == -INFINITY) ? 0.f : exp_nonpos(beta * d);
-  a.s0 += e;
-  a.q += e * e;
-  const bool some = e != 0.f;  // (a NaN passes; e == 0 with d = -inf would be 0 * inf)
-  const float ed = some ? e * d : 0.f;
-  a.s1 += ed;
-  a.s2 += some ? ed * d : 0.f;
-}
-
-// the sums of a maximum that moved up by delta > 0:  d' = d - delta,  e' = e exp(-beta delta).  No term cancels: S1 <= 0 <= S0, S2.
-__device__ __forceinline__ void rescale(Sums& a, float delta, float beta) {
-  const float f = exp_nonpos(-beta * delta);
-  const float s1 = a.s1 - delta * a.s0;
-  a.s2 = f * (a.s2 - 2.f * delta * a.s1 + delta * delta * a.s0);
-  a.s1 = f * s1;
-  a.s0 *= f;
-  a.q *= f * f;
-}
-
 __device__ __forceinline__ void finish_row(const RowOut& o, int64_t row, float beta, float m, Sums a, int bi, float xy,
                                            bool labelled, bool used) {
-  const float nan = __builtin_nanf("");
   if (o.pred) o.pred[row] = (bi == kNoIndex) ? 0 : bi;
-  if (a.s0 == 0.f) a.s0 = nan;  // a row of -inf has no softmax (torch: NaN)
-  const float r = 1.f / a.s0;
-  if (o.conf) o.conf[row] = (!labelled || used) ? r : nan;
-  float nll = nan, brier = nan, g = nan, h = nan;
-  if (used) {
-    const float dy = xy - m, ay = beta * dy;
-    const float py = (xy == -INFINITY) ? 0.f : exp_nonpos(ay) * r;
-    const float mu = a.s1 * r, var = a.s2 * r - mu * mu;
-    nll = logf(a.s0) - ay;
-    brier = a.q * r * r - 2.f * py + 1.f;
-    g = mu - dy;
-    h = (var > 0.f || var != var) ? var : 0.f;
-  }
-  if (o.nll) o.nll[row] = nll;
-  if (o.brier) o.brier[row] = brier;
-  if (o.g) o.g[row] = g;
-  if (o.h) o.h[row] = h;
+  const RowVals v = finish_vals(beta, m, a, xy, used);
+  if (o.conf) o.conf[row] = (!labelled || used) ? v.conf : __builtin_nanf("");
+  if (o.nll) o.nll[row] = v.nll;
+  if (o.brier) o.brier[row] = v.brier;
+  if (o.g) o.g[row] = v.g;
+  if (o.h) o.h[row] = v.h;
 }
 
 // four elements per lane and load: 16 bytes of f32, 8 bytes of f16 / bf16
@@ -288,14 +255,6 @@ static inline int64_t reduce_rows_per_block(int64_t N) {
 static inline int64_t reduce_blocks(int64_t N) {
   const int64_t r = reduce_rows_per_block(N);
   return N > 0 ? (N + r - 1) / r : 1;
-}
-
-// b = clamp((int)ceilf(conf * (float)n_bins) - 1, 0, n_bins - 1); a NaN goes to bin 0 (and makes its conf_sum NaN)
-__device__ __forceinline__ int conf_bin(float conf, int n_bins) {
-  const float t = ceilf(conf * (float)n_bins);
-  int b = (t == t) ? (int)fminf(fmaxf(t, -1.f), (float)n_bins) - 1 : 0;
-  b = b < 0 ? 0 : b;
-  return b > n_bins - 1 ? n_bins - 1 : b;
 }
 
 __global__ __launch_bounds__(kRedThreads) void calib_partial_kernel(const int32_t* __restrict__ pred,

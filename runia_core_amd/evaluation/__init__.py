@@ -26,6 +26,14 @@ from .calibration import (  # noqa: F401
     calibration_metrics,
     fit_temperature,
 )
+from .pixel_calibration import (  # noqa: F401
+    PixelCalibrationAccumulator,
+    PixelCalibrationResult,
+    PixelTemperatureScaler,
+    fit_pixel_temperature,
+    get_pixel_calibration,
+    pixel_calibration_metrics,
+)
 from .conformal import (  # noqa: F401
     ConformalClassifier,
     ConformalResult,

@@ -125,24 +125,24 @@ def calibration_metrics(logits, labels, temperature: float = 1.0, n_bins: int = 
     return _metrics_device(x, y, float(temperature), int(n_bins), ignore_index)
 
 
-def _fit_device(x: Tensor, y: Tensor, ignore_index, max_iter: int, tol: float, bounds) -> float:
+def _newton_beta(sums, max_iter: int, tol: float, bounds, name: str = "fit_temperature") -> float:
+    """The safeguarded Newton loop on ``beta = 1 / T`` around ``sums(beta) -> (n, sum g, sum h)`` (shared with
+    ``evaluation/pixel_calibration.py``) -> the temperature."""
     lo, hi = 1.0 / bounds[1], 1.0 / bounds[0]  # of beta = 1 / T
     beta = min(max(1.0, lo), hi)
     for _ in range(max_iter):
-        rows = _hip.calibration_rows(x, y, beta, ignore_index, want=("g", "h"))
-        rec = _hip.calibration_record(_hip.to_host(_hip.calibration_reduce(rows, y, 0, ignore_index)), 0)
-        n, g, h = rec["n_used"], rec["g"], rec["h"]
+        n, g, h = sums(beta)
         if n == 0:
-            raise ValueError("fit_temperature: no labelled row (labels is empty or all ignore_index)")
+            raise ValueError(f"{name}: no labelled row (labels is empty or all ignore_index)")
         if not (np.isfinite(g) and np.isfinite(h)):
-            raise ValueError("fit_temperature: the likelihood is not finite (a NaN logit, or a label whose logit is -inf)")
+            raise ValueError(f"{name}: the likelihood is not finite (a NaN logit, or a label whose logit is -inf)")
         if abs(g) / n <= tol:
             break
         new = beta - g / h if h > 0 else (4.0 * beta if g < 0 else beta / 4.0)
         new = min(max(new, beta / 4.0), 4.0 * beta)
         new = min(max(new, lo), hi)
         if new == beta:  # at a bound, and the likelihood still improves beyond it
-            warnings.warn(f"fit_temperature: the optimum lies beyond the bound, returning temperature {1.0 / beta:g} "
+            warnings.warn(f"{name}: the optimum lies beyond the bound, returning temperature {1.0 / beta:g} "
                           f"(bounds {tuple(bounds)})")
             break
         done = abs(new - beta) <= 1e-7 * beta
@@ -150,8 +150,17 @@ def _fit_device(x: Tensor, y: Tensor, ignore_index, max_iter: int, tol: float, b
         if done:
             break
     else:
-        warnings.warn(f"fit_temperature: no convergence in {max_iter} iterations (|dNLL/dbeta| = {abs(g) / n:.3e})")
+        warnings.warn(f"{name}: no convergence in {max_iter} iterations (|dNLL/dbeta| = {abs(g) / n:.3e})")
     return 1.0 / beta
+
+
+def _fit_device(x: Tensor, y: Tensor, ignore_index, max_iter: int, tol: float, bounds) -> float:
+    def sums(beta):
+        rows = _hip.calibration_rows(x, y, beta, ignore_index, want=("g", "h"))
+        rec = _hip.calibration_record(_hip.to_host(_hip.calibration_reduce(rows, y, 0, ignore_index)), 0)
+        return rec["n_used"], rec["g"], rec["h"]
+
+    return _newton_beta(sums, max_iter, tol, bounds)
 
 
 def fit_temperature(logits, labels, ignore_index: Optional[int] = None, max_iter: int = 50, tol: float = 1e-6,

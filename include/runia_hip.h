@@ -1405,6 +1405,67 @@ int runia_pixel_calib_accumulate(const void* logits, int dtype, int64_t G, int64
                                  int64_t ignore_index, float beta, int n_bins, int mode, void* record, float* conf_map,
                                  int32_t* pred_map, void* workspace, size_t workspace_bytes, runia_stream_t stream);
 
+/* ---- Standardized Max Logits maps with boundary smoothing (pixel_sml.hip; inference/pixel_sml.py) --------------- *
+ * The three entry points read logits (G, C, H, W) in place through the element strides sn, sc, sh, sw (`dtype` 0 f32, 1 f16,
+ * 2 bf16, widened exactly) in the load forms of runia_pixel_calib_accumulate (four pixels of a class plane per lane; a pixel per
+ * lane over its contiguous classes when sc == 1; a pixel per lane through the strides) and its two kernels (C <= 24: every load
+ * of a pixel is issued before the first compare; any C <= 1024: one walk).  Per pixel m = max_c x_c and label = argmax_c x_c as
+ * torch.max(dim=1) on the CPU gives them: a NaN logit gives m = NaN and the index of the first NaN, ties give the lowest index.
+ * runia_pixel_sml_accumulate: ONE pass that ADDS into `record` (the caller zeroes it once; int64 slots, 8-byte aligned):
+ *     [0] n_used  [1] n_masked  [2] n_bad  [3 .. 7] reserved                         RUNIA_PIXSML_HEAD_SLOTS = 8
+ *     8 ..        count[C]  sum_q[C] (int64)  sq_hi[C]  sq_lo[C] (uint64)
+ *   valid: uint8 / bool (G, H, W) contiguous, or NULL (every pixel).  A pixel whose valid entry is 0 counts in n_masked.  A valid
+ *   pixel is USED when m is finite and |m| < 2^14, and counts in n_bad otherwise.  A used pixel adds q = rint(m * 2^16) (an
+ *   integer, |q| < 2^30; m * 2^16 is exact in f32): count[label] += 1, sum_q[label] += q, and q * q = hi * 2^30 + lo (0 <= lo <
+ *   2^30) as sq_hi[label] += hi, sq_lo[label] += lo.  hi, lo < 2^30, so neither sum overflows a uint64 within the 2^34 pixels
+ *   that ONE RECORD admits over all its calls (the caller keeps the total; a call admits G * H * W <= 2^34 as well).
+ *   Integer adds only (LDS tables per workgroup, 28 bytes a class; 64-bit global integer atomics into the record): the record is
+ *   bit-identical from run to run, under any split of the data into calls, any order of the calls, and adds across GPUs.
+ *   The 2^-16 grid holds every bf16 logit with |x| >= 2^-9 and every f16 logit with |x| >= 2^-6 exactly; an f32 logit is at most
+ *   2^-17 off.  mean_c = sum_q / (count 2^16), var_c = (sumsq - sum_q^2 / count) / (count - 1) / 2^32 with sumsq = sq_hi 2^30 +
+ *   sq_lo: exact in integers / rationals on the host.
+ * runia_pixel_sml_maps: ONE launch.  mean, inv_std f32 [C] on the device.  Outputs (G, H, W) contiguous, each may be NULL, at
+ *   least one set: sml f32 = (m - mean[label]) * inv_std[label] (two f32 operations in this order, no contraction), label int32,
+ *   max_logit f32 = m.  IEEE: a NaN pixel gives sml NaN, a row of -inf gives -inf (inv_std > 0).  Higher = more in-distribution.
+ * Both: 1 <= C <= RUNIA_PIXSML_MAX_CLASSES, G, H, W < 2^31, G * H * W <= 2^34, strides >= 0, no NULL where a pointer is needed;
+ *   RUNIA_E_INVALID otherwise, before anything is launched.  G == 0 or H * W == 0: 0, nothing launched.  No workspace.
+ * runia_pixel_boundary_smooth_f32: score f32 and label int32 (G, H, W) contiguous -> out f32 (G, H, W) contiguous (out must not
+ *   overlap score).  Per image; out-of-image neighbours are taken by clamping coordinates (replicate padding).
+ *   boundary   B[p] = 1 iff the label of p differs from that of one of its in-image 4-neighbours.  dist[p]: the Chebyshev distance
+ *              to the nearest boundary pixel of the image; E_r = {p : dist[p] <= r}.
+ *   suppression  boundary_width Wb in 0 .. 8, boundary_iterations I in 0 .. 8; Wb == 0 or I == 0: skipped; otherwise Wb % I == 0.
+ *              For t = 0 .. I - 1: r_t = Wb - (Wb / I) t - 1, and r_{I-1} = 0.  Every p in E_{r_t} takes the mean of the entries
+ *              of its clamped 3 x 3 window of the PREVIOUS iterate that are not in E_{r_t} (a clamped duplicate counts each time
+ *              it appears; summed row by row in f32, divided by their number n); n == 0 or p outside E_{r_t}: the value stays.
+ *              Entries in E_{r_t} are selected out, not multiplied by 0: a NaN there does not spread.
+ *   smoothing  kernel_size K in {3, 5, 7} (0: skipped), dilation d in 1 .. 8, taps: K f32 values ON THE HOST (copied into the
+ *              launch).  out[i, j] = sum_a g[a] (sum_b g[b] x[clamp(i + (a - (K-1)/2) d), clamp(j + (b - (K-1)/2) d)]), both
+ *              sums in ascending tap order in f32.  Both steps skipped: out = score.
+ *   A workgroup owns a RUNIA_PIXSML_TILE_H x RUNIA_PIXSML_TILE_W tile of one image; suppression and smoothing are one launch
+ *   each, the suppressed map between them in the workspace.  One thread per output pixel, fixed order: run-to-run bit identical.
+ *   G, H, W < 2^31, G * H * W <= 2^34, fewer than 2^31 tiles; RUNIA_E_INVALID otherwise or for a parameter out of range, before
+ *   anything is launched.  workspace: runia_pixel_boundary_smooth_workspace_bytes(G, H, W, Wb, I, K) bytes (4 G H W when both
+ *   steps run, else 0; 0 for what the call refuses), 4-byte aligned, uninitialised (RUNIA_E_WORKSPACE if missing or short).  (The
+ *   query returns int64_t: its values are pinned on a grid of their own in tests/test_pixel_sml_host.py.) */
+#define RUNIA_PIXSML_HEAD_SLOTS 8
+#define RUNIA_PIXSML_MAX_CLASSES 1024
+#define RUNIA_PIXSML_TILE_H 32
+#define RUNIA_PIXSML_TILE_W 64
+#define RUNIA_PIXSML_MAX_WIDTH 8
+#define RUNIA_PIXSML_MAX_DILATION 8
+#define RUNIA_PIXSML_MAX_KERNEL 7
+int runia_pixel_sml_accumulate(const void* logits, int dtype, int64_t G, int64_t C, int64_t H, int64_t W, int64_t sn, int64_t sc,
+                               int64_t sh, int64_t sw, const void* valid, void* record, runia_stream_t stream);
+int runia_pixel_sml_maps(const void* logits, int dtype, int64_t G, int64_t C, int64_t H, int64_t W, int64_t sn, int64_t sc,
+                         int64_t sh, int64_t sw, const float* mean, const float* inv_std, float* sml, int32_t* label,
+                         float* max_logit, runia_stream_t stream);
+int64_t runia_pixel_boundary_smooth_workspace_bytes(int64_t G, int64_t H, int64_t W, int boundary_width,
+                                                    int boundary_iterations, int kernel_size);
+int runia_pixel_boundary_smooth_f32(const float* score, const int32_t* label, int64_t G, int64_t H, int64_t W,
+                                    int boundary_width, int boundary_iterations, int kernel_size, int dilation,
+                                    const float* taps, float* out, void* workspace, size_t workspace_bytes,
+                                    runia_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

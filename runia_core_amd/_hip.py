@@ -914,6 +914,121 @@ def pixel_calibration_record(record: np.ndarray, c: int, n_bins: int, classwise:
     return out
 
 
+PIXSML_HEAD_SLOTS = _HEADER_MACROS["RUNIA_PIXSML_HEAD_SLOTS"]
+PIXSML_MAX_CLASSES = _HEADER_MACROS["RUNIA_PIXSML_MAX_CLASSES"]
+PIXSML_TILE = (_HEADER_MACROS["RUNIA_PIXSML_TILE_H"], _HEADER_MACROS["RUNIA_PIXSML_TILE_W"])
+PIXSML_MAX_WIDTH = _HEADER_MACROS["RUNIA_PIXSML_MAX_WIDTH"]
+PIXSML_MAX_DILATION = _HEADER_MACROS["RUNIA_PIXSML_MAX_DILATION"]
+PIXSML_KERNEL_SIZES = (3, 5, 7)
+PIXSML_MAX_PIXELS = 1 << 34   # of one call, and of one record over all its calls
+PIXSML_Q_BITS = 16            # a used max logit enters the record as rint(m * 2^16)
+
+
+def pixel_sml_record_slots(c: int) -> int:
+    """8-byte slots of the record of ``runia_pixel_sml_accumulate`` for ``c`` classes."""
+    return PIXSML_HEAD_SLOTS + 4 * c
+
+
+def _logits_view(logits: torch.Tensor):
+    assert logits.is_cuda and logits.dim() == 4 and logits.dtype in ELEM_DTYPE_CODES, \
+        f"logits: a (G, C, H, W) device tensor of float32, float16 or bfloat16, got {tuple(logits.shape)} {logits.dtype}"
+    return tuple(int(v) for v in logits.shape), tuple(int(v) for v in logits.stride())
+
+
+@_device_guard()
+def pixel_sml_accumulate(logits: torch.Tensor, record: torch.Tensor, valid: Optional[torch.Tensor] = None) -> None:
+    """One pass over ``logits`` (G, C, H, W) (f32 / f16 / bf16 on the device, any strides, read in place) that ADDS the integer
+    moments of every pixel's max logit, by predicted class, into ``record`` (int64 device tensor the caller zeroed, at least
+    ``pixel_sml_record_slots(C)`` long; ``pixel_sml_record`` splits a host copy) - ``runia_pixel_sml_accumulate``.  ``valid``:
+    bool / uint8 (G, H, W) or None (every pixel).  Stream-ordered; nothing is read back."""
+    (g, c, h, w), (sn, sc, sh, sw) = _logits_view(logits)
+    assert record.is_cuda and record.dtype == torch.int64 and record.is_contiguous() and \
+        record.numel() >= pixel_sml_record_slots(c), f"record: an int64 device tensor of at least {pixel_sml_record_slots(c)} slots"
+    if valid is not None:
+        assert valid.is_cuda and valid.dtype in (torch.bool, torch.uint8) and tuple(valid.shape) == (g, h, w), \
+            f"valid: a (G, H, W) device tensor of bool or uint8 matching the logits, got {tuple(valid.shape)} {valid.dtype}"
+        valid = valid.contiguous()
+    require_gpu()
+    if g == 0 or h * w == 0:
+        return
+    launch("runia_pixel_sml_accumulate", logits.data_ptr(), ELEM_DTYPE_CODES[logits.dtype], g, c, h, w, sn, sc, sh, sw,
+           _ptr(valid), record.data_ptr())
+
+
+def pixel_sml_record(record: np.ndarray, c: int) -> dict:
+    """A host copy of the record of ``pixel_sml_accumulate`` -> its named parts: Python ints and lists of Python ints
+    (``sumsq = sq_hi * 2^30 + sq_lo`` put together exactly)."""
+    record = np.ascontiguousarray(record, dtype=np.int64)
+    u = record.view(np.uint64)
+    o = PIXSML_HEAD_SLOTS
+    return {"n_used": int(record[0]), "n_masked": int(record[1]), "n_bad": int(record[2]),
+            "count": [int(v) for v in record[o:o + c]], "sum_q": [int(v) for v in record[o + c:o + 2 * c]],
+            "sumsq": [(int(hi) << 30) + int(lo) for hi, lo in zip(u[o + 2 * c:o + 3 * c], u[o + 3 * c:o + 4 * c])]}
+
+
+@_device_guard()
+def pixel_sml_maps(logits: torch.Tensor, mean: torch.Tensor, inv_std: torch.Tensor, want_max_logit: bool = False) -> dict:
+    """``{"sml": f32, "label": int32[, "max_logit": f32]}`` (G, H, W) of ``logits`` (G, C, H, W) read in place: ``sml = (m -
+    mean[label]) * inv_std[label]`` with ``m``, ``label`` the max and argmax over the classes - ``runia_pixel_sml_maps``, one
+    launch.  ``mean``, ``inv_std``: f32 [C] on the device."""
+    (g, c, h, w), (sn, sc, sh, sw) = _logits_view(logits)
+    for name, t in (("mean", mean), ("inv_std", inv_std)):
+        assert t.is_cuda and t.dtype == torch.float32 and tuple(t.shape) == (c,) and t.is_contiguous(), \
+            f"{name}: a contiguous float32 device tensor of {c} entries, got {tuple(t.shape)} {t.dtype}"
+    dev = logits.device
+    out = {"sml": torch.empty((g, h, w), dtype=torch.float32, device=dev),
+           "label": torch.empty((g, h, w), dtype=torch.int32, device=dev)}
+    if want_max_logit:
+        out["max_logit"] = torch.empty((g, h, w), dtype=torch.float32, device=dev)
+    require_gpu()
+    if g == 0 or h * w == 0:
+        return out
+    launch("runia_pixel_sml_maps", logits.data_ptr(), ELEM_DTYPE_CODES[logits.dtype], g, c, h, w, sn, sc, sh, sw,
+           mean.data_ptr(), inv_std.data_ptr(), out["sml"].data_ptr(), out["label"].data_ptr(), _ptr(out.get("max_logit")))
+    return out
+
+
+def gaussian_taps(kernel_size: int, sigma: float) -> np.ndarray:
+    """The ``kernel_size`` taps ``exp(-(a - (K - 1) / 2)^2 / (2 sigma^2))`` in float64, normalised to sum 1, rounded to f32."""
+    a = np.arange(kernel_size, dtype=np.float64) - (kernel_size - 1) / 2.0
+    g = np.exp(-(a * a) / (2.0 * float(sigma) * float(sigma)))
+    return np.ascontiguousarray((g / g.sum()).astype(np.float32))
+
+
+@_device_guard()
+def pixel_boundary_smooth(score: torch.Tensor, label: Optional[torch.Tensor], boundary_width: int = 4,
+                          boundary_iterations: int = 4, taps: Optional[np.ndarray] = None, dilation: int = 6) -> torch.Tensor:
+    """Boundary suppression (skipped when ``boundary_width`` or ``boundary_iterations`` is 0), then the dilated Gaussian smoothing
+    with the host f32 ``taps`` (3, 5 or 7 of them; None: skipped) of a contiguous f32 (G, H, W) device map, per image, with
+    clamped coordinates at the image border - ``runia_pixel_boundary_smooth_f32``.  ``label``: int32 (G, H, W), needed by the
+    suppression.  Returns a new map."""
+    assert score.is_cuda and score.dim() == 3 and score.dtype == torch.float32 and score.is_contiguous(), \
+        f"score: a contiguous float32 (G, H, W) device tensor, got {tuple(score.shape)} {score.dtype}"
+    g, h, w = (int(v) for v in score.shape)
+    wb, it = int(boundary_width), int(boundary_iterations)
+    suppress = wb > 0 and it > 0
+    assert 0 <= wb <= PIXSML_MAX_WIDTH and 0 <= it <= PIXSML_MAX_WIDTH and (not suppress or wb % it == 0), \
+        f"boundary_width {wb} / boundary_iterations {it}: 0 .. {PIXSML_MAX_WIDTH}, the width a multiple of the iterations"
+    if suppress:
+        assert label is not None and label.is_cuda and label.dtype == torch.int32 and tuple(label.shape) == (g, h, w) and \
+            label.is_contiguous(), "label: a contiguous int32 (G, H, W) device tensor matching the score map"
+    k = 0
+    if taps is not None:
+        taps = np.ascontiguousarray(taps, dtype=np.float32)
+        k = int(taps.size)
+        assert taps.ndim == 1 and k in PIXSML_KERNEL_SIZES and 1 <= int(dilation) <= PIXSML_MAX_DILATION, \
+            f"{k} taps at dilation {dilation}: 3, 5 or 7 taps, dilation 1 .. {PIXSML_MAX_DILATION}"
+    require_gpu()
+    out = torch.empty_like(score)
+    if g == 0 or h * w == 0:
+        return out
+    ws_bytes = query("runia_pixel_boundary_smooth_workspace_bytes", g, h, w, wb, it, k)
+    ws = workspace(ws_bytes, score.device)
+    launch("runia_pixel_boundary_smooth_f32", score.data_ptr(), _ptr(label) if suppress else None, g, h, w, wb, it, k,
+           int(dilation) if k else 0, taps.ctypes.data if k else None, out.data_ptr(), ws.data_ptr(), ws_bytes)
+    return out
+
+
 CONFORMAL_METHODS = {"lac": 0, "aps": 1, "raps": 2}  # `method` of the runia_conformal_* entry points
 
 

@@ -187,16 +187,6 @@ __device__ __forceinline__ void account_class(const Tables& t, int k, const floa
   flush();
 }
 
-template <class T, int LOAD>
-__device__ __forceinline__ void load_px(const typename T::elem* p, float* x) {
-  if constexpr (LOAD == kLoadVec) {
-    if constexpr (T::kBytes == 4) ld16<T>(p, x);
-    else ld8<T>(p, x);
-  } else {
-    x[0] = ld1<T>(p);
-  }
-}
-
 // CMAX > 0: the register form (EXACT: C == CMAX); CMAX == 0: the general form
 template <class T, int LOAD, int CMAX, bool EXACT>
 __global__ __launch_bounds__(kThreads) void pixcal_kernel(CalArgs a) {

@@ -137,6 +137,18 @@ __device__ __forceinline__ int staged_pixels(const MapView& v, int64_t p0, int t
   }
 }
 
+// ---- one lane, one class plane (pixel_calibration.hip, pixel_sml.hip) -----------------------------------------------------------
+// the logits of class plane p for a lane's pixels: four neighbouring pixels in the vector form, one otherwise
+template <class T, int LOAD>
+__device__ __forceinline__ void load_px(const typename T::elem* p, float* x) {
+  if constexpr (LOAD == kLoadVec) {
+    if constexpr (T::kBytes == 4) ld16<T>(p, x);
+    else ld8<T>(p, x);
+  } else {
+    x[0] = ld1<T>(p);
+  }
+}
+
 // ---- host side --------------------------------------------------------------------------------------------------------------------
 constexpr int64_t kLim = 0x7fffffffll;
 

@@ -42,6 +42,14 @@ from .pixel_knn import (  # noqa: F401
     get_pixel_knn_maps,
     kcenter_greedy,
 )
+from .pixel_sml import (  # noqa: F401
+    PIXEL_SML_OUTPUTS,
+    PixelSML,
+    PixelSMLAccumulator,
+    fit_pixel_sml,
+    get_pixel_sml_maps,
+    suppress_and_smooth,
+)
 from .postprocessors import (  # noqa: F401
     ASH,
     DDU,

@@ -1466,6 +1466,48 @@ int runia_pixel_boundary_smooth_f32(const float* score, const int32_t* label, in
                                     const float* taps, float* out, void* workspace, size_t workspace_bytes,
                                     runia_stream_t stream);
 
+/* ---- sample-consistency scores of LLM generations (llm_uncertainty/consistency.py; csrc/consistency.hip) ----
+ * Black-box scores from the sampled token ids alone: lexical similarity (mean pairwise ROUGE-L, Fomicheva et al. 2020) and
+ * NumSet / Deg / Ecc / EigV over a pairwise similarity (Lin, Trivedi and Sun 2023).  Rows are prompt-major: group g = rows
+ * g*k .. g*k+k-1.
+ * runia_cons_pairs: ids holds groups * k rows of T ids, id_bytes 4 (int32) or 8 (int64, compared on all 64 bits), row_stride
+ *   and col_stride in elements (both >= 0: sequences[:, start:] is passed as a view).  The content of a row ends before its
+ *   first id that equals one of eos[0 .. n_eos-1] (int64, device; n_eos <= RUNIA_CONS_MAX_EOS, 0: none) and at lengths[row]
+ *   (int64, device, nullable; clamped to [0, T]).  `what` = RUNIA_CONS_LCS | RUNIA_CONS_JACCARD selects the tables (int32):
+ *     len   [groups * k]     content length n_i (always written);
+ *     lcs   [groups, k, k]   length of the longest common subsequence of contents i and j, lcs[i, i] = n_i;
+ *     uniq  [groups * k]     distinct ids of content i;          inter [groups, k, k]  distinct ids common to i and j.
+ *   One wave per row (len), per unordered pair (lcs: the longer content across the lanes in registers, the shorter walked
+ *   one wave-uniform id per step, row = prefix-max of the candidates; inter: binary search in the sorted distinct ids), one
+ *   workgroup per row for the sort (bitonic in LDS, duplicates dropped).  Two launches for lcs, three for Jaccard, no
+ *   synchronisation, no atomics: an entry depends on its own two rows only and two calls give equal bits.
+ *   workspace: runia_cons_pairs_workspace_bytes(groups, k, T, what) bytes (the sorted distinct ids; 0 without
+ *   RUNIA_CONS_JACCARD; the query returns int64_t), 8-byte aligned (RUNIA_E_WORKSPACE if missing or short).
+ *   2 <= k <= RUNIA_CONS_MAX_K, 0 <= T <= RUNIA_CONS_MAX_T, groups >= 1, groups * k * k < 2^31; RUNIA_E_INVALID otherwise.
+ * runia_cons_graph: W [groups, k, k] f64, contiguous; only the upper triangle is read and the diagonal is taken as 1.  With
+ *   d_i = sum_j w_ij and L = I - D^-1/2 W D^-1/2 (eigenvalues lambda ascending, cyclic Jacobi in LDS with eigenvectors,
+ *   eigen_score_kernel's rotation rule, ordering and stopping rule):
+ *     eigenvalues [groups, k];  lexsim = mean_{i<j} w_ij;  u_deg = 1 - sum_ij w_ij / k^2;  c_deg[i] = d_i / k;
+ *     u_eigv = sum_r max(0, 1 - lambda_r);  with s_i = the norm of row i of the eigenvectors of lambda < eigv_threshold,
+ *     centred over the rows: c_ecc[i] = -s_i, u_ecc = sqrt(sum_i s_i^2);
+ *     num_sets (int32) = connected components of the graph {w_ij >= set_threshold}.
+ *   One workgroup per group, one launch, no atomics: a group's bits depend on that group alone.  A non-finite entry in the
+ *   upper triangle of a group makes all its float outputs NaN and num_sets -1; a group still rotating after 30 sweeps gets
+ *   NaN in eigenvalues, u_eigv, u_ecc and c_ecc.  2 <= k <= RUNIA_CONS_MAX_K, 1 <= groups < 2^31; RUNIA_E_INVALID otherwise. */
+#define RUNIA_CONS_MAX_K 64
+#define RUNIA_CONS_MAX_T 4096
+#define RUNIA_CONS_MAX_EOS 16
+#define RUNIA_CONS_LCS 1
+#define RUNIA_CONS_JACCARD 2
+int64_t runia_cons_pairs_workspace_bytes(int64_t groups, int64_t k, int64_t T, int what);
+int runia_cons_pairs(const void* ids, int id_bytes, int64_t groups, int64_t k, int64_t T, int64_t row_stride,
+                     int64_t col_stride, const int64_t* eos, int n_eos, const int64_t* lengths, int what, int32_t* len,
+                     int32_t* lcs, int32_t* uniq, int32_t* inter, void* workspace, size_t workspace_bytes,
+                     runia_stream_t stream);
+int runia_cons_graph(const double* W, int64_t groups, int64_t k, double eigv_threshold, double set_threshold,
+                     double* eigenvalues, double* u_deg, double* u_eigv, double* u_ecc, double* lexsim, double* c_deg,
+                     double* c_ecc, int32_t* num_sets, runia_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -2501,6 +2501,51 @@ def eigen_scores(e: torch.Tensor, k: int, alpha: float = 1e-3) -> torch.Tensor:
     return out.cpu() if on_host else out
 
 
+CONS_MAX_K = _HEADER_MACROS["RUNIA_CONS_MAX_K"]
+CONS_MAX_T = _HEADER_MACROS["RUNIA_CONS_MAX_T"]
+CONS_MAX_EOS = _HEADER_MACROS["RUNIA_CONS_MAX_EOS"]
+_CONS_LCS, _CONS_JACCARD = _HEADER_MACROS["RUNIA_CONS_LCS"], _HEADER_MACROS["RUNIA_CONS_JACCARD"]
+
+
+@_device_guard()
+def cons_pairs(ids: torch.Tensor, k: int, eos: Optional[torch.Tensor] = None, lengths: Optional[torch.Tensor] = None,
+               lcs: bool = True, jaccard: bool = True):
+    """ids [G * k, T] int32 / int64 on the GPU (any strides, read in place), eos [n] int64 and lengths [G * k] int64 device
+    tensors or None -> ``(len [G * k], lcs [G, k, k] | None, uniq [G * k] | None, inter [G, k, k] | None)`` int32 device
+    tensors: one call of ``runia_cons_pairs``.  The arguments are checked by ``llm_uncertainty.consistency``."""
+    require_gpu()
+    assert ids.is_cuda and ids.dim() == 2 and ids.dtype in (torch.int32, torch.int64) and (lcs or jaccard)
+    rows, t = (int(v) for v in ids.shape)
+    g = rows // k
+    what = (_CONS_LCS if lcs else 0) | (_CONS_JACCARD if jaccard else 0)
+    i32 = lambda *shape: torch.empty(shape, dtype=torch.int32, device=ids.device)  # noqa: E731
+    ln = i32(rows)
+    lc = i32(g, k, k) if lcs else None
+    uq, it = (i32(rows), i32(g, k, k)) if jaccard else (None, None)
+    ws_bytes = query("runia_cons_pairs_workspace_bytes", g, k, t, what)
+    ws = workspace(ws_bytes, ids.device)
+    launch("runia_cons_pairs", ids.data_ptr(), ids.element_size(), g, k, t, ids.stride(0), ids.stride(1), _ptr(eos),
+           0 if eos is None else int(eos.numel()), _ptr(lengths), what, ln.data_ptr(), _ptr(lc), _ptr(uq), _ptr(it),
+           ws.data_ptr(), ws_bytes)
+    return ln, lc, uq, it
+
+
+@_device_guard()
+def cons_graph(w: torch.Tensor, eigv_threshold: float, set_threshold: float):
+    """w [G, k, k] f64 contiguous on the GPU -> ``(eigenvalues [G, k], u_deg, u_eigv, u_ecc, lexsim [G], c_deg, c_ecc [G, k]``
+    f64, ``num_sets [G]`` int32): one launch of ``runia_cons_graph``."""
+    require_gpu()
+    assert w.is_cuda and w.dtype == torch.float64 and w.dim() == 3 and w.shape[1] == w.shape[2] and w.is_contiguous()
+    g, k = int(w.shape[0]), int(w.shape[1])
+    f64 = lambda *shape: torch.empty(shape, dtype=torch.float64, device=w.device)  # noqa: E731
+    lam, u_deg, u_eigv, u_ecc, lexsim, c_deg, c_ecc = f64(g, k), f64(g), f64(g), f64(g), f64(g), f64(g, k), f64(g, k)
+    sets = torch.empty(g, dtype=torch.int32, device=w.device)
+    launch("runia_cons_graph", w.data_ptr(), g, k, float(eigv_threshold), float(set_threshold), lam.data_ptr(),
+           u_deg.data_ptr(), u_eigv.data_ptr(), u_ecc.data_ptr(), lexsim.data_ptr(), c_deg.data_ptr(), c_ecc.data_ptr(),
+           sets.data_ptr())
+    return lam, u_deg, u_eigv, u_ecc, lexsim, c_deg, c_ecc, sets
+
+
 @_device_guard("boxes", "batch_idx")
 def roi_align(x: torch.Tensor, boxes: torch.Tensor, output_size, spatial_scale: float = 1.0, sampling_ratio: int = -1,
               aligned: bool = False, batch_idx: Optional[torch.Tensor] = None) -> torch.Tensor:

@@ -9,7 +9,9 @@ made with the same keyword arguments and every score comes from this package's d
 - ``RAUQ``: the deterministic log-probs of that pass and the attention maps, read in place (``RAUQ`` / ``rauq_batch``);
 - ``normalized_entropy``: ``generation_scores`` of the sampled output;
 - ``eigen_score``: ``eigen_scores`` (one launch of ``runia_eigen_score_batch`` for every prompt's sample group);
-- ``semantic_entropy``: the host function of ``.scores`` with the NLI model (its forward passes are the cost).
+- ``semantic_entropy``: the host function of ``.scores`` with the NLI model (its forward passes are the cost);
+- ``lexical_similarity``, ``deg``, ``ecc``, ``eigv``, ``num_sets``: the sample-consistency scores of ``.consistency`` from the
+  sampled ids alone (one ``runia_cons_pairs`` call and one ``runia_cons_graph`` launch per call, shared by the requests).
 
 ``model.compute_transition_scores`` is not called.  ``entailment=(nli_model, nli_tokenizer)`` is this package's
 addition: without it a ``semantic_entropy`` request loads ``microsoft/deberta-v2-xxlarge-mnli`` by name, as the
@@ -22,6 +24,7 @@ from typing import Any, Dict, List, Optional, Sequence, Tuple
 import torch
 
 from .. import _hip
+from .consistency import SIMILARITIES, scores_by_kind
 from .logits import generation_scores
 from .rauq import RAUQ, generated_lengths, rauq_batch
 from .scores import eigen_score, semantic_entropy
@@ -29,7 +32,11 @@ from .scores import eigen_score, semantic_entropy
 __all__ = ["eigen_scores", "compute_uncertainties", "compute_uncertainties_batch"]
 
 _NEEDS_SAMPLING = {"eigen_score": True, "normalized_entropy": True, "semantic_entropy": True, "perplexity": False,
-                   "generation_entropy": False, "RAUQ": False}
+                   "generation_entropy": False, "RAUQ": False, "lexical_similarity": True, "deg": True, "ecc": True,
+                   "eigv": True, "num_sets": True}
+# request name -> field of ConsistencyScores
+_CONSISTENCY = {"lexical_similarity": "lexical_similarity", "deg": "u_deg", "ecc": "u_ecc", "eigv": "u_eigv",
+                "num_sets": "num_sets"}
 _NLI_MODEL = "microsoft/deberta-v2-xxlarge-mnli"
 
 
@@ -65,7 +72,19 @@ def _score_name(req: Dict[str, Any]) -> str:
         raise KeyError(method)
     if method == "RAUQ":
         return f"RAUQ_{req['token_aggregation']}_{req['head_aggregation']}"
+    if method in _CONSISTENCY:
+        similarity = req.get("similarity", SIMILARITIES[0])
+        if similarity not in SIMILARITIES:
+            raise KeyError(similarity)
+        return method if similarity == SIMILARITIES[0] else f"{method}_{similarity}"
     return method
+
+
+def _consistency(requests, samp, input_length: int, num_samples: int, eos):
+    """``{similarity: ConsistencyScores}`` of the sampled rows for every similarity the requests name: one count call and
+    one graph launch, whatever the number of requests."""
+    kinds = [req.get("similarity", SIMILARITIES[0]) for req in requests if req["method_name"] in _CONSISTENCY]
+    return scores_by_kind(samp.sequences[:, input_length:], num_samples, kinds, eos_token_id=eos)
 
 
 def _entailment_models(entailment, requests):
@@ -100,8 +119,10 @@ def compute_uncertainties(model, tokenizer, prompt: str, uncertainty_requests: L
     """Generate for ``prompt`` and compute the requested uncertainty scores (reference ``compute_uncertainties``).
 
     ``uncertainty_requests``: dicts with ``method_name`` in eigen_score, normalized_entropy, semantic_entropy, perplexity,
-    generation_entropy, RAUQ; a RAUQ request also names ``token_aggregation`` and ``head_aggregation`` and may give
-    ``alphas`` (default [0.3]) and ``ablation`` (default False).  Returns ``(deterministic_text, scores)``: the text as
+    generation_entropy, RAUQ, lexical_similarity, deg, ecc, eigv, num_sets (the last five: sample consistency of the sampled
+    ids, ``.consistency``; an optional ``"similarity"`` of ``"rouge_l"`` (default) or ``"jaccard"``, which is appended to the
+    key when it is not the default; ``num_sets`` is an int); a RAUQ request also names ``token_aggregation`` and
+    ``head_aggregation`` and may give ``alphas`` (default [0.3]) and ``ablation`` (default False).  Returns ``(deterministic_text, scores)``: the text as
     the reference returns it (a list of one string) and ``{key: score}`` with keys ``method_name`` or
     ``RAUQ_<token_aggregation>_<head_aggregation>``, Python floats (a list for RAUQ with ``ablation=True``), plus
     ``"clusters"`` = ``{text: cluster}`` when semantic entropy is requested.  ``entailment``: the NLI ``(model,
@@ -139,6 +160,12 @@ def compute_uncertainties(model, tokenizer, prompt: str, uncertainty_requests: L
             scores[name] = generation_scores(samp.sequences, samp.scores).normalized_entropy
         elif method == "eigen_score":
             scores[name] = float(eigen_scores(samp.hidden_states, num_samples)[0])
+        elif method in _CONSISTENCY:
+            if "cons" not in cache:
+                cache["cons"] = _consistency(uncertainty_requests, samp, input_length, num_samples,
+                                             _eos_ids(model, gen_config))
+            value = getattr(cache["cons"][req.get("similarity", SIMILARITIES[0])], _CONSISTENCY[method])[0]
+            scores[name] = int(value) if method == "num_sets" else float(value)
         else:  # semantic_entropy
             entropy, clusters = semantic_entropy(nli_model, nli_tokenizer, sampled_texts)
             scores["clusters"] = {sampled_texts[i]: c for c, members in clusters.items() for i in members}
@@ -173,7 +200,8 @@ def compute_uncertainties_batch(model, tokenizer, prompts: Sequence[str], uncert
     deterministic row b cut at its ``generated_lengths`` (through the first eos of ``gen_config`` or
     ``model.generation_config``; every step without one) for perplexity, generation entropy (masked means on the device)
     and RAUQ (``rauq_batch`` with the attention mask), and sample rows ``b*K .. b*K+K-1`` for normalized entropy, eigen
-    score (one ``eigen_scores`` call for all prompts) and semantic entropy.  A batch is not promised to equal B separate
+    score (one ``eigen_scores`` call for all prompts), semantic entropy and the sample-consistency scores (one count call and
+    one graph launch for all prompts; ``num_sets`` comes back as int64).  A batch is not promised to equal B separate
     ``compute_uncertainties`` calls: left padding changes what the model generates."""
     prompts = list(prompts)
     if not prompts or not all(isinstance(p, str) for p in prompts):
@@ -241,6 +269,11 @@ def compute_uncertainties_batch(model, tokenizer, prompts: Sequence[str], uncert
             scores[name] = (-rows.view(B, K).mean(dim=1)).cpu()
         elif method == "eigen_score":
             scores[name] = eigen_scores(samp.hidden_states, K).cpu()
+        elif method in _CONSISTENCY:
+            if "cons" not in cache:
+                cache["cons"] = _consistency(uncertainty_requests, samp, input_length, K, _eos_ids(model, gen_config))
+            value = getattr(cache["cons"][req.get("similarity", SIMILARITIES[0])], _CONSISTENCY[method]).cpu()
+            scores[name] = value.to(torch.int64) if method == "num_sets" else value
         else:  # semantic_entropy
             ent, groups = [], []
             for b in range(B):

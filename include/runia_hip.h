@@ -1508,6 +1508,50 @@ int runia_cons_graph(const double* W, int64_t groups, int64_t k, double eigv_thr
                      double* eigenvalues, double* u_deg, double* u_eigv, double* u_ecc, double* lexsim, double* c_deg,
                      double* c_ecc, int32_t* num_sets, runia_stream_t stream);
 
+/* ---- anomaly maps of a mask classifier: RbA, max score, EAM (mask_level.hip; inference/mask_level.py) ----------- *
+ * A mask classifier (MaskFormer, Mask2Former) gives Q class rows and Q low-resolution mask maps per image.  The reference
+ * project has no such scores; this is the definition.
+ *   class_logits (G, Q, Kc) through the element strides cg, cq, ck; Kc = K + 1 with has_void (the last column is "no object"),
+ *   Kc = K without.  mask_logits (G, Q, h, w) through sn, sc, sh, sw.  Both f32 / f16 / bf16 (`*_dtype` 0, 1, 2), read in place,
+ *   widened exactly, no f32 copy.  Target size (H, W), any ratio to (h, w).
+ * class weights  P[g,q,k] = softmax_j(class_logits[g,q,:])[k], k < K: max-subtracted (the maximum skips NaNs, which then come
+ *   back through exp), e_j = exp(x_j - max), the sum over ascending j in f32, P = e_k / sum.  a[g,q] = max_{k<K} P[g,q,k] (NaN if
+ *   one is).
+ * upsample  bilinear in logit space, the align_corners=False geometry of F.interpolate with the coordinates in integers:
+ *   n = max((2Y + 1) h - H, 0), y0 = n div 2H, ly = (n mod 2H) / 2H rounded once to f32, y1 = min(y0 + 1, h - 1); x likewise.
+ *   u = (1 - ly) ((1 - lx) m00 + lx m01) + ly ((1 - lx) m10 + lx m11), every operation rounded to f32, none contracted.  All four
+ *   taps enter whatever the weights are (0 * inf = NaN, as in torch).  (H, W) == (h, w): u = m itself, no arithmetic.
+ * sigmoid   s = 1 / (1 + exp(-u)) with the device's exp2-based exp and its reciprocal: exactly 0 and 1 at saturation, NaN for NaN.
+ * scores    S[g,k,Y,X] = sum_q P[g,q,k] s[g,q,Y,X] over ascending q as an f32 fma chain (v_mfma_f32_32x32x2_f32).
+ * outputs (each may be NULL, at least one set; (G, H, W) contiguous):
+ *   rba f32       -sum_{k<K} tanh(S_k): the rows k with (k >> 2) even in ascending order, those with (k >> 2) odd likewise, then
+ *                 the first sum plus the second.  Higher = anomalous.
+ *   max_score f32 max_{k<K} S_k; NaN if an S_k is.  (Mask2Anomaly's score is 1 - max_score.)
+ *   label int32   the lowest k attaining the max; -1 when the max is NaN.
+ *   eam f32       -sum_q a[g,q] s[g,q,Y,X] (row K of the same product).  Higher = anomalous.
+ *   semseg f32    (G, K, H, W) contiguous: S itself.
+ *   A NaN mask logit makes the scores of the pixels whose four taps touch it NaN, and no others; a NaN class logit those of
+ *   its own image.  No atomics, every sum in a fixed order: two calls give the same bits, and so does any subset of outputs.
+ * Two launches: the prologue writes the weights Wt[g][row][q] (rows 0 .. K - 1 = P, row K = a, rows and q zero-padded to
+ *   multiples of 32) and the interpolation tables (y0, ly)[H], (x0, lx)[W] into the workspace; the main launch gives a workgroup
+ *   128 consecutive pixels of ONE image.
+ * 1 <= K <= RUNIA_MASKQ_MAX_CLASSES, 1 <= Q <= RUNIA_MASKQ_MAX_QUERIES, G < 2^31, h, w, H, W <= RUNIA_MASKQ_MAX_SIDE (ly and lx
+ *   are then one correctly rounded f32 division), G * H * W <= 2^RUNIA_MASKQ_MAX_PIXELS_LOG2, strides >= 0, the plane of one
+ *   query spans fewer than 2^31 elements ((h - 1) sh + (w - 1) sw < 2^31); RUNIA_E_INVALID otherwise or for a missing pointer,
+ *   before anything is launched.  G == 0 or H * W == 0: 0, nothing launched (h * w == 0 with H * W > 0 is invalid).
+ *   workspace: runia_maskq_workspace_bytes(G, Q, K, H, W, h, w) bytes (0 for what the call refuses), 16-byte aligned,
+ *   uninitialised (RUNIA_E_WORKSPACE if missing or short). */
+#define RUNIA_MASKQ_MAX_CLASSES 255
+#define RUNIA_MASKQ_MAX_QUERIES 1024
+#define RUNIA_MASKQ_MAX_SIDE (1 << 23)
+#define RUNIA_MASKQ_MAX_PIXELS_LOG2 34
+int64_t runia_maskq_workspace_bytes(int64_t G, int64_t Q, int64_t K, int64_t H, int64_t W, int64_t h, int64_t w);
+int runia_maskq_maps(const void* class_logits, int class_dtype, int64_t cg, int64_t cq, int64_t ck, int has_void,
+                     const void* mask_logits, int mask_dtype, int64_t G, int64_t Q, int64_t K, int64_t h, int64_t w,
+                     int64_t sn, int64_t sc, int64_t sh, int64_t sw, int64_t H, int64_t W, float* rba, float* max_score,
+                     int32_t* label, float* eam, float* semseg, void* workspace, size_t workspace_bytes,
+                     runia_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

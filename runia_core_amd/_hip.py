@@ -1029,6 +1029,51 @@ def pixel_boundary_smooth(score: torch.Tensor, label: Optional[torch.Tensor], bo
     return out
 
 
+MASKQ_MAX_CLASSES = _HEADER_MACROS["RUNIA_MASKQ_MAX_CLASSES"]
+MASKQ_MAX_QUERIES = _HEADER_MACROS["RUNIA_MASKQ_MAX_QUERIES"]
+MASKQ_MAX_SIDE = _HEADER_MACROS["RUNIA_MASKQ_MAX_SIDE"]
+MASKQ_MAX_PIXELS = 1 << _HEADER_MACROS["RUNIA_MASKQ_MAX_PIXELS_LOG2"]
+MASKQ_MAX_PLANE_SPAN = (1 << 31) - 1   # (h - 1) sh + (w - 1) sw of the mask logits: the tap offsets are 32-bit
+MASKQ_OUTPUTS = ("rba", "max_score", "label", "eam", "semseg")
+
+
+@_device_guard()
+def maskq_maps(class_logits: torch.Tensor, mask_logits: torch.Tensor, size=None, outputs=("rba",),
+               has_void: bool = True) -> dict:
+    """The maps ``outputs`` (of ``MASKQ_OUTPUTS``) of a mask classifier's ``class_logits`` (G, Q, K + 1; (G, Q, K) without
+    ``has_void``) and ``mask_logits`` (G, Q, h, w), both f32 / f16 / bf16 device tensors read in place through their strides,
+    upsampled to ``size`` = (H, W) (None: (h, w)) - ``runia_maskq_maps``, two launches.  f32 (G, H, W) each, ``label`` int32,
+    ``semseg`` f32 (G, K, H, W)."""
+    for name, t, nd in (("class_logits", class_logits, 3), ("mask_logits", mask_logits, 4)):
+        assert t.is_cuda and t.dim() == nd and t.dtype in ELEM_DTYPE_CODES, \
+            f"{name}: a {nd}-dimensional device tensor of float32, float16 or bfloat16, got {tuple(t.shape)} {t.dtype}"
+    g, q, h, w = (int(v) for v in mask_logits.shape)
+    k = int(class_logits.shape[2]) - (1 if has_void else 0)
+    assert tuple(class_logits.shape[:2]) == (g, q) and 1 <= k <= MASKQ_MAX_CLASSES and 1 <= q <= MASKQ_MAX_QUERIES, \
+        f"class_logits {tuple(class_logits.shape)} against mask_logits {tuple(mask_logits.shape)}: the same G and Q, " \
+        f"1 .. {MASKQ_MAX_CLASSES} classes, 1 .. {MASKQ_MAX_QUERIES} queries"
+    big_h, big_w = (h, w) if size is None else (int(size[0]), int(size[1]))
+    names = tuple(outputs)
+    assert names and all(n in MASKQ_OUTPUTS for n in names), f"outputs: some of {MASKQ_OUTPUTS}, got {names}"
+    assert (h * w > 0 or big_h * big_w == 0) and 0 <= big_h <= MASKQ_MAX_SIDE and 0 <= big_w <= MASKQ_MAX_SIDE and \
+        g * big_h * big_w <= MASKQ_MAX_PIXELS, f"size {(big_h, big_w)} of {g} images from {(h, w)}"
+    dev = mask_logits.device
+    out = {n: torch.empty((g, k, big_h, big_w) if n == "semseg" else (g, big_h, big_w),
+                          dtype=torch.int32 if n == "label" else torch.float32, device=dev) for n in names}
+    require_gpu()
+    if g == 0 or big_h * big_w == 0:
+        return out
+    cg, cq, ck = (int(v) for v in class_logits.stride())
+    sn, sc, sh, sw = (int(v) for v in mask_logits.stride())
+    ws_bytes = query("runia_maskq_workspace_bytes", g, q, k, big_h, big_w, h, w)
+    ws = workspace(ws_bytes, dev)
+    launch("runia_maskq_maps", class_logits.data_ptr(), ELEM_DTYPE_CODES[class_logits.dtype], cg, cq, ck, 1 if has_void else 0,
+           mask_logits.data_ptr(), ELEM_DTYPE_CODES[mask_logits.dtype], g, q, k, h, w, sn, sc, sh, sw, big_h, big_w,
+           _ptr(out.get("rba")), _ptr(out.get("max_score")), _ptr(out.get("label")), _ptr(out.get("eam")),
+           _ptr(out.get("semseg")), ws.data_ptr(), ws_bytes)
+    return out
+
+
 CONFORMAL_METHODS = {"lac": 0, "aps": 1, "raps": 2}  # `method` of the runia_conformal_* entry points
 
 

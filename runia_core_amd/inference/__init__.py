@@ -50,6 +50,11 @@ from .pixel_sml import (  # noqa: F401
     get_pixel_sml_maps,
     suppress_and_smooth,
 )
+from .mask_level import (  # noqa: F401
+    MASK_MAP_OUTPUTS,
+    get_mask_anomaly_maps,
+    mask_anomaly_maps,
+)
 from .postprocessors import (  # noqa: F401
     ASH,
     DDU,

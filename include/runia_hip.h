@@ -51,6 +51,23 @@ int runia_clock_probe(uint64_t* out4, int chain, runia_stream_t stream);
  * - they then carry the kernel's own start and end timestamps, as rocprofv3's kernel trace does, without the dispatch gap an
  * event pair recorded around the launch includes.  Both events must exist (have been recorded once); (NULL, NULL) clears. */
 int runia_time_next_launch(void* start_event, void* stop_event);
+/* The ordered keys of the kernels (csrc/order.hpp) on HOST memory, through the same header code, no GPU touched; pins the key
+ * layer.  values: f32 or f64 [n] (is_f64); keys: uint64 [n], a 32-bit key zero-extended, the signed one as its two's complement;
+ * back (or NULL): [n] of the values' type, the inverse of every key.
+ *   ASC / DESC             by the bits alone: -0 next to +0 on the smaller value's side, a NaN by its sign and payload;
+ *   ASC_FOLD / DESC_FOLD   -0 on the key of +0;
+ *   DESC_ONE_NAN           f64: DESC_FOLD with every NaN on the key of the positive quiet NaN, in front of +inf's;
+ *   DESC_SIGNED            f64: DESC_FOLD as int64 of the same order (runia_sel_key_of_f64_host);
+ *   ASC_NONNEG             f32: ASC without the sign test, for values >= +0.
+ * RUNIA_E_INVALID for a form of the other width. */
+#define RUNIA_ORDER_ASC 0
+#define RUNIA_ORDER_DESC 1
+#define RUNIA_ORDER_ASC_FOLD 2
+#define RUNIA_ORDER_DESC_FOLD 3
+#define RUNIA_ORDER_DESC_ONE_NAN 4
+#define RUNIA_ORDER_DESC_SIGNED 5
+#define RUNIA_ORDER_ASC_NONNEG 6
+int runia_order_keys_host(const void* values, int64_t n, int is_f64, int form, uint64_t* keys, void* back);
 
 /* ---- a1  MC-dropout latent stacking ------------------------------------- *
  * Replaces MCSamplerModule.forward (feature_extraction/abstract_classes.py:81-101)

@@ -2147,6 +2147,22 @@ def sel_key_of_host(confidence: float) -> int:
     return query("runia_sel_key_of_f64_host", float(confidence))
 
 
+ORDER_FORMS = {f: _HEADER_MACROS["RUNIA_ORDER_" + f.upper()]
+               for f in ("asc", "desc", "asc_fold", "desc_fold", "desc_one_nan", "desc_signed", "asc_nonneg")}
+
+
+def order_keys_host(values: np.ndarray, form: str) -> Tuple[np.ndarray, np.ndarray]:
+    """``(keys uint64 [n], back [n])``: the ordered key of csrc/order.hpp of every float32 / float64 value under one of
+    :data:`ORDER_FORMS`, and the inverse of every key in the values' dtype (``runia_order_keys_host``: plain host code over the
+    kernels' header, no GPU touched)."""
+    v = np.ascontiguousarray(values)
+    assert v.ndim == 1 and v.dtype in (np.float32, np.float64), "values: a 1-D float32 or float64 array"
+    keys, back = np.empty(v.shape, dtype=np.uint64), np.empty_like(v)
+    call("runia_order_keys_host", v.ctypes.data, v.size, int(v.dtype == np.float64), ORDER_FORMS[form], keys.ctypes.data,
+         back.ctypes.data)
+    return keys, back
+
+
 class SelOrder(NamedTuple):
     """A confidence table ordered for :func:`sel_curve`: ``keys`` int64 [n] ascending (= descending confidence), ``rows`` int32 [n]
     the row of every key - the shape of :class:`BootOrder` - and ``bad`` [1] (device): whether any confidence is NaN."""

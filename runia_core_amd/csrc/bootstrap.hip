@@ -36,15 +36,6 @@ typedef unsigned long long u64;
 
 // ---- keys -----------------------------------------------------------------------------------------------------------------
 template <typename T>
-__device__ __forceinline__ int64_t boot_key(T v, bool squash) {
-  if (squash) v = (T)1 / ((T)1 + exp(-v));  // torch.sigmoid in the dtype of the scores (metrics.hip: score_key)
-  uint64_t b = (uint64_t)__double_as_longlong((double)v + 0.0);  // (-0.0 and +0.0 share a key)
-  if (v != v) b = 0x7ff8000000000000ull;  // every NaN, of either sign and any payload: one key in front of +inf's (as score_key)
-  b = (b >> 63) ? ~b : (b | 0x8000000000000000ull);              // ascending-sortable
-  return (int64_t)(~b ^ 0x8000000000000000ull);                  // descending, as a signed number
-}
-
-template <typename T>
 __global__ __launch_bounds__(256) void boot_probe_kernel(const T* __restrict__ ind, int64_t n_ind, const T* __restrict__ ood,
                                                          int64_t n_ood, unsigned* __restrict__ any_outside) {
   const int64_t n = n_ind + n_ood;
@@ -63,7 +54,7 @@ __global__ __launch_bounds__(256) void boot_keys_kernel(const T* __restrict__ in
   const int64_t n = n_ind + n_ood;
   const bool squash = *any_outside != 0u;
   for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (int64_t)gridDim.x * 256)
-    keys[i] = boot_key<T>((i < n_ind) ? ind[i] : ood[i - n_ind], squash);
+    keys[i] = signed_view(score_key<T>((i < n_ind) ? ind[i] : ood[i - n_ind], squash));  // the key of metrics.hip, for a sort of int64
 }
 
 template <typename T>

@@ -7,6 +7,7 @@
 #include <atomic>
 
 #include "../../include/runia_hip.h"
+#include "order.hpp"
 #include "wave.hpp"
 #include "workspace.hpp"
 

@@ -1,7 +1,7 @@
 // Conformal prediction sets (evaluation/conformal.py): LAC, APS and RAPS scores from one read of the logits.
 //   runia_conformal_label_scores: the score s_y and the rank r_y of every row's label (the calibration half: no sort)
 //   runia_conformal_sets        : the set {c : s_c <= qhat} of every row: its size, its members as packed bits, whether it holds
-//                                 the label.  The row is ordered inside the workgroup by a bitonic network over LDS.
+//                                 the label.  The row is ordered inside the workgroup in LDS (order.hpp).
 //   runia_conformal_reduce      : size / covered / labels -> an integer record (counts, size histogram, per-class counts)
 // With m the row maximum, e_k = exp(beta (x_k - m)), S0 = sum e_k, p_k = e_k / S0; classes ordered by logit, descending, equal
 // logits by lower index first; r_c the 1-based rank of c and B_c the sum of p_k over the classes ordered before c:
@@ -204,7 +204,7 @@ int launch_label(const void* logits, int64_t stride, const Labels& L, const floa
 // two) slots per row in LDS: key[P] (uint32: ascending key order is descending logit order), idx[P] (uint16), then the set's
 // bits.  Every thread of the workgroup meets every barrier: P and the trip counts depend on C alone.
 //   1. load: slot i <- class i (coalesced), the padding slots sort last; the group's maximum and NaN flag
-//   2. order (aps, raps): the bitonic network on (key, idx) over LDS, P / 2 compare-exchanges per step
+//   2. order (aps, raps): lds_bitonic_sort on (key, idx), P / 2 compare-exchanges per step
 //   3. sums: a thread owns P / TPR consecutive slots: e of each (written over the key), the thread's sum, the group's exclusive
 //      scan of those sums -> S0 and the thread's offset
 //   4. sets: s of each slot from the running sum, the compare with qhat, the bit of its class (integer atomic-or in LDS)
@@ -313,23 +313,13 @@ __global__ __launch_bounds__(256) void conformal_sets_kernel(const typename T::e
     __syncthreads();
     // 2. order
     if (M.kind != kLac) {
-      for (int k2 = 2; k2 <= P; k2 <<= 1) {
-        for (int j = k2 >> 1; j > 0; j >>= 1) {
-          for (int h = t; h < (P >> 1); h += TPR) {
-            const int lo = ((h & ~(j - 1)) << 1) | (h & (j - 1)), hi = lo | j;
-            const uint32_t ka = key[lo], kb = key[hi];
-            const uint32_t ia = idx[lo], ib = idx[hi];
-            const bool a_after_b = ka > kb || (ka == kb && ia > ib);
-            if (a_after_b == ((lo & k2) == 0)) {
-              key[lo] = kb;
-              key[hi] = ka;
-              idx[lo] = (uint16_t)ib;
-              idx[hi] = (uint16_t)ia;
-            }
-          }
-          __syncthreads();
+      lds_bitonic_sort(P, t, TPR, [&](int lo, int hi, bool up) {
+        const uint32_t ka = key[lo], kb = key[hi], ia = idx[lo], ib = idx[hi];
+        if ((ka > kb || (ka == kb && ia > ib)) == up) {  // a after b: by key, ties by index
+          key[lo] = kb, key[hi] = ka;
+          idx[lo] = (uint16_t)ib, idx[hi] = (uint16_t)ia;
         }
-      }
+      });
     }
     // 3. sums
     float mine = 0.f;

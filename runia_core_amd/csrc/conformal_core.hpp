@@ -45,15 +45,9 @@ __device__ __forceinline__ float score_of(const Method& M, float p, float B, flo
   return s + M.lam * (float)(over > 0 ? over : 0);
 }
 
-// uint32 key of a logit: ascending key order is descending logit order
-__device__ __forceinline__ uint32_t descending_key(float x) {
-  x = (x == 0.f) ? 0.f : x;  // -0 and +0 are equal logits
-  const uint32_t b = __float_as_uint(x);
-  return (b & 0x80000000u) ? b : (b ^ 0x7fffffffu);  // ~(orderable ascending key)
-}
-__device__ __forceinline__ float key_logit(uint32_t k) {
-  return __uint_as_float((k & 0x80000000u) ? k : (k ^ 0x7fffffffu));
-}
+// uint32 key of a logit: ascending key order is descending logit order; -0 and +0 are equal logits
+__device__ __forceinline__ uint32_t descending_key(float x) { return desc_key(fold_zero(x)); }
+__device__ __forceinline__ float key_logit(uint32_t k) { return desc_value(k); }
 
 static inline bool method_ok(int method, float beta, float lam, int k_reg) {
   return method >= kLac && method <= kRaps && beta > 0.f && beta < INFINITY && lam >= 0.f && lam < INFINITY && k_reg >= 0;

@@ -13,9 +13,9 @@
 //            rows are non-decreasing: a serial pass over the lane's own columns, one wave_scan_incl (max) of the lane
 //            totals, one pass to fold the lanes before.  Columns past the content are never read back: a prefix only
 //            flows to the right.  int64 ids are compared on all 64 bits.
-//   sort     one workgroup per row: the content as int64 in LDS (32 KB), a bitonic network whose comparators all put
-//            the minimum at the lower index (mirror stage, then half-cleaners), so the slots past n act as +inf without
-//            being stored - ids have no spare value for a sentinel; duplicates are dropped by a block scan of the
+//   sort     one workgroup per row: the content as int64 in LDS (32 KB), padded to a power of two with INT64_MAX (an id
+//            of that value ties with the padding; only the first n sorted slots are read) and sorted by the LDS sort of
+//            order.hpp; duplicates are dropped by a block scan of the
 //            "differs from its left neighbour" flags.  The distinct ids go to the workspace in ascending order; writes
 //            uniq and the diagonal inter[i, i].
 //   inter    one wave per unordered pair: the lanes take the distinct ids of the smaller set and search the larger one
@@ -38,6 +38,7 @@ constexpr int kThreads = 256;
 constexpr int kWaves = kThreads / 64;
 constexpr int kMaxK = RUNIA_CONS_MAX_K;
 constexpr int kMaxT = RUNIA_CONS_MAX_T;
+static_assert((kMaxT & (kMaxT - 1)) == 0, "cons_sort_kernel pads a row to a power of two inside kMaxT slots");
 constexpr int kMaxSweeps = 30;
 
 // lane s of the wave (s wave-uniform) as a scalar
@@ -172,23 +173,11 @@ __global__ __launch_bounds__(kThreads) void cons_sort_kernel(const Id* __restric
   const int64_t row = blockIdx.x;
   const int n = len[row];
   const Id* r = ids + row * rs;
-  for (int c = tid; c < n; c += kThreads) a[c] = (int64_t)r[(int64_t)c * cs];
   int N = 1;
-  while (N < n) N <<= 1;
+  while (N < n) N <<= 1;  // <= kMaxT, a power of two
+  for (int c = tid; c < N; c += kThreads) a[c] = c < n ? (int64_t)r[(int64_t)c * cs] : INT64_MAX;  // the padding sorts last
   __syncthreads();
-  for (int kk = 2; kk <= N; kk <<= 1) {
-    for (int j = kk >> 1; j > 0; j >>= 1) {
-      for (int x = tid; x < N / 2; x += kThreads) {
-        const int lo = ((x & ~(j - 1)) << 1) | (x & (j - 1));         // bit j clear
-        const int hi = (j == kk >> 1) ? (lo ^ (kk - 1)) : (lo ^ j);  // mirror within the block, then half-cleaners
-        if (hi < n) {  // a slot past n holds +inf and keeps it
-          const int64_t v0 = a[lo], v1 = a[hi];
-          if (v0 > v1) { a[lo] = v1; a[hi] = v0; }
-        }
-      }
-      __syncthreads();
-    }
-  }
+  lds_bitonic_sort(a, N, tid, kThreads);
   const int per = (n + kThreads - 1) / kThreads;
   const int first = tid * per < n ? tid * per : n;
   const int end = first + per < n ? first + per : n;

@@ -15,11 +15,6 @@
 
 namespace {
 
-__device__ __forceinline__ unsigned sort_key_f32(float x) {  // ascending in x
-  const unsigned u = __float_as_uint(x);
-  return (u & 0x80000000u) ? ~u : (u | 0x80000000u);
-}
-
 // ---- pred_h / mi ---------------------------------------------------------------------------------------------------
 // One wave per image; lane l holds classes l, l + 64, ...; the rows of an image are n_mc consecutive rows of `logits`
 // (torch.split(samples, n_mc), image-major).  Arithmetic in f32 as torch (softmax = exp(x - max) / sum - exponentials and logarithms on the transcendental unit, ~1 ulp,
@@ -165,7 +160,7 @@ __global__ __launch_bounds__(256) void ash_s_rows_kernel(const float* x, float* 
         __syncthreads();
         const unsigned himask = (shift == 24) ? 0u : (0xFFFFFFFFu << (shift + 8));
         for (int64_t j = tid; j < D; j += 256) {
-          const unsigned key = sort_key_f32(p[j]);
+          const unsigned key = asc_key(p[j]);
           if ((key & himask) == prefix) atomicAdd(&hist[(key >> shift) & 255u], 1u);
         }
         __syncthreads();
@@ -201,7 +196,7 @@ __global__ __launch_bounds__(256) void ash_s_rows_kernel(const float* x, float* 
       for (int64_t j0 = 0; j0 < D; j0 += 256) {
         const int64_t j = j0 + tid;
         const float v = (j < D) ? p[j] : 0.f;
-        const unsigned key = (j < D) ? sort_key_f32(v) : 0u;
+        const unsigned key = (j < D) ? asc_key(v) : 0u;
         const bool tie = (k > 0) && (j < D) && key == thr;
         const unsigned long long mk = __ballot(tie);
         __syncthreads();
@@ -319,7 +314,7 @@ __global__ __launch_bounds__(256) void gen_wide_kernel(const float* __restrict__
         __syncthreads();
         const unsigned himask = (shift == 24) ? 0u : (0xFFFFFFFFu << (shift + 8));
         for (int64_t j = tid; j < C; j += 256) {
-          const unsigned key = __float_as_uint(prob(j)) | 0x80000000u;  // p >= 0
+          const unsigned key = asc_key_nonneg(prob(j));
           if ((key & himask) == prefix) atomicAdd(&hist[(key >> shift) & 255u], 1u);
         }
         __syncthreads();
@@ -341,10 +336,10 @@ __global__ __launch_bounds__(256) void gen_wide_kernel(const float* __restrict__
       // `want` of the entries equal to the threshold belong to the M largest
       for (int64_t j = tid; j < C; j += 256) {
         const float pv = prob(j);
-        if ((__float_as_uint(pv) | 0x80000000u) > prefix) acc += gen_term(pv, gamma);
+        if (asc_key_nonneg(pv) > prefix) acc += gen_term(pv, gamma);
       }
       acc = block_sum_f32(acc, red, tid);
-      const float pt = __uint_as_float(prefix & 0x7fffffffu);
+      const float pt = asc_value_nonneg(prefix);
       acc += (float)want * (gen_term(pt, gamma));
     }
     if (tid == 0) score[row] = -acc;

@@ -458,7 +458,7 @@ __global__ __launch_bounds__(256) void kth_select_range_kernel(float* __restrict
         const float d = drow[m];  // wave-uniform
         if (d >= lo && d <= hi) {
           const float acc = exact_sqdist_wave(qr, bank + knn_perm_row(m, pm) * D, D, lane);
-          if (lane == 0) drow[m] = __uint_as_float(__float_as_uint(acc) | 0x80000000u);
+          if (lane == 0) drow[m] = __uint_as_float(asc_key_nonneg(acc));  // (the key bit doubles as the "exact" mark)
         }
       }
       __threadfence_block();

@@ -4,7 +4,7 @@
 // walked in ascending order, v += m for a member of the first set of p and v -= n otherwise, and T[p, d] = max |v| over the last
 // positions of the runs of equal values: an exact integer <= n m (the KS statistic is T / (n m)).
 //   * ks_sort_kernel: one workgroup per column of the pass.  The column is read where it lies, turned into monotone u32 keys (-0
-//     folded into +0, NaN flagged), and (key, row) pairs are sorted in LDS by a bitonic network.  It writes, per sorted position,
+//     folded into +0, NaN flagged), and (key, row) pairs are sorted in LDS (order.hpp).  It writes, per sorted position,
 //     the row index with the run-end flag in bit 31, and the column's valid flag.
 //   * ks_transpose_kernel: the membership bits of shift.hip (row p, bit i) once per call as [N, words of 32 permutations], rows
 //     padded to whole groups of 8 words, so that the permutations of one sorted position are consecutive words.
@@ -58,24 +58,14 @@ __global__ __launch_bounds__(1024) void ks_sort_kernel(Cols c, int64_t d0, int n
     if (i < N) {
       const float v = col_value<T>(c, i, d);
       nan |= v != v;
-      uint32_t u = __float_as_uint(v);
-      if ((u & 0x7fffffffu) == 0u) u = 0u;               // -0 == +0
-      u = (u >> 31) ? ~u : (u | 0x80000000u);            // ascending as numbers; +-inf are ordinary extremes
-      e = ((unsigned long long)u << 32) | (unsigned long long)i;
+      // ascending as numbers, -0 == +0; +-inf are ordinary extremes
+      e = ((unsigned long long)asc_key(fold_zero(v)) << 32) | (unsigned long long)i;
     }
     s[i] = e;
   }
   if (nan) s_nan = 1;  // (every writer stores the same value)
   __syncthreads();
-  for (int k = 2; k <= np2; k <<= 1)
-    for (int j = k >> 1; j > 0; j >>= 1) {
-      for (int t = tid; t < (np2 >> 1); t += nt) {
-        const int lo = ((t & ~(j - 1)) << 1) | (t & (j - 1)), hi = lo | j;
-        const unsigned long long a = s[lo], b = s[hi];
-        if ((a > b) == ((lo & k) == 0)) { s[lo] = b; s[hi] = a; }
-      }
-      __syncthreads();
-    }
+  lds_bitonic_sort(s, np2, tid, nt);
   uint32_t* out = order + (int64_t)blockIdx.x * ord_stride;
   for (int k = tid; k < N; k += nt) {
     const unsigned long long e = s[k];

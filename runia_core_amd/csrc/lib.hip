@@ -63,3 +63,31 @@ extern "C" int runia_clock_probe(uint64_t* out4, int chain, runia_stream_t strea
   hipLaunchKernelGGL(clock_probe_kernel, dim3(1), dim3(64), 0, as_stream(stream), out4, chain);
   return runia_check_launch();
 }
+
+// ---- the key layer of order.hpp on host memory ---------------------------------------------------------------------------
+template <class F>
+static int order_keys_host(const F* v, int64_t n, int form, uint64_t* keys, F* back) {
+  for (int64_t i = 0; i < n; ++i) {
+    const F x = v[i], z = fold_zero(x), y = (form & 2) ? z : x;  // forms 0 .. 3: bit 0 descending, bit 1 folded
+    order_key_t<F> k;
+    F b;
+    if (form <= RUNIA_ORDER_DESC_FOLD) b = (form & 1) ? desc_value(k = desc_key(y)) : asc_value(k = asc_key(y));
+    else if constexpr (sizeof(F) == 8) {  // the two f64 forms
+      if (form == RUNIA_ORDER_DESC_ONE_NAN) b = desc_value(k = desc_key_one_nan(x));
+      else if (form == RUNIA_ORDER_DESC_SIGNED) b = desc_value(unsigned_view((int64_t)(k = (uint64_t)signed_view(desc_key(z)))));
+      else return RUNIA_E_INVALID;
+    } else {  // the f32 form
+      if (form != RUNIA_ORDER_ASC_NONNEG) return RUNIA_E_INVALID;
+      b = asc_value_nonneg(k = asc_key_nonneg(x));
+    }
+    keys[i] = k;
+    if (back) back[i] = b;
+  }
+  return RUNIA_OK;
+}
+
+extern "C" int runia_order_keys_host(const void* values, int64_t n, int is_f64, int form, uint64_t* keys, void* back) {
+  if (n < 0 || (n > 0 && (!values || !keys)) || form < RUNIA_ORDER_ASC || form > RUNIA_ORDER_ASC_NONNEG) return RUNIA_E_INVALID;
+  return is_f64 ? order_keys_host(static_cast<const double*>(values), n, form, keys, static_cast<double*>(back))
+                : order_keys_host(static_cast<const float*>(values), n, form, keys, static_cast<float*>(back));
+}

@@ -27,13 +27,6 @@ namespace {
 constexpr int kTile = METRICS_TILE;  // elements per workgroup in every pass
 constexpr int kItems = kTile / 256;
 
-__device__ __forceinline__ uint64_t sortable_desc(double v) {
-  // ascending order of the key == descending order of v (score_key gives every NaN one key in front of +inf's)
-  uint64_t b = (uint64_t)__double_as_longlong(v);
-  b = (b >> 63) ? ~b : (b | 0x8000000000000000ull);  // ascending-sortable
-  return ~b;
-}
-
 // ---- curve: cumulative positives and the previous run end of every run end ------------------------------------------------
 // tile pass 1: (label sum, index of the last run end) of every tile
 __device__ __forceinline__ void tile_summary_body(const uint64_t* __restrict__ keys, const uint8_t* __restrict__ lab,
@@ -285,14 +278,8 @@ struct MsdState {
 // Every NaN score - either sign, any payload - takes ONE key, that of the positive quiet NaN: the smallest key in use, in
 // front of +inf.  All NaNs are one tie group at the top of the descending order (one curve point), whatever sign the
 // sigmoid hands back; by its bits a NaN with the sign bit set would sort behind -inf and NaNs of two payloads would be
-// two runs.  (The key differs from the ~0 padding of wave_sort_load, which no score can produce any more.)
-constexpr uint64_t kNanKey = 0x0007ffffffffffffull;  // sortable_desc of 0x7ff8000000000000
-template <typename T>
-__device__ __forceinline__ uint64_t score_key(T v, bool squash) {
-  if (squash) v = (T)1 / ((T)1 + exp(-v));  // torch.sigmoid in the dtype of the scores
-  if (v != v) return kNanKey;
-  return sortable_desc((double)v + 0.0);     // (-0.0 and +0.0 share a key: one tie group, as torchmetrics)
-}
+// two runs.  (The key differs from the ~0 padding of wave_sort_load, which no score can produce any more.)  -0.0 and +0.0
+// share a key: one tie group, as torchmetrics.  That is score_key / kNanKey of order.hpp.
 
 template <typename T>
 __global__ __launch_bounds__(256) void msd_probe_kernel(const T* __restrict__ ind, int64_t n_ind, const T* __restrict__ ood,
@@ -373,11 +360,6 @@ __device__ __forceinline__ ProbeResult msd_reduce_probe(MsdState* st, unsigned n
 // monotone, so the range of the squashed scores is [sigmoid(smallest), sigmoid(largest)] - two exps per workgroup instead of
 // one per score in the probe.  The NaN key and +inf lie below every splitter and go to the first bucket, -inf to the last
 // (the sort inside a bucket uses the whole key).
-__device__ __forceinline__ double unkey(uint64_t k) {  // inverse of sortable_desc
-  uint64_t b = ~k;
-  b = (b >> 63) ? (b & 0x7fffffffffffffffull) : ~b;
-  return __longlong_as_double((long long)b);
-}
 // Round 5: the buckets are linear in the RAW score, not in the squashed one.  The sigmoid turns the smooth score sets the
 // postprocessors actually produce - LaREM's -chi2(256), LaRED's log-densities of -300 ... -2000, energies around 9 - into sets
 // crowded against 0 or 1: value-linear buckets of sigmoid(score) then put nearly every key into ONE bucket, which takes the
@@ -391,7 +373,7 @@ __device__ __forceinline__ MsdRange msd_range_of(unsigned long long nkmin, unsig
   MsdRange r{0.0, 0.0};
   const unsigned long long lo_k = ~nkmin, hi_k = kmax;
   if (lo_k > hi_k) return r;  // (no finite score)
-  const double v_hi = unkey(lo_k), v_lo = unkey(hi_k);  // largest / smallest finite raw score
+  const double v_hi = desc_value(lo_k), v_lo = desc_value(hi_k);  // largest / smallest finite raw score
   r.hi = v_hi;
   const double span = v_hi - v_lo;
   r.scale = (span > 0.0 && span < __builtin_inf()) ? (double)kMsdBuckets / span : 0.0;

@@ -20,15 +20,6 @@ constexpr int kCandThreads = 256;  // anchors per workgroup of the candidate ker
 constexpr int kSortThreads = 1024;
 constexpr int kWalkThreads = 256;
 
-// IEEE f32 -> uint32 that orders like the float, descending: larger score -> smaller key.  -0 is folded onto +0 (they
-// compare equal for torch.sort as well); a NaN sorts before +inf, where torch.sort(descending=True) puts it.
-__device__ __forceinline__ uint32_t desc_score_key(float s) {
-  if (s == 0.f) s = 0.f;
-  uint32_t u = __float_as_uint(s);
-  u = (u & 0x80000000u) ? ~u : (u | 0x80000000u);
-  return ~u;
-}
-
 __device__ __forceinline__ int64_t key_index(int64_t key) { return key & 0x7fffffff; }
 
 // ---- YOLOv8 candidates -------------------------------------------------------------------------------------------------
@@ -121,7 +112,8 @@ __global__ void __launch_bounds__(kCandThreads) yolo_compact_kernel(
 // ---- sort keys ---------------------------------------------------------------------------------------------------------
 __global__ void nms_keys_kernel(const float* __restrict__ scores, int64_t n, int64_t* __restrict__ keys) {
   for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x)
-    keys[i] = ((int64_t)desc_score_key(scores[i]) << 31) | i;
+    // larger score, smaller key; -0 on +0 (equal for torch.sort as well); a NaN before +inf, as torch.sort(descending=True)
+    keys[i] = ((int64_t)desc_key(fold_zero(scores[i])) << 31) | i;
 }
 
 // bitonic sort of n <= RUNIA_NMS_SORT_MAX keys in LDS, padded to a power of two with INT64_MAX (above every key)
@@ -129,19 +121,7 @@ __global__ void __launch_bounds__(kSortThreads) nms_sort_small_kernel(int64_t* _
   __shared__ int64_t s[RUNIA_NMS_SORT_MAX];
   for (int i = threadIdx.x; i < p; i += kSortThreads) s[i] = i < n ? keys[i] : INT64_MAX;
   __syncthreads();
-  for (int k = 2; k <= p; k <<= 1) {
-    for (int j = k >> 1; j > 0; j >>= 1) {
-      for (int i = threadIdx.x; i < p; i += kSortThreads) {
-        const int l = i ^ j;
-        if (l > i) {
-          const int64_t x = s[i], y = s[l];
-          const bool up = (i & k) == 0;
-          if (up ? (x > y) : (x < y)) { s[i] = y; s[l] = x; }
-        }
-      }
-      __syncthreads();
-    }
-  }
+  lds_bitonic_sort(s, p, (int)threadIdx.x, kSortThreads);
   for (int i = threadIdx.x; i < n; i += kSortThreads) keys[i] = s[i];
 }
 

@@ -180,11 +180,7 @@ __global__ __launch_bounds__(64 * kRowWaves) void l2_normalize_kernel(const floa
 
 // ---- per-row order statistics in registers (ASH-S pruning, GEN top-M) -------------------------------------
 // One wave owns one row; lane l holds elements l, l+64, ...  The k-th largest value is found by a binary search, bit
-// by bit, on the order-preserving integer image of the floats (count(key >= candidate)) - no sort.
-__device__ __forceinline__ unsigned sort_key(float x) {
-  const unsigned u = __float_as_uint(x);
-  return (u & 0x80000000u) ? ~u : (u | 0x80000000u);  // ascending in x
-}
+// by bit, on the order-preserving integer image of the floats (asc_key of order.hpp; count(key >= candidate)) - no sort.
 
 // count(key >= cand) on the scalar side: one v_cmp per register, population count and sum of the 64-bit masks in scalar
 // registers - no per-lane counter, no cross-lane reduction (ASH-S 262 144 x 2048: 1.55 -> 1.46 ms, GEN 1 M x 1000: 9.8 -> 9.0 ms)
@@ -286,7 +282,7 @@ __global__ __launch_bounds__(64 * kRowWaves) void ash_s_kernel(const float* __re
     for (int t = 0; t < NV; ++t) {
       const int j = lane + 64 * t;
       v[t] = (j < D) ? p[j] : 0.f;
-      key[t] = (j < D) ? sort_key(v[t]) : 0u;  // padding sorts below every real value
+      key[t] = (j < D) ? asc_key(v[t]) : 0u;  // padding sorts below every real value
       s1 += v[t];
     }
     s1 = wave_sum_f32(s1);

@@ -5,7 +5,7 @@
 //   neighbouring order statistics; an order statistic of 32-bit keys is three histogram passes (11 + 11 + 10 bits): each pass
 //   counts, among the elements whose key starts with the prefix found so far, the next digit; the host picks the bin that holds
 //   the rank and narrows the prefix (runia_core_amd/_hip.py: kth_smallest_flat).  One read of the array per pass at HBM rate.
-// Keys: the usual order-preserving map of a float's bits (negative: all bits flipped, else the sign bit set): ascending in value,
+// Keys: asc_key of order.hpp, by the bits alone (kth_smallest_flat decodes a prefix of it): ascending in value,
 // -0.0 directly below +0.0, NaNs above +inf (the caller rejects arrays with NaNs: NumPy's percentile returns NaN for them).
 #include "common.hpp"
 
@@ -13,18 +13,13 @@ namespace {
 
 constexpr int kSelectBins = 2048;
 
-__device__ __forceinline__ unsigned select_key(float v) {
-  const unsigned u = __float_as_uint(v);
-  return (u & 0x80000000u) ? ~u : (u | 0x80000000u);
-}
-
 __global__ __launch_bounds__(256) void select_hist_kernel(const float* __restrict__ x, int64_t n, unsigned prefix, unsigned prefix_mask,
                                                            int shift, unsigned* __restrict__ hist) {
   __shared__ unsigned bins[kSelectBins];
   for (int i = threadIdx.x; i < kSelectBins; i += 256) bins[i] = 0u;
   __syncthreads();
   // +0.0 is a seventh of a ReLU layer's output: its hits are counted once per wave (one LDS atomic instead of up to 64 on one word)
-  const unsigned zero_key = 0x80000000u;
+  const unsigned zero_key = asc_key(0.f);
   const bool zero_in = (zero_key & prefix_mask) == prefix;
   const unsigned zero_bin = (zero_key >> shift) & (kSelectBins - 1);
   const int lane = threadIdx.x & 63;
@@ -32,7 +27,7 @@ __global__ __launch_bounds__(256) void select_hist_kernel(const float* __restric
   for (int64_t i0 = (int64_t)blockIdx.x * 256; i0 < n; i0 += stride) {  // (uniform trip count per wave: the ballot sees whole waves)
     const int64_t i = i0 + threadIdx.x;
     const bool have = i < n;
-    const unsigned key = have ? select_key(x[i]) : 0u;
+    const unsigned key = have ? asc_key(x[i]) : 0u;
     const bool is_zero = have && key == zero_key;
     const unsigned long long zm = __ballot(is_zero);
     if (zero_in && lane == 0 && zm) atomicAdd(&bins[zero_bin], (unsigned)__popcll(zm));

@@ -37,17 +37,11 @@ constexpr int kNoEnd = 0x7fffffff;
 constexpr int kMaxGrid = 64, kMaxBins = 512;
 
 // ---- keys -----------------------------------------------------------------------------------------------------------------
-__host__ __device__ inline int64_t sel_key(double v) {
-  uint64_t b = __builtin_bit_cast(uint64_t, v + 0.0);  // (-0.0 and +0.0 share a key)
-  b = (b >> 63) ? ~b : (b | 0x8000000000000000ull);    // ascending-sortable
-  return (int64_t)(~b ^ 0x8000000000000000ull);        // descending, as a signed number
-}
+// descending, as a signed number; -0.0 and +0.0 share a key
+__host__ __device__ inline int64_t sel_key(double v) { return signed_view(desc_key(fold_zero(v))); }
 
 // the confidence a key stands for, as f64 (-0.0 comes back as +0.0: the same term of a sum)
-__device__ __forceinline__ double sel_conf_of_key(int64_t key) {
-  const uint64_t b = ~((uint64_t)key ^ 0x8000000000000000ull);
-  return __builtin_bit_cast(double, (b >> 63) ? (b ^ 0x8000000000000000ull) : ~b);
-}
+__device__ __forceinline__ double sel_conf_of_key(int64_t key) { return desc_value(unsigned_view(key)); }
 
 template <typename T>
 __global__ __launch_bounds__(256) void sel_keys_kernel(const T* __restrict__ conf, int64_t n, int64_t* __restrict__ keys,

@@ -183,6 +183,41 @@ def test_ties_are_ordered_by_index(c):
         assert (host(got.size) == k).all() and np.array_equal(host(got.covered).astype(bool), want[np.arange(33), y])
 
 
+@pytest.mark.parametrize("c", [1, 2, 3, 4, 5, 64, 65, 1024, 1025, cases.MAX_CLASSES])
+def test_widths_around_the_sorted_powers_of_two(c):
+    """The row sort of conformal_sets pads a row to a power of two of slots: widths at, one above and far below such a size, up
+    to the widest row.  Integer logits (ties broken by index), row 0 all equal, row 1 with a -0 / +0 pair, row 2 with -inf on
+    every second class.  raps at lam = 10 cuts the order after exactly K classes (test_ties_are_ordered_by_index): sizes,
+    members and ranks are exact.  aps and raps at the seeded regularisation are held by the margin of check_sets."""
+    from runia_core_amd import _hip as hip
+
+    assert cases.MAX_CLASSES == hip.conformal_max_classes()
+    n = 7
+    x, y = cases.ties_case(n, c, 300 + c)
+    x[0, :] = 2.0
+    if c >= 2:
+        x[1, :2] = [-0.0, 0.0]
+    if c >= 3:
+        x[2, 1::2] = -np.inf
+    u = cases.row_numbers(n, c)
+    xd, yd, ud = dev(x), dev(y), dev(u)
+    assert cases.row_valid(x).all()
+    order = cases.order(x)
+    for method in ("aps", "raps"):
+        _, rk = hip.conformal_label_scores(xd, yd, method, 1.0, ud, **params(method))
+        assert np.array_equal(host(rk), cases.label_scores_f64(x, y, method, **params(method))[1])
+        s64, _, mgn, _ = reference(x, method, 1.0, u, order)
+        qhat = float(np.float32(np.quantile(s64, 0.6)))
+        got = hip.conformal_sets(xd, qhat, method, 1.0, ud, labels=yd, **params(method))
+        check_sets(got, s64, y, qhat, mgn, c, what=f"sort edges c={c} {method}")
+    for k in sorted(k for k in {1, 2, c // 2, c - 1, c} if 1 <= k <= c):
+        got = hip.conformal_sets(xd, 10.0 * k + 5.0, "raps", 1.0, None, lam=10.0, k_reg=0, labels=yd)
+        want = np.zeros((n, c), bool)
+        np.put_along_axis(want, order[:, :k], True, 1)
+        assert np.array_equal(cases.unpack_bits(host(got.members), c), want), k
+        assert (host(got.size) == k).all() and np.array_equal(host(got.covered).astype(bool), want[np.arange(n), y])
+
+
 @pytest.mark.parametrize("c", [1, 10, 100, 2052])
 def test_sets_edges(c):
     from runia_core_amd import _hip as hip

@@ -155,6 +155,24 @@ def test_jaccard_tables(name):
         assert w[0, 0, 1].item() == 0.0 and w[0, 1, 1].item() == 1.0
 
 
+def test_set_sizes_around_the_sorted_powers_of_two():
+    """The row sort pads a content to a power of two: lengths at, one above and one below such a size, from the empty row to
+    MAX_T, drawn from 38 ids so that duplicates abound, and one row of a single repeated id.  Set overlap only (lcs=False); the
+    reference's LCS is switched off as well (its DP would take minutes at MAX_T)."""
+    lengths = np.array([0, 1, 2, 3, 4, 5, 64, 65, cc.MAX_T - 1, cc.MAX_T, 100], dtype=np.int64)
+    k = len(lengths)
+    ids = np.random.default_rng(5).integers(2, 40, size=(k, cc.MAX_T)).astype(np.int64)
+    ids[k - 1] = 7
+    _, _, uq, it = cc.pair_counts(ids, k, lengths=lengths, lcs=lambda a, b: 0)
+    assert uq[0] == 0 and uq[1] == 1 and uq[-1] == 1 and uq[8] == uq[9] == 38
+    got = L.pairwise_counts(dev(ids), k, lengths=dev(lengths), lcs=False)
+    assert got.lcs is None
+    assert np.array_equal(got.uniq.cpu().numpy(), uq)
+    assert np.array_equal(got.inter.cpu().numpy(), it)
+    got32 = L.pairwise_counts(dev(ids, torch.int32), k, lengths=dev(lengths), lcs=False)
+    assert torch.equal(got32.uniq, got.uniq) and torch.equal(got32.inter, got.inter)
+
+
 def test_host_ids_go_up_and_the_tables_come_back():
     ids, lengths, want = mix_reference()
     got = L.pairwise_counts(torch.from_numpy(ids), 8, lengths=torch.from_numpy(lengths))

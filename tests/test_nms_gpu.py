@@ -58,18 +58,23 @@ def test_ties_degenerate_and_shared_edges_by_hand():
     assert got == [3, 4, 5, 0, 2]
 
 
-@pytest.mark.parametrize("n", [S - 1, S, S + 1])
+@pytest.mark.parametrize("n", [1, 2, 3, 4, 5, 1023, 1024, 1025, 2049, S - 1, S, S + 1])
 def test_sort_paths_give_the_same_order(n):
     """The LDS bitonic sort (n <= NMS_SORT_MAX) and the device torch.sort above it order the same keys: descending score,
-    ties by ascending index, -0 as +0."""
+    ties by ascending index, -0 as +0.  The sizes lie around the powers of two the LDS sort pads a list to."""
     g = np.random.default_rng(n)
     s = (np.floor(g.random(n) * 32) / 32).astype(np.float32)
     s[: n // 4] *= -1
-    s[g.integers(0, n, 50)] = -0.0
-    keys = _hip.nms_sorted_keys(torch.from_numpy(s).cuda()).cpu().numpy()
+    s[g.integers(0, n, min(50, n // 2))] = -0.0
+    sd = torch.from_numpy(s).cuda()
+    sorted_keys = _hip.nms_sorted_keys(sd)
+    keys = sorted_keys.cpu().numpy()
     order = np.argsort(-(s + np.float32(0)), kind="stable")
     np.testing.assert_array_equal(keys & 0x7FFFFFFF, order)
     assert np.all(np.diff(keys) > 0)
+    raw = torch.empty(n, dtype=torch.int64, device="cuda")  # the same distinct keys, unsorted
+    _hip.launch("runia_nms_keys_f32", sd.data_ptr(), n, raw.data_ptr())
+    assert torch.equal(sorted_keys, torch.sort(raw).values)
 
 
 def test_host_and_other_dtype_inputs():

@@ -93,6 +93,23 @@ def test_small_sets(n, m):
         assert np.all(got == 1)
 
 
+@pytest.mark.parametrize("N", [2, 3, 4, 5, 1024, 1025, 16384])
+def test_pooled_sizes_around_the_sorted_powers_of_two(N):
+    """The column sort pads the N pooled rows to a power of two: N at, one above and far below it, up to the row cap.  Column 0 is
+    heavy with ties and holds both zeros and both infinities, column 1 is continuous, column 2 holds a NaN."""
+    assert N <= _hip.ks_max_rows()
+    rng = np.random.default_rng(N)
+    z = rng.standard_normal((N, 3)).astype(np.float32)
+    ties = rng.integers(-1, 3, N).astype(np.float32)
+    special = np.array([-0.0, 0.0, np.inf, -np.inf], dtype=np.float32)[:min(N, 4)]
+    ties[rng.permutation(N)[:len(special)]] = special
+    z[:, 0] = ties
+    z[rng.integers(0, N), 2] = np.nan
+    n = max(1, N // 3)
+    got, valid = check_table(dev(z[:n]), dev(z[n:]), 5, 13)
+    assert valid.tolist() == [True, True, False] and np.all(got[:, 2] == -1)
+
+
 def test_column_pass_boundary():
     x, y = kc.normal_tables(7, 13, 1, 4)
     check_table(dev(x), dev(y), 3, 2)                                               # D = 1

@@ -497,7 +497,9 @@ int runia_roi_mc_entropy_f32(const float* feat_nhwc, const float* boxes, const i
  * (runia_nchw_to_nhwc_f32), boxes [K, 4] xyxy, batch_idx [K] or NULL (B == 1), roi_align's PH, PW, spatial_scale,
  * sampling_ratio, aligned -> out[k * ldo + col_offset + c] f32 for c < C: each hooked layer writes its own column slice of one
  * (K, C_total) matrix.  The (K, C, PH, PW) tensor is never written: the mean is the separable sum of per-axis bilinear
- * weights (f64) over the box's pixels.  A batch index outside [0, B) gives a row of zeros.  Limits: H + W <=
+ * weights (f64) over the box's pixels.  A batch index outside [0, B) gives a row of zeros.  A non-finite pixel whose weight
+ * for a box is exactly zero (every sample next to it on an integer coordinate) is unspecified: this form skips it, roi_align's
+ * 0 * inf would not.  Limits: H + W <=
  * RUNIA_ROI_MEANS_MAX_HW, H * W * C * 4 < 2^30 bytes per image (RUNIA_E_INVALID otherwise); any K (K = 0: nothing).  No
  * workspace, no atomics. */
 #define RUNIA_ROI_MEANS_MAX_HW 2048
@@ -864,7 +866,9 @@ int runia_osod_curves(const int32_t* part, const int64_t* bucket_start, const ui
  *   number.  Rows 0-3 are taken as they are (xyxy in the reference's reading).  A <= RUNIA_YOLO_MAX_ANCHORS.
  *   Workspace: runia_yolo_candidates_workspace_bytes(A) = 8 * A + 4 * ceil(A / 256).
  * runia_nms_keys_f32: keys[i] = (desc(scores[i]) << 31) | i, int64, desc = the order-reversing uint32 image of the f32 score
- *   (-0 folded onto +0, NaN before +inf).  Ascending keys = descending score, ties by ascending index (stable).
+ *   (-0 folded onto +0); a NaN score - either sign, any payload - has desc = 0, the one value in front of +inf's that no
+ *   other score takes.  Ascending keys = descending score with every NaN first, ties and NaNs by ascending index: the
+ *   order of torch.sort(descending=True, stable=True).
  * runia_nms_sort_keys: sorts n <= RUNIA_NMS_SORT_MAX keys in place (one workgroup, LDS bitonic sort).  Longer lists may be
  *   sorted by any device sort of the same keys: they are distinct, so the order is the same.
  * runia_nms_sorted_f32: boxes [*, 4] xyxy f32 indexed by key & 0x7fffffff; the first m sorted keys (m <=

@@ -2849,7 +2849,7 @@ def nms_workspace_bytes(m: int) -> int:
 @_device_guard()
 def nms_sorted_keys(scores: torch.Tensor) -> torch.Tensor:
     """scores [n] f32 (device) -> the int64 keys ``(desc(score) << 31) | i`` in ascending order = descending score, ties by
-    ascending index (``runia_nms_keys_f32``, then ``runia_nms_sort_keys`` up to :data:`NMS_SORT_MAX` keys, a device
+    ascending index, every NaN (desc = 0) in front of +inf (``runia_nms_keys_f32``, then ``runia_nms_sort_keys`` up to :data:`NMS_SORT_MAX` keys, a device
     ``torch.sort`` of the same distinct keys above: one order either way)."""
     require_gpu()
     assert scores.is_cuda and scores.dtype == torch.float32 and scores.dim() == 1

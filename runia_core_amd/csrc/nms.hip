@@ -111,9 +111,13 @@ __global__ void __launch_bounds__(kCandThreads) yolo_compact_kernel(
 
 // ---- sort keys ---------------------------------------------------------------------------------------------------------
 __global__ void nms_keys_kernel(const float* __restrict__ scores, int64_t n, int64_t* __restrict__ keys) {
-  for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x)
-    // larger score, smaller key; -0 on +0 (equal for torch.sort as well); a NaN before +inf, as torch.sort(descending=True)
-    keys[i] = ((int64_t)desc_key(fold_zero(scores[i])) << 31) | i;
+  for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x) {
+    // larger score, smaller key; -0 on +0 (equal for torch.sort as well).  Every NaN - either sign, any payload - takes the one
+    // key 0, in front of +inf's (no other value has it: it is desc_key of the all-ones NaN alone), so the index orders the NaNs
+    // among themselves: torch.sort(descending=True, stable=True).  By its bits a sign-set NaN would come last, behind -inf.
+    const float v = scores[i];
+    keys[i] = ((int64_t)(v != v ? 0u : desc_key(fold_zero(v))) << 31) | i;
+  }
 }
 
 // bitonic sort of n <= RUNIA_NMS_SORT_MAX keys in LDS, padded to a power of two with INT64_MAX (above every key)

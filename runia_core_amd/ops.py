@@ -23,8 +23,9 @@ def nms(boxes: Tensor, scores: Tensor, iou_threshold: float) -> Tensor:
     ``inter / (area_a + area_b - inter)``; a degenerate pair (0 / 0) is NaN and suppresses nothing.
 
     Order of equal scores: STABLE - boxes of equal score are ranked by ascending index (torchvision also sorts by
-    descending score; its order among ties is not specified).  -0.0 ranks as +0.0.  At most ``_hip.NMS_MAX_BOXES`` boxes
-    per call."""
+    descending score; its order among ties is not specified).  -0.0 ranks as +0.0.  A NaN score - either sign, any
+    payload - ranks in front of +inf, NaNs among themselves by ascending index: the order of
+    ``torch.sort(descending=True, stable=True)``.  At most ``_hip.NMS_MAX_BOXES`` boxes per call."""
     if boxes.dim() != 2 or boxes.shape[-1] != 4:
         raise ValueError(f"nms: boxes must be [N, 4], got {tuple(boxes.shape)}")
     if scores.dim() != 1 or scores.shape[0] != boxes.shape[0]:

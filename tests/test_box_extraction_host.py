@@ -18,11 +18,14 @@ NAMES = ["SUPPORTED_OBJECT_DETECTION_ARCHITECTURES", "Extractor", "ObjectDetecti
 
 # ---- shared with tests/test_nms_gpu.py and tests/test_box_extraction_gpu.py -------------------------------------------
 def np_nms(boxes, scores, iou_threshold):
-    """Greedy NMS in NumPy: f32 IoU in torchvision's expression and order, stable descending sort of the scores."""
+    """Greedy NMS in NumPy: f32 IoU in torchvision's expression and order, stable descending sort of the scores with every
+    NaN score in front of +inf (``torch.sort(descending=True, stable=True)``; ``argsort(-s)`` alone puts NaNs last)."""
     b = np.asarray(boxes, np.float32).reshape(-1, 4)
     s = np.asarray(scores, np.float32).reshape(-1)
     thr = np.float32(iou_threshold)
-    order = np.argsort(-s, kind="stable")
+    nan = np.isnan(s)
+    rest = np.nonzero(~nan)[0]
+    order = np.concatenate([np.nonzero(nan)[0], rest[np.argsort(-s[rest], kind="stable")]])
     x1, y1, x2, y2 = b[:, 0], b[:, 1], b[:, 2], b[:, 3]
     area = (x2 - x1) * (y2 - y1)
     removed = np.zeros(len(s), bool)

@@ -23,14 +23,15 @@
 //
 // runia_cons_graph - one workgroup of 256 threads per group, W [k, k] f64 (upper triangle read, diagonal taken as 1):
 //   degrees, adjacency masks (64-bit, closed by six squaring steps: paths of up to 64 edges), the normalised Laplacian
-//   L = I - D^-1/2 W D^-1/2 in LDS, then the cyclic Jacobi of eigen_score_kernel (same rotation rule, round-robin ordering
-//   and stopping rule; NaN after 30 sweeps) with the rotations also applied to V (eigenvectors in its columns).  Ecc is
+//   L = I - D^-1/2 W D^-1/2 in LDS, then the cyclic Jacobi in LDS of jacobi.hpp (jacobi_lds_sweeps: eigenvalue form of the
+//   threshold; NaN after 30 sweeps) with the rotations also applied to V (eigenvectors in its columns).  Ecc is
 //   formed as the norm of the centred rows of the selected eigenvectors - equal to the projector form P_ii - 2 (P 1)_i / k +
 //   1'P1 / k^2 but without its cancellation (an s_i^2 of 0 would otherwise come out as 1e-17 and its root as 3e-9).
 //   LDS: two 32 KB matrices + 8 KB of vectors (dynamic, above the 64 KB static limit).  Every sum runs in index order.
 #include <math.h>
 
 #include "common.hpp"
+#include "jacobi.hpp"
 
 namespace {
 
@@ -236,18 +237,6 @@ constexpr int kMat = kMaxK * kMaxK;  // doubles per LDS matrix
 constexpr int kVec = 1024;           // doubles of vectors behind the two matrices
 constexpr int kGraphLdsBytes = (2 * kMat + kVec) * 8;
 
-// pair j (0 <= j < m/2) of round t (0 <= t < m-1) of the circle method on m (even) players (eigen_score.hip)
-__device__ __forceinline__ void tournament_pair(int m, int t, int j, int& p, int& q) {
-  if (j == 0) {
-    p = m - 1;
-    q = t;
-  } else {
-    p = (t + j) % (m - 1);
-    q = (t - j + (m - 1)) % (m - 1);
-  }
-  if (p > q) { const int s = p; p = q; q = s; }
-}
-
 __global__ __launch_bounds__(kThreads) void cons_graph_kernel(const double* __restrict__ W, int k, double eigv_thr,
                                                               double set_thr, double* __restrict__ eigenvalues,
                                                               double* __restrict__ u_deg, double* __restrict__ u_eigv,
@@ -258,8 +247,7 @@ __global__ __launch_bounds__(kThreads) void cons_graph_kernel(const double* __re
   double* G = lds;         // [k, k] row-major: W, then the Laplacian, diagonalised in place
   double* V = lds + kMat;  // [k, k] row-major: eigenvectors in the columns
   double* x = lds + 2 * kMat;
-  double* rot_c = x;         // [32]
-  double* rot_s = x + 32;    // [32]
+  double* rot = x;           // [64]: cosines, sines of the step's rotations
   double* part = x + 64;     // [256]: Frobenius norm partials
   double* deg = x + 320;     // [64]
   double* dinv = x + 384;    // [64]
@@ -340,85 +328,8 @@ __global__ __launch_bounds__(kThreads) void cons_graph_kernel(const double* __re
   }
   __syncthreads();
 
-  // ---- cyclic Jacobi on G, rotations accumulated in V (eigen_score_kernel's rule, ordering and stopping) --------------------
-  {
-    double s = 0.0;
-    for (int idx = tid; idx < k * k; idx += kThreads) s += G[idx] * G[idx];
-    part[tid] = s;
-    __syncthreads();
-    for (int o = kThreads / 2; o > 0; o >>= 1) {
-      if (tid < o) part[tid] += part[tid + o];
-      __syncthreads();
-    }
-  }
-  const double anorm = sqrt(part[0]);
-  const int m = (k + 1) & ~1, half = m / 2;
-  bool converged = false;
-  for (int sweep = 0; sweep < kMaxSweeps; ++sweep) {
-    if (tid == 0) flag[0] = 0;
-    __syncthreads();
-    for (int t = 0; t < m - 1; ++t) {
-      if (tid < half) {
-        int p, q;
-        tournament_pair(m, t, tid, p, q);
-        double c = 1.0, s = 0.0;
-        if (q < k) {
-          const double app = G[p * k + p], aqq = G[q * k + q], apq = G[p * k + q];
-          const double thr = fmax(1e-19 * anorm, 1e-17 * sqrt(fabs(app * aqq)));
-          if (fabs(apq) > thr) {
-            const double theta = (aqq - app) / (2.0 * apq);
-            const double tt = (theta >= 0.0 ? 1.0 : -1.0) / (fabs(theta) + sqrt(theta * theta + 1.0));
-            c = 1.0 / sqrt(tt * tt + 1.0);
-            s = tt * c;
-            flag[0] = 1;
-          }
-        }
-        rot_c[tid] = c;
-        rot_s[tid] = s;
-      }
-      __syncthreads();
-      // G <- J^T G J on the 2 x 2 blocks {pa, qa} x {pb, qb}, ka <= kb, mirrored
-      for (int idx = tid; idx < half * half; idx += kThreads) {
-        const int ka = idx / half, kbk = idx - ka * half;
-        if (ka > kbk) continue;
-        const double rac = rot_c[ka], ras = rot_s[ka], rbc = rot_c[kbk], rbs = rot_s[kbk];
-        if (ras == 0.0 && rbs == 0.0) continue;
-        int pa, qa, pb, qb;
-        tournament_pair(m, t, ka, pa, qa);
-        tournament_pair(m, t, kbk, pb, qb);
-        const bool qa_ok = qa < k, qb_ok = qb < k;  // the bye index of odd k leaves its partner untouched
-        const double b00 = G[pa * k + pb];
-        const double b01 = qb_ok ? G[pa * k + qb] : 0.0;
-        const double b10 = qa_ok ? G[qa * k + pb] : 0.0;
-        const double b11 = (qa_ok && qb_ok) ? G[qa * k + qb] : 0.0;
-        const double t00 = rac * b00 - ras * b10, t01 = rac * b01 - ras * b11;
-        const double t10 = ras * b00 + rac * b10, t11 = ras * b01 + rac * b11;
-        double n00 = t00 * rbc - t01 * rbs, n01 = t00 * rbs + t01 * rbc;
-        double n10 = t10 * rbc - t11 * rbs, n11 = t10 * rbs + t11 * rbc;
-        if (ka == kbk) { n01 = 0.0; n10 = 0.0; }  // the rotated pair is annihilated by construction
-        G[pa * k + pb] = n00;
-        G[pb * k + pa] = n00;
-        if (qb_ok) { G[pa * k + qb] = n01; G[qb * k + pa] = n01; }
-        if (qa_ok) { G[qa * k + pb] = n10; G[pb * k + qa] = n10; }
-        if (qa_ok && qb_ok) { G[qa * k + qb] = n11; G[qb * k + qa] = n11; }
-      }
-      // V <- V J: columns p and q of every row
-      for (int idx = tid; idx < half * k; idx += kThreads) {
-        const int ka = idx / k, r = idx - ka * k;
-        const double c = rot_c[ka], s = rot_s[ka];
-        if (s == 0.0) continue;
-        int p, q;
-        tournament_pair(m, t, ka, p, q);
-        const double vp = V[r * k + p], vq = V[r * k + q];
-        V[r * k + p] = c * vp - s * vq;
-        V[r * k + q] = s * vp + c * vq;
-      }
-      __syncthreads();
-    }
-    const int any = flag[0];
-    __syncthreads();  // every thread has read the flag before thread 0 clears it for the next sweep
-    if (!any) { converged = true; break; }
-  }
+  // ---- cyclic Jacobi on G, rotations accumulated in V -----------------------------------------------------------------------
+  const bool converged = jacobi_lds_sweeps<kThreads, true>(G, V, k, kMaxSweeps, rot, part, flag);
 
   // ---- scores -------------------------------------------------------------------------------------------------------------
   if (tid < k) {

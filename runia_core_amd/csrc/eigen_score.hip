@@ -16,17 +16,15 @@
 //            in f64).  The k(k+1)/2 entries are covered by Q = kb(kb+1)/2 tiles of 4 x 4 entries (kb = kpad / 4, tile
 //            rows <= tile columns): one tile per thread, 16 accumulators, 8 LDS reads per 16 products; R = 256 / Q
 //            threads share a tile and take every R-th column.  The R partials are summed in slot order into G (half 1).
-//   Jacobi   cyclic two-sided Jacobi on G in LDS without eigenvectors: round-robin (circle method) ordering of m/2 disjoint
-//            pairs per step, the rotation rule of jacobi_angles_kernel (eigh.hip) with the threshold
-//            max(1e-19 |G|_F, 1e-17 sqrt|g_pp g_qq|) on every pair (only eigenvalues are wanted here: an entry left under
-//            the absolute floor enters them squared; eigh.hip, which returns eigenvectors, keeps the floor for noise-level
-//            diagonals only), 2 x 2 block updates of the upper block triangle mirrored (G stays exactly symmetric).  The "rotated" flag lives in LDS; the loop
-//            stops after the first sweep that applies no rotation, and a group still rotating after 30 sweeps gets NaN.
+//   Jacobi   cyclic two-sided Jacobi on G in LDS without eigenvectors: jacobi_lds_sweeps of jacobi.hpp (ordering, the
+//            eigenvalue form of the rotation threshold, block updates and stopping rule are described there); a group
+//            still rotating after 30 sweeps gets NaN.
 //   Score    diag(G) clamped at 0, ranked in descending order, the top min(k, hidden) summed in that order in f64.
 #include <math.h>
 
 #include "common.hpp"
 #include "elem.hpp"
+#include "jacobi.hpp"
 
 namespace {
 
@@ -34,18 +32,6 @@ constexpr int kThreads = 256;
 constexpr int kMaxK = 64;
 constexpr int kHalf = 4096;  // doubles per LDS half: kMaxK x kMaxK, and the staged chunk
 constexpr int kMaxSweeps = 30;
-
-// pair j (0 <= j < m/2) of round t (0 <= t < m-1) of the circle method on m (even) players (eigh.hip tournament_pair)
-__device__ __forceinline__ void tournament_pair(int m, int t, int j, int& p, int& q) {
-  if (j == 0) {
-    p = m - 1;
-    q = t;
-  } else {
-    p = (t + j) % (m - 1);
-    q = (t - j + (m - 1)) % (m - 1);
-  }
-  if (p > q) { const int s = p; p = q; q = s; }
-}
 
 template <class T>
 __global__ __launch_bounds__(kThreads) void eigen_score_kernel(const void* __restrict__ e, int k, int64_t hidden,
@@ -127,79 +113,12 @@ __global__ __launch_bounds__(kThreads) void eigen_score_kernel(const void* __res
   __syncthreads();
 
   // ---- cyclic Jacobi on G ---------------------------------------------------------------------------------------------
-  double* rot_c = stage;           // [32]
-  double* rot_s = stage + 32;      // [32]
+  double* rot = stage;             // [64]: cosines, sines of the step's rotations
   double* part = stage + 64;       // [256]: Frobenius norm partials
   double* lam = stage + 320;       // [64]: eigenvalues in descending order
   int* flag = reinterpret_cast<int*>(stage + 384);
   int* nan_seen = flag + 1;
-  {
-    double s = 0.0;
-    for (int idx = tid; idx < k * k; idx += kThreads) s += G[idx] * G[idx];
-    part[tid] = s;
-    __syncthreads();
-    for (int o = kThreads / 2; o > 0; o >>= 1) {
-      if (tid < o) part[tid] += part[tid + o];
-      __syncthreads();
-    }
-  }
-  const double anorm = sqrt(part[0]);
-  const int m = (k + 1) & ~1, half = m / 2;
-  bool converged = false;
-  for (int sweep = 0; sweep < kMaxSweeps; ++sweep) {
-    if (tid == 0) flag[0] = 0;
-    __syncthreads();
-    for (int t = 0; t < m - 1; ++t) {
-      if (tid < half) {
-        int p, q;
-        tournament_pair(m, t, tid, p, q);
-        double c = 1.0, s = 0.0;
-        if (q < k) {
-          const double app = G[p * k + p], aqq = G[q * k + q], apq = G[p * k + q];
-          const double thr = fmax(1e-19 * anorm, 1e-17 * sqrt(fabs(app * aqq)));
-          if (fabs(apq) > thr) {
-            const double theta = (aqq - app) / (2.0 * apq);
-            const double tt = (theta >= 0.0 ? 1.0 : -1.0) / (fabs(theta) + sqrt(theta * theta + 1.0));
-            c = 1.0 / sqrt(tt * tt + 1.0);
-            s = tt * c;
-            flag[0] = 1;
-          }
-        }
-        rot_c[tid] = c;
-        rot_s[tid] = s;
-      }
-      __syncthreads();
-      // G <- J^T G J on the 2 x 2 blocks {pa, qa} x {pb, qb}, ka <= kb, mirrored (eigh.hip jacobi_apply_kernel)
-      for (int idx = tid; idx < half * half; idx += kThreads) {
-        const int ka = idx / half, kbk = idx - ka * half;
-        if (ka > kbk) continue;
-        const double rac = rot_c[ka], ras = rot_s[ka], rbc = rot_c[kbk], rbs = rot_s[kbk];
-        if (ras == 0.0 && rbs == 0.0) continue;
-        int pa, qa, pb, qb;
-        tournament_pair(m, t, ka, pa, qa);
-        tournament_pair(m, t, kbk, pb, qb);
-        const bool qa_ok = qa < k, qb_ok = qb < k;  // the bye index of odd k leaves its partner untouched
-        const double b00 = G[pa * k + pb];
-        const double b01 = qb_ok ? G[pa * k + qb] : 0.0;
-        const double b10 = qa_ok ? G[qa * k + pb] : 0.0;
-        const double b11 = (qa_ok && qb_ok) ? G[qa * k + qb] : 0.0;
-        const double t00 = rac * b00 - ras * b10, t01 = rac * b01 - ras * b11;
-        const double t10 = ras * b00 + rac * b10, t11 = ras * b01 + rac * b11;
-        double n00 = t00 * rbc - t01 * rbs, n01 = t00 * rbs + t01 * rbc;
-        double n10 = t10 * rbc - t11 * rbs, n11 = t10 * rbs + t11 * rbc;
-        if (ka == kbk) { n01 = 0.0; n10 = 0.0; }  // the rotated pair is annihilated by construction
-        G[pa * k + pb] = n00;
-        G[pb * k + pa] = n00;
-        if (qb_ok) { G[pa * k + qb] = n01; G[qb * k + pa] = n01; }
-        if (qa_ok) { G[qa * k + pb] = n10; G[pb * k + qa] = n10; }
-        if (qa_ok && qb_ok) { G[qa * k + qb] = n11; G[qb * k + qa] = n11; }
-      }
-      __syncthreads();
-    }
-    const int any = flag[0];
-    __syncthreads();  // every thread has read the flag before thread 0 clears it for the next sweep
-    if (!any) { converged = true; break; }
-  }
+  const bool converged = jacobi_lds_sweeps<kThreads, false>(G, nullptr, k, kMaxSweeps, rot, part, flag);
 
   // ---- score ----------------------------------------------------------------------------------------------------------
   if (tid == 0) nan_seen[0] = 0;

@@ -12,20 +12,9 @@
 // One C call = one sweep (n-1 steps); the caller loops until the sweep reports no rotation (the call itself never
 // synchronises).
 #include "common.hpp"
+#include "jacobi.hpp"
 
 namespace {
-
-// pair k (0 <= k < m/2) of round t (0 <= t < m-1) of the circle method on m (even) players
-__device__ __forceinline__ void tournament_pair(int m, int t, int k, int& p, int& q) {
-  if (k == 0) {
-    p = m - 1;
-    q = t;
-  } else {
-    p = (t + k) % (m - 1);
-    q = (t - k + (m - 1)) % (m - 1);
-  }
-  if (p > q) { const int s = p; p = q; q = s; }
-}
 
 struct Rot { double c, s; };  // J = [[c, s], [-s, c]] in the (p, q) plane; identity = (1, 0)
 
@@ -40,23 +29,7 @@ __global__ __launch_bounds__(256) void jacobi_angles_kernel(const double* __rest
   bool rotated = false;
   if (q < n) {
     const double app = A[(int64_t)p * n + p], aqq = A[(int64_t)q * n + q], apq = A[(int64_t)p * n + q];
-    // rotate when |apq| > 1e-17 sqrt|app aqq|: the relative rule, under which the small eigenvalues of a graded matrix AND
-    // their eigenvectors come out accurately (Demmel & Veselic 1992).  The absolute floor 1e-19 |A|_F joins it only where a
-    // diagonal entry of the pair is itself rounding noise (<= 1e-16 |A|_F: zero diagonals, the null space of a
-    // rank-deficient matrix - below the pinvh cut-off n eps max|w|), where the relative rule alone would chase noise.
-    // With the floor on EVERY pair the eigenvalues stayed accurate (an off-diagonal entry enters them squared) but two
-    // small eigenvalues w kept a residue of 1e-19 |A|_F between them, their vectors mixed by that over their gap, and
-    // U diag(1/w) U^T of a matrix scaled over ten decades was off by 3e-10 where 1e-14 is to be had.
-    const double rel = 1e-17 * sqrt(fabs(app * aqq));
-    const bool noise = fmin(fabs(app), fabs(aqq)) <= 1e-16 * anorm[0];
-    const double thr = noise ? fmax(1e-19 * anorm[0], rel) : rel;
-    if (fabs(apq) > thr) {
-      const double theta = (aqq - app) / (2.0 * apq);
-      const double tt = (theta >= 0.0 ? 1.0 : -1.0) / (fabs(theta) + sqrt(theta * theta + 1.0));
-      r.c = 1.0 / sqrt(tt * tt + 1.0);
-      r.s = tt * r.c;
-      rotated = true;
-    }
+    rotated = jacobi_rotation(app, aqq, apq, jacobi_thr_vectors(app, aqq, anorm[0]), r.c, r.s);
   }
   rot[k] = r;
   // the sweep's rotation count (convergence test of the host loop): one atomic per wave, not per rotation - atomics on
@@ -94,13 +67,8 @@ __global__ __launch_bounds__(256) void jacobi_apply_kernel(double* __restrict__ 
   const double b01 = qb_ok ? A[(int64_t)pa * n + qb] : 0.0;
   const double b10 = qa_ok ? A[(int64_t)qa * n + pb] : 0.0;
   const double b11 = (qa_ok && qb_ok) ? A[(int64_t)qa * n + qb] : 0.0;
-  // J_a^T B
-  const double t00 = ra.c * b00 - ra.s * b10, t01 = ra.c * b01 - ra.s * b11;
-  const double t10 = ra.s * b00 + ra.c * b10, t11 = ra.s * b01 + ra.c * b11;
-  // (J_a^T B) J_b
-  double n00 = t00 * rb.c - t01 * rb.s, n01 = t00 * rb.s + t01 * rb.c;
-  double n10 = t10 * rb.c - t11 * rb.s, n11 = t10 * rb.s + t11 * rb.c;
-  if (ka == kb) { n01 = 0.0; n10 = 0.0; }  // the rotated pair is annihilated by construction
+  double n00, n01, n10, n11;
+  jacobi_block(ra.c, ra.s, rb.c, rb.s, b00, b01, b10, b11, ka == kb, n00, n01, n10, n11);
   A[(int64_t)pa * n + pb] = n00;
   A[(int64_t)pb * n + pa] = n00;
   if (qb_ok) { A[(int64_t)pa * n + qb] = n01; A[(int64_t)qb * n + pa] = n01; }
@@ -118,12 +86,7 @@ __global__ __launch_bounds__(256) void eigh_init_kernel(const double* __restrict
     s += a * a;
     V[i] = (i / n == i % n) ? 1.0 : 0.0;
   }
-  part[threadIdx.x] = s;
-  __syncthreads();
-  for (int o = 128; o > 0; o >>= 1) {
-    if (threadIdx.x < o) part[threadIdx.x] += part[threadIdx.x + o];
-    __syncthreads();
-  }
+  block_tree_sum<256>(s, part);
   if (threadIdx.x == 0) anorm[0] = sqrt(part[0]);
 }
 
@@ -162,12 +125,7 @@ __global__ __launch_bounds__(256) void centred_gram_kernel(const float* __restri
     mean /= (double)n;
     s += ((double)E[(int64_t)i * H + h] - mean) * ((double)E[(int64_t)j * H + h] - mean);
   }
-  part[threadIdx.x] = s;
-  __syncthreads();
-  for (int o = 128; o > 0; o >>= 1) {
-    if (threadIdx.x < o) part[threadIdx.x] += part[threadIdx.x + o];
-    __syncthreads();
-  }
+  block_tree_sum<256>(s, part);
   if (threadIdx.x == 0) {
     G[(int64_t)i * n + j] = part[0] / denom;
     G[(int64_t)j * n + i] = part[0] / denom;

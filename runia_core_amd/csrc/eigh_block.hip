@@ -2,6 +2,8 @@
 // is O(n / 32) launches of matrix-core work instead of 2 (n - 1) launches of 2 x 2 rotations (n = 512: 1 022 launches per
 // sweep at ~8.7 us each were 89 ms of launch latency; n = 2048: 1.04 s against LAPACK's 0.43 s on the host).
 //
+// Pairing and the 2 x 2 block update are those of jacobi.hpp; the rotation itself is this file's own (squared comparison,
+// wider relative bound, hardware seeds - see block_solve_kernel) and is not the scalar rule of that header.
 // Columns are cut into blocks of 32; a step pairs the blocks by the round-robin tournament (nb / 2 disjoint pairs (I, J)):
 //   block_solve   one workgroup per pair: the 64 x 64 sub-matrix S = A[IJ, IJ] goes to LDS, ONE cyclic Jacobi sweep over
 //                 its 64 indices runs there (63 inner steps of 32 disjoint rotations, S updated in place, the rotations
@@ -14,6 +16,7 @@
 // weights (inference/pipeline.py) - reference call sites: inference/postprocessors.py:213-220, inference/funcs.py:52-66,
 // dimensionality_reduction.py:70-71, llm_uncertainty/scores.py:49-66.
 #include "common.hpp"
+#include "jacobi.hpp"
 
 namespace {
 
@@ -21,17 +24,6 @@ constexpr int BS = 32;   // columns per block
 constexpr int SB = 64;   // sub-problem size (a pair of blocks)
 constexpr int SP = 65;   // LDS pitch of the solve kernel (odd: rows p and q of a rotation never share a bank)
 constexpr int UP = 66;   // LDS pitch of the update kernel (== 2 mod 32: conflict-free 16-row MFMA operand reads)
-
-__device__ __forceinline__ void round_robin_pair(int m, int t, int k, int& p, int& q) {
-  if (k == 0) {
-    p = m - 1;
-    q = t;
-  } else {
-    p = (t + k) % (m - 1);
-    q = (t - k + (m - 1)) % (m - 1);
-  }
-  if (p > q) { const int s = p; p = q; q = s; }
-}
 
 // global index of local index e (0..63) of the block pair (I, J)
 __device__ __forceinline__ int64_t gidx(int I, int J, int e) { return (int64_t)(e < BS ? I : J) * BS + (e & (BS - 1)); }
@@ -50,7 +42,7 @@ __global__ __launch_bounds__(256) void block_solve_kernel(const double* __restri
   unsigned char* qq = pp + 32;                                       // [32] second index
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   int I, J;
-  round_robin_pair(nb, t, blockIdx.x, I, J);
+  tournament_pair(nb, t, blockIdx.x, I, J);
   for (int i = tid; i < SB * SB; i += 256) {
     const int r = i >> 6, c = i & 63;
     S[r * SP + c] = A[gidx(I, J, r) * N + gidx(I, J, c)];
@@ -81,7 +73,7 @@ __global__ __launch_bounds__(256) void block_solve_kernel(const double* __restri
       bool rotated = false;
       if (lane < 32) {
         int p, q;
-        round_robin_pair(SB, ts, lane, p, q);
+        tournament_pair(SB, ts, lane, p, q);
         const double app = S[p * SP + p], aqq = S[q * SP + q], apq = S[p * SP + q];
         double c = 1.0, s = 0.0;
         // rotate when |apq| > 2e-15 sqrt|app aqq| (and > 1e-19 |A| where a diagonal entry is noise, see below), compared
@@ -93,8 +85,8 @@ __global__ __launch_bounds__(256) void block_solve_kernel(const double* __restri
         // Small-angle rotations leave no such residue (their product terms are O(angle) small), so 2e-15 costs no accuracy
         // where eigenvalues are separated: measured |w - LAPACK| <= 8e-12 |A| up to n = 2048.
         // The absolute floor applies only where a diagonal entry of the pair is itself rounding noise (<= 1e-16 |A|: zero
-        // diagonals, the null space of a rank-deficient matrix), as in jacobi_angles_kernel: on every pair it left two
-        // small eigenvalues of a graded matrix coupled by 1e-19 |A|, which their eigenvectors - and pinvh - feel.
+        // diagonals, the null space of a rank-deficient matrix), as in jacobi_thr_vectors (jacobi.hpp): on every pair it left
+        // two small eigenvalues of a graded matrix coupled by 1e-19 |A|, which their eigenvectors - and pinvh - feel.
         const double rel2 = 4e-30 * fabs(app * aqq);
         const bool noise = fmin(fabs(app), fabs(aqq)) <= 1e-16 * a_norm;
         if (apq * apq > (noise ? fmax(1e-38 * a_norm * a_norm, rel2) : rel2)) {
@@ -152,11 +144,9 @@ __global__ __launch_bounds__(256) void block_solve_kernel(const double* __restri
 #pragma unroll
     for (int j = 0; j < 3; ++j) {
       if (bka[j] < 0 || (sa[j] == 0.0 && sb[j] == 0.0)) continue;
-      const double t00 = ca[j] * b00[j] - sa[j] * b10[j], t01 = ca[j] * b01[j] - sa[j] * b11[j];
-      const double t10 = sa[j] * b00[j] + ca[j] * b10[j], t11 = sa[j] * b01[j] + ca[j] * b11[j];
-      double n00 = t00 * cb[j] - t01 * sb[j], n01 = t00 * sb[j] + t01 * cb[j];
-      double n10 = t10 * cb[j] - t11 * sb[j], n11 = t10 * sb[j] + t11 * cb[j];
-      if (bka[j] == (bkb[j] & 31)) { n01 = 0.0; n10 = 0.0; }  // the rotated pair is annihilated by construction
+      double n00, n01, n10, n11;
+      jacobi_block(ca[j], sa[j], cb[j], sb[j], b00[j], b01[j], b10[j], b11[j], bka[j] == (bkb[j] & 31), n00, n01, n10,
+                   n11);
       S[pa[j] * SP + pb[j]] = n00; S[pb[j] * SP + pa[j]] = n00;
       S[pa[j] * SP + qb[j]] = n01; S[qb[j] * SP + pa[j]] = n01;
       S[qa[j] * SP + pb[j]] = n10; S[pb[j] * SP + qa[j]] = n10;
@@ -203,7 +193,7 @@ __global__ __launch_bounds__(256) void block_update_kernel(double* __restrict__ 
   const int np = nb / 2;
   const int b = blockIdx.x;
   int Ib, Jb;
-  round_robin_pair(nb, t, b, Ib, Jb);
+  tournament_pair(nb, t, b, Ib, Jb);
   const double* Rbg = Rg + (int64_t)b * SB * SB;
   if ((int)blockIdx.y >= np) {  // ---- eigenvector rows
     const int64_t r0 = (int64_t)(blockIdx.y - np) * SB;
@@ -225,7 +215,7 @@ __global__ __launch_bounds__(256) void block_update_kernel(double* __restrict__ 
   const int a = blockIdx.y;
   if (a > b) return;
   int Ia, Ja;
-  round_robin_pair(nb, t, a, Ia, Ja);
+  tournament_pair(nb, t, a, Ia, Ja);
   const double* Rag = Rg + (int64_t)a * SB * SB;
   for (int i = tid; i < SB * SB; i += 256) {
     const int r = i >> 6, c = i & 63;
@@ -281,12 +271,7 @@ __global__ __launch_bounds__(256) void block_init_kernel(const double* __restric
     s += a * a;
     V[i] = (i / N == i % N) ? 1.0 : 0.0;
   }
-  part[threadIdx.x] = s;
-  __syncthreads();
-  for (int o = 128; o > 0; o >>= 1) {
-    if (threadIdx.x < o) part[threadIdx.x] += part[threadIdx.x + o];
-    __syncthreads();
-  }
+  block_tree_sum<256>(s, part);
   if (threadIdx.x == 0) partial[blockIdx.x] = part[0];
 }
 
@@ -295,12 +280,7 @@ __global__ __launch_bounds__(256) void block_norm_kernel(const double* __restric
   __shared__ double part[256];
   double s = 0.0;
   for (int i = threadIdx.x; i < count; i += 256) s += partial[i];
-  part[threadIdx.x] = s;
-  __syncthreads();
-  for (int o = 128; o > 0; o >>= 1) {
-    if (threadIdx.x < o) part[threadIdx.x] += part[threadIdx.x + o];
-    __syncthreads();
-  }
+  block_tree_sum<256>(s, part);
   if (threadIdx.x == 0) anorm[0] = sqrt(part[0]);
 }
 

@@ -111,3 +111,18 @@ template <int THREADS, class T>  // the sum of an arithmetic T
 __device__ __forceinline__ T block_scan_excl(T v, T* wave_totals, T& total) {
   return block_scan_excl<THREADS>(v, [](T a, T b) { return a + b; }, T(0), wave_totals, total);
 }
+
+// ---- sum over the THREADS threads of a (one-dimensional) workgroup by the LDS tree: part [THREADS] ------------------------
+// Every thread calls it; the sum is in part[0] for every thread on return (a barrier closes every halving step).  The
+// order is fixed - thread i adds thread i + o, o = THREADS / 2 down to 1 - so a sum has the same bits on every run.
+template <int THREADS, class T>
+__device__ __forceinline__ void block_tree_sum(T v, T* part) {
+  static_assert((THREADS & (THREADS - 1)) == 0, "halving steps");
+  T* mine = part + threadIdx.x;  // both reads of a step from one address: they stay one ds_read2_b64 down to o = 1
+  *mine = v;
+  __syncthreads();
+  for (int o = THREADS / 2; o > 0; o >>= 1) {
+    if (threadIdx.x < o) *mine += mine[o];
+    __syncthreads();
+  }
+}

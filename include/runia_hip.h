@@ -1426,6 +1426,51 @@ int runia_pixel_calib_accumulate(const void* logits, int dtype, int64_t G, int64
                                  int64_t ignore_index, float beta, int n_bins, int mode, void* record, float* conf_map,
                                  int32_t* pred_map, void* workspace, size_t workspace_bytes, runia_stream_t stream);
 
+/* ---- Vector, matrix and Dirichlet calibration (affine_calibration.hip; evaluation/affine_calibration.py) -------- *
+ * A row has logits x in R^C and a label y.  Its input u and parameter block W are
+ *     vector     (kind 0)  u = x                                         W = diag(w), `W` holds w [C]
+ *     matrix     (kind 1)  u = x                                         `W` [C, C] row-major (row = output class)
+ *     dirichlet  (kind 2)  u_k = max(log_softmax(x)_k, log FLT_MIN)      `W` [C, C]       (log FLT_MIN = -87.33654...: the log
+ *                          of the smallest normal f32 probability, so a class at -inf stays finite)
+ *   and z = W u + b, q = softmax(z).  The objective is
+ *     L(W, b) = (1/n) sum_rows -log q_y + lam / (C (C - 1)) sum_{i != j} W_ij^2 + mu / C sum_j b_j^2
+ *   (the off-diagonal term absent for `vector` and for C == 1; lam, mu >= 0), convex in (W, b), with
+ *     dL/dW = (1/n) sum_rows (q - e_y) u^T + 2 lam / (C (C - 1)) offdiag(W)      (its diagonal for `vector`)
+ *     dL/db = (1/n) sum_rows (q - e_y) + 2 mu / C b
+ *   over the n rows whose label is not ignore_index.
+ * runia_affcal_eval: the row sums of ONE evaluation from ONE read of logits [N, C] (`row_stride` >= C elements between rows;
+ *   `dtype` 0 f32, 1 f16, 2 bf16, widened exactly, f32 arithmetic), labels [N] int32 (labels_i64 == 0) or int64 or NULL, W and b
+ *   in f32.  A row is USED when 0 <= y < C and not (has_ignore and y == ignore_index).  Outputs, each optional (NULL):
+ *     record  f64 [2 + S]: [0] n_used  [1] sum nll  [2 ..) sum (q - e_y) u^T (C * C slots, row-major; C slots, the diagonal, for
+ *             `vector`), then sum (q - e_y) (C slots).  The 1 / n and the regulariser terms are the caller's.  Needs labels.
+ *     pred i32 [N], conf, nll, brier f32 [N] of q, with the layout and meaning of runia_calib_rows (nll and brier need labels; a
+ *             labelled row that is not used gets NaN in all three floats), so runia_calib_reduce_f32 takes them as they are
+ *     logq f32 [N, C] contiguous: log q
+ *   A non-finite logit of `vector` / `matrix`, or a NaN anywhere, makes the row's floats (and the record's sums) NaN.
+ *   `matrix` and `dirichlet` (C <= RUNIA_AFFCAL_MAX_FULL): row tiles through LDS, Z = U W^T and G += (Q - onehot)^T U on the f32
+ *   matrix cores, C padded to 32 / 64 / 128 / 256 inside the kernel (padding is never read from the caller's memory), the
+ *   accumulators of G in registers across a workgroup's tiles.  `vector` (C <= RUNIA_AFFCAL_MAX_VECTOR): a wave per row, the row
+ *   and its column sums in registers.  Per-workgroup partials (f64 n and nll, f32 gradient sums) go to the workspace and one
+ *   more launch adds them in workgroup order in f64: no floating-point atomics, the grid depends on (N, C, kind) alone, the
+ *   same inputs give the same bits.  RUNIA_E_INVALID for C beyond the caps, an unknown kind, row_stride < C, a record without
+ *   labels or no output at all, before anything is launched.  N == 0: a zero record.
+ *   workspace: runia_affcal_workspace_bytes(N, C, kind) bytes, 8-byte aligned, only when `record` is asked for
+ *   (RUNIA_E_WORKSPACE if missing or short; 0 for shapes the call refuses).  (The query returns int64_t: its values are pinned
+ *   in tests/test_affine_calibration_host.py.)
+ * runia_affcal_round_rows: the rows that the workgroups' first trip over the tiles covers (the grid's cap times the rows of
+ *   a tile; a workgroup of a longer batch takes a second tile); 0 for shapes the call refuses. */
+#define RUNIA_AFFCAL_KIND_VECTOR 0
+#define RUNIA_AFFCAL_KIND_MATRIX 1
+#define RUNIA_AFFCAL_KIND_DIRICHLET 2
+#define RUNIA_AFFCAL_MAX_FULL 256
+#define RUNIA_AFFCAL_MAX_VECTOR 4096
+int64_t runia_affcal_workspace_bytes(int64_t N, int64_t C, int kind);
+int64_t runia_affcal_round_rows(int64_t C, int kind);
+int runia_affcal_eval(const void* logits, int dtype, int64_t row_stride, const void* labels, int labels_i64, int has_ignore,
+                      int64_t ignore_index, int kind, const float* W, const float* b, void* record, int32_t* pred, float* conf,
+                      float* nll, float* brier, float* logq, int64_t N, int64_t C, void* workspace, size_t workspace_bytes,
+                      runia_stream_t stream);
+
 /* ---- Standardized Max Logits maps with boundary smoothing (pixel_sml.hip; inference/pixel_sml.py) --------------- *
  * The three entry points read logits (G, C, H, W) in place through the element strides sn, sc, sh, sw (`dtype` 0 f32, 1 f16,
  * 2 bf16, widened exactly) in the load forms of runia_pixel_calib_accumulate (four pixels of a class plane per lane; a pixel per

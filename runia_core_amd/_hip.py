@@ -842,6 +842,74 @@ def calibration_record(record: np.ndarray, n_bins: int) -> dict:
             "conf_sum": f[6 + 2 * n_bins:6 + 3 * n_bins].copy()}
 
 
+AFFCAL_KINDS = {k: _HEADER_MACROS["RUNIA_AFFCAL_KIND_" + k.upper()] for k in ("vector", "matrix", "dirichlet")}
+AFFCAL_MAX_FULL = _HEADER_MACROS["RUNIA_AFFCAL_MAX_FULL"]
+AFFCAL_MAX_VECTOR = _HEADER_MACROS["RUNIA_AFFCAL_MAX_VECTOR"]
+
+
+class AffineCalibrationEval(NamedTuple):
+    """What ``affine_calibration_eval`` returns, ``None`` where not asked for: ``record`` float64 [2 + S] on the device (n_used,
+    sum nll, the gradient sums of W, then of b), ``rows`` the per-row table of q, ``logq`` float32 [N, C]."""
+
+    record: Optional[torch.Tensor]
+    rows: Optional[CalibrationRows]
+    logq: Optional[torch.Tensor]
+
+
+def affine_calibration_cap(kind: str) -> int:
+    """The widest C the variant serves; an unknown variant raises ``ValueError``."""
+    if kind not in AFFCAL_KINDS:
+        raise ValueError(f"kind must be one of {tuple(AFFCAL_KINDS)}, got {kind!r}")
+    return AFFCAL_MAX_VECTOR if kind == "vector" else AFFCAL_MAX_FULL
+
+
+def affine_calibration_check(c: int, kind: str, W=None, b=None) -> None:
+    """Refuse a variant, a width or parameter shapes that ``runia_affcal_eval`` does not take (before the library is touched)."""
+    cap = affine_calibration_cap(kind)
+    if c > cap:
+        raise ValueError(f"{kind} calibration serves at most {cap} classes "
+                         f"({'RUNIA_AFFCAL_MAX_VECTOR' if kind == 'vector' else 'RUNIA_AFFCAL_MAX_FULL'}), got C = {c}")
+    w_shape = (c,) if kind == "vector" else (c, c)
+    if W is not None and tuple(W.shape) != w_shape:
+        raise ValueError(f"{kind} calibration of {c} classes takes W of shape {w_shape}, got {tuple(W.shape)}")
+    if b is not None and tuple(b.shape) != (c,):
+        raise ValueError(f"b must have shape ({c},), got {tuple(b.shape)}")
+
+
+@_device_guard()
+def affine_calibration_eval(x: torch.Tensor, y: Optional[torch.Tensor], kind: str, W: torch.Tensor, b: torch.Tensor,
+                            ignore_index: Optional[int] = None, want=("record",)) -> AffineCalibrationEval:
+    """One evaluation of vector / matrix / Dirichlet calibration at ``(W, b)`` (float32 device tensors) from one read of the
+    logits ``x`` [N, C] (f32 / f16 / bf16; rows may be strided, classes are contiguous) - ``runia_affcal_eval``.  ``want``: a
+    subset of ``record``, ``pred``, ``conf``, ``nll``, ``brier``, ``logq``; ``record``, ``nll`` and ``brier`` need labels."""
+    names = ("record", "pred", "conf", "nll", "brier", "logq")
+    if not (x.dim() == 2 and x.shape[1] >= 1 and x.dtype in ELEM_DTYPE_CODES):
+        raise ValueError(f"logits: a [N, C] tensor of float32, float16 or bfloat16, got {tuple(x.shape)} {x.dtype}")
+    n, c = x.shape
+    affine_calibration_check(c, kind, W, b)
+    if not want or not set(want) <= set(names):
+        raise ValueError(f"want: a non-empty subset of {names}, got {want!r}")
+    if y is None and set(want) & {"record", "nll", "brier"}:
+        raise ValueError("record, nll and brier need labels")
+    require_gpu()
+    assert x.is_cuda and W.is_cuda and b.is_cuda and W.dtype == b.dtype == torch.float32
+    if (c > 1 and x.stride(1) != 1) or (n > 1 and x.stride(0) < c):
+        x = x.contiguous()
+    W, b = W.contiguous(), b.contiguous()
+    y, is64, has_ignore, ignore = _calib_labels(y, n, ignore_index)
+    dev = x.device
+    record = torch.empty((2 + W.numel() + c,), dtype=torch.float64, device=dev) if "record" in want else None
+    rows = CalibrationRows(*(torch.empty((n,), dtype=torch.int32 if k == "pred" else torch.float32, device=dev)
+                             if k in want else None for k in CalibrationRows._fields))
+    logq = torch.empty((n, c), dtype=torch.float32, device=dev) if "logq" in want else None
+    ws_bytes = query("runia_affcal_workspace_bytes", n, c, AFFCAL_KINDS[kind]) if record is not None else 0
+    ws = workspace(ws_bytes, dev) if record is not None else None
+    launch("runia_affcal_eval", x.data_ptr(), ELEM_DTYPE_CODES[x.dtype], x.stride(0) if n > 1 else c, _ptr(y), is64, has_ignore,
+           ignore, AFFCAL_KINDS[kind], W.data_ptr(), b.data_ptr(), _ptr(record), _ptr(rows.pred), _ptr(rows.conf),
+           _ptr(rows.nll), _ptr(rows.brier), _ptr(logq), n, c, _ptr(ws), ws_bytes)
+    return AffineCalibrationEval(record, rows if any(t is not None for t in rows) else None, logq)
+
+
 PIXCAL_MODES = {m: _HEADER_MACROS["RUNIA_PIXCAL_MODE_" + m.upper()] for m in ("head", "top", "classwise")}
 PIXCAL_HEAD_SLOTS = _HEADER_MACROS["RUNIA_PIXCAL_HEAD_SLOTS"]
 PIXCAL_MAX_BINS = _HEADER_MACROS["RUNIA_PIXCAL_MAX_BINS"]

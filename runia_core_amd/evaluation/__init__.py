@@ -19,6 +19,7 @@ from .open_set import (  # noqa: F401
     voc_eval,
 )
 from .box_subsets import get_gtu_uu_metrics, subset_boxes  # noqa: F401
+from .affine_calibration import AffineCalibrator, fit_affine_calibration  # noqa: F401
 from .calibration import (  # noqa: F401
     CalibrationResult,
     ReliabilityBins,

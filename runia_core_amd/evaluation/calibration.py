@@ -94,6 +94,12 @@ def _prepare(logits, labels, ignore_index) -> Tuple[Tensor, Tensor]:
 
 def _metrics_device(x: Tensor, y: Tensor, temperature: float, n_bins: int, ignore_index) -> CalibrationResult:
     rows = _hip.calibration_rows(x, y, 1.0 / temperature, ignore_index, want=("pred", "conf", "nll", "brier"))
+    return _result_from_rows(rows, y, temperature, n_bins, ignore_index)
+
+
+def _result_from_rows(rows, y: Tensor, temperature: float, n_bins: int, ignore_index) -> CalibrationResult:
+    """The per-row table of a row pass (pred, conf, nll, brier) -> the reduce and the metrics (shared with
+    ``evaluation/affine_calibration.py``)."""
     rec = _hip.calibration_record(_hip.to_host(_hip.calibration_reduce(rows, y, n_bins, ignore_index)), n_bins)
     n = rec["n_used"]
     count = rec["count"]

@@ -1618,6 +1618,41 @@ int runia_maskq_maps(const void* class_logits, int class_dtype, int64_t cg, int6
                      int32_t* label, float* eam, float* semseg, void* workspace, size_t workspace_bytes,
                      runia_stream_t stream);
 
+/* ---- Gram-matrix OoD statistics of a hooked activation (gram.hip; inference/gram.py) ------------------------------ *
+ * Sastry & Oore (ICML 2020) sum the rows of the Gram matrices G_p = F^p (F^p)^T of a layer's map F (C, HW).  That row sum is
+ *   t[b,p,c] = sum_x F[b,c,x]^p S_p[b,x],   S_p[b,x] = sum_j F[b,j,x]^p,   v[b,p,c] = sign(t) |t|^(1/p),   p = 1 .. P,
+ * which needs no (C, C) matrix.  x (B, C, H, W) through the element strides sb, sc, sh, sw (>= 0), `dtype` 0 / 1 / 2 = f32 /
+ * f16 / bf16, read in place, widened exactly; every power and sum in f32.  1 <= P <= RUNIA_GRAM_MAX_POWERS, B, C, H * W and
+ * P * C below 2^31; RUNIA_E_INVALID otherwise or for a missing pointer, before anything is launched.  B == 0: 0, no launch.
+ * Two launches: workgroups of (image, 128 pixels) write (P, C) partial sums to the workspace; the finish adds them in pixel
+ * order, takes the root (p = 1, 2, 4, 8, 16 by sqrt chains, else exp2(log2|t| / p)) and, by `mode`:
+ *   RUNIA_GRAM_STATS  out f32 (B, P, C) = v.
+ *   RUNIA_GRAM_FIT    mins / maxs are uint32 tables [K][P][C] of ordered keys (the ascending key of order.hpp: a negative float's
+ *                     bits complemented, any other with the sign bit set), started by runia_gram_table_init at the keys of
+ *                     +inf / -inf; row labels[b] takes min / max with v[b] through integer atomics.  A label outside [0, K)
+ *                     fits nothing.  The result does not depend on the order of the images or of the calls.
+ *   RUNIA_GRAM_SCORE  mins / maxs are f32 tables [K][P][C]; out f32 (B):
+ *                       dev[b] = sum_{p,c} max(mins - v, 0) / |mins + 1e-6| + max(v - maxs, 0) / |maxs + 1e-6|  at row labels[b],
+ *                     each thread of the image's workgroup over its (p, c) in ascending order, the threads by a butterfly and the
+ *                     waves in order.  +inf when mins > maxs anywhere in the row (a class nothing was fitted to) or when the
+ *                     label lies outside [0, K) (no table is read then).  v is not written.
+ * labels: int32, or int64 with label64.  No float atomics; STATS and SCORE give the same bits from run to run, and an image's
+ * bits do not depend on the rest of the batch.  The tile width X (pixels staged at once) and the channels staged at once follow
+ * from C and the element type alone: runia_gram_tile_width, runia_gram_chunk_channels (0 for what the call refuses).
+ * workspace: runia_gram_workspace_bytes(dtype, B, C, H, W, P) bytes, 16-byte aligned, uninitialised (RUNIA_E_WORKSPACE if
+ * missing or short). */
+#define RUNIA_GRAM_MAX_POWERS 16
+#define RUNIA_GRAM_STATS 0
+#define RUNIA_GRAM_FIT 1
+#define RUNIA_GRAM_SCORE 2
+int64_t runia_gram_tile_width(int dtype, int64_t C);
+int64_t runia_gram_chunk_channels(int dtype, int64_t C);
+int64_t runia_gram_workspace_bytes(int dtype, int64_t B, int64_t C, int64_t H, int64_t W, int P);
+int runia_gram_table_init(uint32_t* kmin, uint32_t* kmax, int64_t n, runia_stream_t stream);
+int runia_gram_layer(const void* x, int dtype, int64_t B, int64_t C, int64_t H, int64_t W, int64_t sb, int64_t sc, int64_t sh,
+                     int64_t sw, int P, int mode, const void* labels, int label64, int64_t K, void* mins, void* maxs, float* out,
+                     void* workspace, size_t workspace_bytes, runia_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -1142,6 +1142,110 @@ def maskq_maps(class_logits: torch.Tensor, mask_logits: torch.Tensor, size=None,
     return out
 
 
+GRAM_MAX_POWERS = _HEADER_MACROS["RUNIA_GRAM_MAX_POWERS"]
+_GRAM_MODES = {m: _HEADER_MACROS["RUNIA_GRAM_" + m.upper()] for m in ("stats", "fit", "score")}
+_GRAM_LABEL_DTYPES = (torch.int32, torch.int64)
+
+
+def gram_tile_width(c: int, dtype: torch.dtype = torch.float32) -> int:
+    """Pixels of one LDS tile of ``runia_gram_layer`` for a layer of ``c`` channels of ``dtype`` (a host query)."""
+    assert dtype in ELEM_DTYPE_CODES, f"unsupported activation dtype {dtype} (float32, float16, bfloat16)"
+    return query("runia_gram_tile_width", ELEM_DTYPE_CODES[dtype], int(c))
+
+
+def gram_chunk_channels(c: int, dtype: torch.dtype = torch.float32) -> int:
+    """Channels ``runia_gram_layer`` stages at once: ``c`` itself up to the single-pass limit, the chunk size beyond it."""
+    assert dtype in ELEM_DTYPE_CODES, f"unsupported activation dtype {dtype} (float32, float16, bfloat16)"
+    return query("runia_gram_chunk_channels", ELEM_DTYPE_CODES[dtype], int(c))
+
+
+def gram_key_tables(k: int, p: int, c: int, device):
+    """The ordered-key tables ``(mins, maxs)`` of ``gram_layer_fit``, int32 ``(k, p, c)``, at the keys of +inf / -inf."""
+    require_gpu()
+    kmin, kmax = (torch.empty((k, p, c), dtype=torch.int32, device=device) for _ in range(2))
+    launch("runia_gram_table_init", kmin.data_ptr(), kmax.data_ptr(), kmin.numel())
+    return kmin, kmax
+
+
+def gram_keys_to_values(keys: torch.Tensor) -> torch.Tensor:
+    """Ordered keys (int32 bits of ``asc_key``, csrc/order.hpp) -> the f32 values they stand for."""
+    assert keys.dtype == torch.int32
+    return torch.where(keys < 0, keys ^ -(1 << 31), ~keys).view(torch.float32)
+
+
+def gram_values_to_keys(values: torch.Tensor) -> torch.Tensor:
+    """f32 values -> their ordered keys as int32 bits, the inverse of ``gram_keys_to_values``."""
+    assert values.dtype == torch.float32
+    bits = values.contiguous().view(torch.int32)
+    return torch.where(bits < 0, ~bits, bits ^ -(1 << 31))
+
+
+def _gram_layer(mode: str, x: torch.Tensor, powers: int, labels=None, mins=None, maxs=None):
+    # shapes and dtypes first, then the devices: every refusal comes before the library is touched
+    assert isinstance(x, torch.Tensor) and x.dim() in (2, 4), "the activation must be (B, F) or (B, C, H, W)"
+    assert x.dtype in ELEM_DTYPE_CODES, f"unsupported activation dtype {x.dtype} (float32, float16, bfloat16)"
+    assert isinstance(powers, (int, np.integer)) and 1 <= powers <= GRAM_MAX_POWERS, \
+        f"powers must be an integer in 1 .. {GRAM_MAX_POWERS}, got {powers!r}"
+    b, c = int(x.shape[0]), int(x.shape[1])
+    assert c >= 1 and all(int(s) >= 1 for s in x.shape[2:]), f"an empty activation {tuple(x.shape)}"
+    p, k = int(powers), 0
+    if mode != "stats":
+        assert isinstance(labels, torch.Tensor) and labels.dtype in _GRAM_LABEL_DTYPES and tuple(labels.shape) == (b,), \
+            f"labels must be an int32 or int64 tensor of shape ({b},)"
+        want = torch.int32 if mode == "fit" else torch.float32
+        for name, t in (("mins", mins), ("maxs", maxs)):
+            assert isinstance(t, torch.Tensor) and t.dtype == want and t.dim() == 3 and tuple(t.shape[1:]) == (p, c) and \
+                t.shape[0] >= 1 and t.is_contiguous(), f"{name} must be a contiguous {want} table of shape (K, {p}, {c})"
+        assert mins.shape == maxs.shape, "mins and maxs must have one shape"
+        k = int(mins.shape[0])
+    assert x.is_cuda, "the activation must be a device tensor"
+    if mode != "stats":
+        assert labels.is_cuda and labels.device == x.device, "the labels must be on the activation's device"
+        assert mins.is_cuda and maxs.is_cuda and mins.device == x.device and maxs.device == x.device, \
+            "the tables must be on the activation's device"
+    require_gpu()
+    out = None
+    if mode == "stats":
+        out = torch.empty((b, p, c), dtype=torch.float32, device=x.device)
+    elif mode == "score":
+        out = torch.empty((b,), dtype=torch.float32, device=x.device)
+    if b == 0:
+        return out
+    if x.dim() == 2:
+        x = x[:, :, None, None]
+    if labels is not None:
+        labels = labels.contiguous()
+    code = ELEM_DTYPE_CODES[x.dtype]
+    ws_bytes = query("runia_gram_workspace_bytes", code, b, c, x.shape[2], x.shape[3], p)
+    ws = workspace(ws_bytes, x.device)
+    launch("runia_gram_layer", x.data_ptr(), code, b, c, x.shape[2], x.shape[3], x.stride(0), x.stride(1), x.stride(2),
+           x.stride(3), p, _GRAM_MODES[mode], _ptr(labels), 1 if labels is not None and labels.dtype == torch.int64 else 0, k,
+           _ptr(mins), _ptr(maxs), _ptr(out), ws.data_ptr(), ws_bytes)
+    return out
+
+
+@_device_guard()
+def gram_layer_stats(x: torch.Tensor, powers: int = 10) -> torch.Tensor:
+    """``v[b, p, c] = sign(t) |t|^(1/(p+1))`` with ``t`` the row sums of the Gram matrix of ``x**(p+1)``, f32 ``(B, powers, C)``:
+    ``runia_gram_layer`` in its STATS mode on ``x`` ((B, C, H, W) or (B, F); f32 / f16 / bf16; any strides, read in place)."""
+    return _gram_layer("stats", x, powers)
+
+
+@_device_guard()
+def gram_layer_fit(x: torch.Tensor, labels: torch.Tensor, mins: torch.Tensor, maxs: torch.Tensor) -> None:
+    """Fold the statistics of ``x`` into rows ``labels[b]`` of the ordered-key tables of ``gram_key_tables`` (FIT mode)."""
+    powers = int(mins.shape[1]) if isinstance(mins, torch.Tensor) and mins.dim() == 3 else 0
+    _gram_layer("fit", x, powers, labels, mins, maxs)
+
+
+@_device_guard()
+def gram_layer_deviation(x: torch.Tensor, labels: torch.Tensor, mins: torch.Tensor, maxs: torch.Tensor) -> torch.Tensor:
+    """The layer deviation of every image of ``x`` from rows ``labels[b]`` of the f32 tables ``mins`` / ``maxs`` (K, P, C), f32
+    ``(B,)`` (SCORE mode); ``+inf`` for a class nothing was fitted to and for a label outside ``[0, K)``."""
+    powers = int(mins.shape[1]) if isinstance(mins, torch.Tensor) and mins.dim() == 3 else 0
+    return _gram_layer("score", x, powers, labels, mins, maxs)
+
+
 CONFORMAL_METHODS = {"lac": 0, "aps": 1, "raps": 2}  # `method` of the runia_conformal_* entry points
 
 

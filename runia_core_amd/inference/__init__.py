@@ -55,6 +55,12 @@ from .mask_level import (  # noqa: F401
     get_mask_anomaly_maps,
     mask_anomaly_maps,
 )
+from .gram import (  # noqa: F401
+    GramDetector,
+    fit_gram_detector,
+    get_gram_scores,
+    gram_statistics,
+)
 from .postprocessors import (  # noqa: F401
     ASH,
     DDU,

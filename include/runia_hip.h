@@ -1653,6 +1653,38 @@ int runia_gram_layer(const void* x, int dtype, int64_t B, int64_t C, int64_t H, 
                      int64_t sw, int P, int mode, const void* labels, int label64, int64_t K, void* mins, void* maxs, float* out,
                      void* workspace, size_t workspace_bytes, runia_stream_t stream);
 
+/* ---- per-pixel class-Gaussian log densities, pixel DDU (pixel_density.hip; inference/pixel_density.py) ------------ *
+ * runia_pixdens_score: log sum_c pi_c N(x; mu_c, Sigma_c) with a covariance of its own per class at every pixel of G feature
+ * maps, ONE launch, the maps read where the model left them.
+ *   features, dtype, G, C, H, W, sn sc sh sw   as for runia_pixfeat_score (NCHW, channels_last and sliced views in place).
+ *   means      f32 [K, C].
+ *   w_tril     f32 [K, C, C] row-major, LOWER TRIANGULAR, W_c = L_c^-1 of the class covariance: what lies above the diagonal
+ *              is never read past the 32-column chunk of its row, and must be zero.
+ *   consts     f64 [K]: -C/2 log(2 pi) - sum log diag L_c (+ log pi_c).  -inf marks an excluded (empty) class.
+ *   outputs    contiguous, each may be NULL, at least one set:
+ *                log_density         f32 (G, H, W)    logsumexp_c lp_c,  lp_c = (float)(consts[c] - 0.5 |W_c (x - mu_c)|^2)
+ *                nearest             int32 (G, H, W)  the argmax of lp_c, lowest index on ties, 0 when every class is excluded
+ *                class_log_densities f32 (G, K, H, W) lp_c
+ *              x - mu_c is formed in f32, the products run on the f32 matrix cores over the k <= j half of W_c only, the squares
+ *              are summed in f32 per 128-row block and in f64 across the blocks (runia_gmm_log_prob_f32's arithmetic); the
+ *              logsumexp is an online (max, sum) update in f64 over the classes in ascending order.  An excluded class has
+ *              lp_c = -inf; all excluded: log_density -inf.  A pixel with a NaN or infinite feature has NaN in every output
+ *              (nearest 0); no other pixel is touched by it.  A finite pixel whose squared distance to class c overflows
+ *              has lp_c = -inf, not NaN.
+ *   A 256-thread workgroup keeps its pixels - runia_pixdens_tile_pixels(C): 128 up to C = 256, 64 up to 512, 32 up to 1024;
+ *   0 for what the call refuses - resident in LDS for all K classes while the W_c stream past in 128 x 32 chunks.  Fixed
+ *   summation order, no atomics: run-to-run bit identical, the same bits on the three load paths, and a pixel's result does
+ *   not depend on its position in the batch.
+ *   1 <= C <= 1024, 1 <= K <= 256, sizes as for runia_pixfeat_score; RUNIA_E_INVALID otherwise (checked on the host before
+ *   anything else).  G == 0 or H * W == 0: 0, nothing launched.  workspace: runia_pixdens_workspace_bytes(C, K) bytes - a
+ *   function of C and K alone, never of the pixels (0 today: the arguments are kept for the ABI). */
+int64_t runia_pixdens_tile_pixels(int64_t C);
+int64_t runia_pixdens_workspace_bytes(int64_t C, int64_t K);
+int runia_pixdens_score(const void* features, int dtype, int64_t G, int64_t C, int64_t H, int64_t W, int64_t sn, int64_t sc,
+                        int64_t sh, int64_t sw, const float* means, const float* w_tril, const double* consts, int64_t K,
+                        float* log_density, int32_t* nearest, float* class_log_densities, void* workspace,
+                        size_t workspace_bytes, runia_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

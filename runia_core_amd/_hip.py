@@ -1945,6 +1945,53 @@ def pixfeat_gather_rows(features: torch.Tensor, labels: torch.Tensor, keep_prob:
     return rows, row_labels
 
 
+PIXDENS_OUTPUTS = ("log_density", "nearest", "class_log_densities")
+PIXDENS_MAX_CHANNELS, PIXDENS_MAX_CLASSES = 1024, 256  # the limits of runia_pixdens_score
+
+
+def pixdens_tile_pixels(c: int) -> int:
+    """Pixels a workgroup of ``runia_pixdens_score`` keeps resident for ``c`` channels (a host query; 0 outside the limits)."""
+    return query("runia_pixdens_tile_pixels", int(c))
+
+
+@_device_guard()
+def pixdens_score(features: torch.Tensor, means: torch.Tensor, w_tril: torch.Tensor, consts: torch.Tensor,
+                  outputs=("log_density",)):
+    """Per-pixel class-Gaussian log densities, one launch (``runia_pixdens_score``).  ``features`` (G, C, h, w) f32 / f16 /
+    bf16 on the device, any strides, read in place; ``means`` [K, C] f32, ``w_tril`` [K, C, C] f32 lower triangular
+    (``L_c^-1``) and ``consts`` [K] f64 on the device (``-inf`` excludes its class).  Returns a dict with the requested
+    ``outputs``: ``"log_density"`` f32 (G, h, w), ``"nearest"`` int32 (G, h, w), ``"class_log_densities"`` f32 (G, K, h, w)."""
+    assert all(o in PIXDENS_OUTPUTS for o in outputs) and len(outputs) > 0, f"outputs must be among {PIXDENS_OUTPUTS}"
+    assert isinstance(features, torch.Tensor) and features.dim() == 4 and features.dtype in ELEM_DTYPE_CODES, \
+        "features must be a (G, C, h, w) tensor of float32, float16 or bfloat16"
+    g, c, h, wd = (int(v) for v in features.shape)
+    assert 1 <= c <= PIXDENS_MAX_CHANNELS, f"features have {c} channels: 1 .. {PIXDENS_MAX_CHANNELS} are supported"
+    assert isinstance(means, torch.Tensor) and means.dim() == 2, "means must be a [K, C] tensor"
+    k = int(means.shape[0])
+    assert 1 <= k <= PIXDENS_MAX_CLASSES, f"{k} classes: 1 .. {PIXDENS_MAX_CLASSES} are supported"
+    for name, t, shape, dt in (("means", means, (k, c), torch.float32), ("w_tril", w_tril, (k, c, c), torch.float32),
+                               ("consts", consts, (k,), torch.float64)):
+        assert isinstance(t, torch.Tensor) and t.dtype == dt and tuple(t.shape) == shape and t.is_contiguous(), \
+            f"{name} must be a contiguous {dt} tensor of shape {shape}"
+    assert features.is_cuda and means.is_cuda and w_tril.is_cuda and consts.is_cuda, "the operands must be device tensors"
+    require_gpu()
+    dev = features.device
+    out = {}
+    if "log_density" in outputs:
+        out["log_density"] = torch.empty((g, h, wd), dtype=torch.float32, device=dev)
+    if "nearest" in outputs:
+        out["nearest"] = torch.empty((g, h, wd), dtype=torch.int32, device=dev)
+    if "class_log_densities" in outputs:
+        out["class_log_densities"] = torch.empty((g, k, h, wd), dtype=torch.float32, device=dev)
+    need = query("runia_pixdens_workspace_bytes", c, k)
+    ws = workspace(need, dev, 0) if need else None
+    sn, sc, sh, sw = (int(v) for v in features.stride())
+    launch("runia_pixdens_score", features.data_ptr(), ELEM_DTYPE_CODES[features.dtype], g, c, h, wd, sn, sc, sh, sw,
+           means.data_ptr(), w_tril.data_ptr(), consts.data_ptr(), k, _ptr(out.get("log_density")), _ptr(out.get("nearest")),
+           _ptr(out.get("class_log_densities")), _ptr(ws), need)
+    return out
+
+
 PIXKNN_OUTPUTS = ("kth_distance", "mean_distance", "distances", "indices")
 PIXKNN_MAX_CHANNELS, PIXKNN_MAX_K, PIXKNN_MAX_BANK = 1024, 16, 1 << 22  # the limits of runia_pixknn_score
 KCENTER_MAX_COLUMNS = 1024                                               # and of runia_kcenter_greedy_f32

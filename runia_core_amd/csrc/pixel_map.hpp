@@ -3,6 +3,9 @@
 // bank): the view through the strides, and the staging of a 32-channel x 128-pixel chunk of x - centre into LDS as
 // Xs[channel][pixel] by a 256-thread workgroup, in one of three load forms that fill the same Xs with the same bits, and the
 // staging of 128 rows x 32 columns of the matrix as Ws[row][34].
+// pixel_density.hip keeps the whole tile resident and narrows it for wide maps: the X staging takes the tile width TP (128,
+// 64 or 32 pixels: a staged chunk is then 4096 / TP channels) and the pitch of Xs as template arguments, and can leave the
+// values uncentred.
 // Include after common.hpp and elem.hpp.
 #pragma once
 
@@ -33,13 +36,14 @@ __device__ __forceinline__ int64_t pixel_offset(const MapView& v, int64_t p) {
 enum { kLoadVec = 0, kLoadElem = 1, kLoadCLast = 2 };
 
 // X chunk: thread t owns the pixel group t & 31 (four neighbouring pixels) of the channel rows (t >> 5) + 8 i, i = 0 .. 3
-template <class T, bool VEC>
+// (TP pixels: group t % (TP / 4) of the rows t / (TP / 4) + (1024 / TP) i)
+template <class T, bool VEC, int TP = kTP>
 __device__ __forceinline__ void load_x(const MapView& v, const int64_t (&off)[4], int nv, int k0, int tid, float (&xr)[16]) {
   typedef typename T::elem E;
   const E* x = static_cast<const E*>(v.x);
 #pragma unroll
   for (int i = 0; i < 4; ++i) {
-    const int c = k0 + i * 8 + (tid >> 5);
+    const int c = k0 + i * (1024 / TP) + (int)((unsigned)tid / (TP / 4));
     const bool in = c < v.C && nv > 0;
     const int cc = c < v.C ? c : v.C - 1;  // (every load is issued: a row past C re-reads the last plane and is masked)
     float t[4];
@@ -60,21 +64,26 @@ __device__ __forceinline__ void load_x(const MapView& v, const int64_t (&off)[4]
   }
 }
 
-__device__ __forceinline__ void store_x(const float (&xr)[16], float (*Xs)[kXP], const float* m0s, int k0, int tid) {
+// (CENTRE false: the widened values as they are, m0s is not read)
+template <int TP = kTP, bool CENTRE = true, int XP>
+__device__ __forceinline__ void store_x(const float (&xr)[16], float (*Xs)[XP], const float* m0s, int k0, int tid) {
 #pragma unroll
   for (int i = 0; i < 4; ++i) {
-    const int row = i * 8 + (tid >> 5);
-    const float m = m0s[k0 + row];  // 0 past C: the padding stays 0
-    *reinterpret_cast<float4*>(&Xs[row][4 * (tid & 31)]) =
-        make_float4(xr[4 * i] - m, xr[4 * i + 1] - m, xr[4 * i + 2] - m, xr[4 * i + 3] - m);
+    const int row = i * (1024 / TP) + (int)((unsigned)tid / (TP / 4));
+    float m = 0.f;
+    if constexpr (CENTRE) m = m0s[k0 + row];  // 0 past C: the padding stays 0
+    float4 o = make_float4(xr[4 * i], xr[4 * i + 1], xr[4 * i + 2], xr[4 * i + 3]);
+    if constexpr (CENTRE) o = make_float4(o.x - m, o.y - m, o.z - m, o.w - m);
+    *reinterpret_cast<float4*>(&Xs[row][4 * ((unsigned)tid % (TP / 4))]) = o;
   }
 }
 
 // channels_last: thread t owns channels 16 (t & 1) .. + 15 of the chunk for pixel t >> 1
-template <class T>
+// (TP pixels: channels 16 (t % (256 / TP)) .. + 15 for pixel t / (256 / TP))
+template <class T, int TP = kTP>
 __device__ __forceinline__ void load_x_cl(const MapView& v, int64_t off, bool valid, int k0, int tid, float (&xr)[16]) {
   typedef typename T::elem E;
-  const int kb = k0 + (tid & 1) * 16;
+  const int kb = k0 + (int)((unsigned)tid % (256 / TP)) * 16;
   const int kc = kb < v.C ? kb : 0;  // (a half past C reads nothing)
   const E* p = static_cast<const E*>(v.x) + off + kc;
   if (valid && kb + 16 <= v.C) {
@@ -86,10 +95,14 @@ __device__ __forceinline__ void load_x_cl(const MapView& v, int64_t off, bool va
   }
 }
 
-__device__ __forceinline__ void store_x_cl(const float (&xr)[16], float (*Xs)[kXP], const float* m0s, int k0, int tid) {
-  const int pix = tid >> 1, r0 = (tid & 1) * 16;
+template <int TP = kTP, bool CENTRE = true, int XP>
+__device__ __forceinline__ void store_x_cl(const float (&xr)[16], float (*Xs)[XP], const float* m0s, int k0, int tid) {
+  const int pix = (int)((unsigned)tid / (256 / TP)), r0 = (int)((unsigned)tid % (256 / TP)) * 16;
 #pragma unroll
-  for (int i = 0; i < 16; ++i) Xs[r0 + i][pix] = xr[i] - m0s[k0 + r0 + i];
+  for (int i = 0; i < 16; ++i) {
+    if constexpr (CENTRE) Xs[r0 + i][pix] = xr[i] - m0s[k0 + r0 + i];
+    else Xs[r0 + i][pix] = xr[i];
+  }
 }
 
 // W chunk: rows j0 .. j0 + 127, columns k0 .. k0 + 31 of a row-major [rows, C] matrix, zero outside it
@@ -119,16 +132,16 @@ __device__ __forceinline__ void store_w(const float (&wr)[16], float (*Ws)[kWP],
 
 // the four pixels (channels_last: the one pixel) thread `tid` of the workgroup at pixel p0 stages -> the number of them
 // inside the map, their element offsets in `off`
-template <int LOAD>
+template <int LOAD, int TP = kTP>
 __device__ __forceinline__ int staged_pixels(const MapView& v, int64_t p0, int tid, int64_t (&off)[4]) {
   off[0] = off[1] = off[2] = off[3] = 0;
   if constexpr (LOAD == kLoadCLast) {
-    const int64_t ps = p0 + (tid >> 1);
+    const int64_t ps = p0 + (int)((unsigned)tid / (256 / TP));
     const int nv = ps < v.P ? 1 : 0;
     off[0] = nv ? pixel_offset(v, ps) : 0;
     return nv;
   } else {
-    const int64_t ps = p0 + 4 * (tid & 31);
+    const int64_t ps = p0 + 4 * (int)((unsigned)tid % (TP / 4));
     const int64_t left = v.P - ps;
     const int nv = left >= 4 ? 4 : (left > 0 ? (int)left : 0);
 #pragma unroll

@@ -36,6 +36,12 @@ from .pixel_features import (  # noqa: F401
     get_pixel_mahalanobis_maps,
     pixel_feature_rows,
 )
+from .pixel_density import (  # noqa: F401
+    PIXEL_DENSITY_OUTPUTS,
+    PixelGaussianDensity,
+    fit_pixel_density,
+    get_pixel_density_maps,
+)
 from .pixel_knn import (  # noqa: F401
     PixelKNN,
     fit_pixel_knn,

@@ -94,7 +94,87 @@ def pixel_feature_rows(features: Tensor, labels: Tensor, keep_prob, ignore_index
     return _hip.pixfeat_gather_rows(f, lab, kp_d, int(ignore_index), int(seed), int(image_offset))
 
 
-class PixelMahalanobis:
+class _LabelledPixelRows:
+    """The fitting front of the pixel-feature Gaussians (``PixelMahalanobis``, ``pixel_density.PixelGaussianDensity``): the
+    checked constructor arguments, the deterministic gather of ``partial_fit`` and the pickle that drops the device cache.
+    A subclass names its fitted arrays in ``_fitted_attrs`` and forms them in ``finalize()``."""
+
+    _device_cache_attrs = ("_dev",)
+    _fitted_attrs = ()
+
+    def __init__(self, n_classes: int, ignore_index: int = 255, rows_per_class_per_batch: int = 4096, ridge: float = 0.0,
+                 seed: int = 0):
+        self.n_classes = _check_classes(n_classes)
+        if not isinstance(rows_per_class_per_batch, (int, np.integer)) or rows_per_class_per_batch < 1:
+            raise ValueError(f"rows_per_class_per_batch must be a positive integer, got {rows_per_class_per_batch!r}")
+        if not (ridge >= 0.0):
+            raise ValueError(f"ridge must not be negative, got {ridge!r}")
+        self.ignore_index = int(ignore_index)
+        self.rows_per_class_per_batch = int(rows_per_class_per_batch)
+        self.ridge = float(ridge)
+        self.seed = int(seed)
+        self._reset()
+
+    def _clear_fit(self) -> None:
+        for name in self._fitted_attrs:
+            setattr(self, name, None)
+        self._dev = None
+
+    def _reset(self) -> None:
+        self._rows = []        # kept rows per batch, host f32 (n_b, C)
+        self._row_labels = []  # their labels, host int32 (n_b,)
+        self._images_seen = 0
+        self.pixel_counts_ = np.zeros(self.n_classes, dtype=np.int64)  # labelled pixels seen per class
+        self.dropped_pixels_ = 0                                        # ignored or out of range
+        self.class_counts_ = np.zeros(self.n_classes, dtype=np.int64)  # kept rows per class
+        self.n_channels_ = None
+        self._clear_fit()
+
+    def __getstate__(self):
+        state = dict(self.__dict__)
+        for name in self._device_cache_attrs:
+            if name in state:
+                state[name] = None
+        return state
+
+    def partial_fit(self, features: Tensor, labels: Tensor):
+        _check_features(features, self.n_channels_)
+        _check_labels(labels, features)
+        device = _hip.require_gpu()
+        f = features.detach() if features.is_cuda else features.detach().to(device)
+        lab = labels.detach().to(f.device)
+        counts_d, dropped_d = _hip.pixfeat_label_hist(lab, self.n_classes, self.ignore_index)
+        counts = _hip.to_host(counts_d).astype(np.int64)
+        keep = np.minimum(1.0, self.rows_per_class_per_batch / np.maximum(counts, 1).astype(np.float64))
+        rows, row_labels = _hip.pixfeat_gather_rows(f, lab, torch.from_numpy(keep.astype(np.float32)).to(f.device),
+                                                    self.ignore_index, self.seed, self._images_seen)
+        self._images_seen += int(f.shape[0])
+        self.n_channels_ = int(f.shape[1])
+        self.pixel_counts_ = self.pixel_counts_ + counts
+        self.dropped_pixels_ += int(dropped_d.item())
+        if rows.shape[0]:
+            rl = np.array(_hip.to_host(row_labels), dtype=np.int32)
+            self._rows.append(np.array(_hip.to_host(rows), dtype=np.float32))
+            self._row_labels.append(rl)
+            self.class_counts_ = self.class_counts_ + np.bincount(rl, minlength=self.n_classes).astype(np.int64)
+        self._clear_fit()
+        return self
+
+    def _rows_by_class(self, device):
+        """The kept rows sorted by class, each class in the order its rows were seen -> (rows f32 on the device, counts,
+        starts)."""
+        x = np.concatenate(self._rows, axis=0)
+        lab = np.concatenate(self._row_labels, axis=0)
+        order = np.argsort(lab, kind="stable")
+        counts = np.bincount(lab, minlength=self.n_classes).astype(np.int64)
+        return torch.from_numpy(x[order]).to(device), counts, np.concatenate([[0], np.cumsum(counts)])
+
+    def fit(self, features: Tensor, labels: Tensor):
+        self._reset()
+        return self.partial_fit(features, labels).finalize()
+
+
+class PixelMahalanobis(_LabelledPixelRows):
     """Class Gaussians with one shared covariance over the pixels of a decoder's feature maps.
 
     ``partial_fit(features, labels)`` takes a batch of maps ``(G, C, h, w)`` with labels ``(G, h, w)`` at the same
@@ -115,76 +195,15 @@ class PixelMahalanobis:
     ``class_offsets_``, ``class_counts_``); the f32 device copies are a cache that is rebuilt on first use, so a pickle
     loads on a host without a GPU."""
 
-    _device_cache_attrs = ("_dev",)
-
-    def __init__(self, n_classes: int, ignore_index: int = 255, rows_per_class_per_batch: int = 4096, ridge: float = 0.0,
-                 seed: int = 0):
-        self.n_classes = _check_classes(n_classes)
-        if not isinstance(rows_per_class_per_batch, (int, np.integer)) or rows_per_class_per_batch < 1:
-            raise ValueError(f"rows_per_class_per_batch must be a positive integer, got {rows_per_class_per_batch!r}")
-        if not (ridge >= 0.0):
-            raise ValueError(f"ridge must not be negative, got {ridge!r}")
-        self.ignore_index = int(ignore_index)
-        self.rows_per_class_per_batch = int(rows_per_class_per_batch)
-        self.ridge = float(ridge)
-        self.seed = int(seed)
-        self._reset()
-
-    def _reset(self) -> None:
-        self._rows = []        # kept rows per batch, host f32 (n_b, C)
-        self._row_labels = []  # their labels, host int32 (n_b,)
-        self._images_seen = 0
-        self.pixel_counts_ = np.zeros(self.n_classes, dtype=np.int64)  # labelled pixels seen per class
-        self.dropped_pixels_ = 0                                        # ignored or out of range
-        self.class_counts_ = np.zeros(self.n_classes, dtype=np.int64)  # kept rows per class
-        self.n_channels_ = None
-        self.class_means_ = self.covariance_ = self.center_ = self.whitening_ = self.class_offsets_ = None
-        self._dev = None
-
-    def __getstate__(self):
-        state = dict(self.__dict__)
-        for name in self._device_cache_attrs:
-            if name in state:
-                state[name] = None
-        return state
-
-    # ---- fitting ----------------------------------------------------------------------------------------------------------------
-    def partial_fit(self, features: Tensor, labels: Tensor) -> "PixelMahalanobis":
-        _check_features(features, self.n_channels_)
-        _check_labels(labels, features)
-        device = _hip.require_gpu()
-        f = features.detach() if features.is_cuda else features.detach().to(device)
-        lab = labels.detach().to(f.device)
-        counts_d, dropped_d = _hip.pixfeat_label_hist(lab, self.n_classes, self.ignore_index)
-        counts = _hip.to_host(counts_d).astype(np.int64)
-        keep = np.minimum(1.0, self.rows_per_class_per_batch / np.maximum(counts, 1).astype(np.float64))
-        rows, row_labels = _hip.pixfeat_gather_rows(f, lab, torch.from_numpy(keep.astype(np.float32)).to(f.device),
-                                                    self.ignore_index, self.seed, self._images_seen)
-        self._images_seen += int(f.shape[0])
-        self.n_channels_ = int(f.shape[1])
-        self.pixel_counts_ = self.pixel_counts_ + counts
-        self.dropped_pixels_ += int(dropped_d.item())
-        if rows.shape[0]:
-            rl = np.array(_hip.to_host(row_labels), dtype=np.int32)
-            self._rows.append(np.array(_hip.to_host(rows), dtype=np.float32))
-            self._row_labels.append(rl)
-            self.class_counts_ = self.class_counts_ + np.bincount(rl, minlength=self.n_classes).astype(np.int64)
-        self.class_means_ = self.covariance_ = self.center_ = self.whitening_ = self.class_offsets_ = None
-        self._dev = None
-        return self
+    _fitted_attrs = ("class_means_", "covariance_", "center_", "whitening_", "class_offsets_")
 
     def finalize(self) -> "PixelMahalanobis":
         if not self._rows:
             raise ValueError("finalize() before any labelled pixel was seen: call partial_fit first")
         device = _hip.require_gpu()
-        x = np.concatenate(self._rows, axis=0)
-        lab = np.concatenate(self._row_labels, axis=0)
-        n, c = x.shape
+        xs, counts, starts = self._rows_by_class(device)
+        n, c = (int(v) for v in xs.shape)
         k = self.n_classes
-        order = np.argsort(lab, kind="stable")  # the rows of a class in the order they were seen
-        xs = torch.from_numpy(x[order]).to(device)
-        counts = np.bincount(lab, minlength=k).astype(np.int64)
-        starts = np.concatenate([[0], np.cumsum(counts)])
         means = torch.full((k, c), float("nan"), dtype=torch.float64, device=device)
         cov = torch.zeros((c, c), dtype=torch.float64, device=device)
         m0 = torch.zeros((c,), dtype=torch.float64, device=device)
@@ -214,10 +233,6 @@ class PixelMahalanobis:
         self.class_offsets_ = np.array(_hip.to_host(mz), dtype=np.float64)
         self._dev = None
         return self
-
-    def fit(self, features: Tensor, labels: Tensor) -> "PixelMahalanobis":
-        self._reset()
-        return self.partial_fit(features, labels).finalize()
 
     # ---- scoring ----------------------------------------------------------------------------------------------------------------
     def _device_params(self, device):

@@ -1685,6 +1685,43 @@ int runia_pixdens_score(const void* features, int dtype, int64_t G, int64_t C, i
                         float* log_density, int32_t* nearest, float* class_log_densities, void* workspace,
                         size_t workspace_bytes, runia_stream_t stream);
 
+/* ---- LLM-Check  hidden and attention scores of one generation from one pass (llm_check.hip; llm_uncertainty/llm_check.py, ---- *
+ * DESIGN 4.59).  Row b of a batch has the token window [s_b, s_b + T_b) of positions; position p < P lies in step 0, position
+ * P + g - 1 in step g >= 1 (a forward pass is one step with P = its length).
+ *   rows       device array of B {s_b, T_b} int64 pairs; host_rows its host copy, which the call checks: T_b >= 1 and the
+ *              window inside the P + n_steps - 1 positions.
+ *   dtype      0 f32, 1 f16, 2 bf16 (all tensors of one call).
+ * runia_llmcheck_hidden: scores [B, L] f64 = (1/T_b) log det(C C^T + alpha I), C = the T_b x d states of the window with
+ *   every token centred over d (c_t = z_t - mean_j z_tj), = the mean log-eigenvalue of the token covariance.
+ *   table      device array of n_steps * L descriptors, step-major, 3 int64 each: {pointer to batch 0 of the step's (B, q, d)
+ *              hidden states, batch stride, row stride (elements)}; unit stride along d.  L counts the layers scored.
+ *   Three launches: the f64 token means (one wave per token, one order); the centred Gram matrices on the f64 matrix cores,
+ *   one workgroup per 64 x 64 tile pair of the lower triangle, d in 32-deep chunks widened exactly and centred in f64 while
+ *   staged, alpha added on the diagonal; a blocked Cholesky by 64-column panels, one workgroup per matrix, which sums
+ *   log L_ii and writes 2 sum / T_b.  A row with d < T_b is scored through the d x d form of the same determinant,
+ *   det(C C^T + alpha I_T) = alpha^(T_b - d) det(C^T C + alpha I_d): one eigenvalue at alpha instead of T_b - d + 1, the smaller
+ *   matrix; the choice depends on the row's own window alone.  No atomics, no split of a sum across workgroups: a matrix's bits depend on its own
+ *   row alone.  A pivot that is not positive, or NaN (a NaN state, alpha <= 0 on a rank-deficient window), gives NaN for
+ *   that matrix alone.  1 <= T_b <= 1024, d >= 1; RUNIA_E_INVALID otherwise, checked on the host before anything else.
+ *   workspace: runia_llmcheck_workspace_bytes(B * L, max_b T_b) bytes, 16-byte aligned (0 outside the limits).
+ * runia_llmcheck_gram: the first two launches alone; sigma [B * L, Tpad, Tpad] f64, Tpad = max_b T_b rounded up to 64,
+ *   receives the lower 64 x 64 tiles of every matrix (of order min(T_b, d): C^T C + alpha I where d < T_b; tiles above the diagonal are not written; a row past T_b has a unit
+ *   diagonal and zeros).  The same workspace.
+ * runia_llmcheck_attention: per_head [B, L, H] f64 = (1/T_b) sum_t log A[b, h, t, t] over the window, scores [B, L] f64 their
+ *   sum over the heads in ascending order.  table: the 7-int64 descriptors of the batched RAUQ entries, n_steps * L of
+ *   them; the diagonal of the prompt block at step 0 (q >= P rows), the last column of the one query row at step g.  One
+ *   wave per (b, l, h), f64 log, one fixed-order sum; a zero entry gives -inf, NaN propagates.  No workspace. */
+int64_t runia_llmcheck_workspace_bytes(int64_t M, int64_t T_max);
+int runia_llmcheck_hidden(const void* table, const void* rows, const int64_t* host_rows, int dtype, int64_t B, int64_t n_steps,
+                          int64_t L, int64_t P, int64_t d, double alpha, double* scores, void* workspace,
+                          size_t workspace_bytes, runia_stream_t stream);
+int runia_llmcheck_gram(const void* table, const void* rows, const int64_t* host_rows, int dtype, int64_t B, int64_t n_steps,
+                        int64_t L, int64_t P, int64_t d, double alpha, double* sigma, void* workspace, size_t workspace_bytes,
+                        runia_stream_t stream);
+int runia_llmcheck_attention(const void* table, const void* rows, const int64_t* host_rows, int dtype, int64_t B,
+                             int64_t n_steps, int64_t L, int64_t H, int64_t P, double* per_head, double* scores,
+                             runia_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -7,6 +7,8 @@ made with the same keyword arguments and every score comes from this package's d
 
 - ``perplexity``, ``generation_entropy``: ``generation_scores`` of the deterministic output (one pass over its logits);
 - ``RAUQ``: the deterministic log-probs of that pass and the attention maps, read in place (``RAUQ`` / ``rauq_batch``);
+- ``hidden_score``, ``attention_score``: LLM-Check (``.llm_check``) of the deterministic output's hidden states / attention
+  maps at the request's ``layer`` (default 15), read in place; no sampling;
 - ``normalized_entropy``: ``generation_scores`` of the sampled output;
 - ``eigen_score``: ``eigen_scores`` (one launch of ``runia_eigen_score_batch`` for every prompt's sample group);
 - ``semantic_entropy``: the host function of ``.scores`` with the NLI model (its forward passes are the cost);
@@ -25,6 +27,7 @@ import torch
 
 from .. import _hip
 from .consistency import SIMILARITIES, scores_by_kind
+from .llm_check import attention_score, hidden_score
 from .logits import generation_scores
 from .rauq import RAUQ, generated_lengths, rauq_batch
 from .scores import eigen_score, semantic_entropy
@@ -33,7 +36,10 @@ __all__ = ["eigen_scores", "compute_uncertainties", "compute_uncertainties_batch
 
 _NEEDS_SAMPLING = {"eigen_score": True, "normalized_entropy": True, "semantic_entropy": True, "perplexity": False,
                    "generation_entropy": False, "RAUQ": False, "lexical_similarity": True, "deg": True, "ecc": True,
-                   "eigv": True, "num_sets": True}
+                   "eigv": True, "num_sets": True, "hidden_score": False, "attention_score": False}
+# LLM-Check request name -> (its function, the generate() output it reads); "layer" defaults to _LLM_CHECK_LAYER
+_LLM_CHECK = {"hidden_score": (hidden_score, "hidden_states"), "attention_score": (attention_score, "attentions")}
+_LLM_CHECK_LAYER = 15
 # request name -> field of ConsistencyScores
 _CONSISTENCY = {"lexical_similarity": "lexical_similarity", "deg": "u_deg", "ecc": "u_ecc", "eigv": "u_eigv",
                 "num_sets": "num_sets"}
@@ -77,6 +83,9 @@ def _score_name(req: Dict[str, Any]) -> str:
         if similarity not in SIMILARITIES:
             raise KeyError(similarity)
         return method if similarity == SIMILARITIES[0] else f"{method}_{similarity}"
+    if method in _LLM_CHECK:
+        layer = int(req.get("layer", _LLM_CHECK_LAYER))
+        return method if layer == _LLM_CHECK_LAYER else f"{method}_{layer}"
     return method
 
 
@@ -108,6 +117,12 @@ def _generate(model, tokenizer, inputs, gen_config, num_samples: int, sample: bo
                           output_scores=True, return_dict_in_generate=True)
 
 
+def _llm_check(req, det, **windows) -> torch.Tensor:
+    """(B,) f64 LLM-Check score of the deterministic generation at the request's layer, on the device."""
+    fn, source = _LLM_CHECK[req["method_name"]]
+    return fn(getattr(det, source), (int(req.get("layer", _LLM_CHECK_LAYER)),), **windows)[:, 0]
+
+
 def _rauq_args(req):
     return (req.get("token_aggregation", "mean_all_tokens"), req.get("head_aggregation", "rollout"),
             req.get("alphas", [0.3]), req.get("ablation", False))
@@ -119,7 +134,8 @@ def compute_uncertainties(model, tokenizer, prompt: str, uncertainty_requests: L
     """Generate for ``prompt`` and compute the requested uncertainty scores (reference ``compute_uncertainties``).
 
     ``uncertainty_requests``: dicts with ``method_name`` in eigen_score, normalized_entropy, semantic_entropy, perplexity,
-    generation_entropy, RAUQ, lexical_similarity, deg, ecc, eigv, num_sets (the last five: sample consistency of the sampled
+    generation_entropy, RAUQ, hidden_score, attention_score (LLM-Check at ``"layer"``, default 15; the key gets ``_<layer>``
+    appended for another layer), lexical_similarity, deg, ecc, eigv, num_sets (the last five: sample consistency of the sampled
     ids, ``.consistency``; an optional ``"similarity"`` of ``"rouge_l"`` (default) or ``"jaccard"``, which is appended to the
     key when it is not the default; ``num_sets`` is an int); a RAUQ request also names ``token_aggregation`` and
     ``head_aggregation`` and may give ``alphas`` (default [0.3]) and ``ablation`` (default False).  Returns ``(deterministic_text, scores)``: the text as
@@ -156,6 +172,8 @@ def compute_uncertainties(model, tokenizer, prompt: str, uncertainty_requests: L
         elif method == "RAUQ":
             tok, head, alphas, ablation = _rauq_args(req)
             scores[name] = RAUQ(det_scores().log_probs, det.attentions, input_length, tok, head, alphas, ablation)
+        elif method in _LLM_CHECK:
+            scores[name] = float(_llm_check(req, det, input_length=input_length)[0])
         elif method == "normalized_entropy":
             scores[name] = generation_scores(samp.sequences, samp.scores).normalized_entropy
         elif method == "eigen_score":
@@ -230,14 +248,18 @@ def compute_uncertainties_batch(model, tokenizer, prompts: Sequence[str], uncert
 
     cache: Dict[str, Any] = {}
 
-    def det_scores():
-        if "det" not in cache:
-            gs = generation_scores(det.sequences, det.scores)
+    def det_lengths():
+        if "lengths" not in cache:
             eos = _eos_ids(model, gen_config)
             T = len(det.scores)
             lengths = (generated_lengths(det.sequences, input_length, eos) if eos is not None
                        else torch.full((B,), T, dtype=torch.int64))
-            cache["det"] = (gs, lengths.clamp_max(T))
+            cache["lengths"] = lengths.clamp_max(T)
+        return cache["lengths"]
+
+    def det_scores():
+        if "det" not in cache:
+            cache["det"] = (generation_scores(det.sequences, det.scores), det_lengths())
         return cache["det"]
 
     def samp_scores():
@@ -260,6 +282,9 @@ def compute_uncertainties_batch(model, tokenizer, prompts: Sequence[str], uncert
             r = rauq_batch(gs.log_probs, det.attentions, input_length, tok, head, alphas, inputs["attention_mask"],
                            lengths).double().cpu()
             scores[name] = r if ablation else r[:, 0]
+        elif method in _LLM_CHECK:
+            scores[name] = _llm_check(req, det, input_length=input_length, attention_mask=inputs["attention_mask"],
+                                      lengths=det_lengths()).cpu()  # (no pass over the logits)
         elif method == "normalized_entropy":
             # per sample row the mean of its finite log-probs (-inf = padding), then -mean over the prompt's K rows
             lp = samp_scores().log_probs

@@ -1722,6 +1722,38 @@ int runia_llmcheck_attention(const void* table, const void* rows, const int64_t*
                              int64_t n_steps, int64_t L, int64_t H, int64_t P, double* per_head, double* scores,
                              runia_stream_t stream);
 
+/* ---- Logit lens  a layer's next-token distribution, scored while the unembedding product is formed (logit_lens.hip; ---- *
+ * llm_uncertainty/logit_lens.py).  z_v = sum_k x_k W[v, k] of a state row x and the unembedding W [V, d], the
+ * element type's exact products accumulated in f32 on the matrix cores.  Per row (all [planes, N]; any output may be null):
+ *   lse           log sum_v exp(z_v)
+ *   entropy       lse - sum_v p_v z_v, p = softmax(z), in nats
+ *   log_prob      z_tok - lse, tok = tokens[n]; NaN without tokens, for -1 and for an id outside [0, V)
+ *   top_log_prob  max_v z_v - lse;  top_token: the smallest v that attains the maximum
+ *   kl_final      sum_v q_v (log q_v - log p_v), q = softmax of row n of plane `final_plane`; NaN with final_plane = -1
+ * A NaN or infinite state value makes the row's float outputs NaN, its top_token -1 and the kl_final of the rows whose final
+ * partner it is NaN; no other row changes by a bit.
+ *   states   [planes, N, d] dense, element type `dtype` (0 f32, 1 f16, 2 bf16: both operands)
+ *   weight   [V, d], unit stride along d, `weight_row_stride` elements between rows (>= d), any alignment
+ *   tokens   device [N] int64 or null, shared by the planes
+ * One workgroup scores one vocabulary chunk of 32 positions of a group of RUNIA_LENS_GROUP_PLANES planes (with a final
+ * plane: that plane and the next RUNIA_LENS_GROUP_PLANES - 1 others), RUNIA_LENS_VOCAB_STEP ids per step, 2 x 2 tiles of
+ * RUNIA_LENS_VOCAB_TILE x 32 per wave; V is cut into S(V) = ceil(steps / ceil(steps / RUNIA_LENS_MAX_SPLIT)) chunks, steps =
+ * ceil(V / RUNIA_LENS_VOCAB_STEP) - a function of V alone, so a row's bits do not depend on N or on the other rows - and a
+ * second kernel folds the S records of a row in ascending chunk order in f64.  No atomics: the same call gives the same bits.
+ * planes, N, V, d >= 1, V <= RUNIA_LENS_MAX_VOCAB; RUNIA_E_INVALID otherwise, checked on the host before anything else.
+ *   workspace: runia_lens_workspace_bytes(planes, N, V, d) bytes, 16-byte aligned (0 outside the limits): 32 bytes per row and
+ *   chunk for min(steps, RUNIA_LENS_MAX_SPLIT) chunks - V enters through that count alone, nothing of size N x V exists. */
+#define RUNIA_LENS_VOCAB_TILE 32
+#define RUNIA_LENS_VOCAB_STEP 128
+#define RUNIA_LENS_MAX_SPLIT 64
+#define RUNIA_LENS_GROUP_PLANES 4
+#define RUNIA_LENS_MAX_VOCAB (1 << 24)
+int64_t runia_lens_workspace_bytes(int64_t planes, int64_t N, int64_t V, int64_t d);
+int runia_lens_scores(const void* states, const void* weight, int64_t weight_row_stride, int dtype, int64_t planes, int64_t N,
+                      int64_t V, int64_t d, const int64_t* tokens, int64_t final_plane, float* lse, float* entropy,
+                      float* log_prob, float* top_log_prob, int32_t* top_token, float* kl_final, void* workspace,
+                      size_t workspace_bytes, runia_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -9,6 +9,9 @@ made with the same keyword arguments and every score comes from this package's d
 - ``RAUQ``: the deterministic log-probs of that pass and the attention maps, read in place (``RAUQ`` / ``rauq_batch``);
 - ``hidden_score``, ``attention_score``: LLM-Check (``.llm_check``) of the deterministic output's hidden states / attention
   maps at the request's ``layer`` (default 15), read in place; no sampling;
+- ``lens_entropy``, ``lens_log_prob``, ``lens_kl``: the logit lens (``.logit_lens``) of the deterministic output's hidden states at
+  the request's ``layer`` (default 15) - window means of the layer's entropy, of its log-probability of the emitted tokens and
+  of the final layer's divergence from it; the unembedding is ``model.get_output_embeddings().weight``; no sampling;
 - ``normalized_entropy``: ``generation_scores`` of the sampled output;
 - ``eigen_score``: ``eigen_scores`` (one launch of ``runia_eigen_score_batch`` for every prompt's sample group);
 - ``semantic_entropy``: the host function of ``.scores`` with the NLI model (its forward passes are the cost);
@@ -28,6 +31,7 @@ import torch
 from .. import _hip
 from .consistency import SIMILARITIES, scores_by_kind
 from .llm_check import attention_score, hidden_score
+from .logit_lens import logit_lens
 from .logits import generation_scores
 from .rauq import RAUQ, generated_lengths, rauq_batch
 from .scores import eigen_score, semantic_entropy
@@ -36,10 +40,13 @@ __all__ = ["eigen_scores", "compute_uncertainties", "compute_uncertainties_batch
 
 _NEEDS_SAMPLING = {"eigen_score": True, "normalized_entropy": True, "semantic_entropy": True, "perplexity": False,
                    "generation_entropy": False, "RAUQ": False, "lexical_similarity": True, "deg": True, "ecc": True,
-                   "eigv": True, "num_sets": True, "hidden_score": False, "attention_score": False}
+                   "eigv": True, "num_sets": True, "hidden_score": False, "attention_score": False, "lens_entropy": False,
+                   "lens_log_prob": False, "lens_kl": False}
 # LLM-Check request name -> (its function, the generate() output it reads); "layer" defaults to _LLM_CHECK_LAYER
 _LLM_CHECK = {"hidden_score": (hidden_score, "hidden_states"), "attention_score": (attention_score, "attentions")}
 _LLM_CHECK_LAYER = 15
+# logit-lens request name -> field of LogitLensScores; "layer" and the key suffix as for the LLM-Check requests
+_LENS = {"lens_entropy": "mean_entropy", "lens_log_prob": "mean_log_prob", "lens_kl": "mean_kl_final"}
 # request name -> field of ConsistencyScores
 _CONSISTENCY = {"lexical_similarity": "lexical_similarity", "deg": "u_deg", "ecc": "u_ecc", "eigv": "u_eigv",
                 "num_sets": "num_sets"}
@@ -83,7 +90,7 @@ def _score_name(req: Dict[str, Any]) -> str:
         if similarity not in SIMILARITIES:
             raise KeyError(similarity)
         return method if similarity == SIMILARITIES[0] else f"{method}_{similarity}"
-    if method in _LLM_CHECK:
+    if method in _LLM_CHECK or method in _LENS:
         layer = int(req.get("layer", _LLM_CHECK_LAYER))
         return method if layer == _LLM_CHECK_LAYER else f"{method}_{layer}"
     return method
@@ -123,6 +130,39 @@ def _llm_check(req, det, **windows) -> torch.Tensor:
     return fn(getattr(det, source), (int(req.get("layer", _LLM_CHECK_LAYER)),), **windows)[:, 0]
 
 
+def _lens_parts(model, requests):
+    """``{id(request): (weight, norm)}`` of the logit-lens requests; ValueError for a head the kernel does not model."""
+    parts = {}
+    for req in requests:
+        if req["method_name"] not in _LENS:
+            continue
+        head = model.get_output_embeddings()
+        if head is None or getattr(head, "weight", None) is None:
+            raise ValueError("the logit lens needs model.get_output_embeddings().weight")
+        if getattr(head, "bias", None) is not None:
+            raise ValueError("the logit lens does not model an lm_head bias")
+        config = getattr(model, "config", None)
+        for name in ("final_logit_softcapping", "logit_scale"):
+            if getattr(config, name, None) is not None:
+                raise ValueError(f"the logit lens does not model config.{name}={getattr(config, name)!r}")
+        norm = req.get("norm")
+        if norm is None:
+            base = getattr(model, "base_model", None)
+            norm = next((getattr(base, n) for n in ("norm", "final_layernorm", "ln_f") if getattr(base, n, None) is not None), None)
+        if norm is None:
+            raise ValueError('no final norm found (base_model.norm, .final_layernorm, .ln_f): name it in the request\'s "norm"')
+        parts[id(req)] = (head.weight, norm)
+    return parts
+
+
+def _lens(req, parts, det, **windows) -> torch.Tensor:
+    """(B,) f64 window mean of a logit-lens score of the deterministic generation at the request's layer, on the device."""
+    weight, norm = parts[id(req)]
+    scores = logit_lens(det.hidden_states, weight, (int(req.get("layer", _LLM_CHECK_LAYER)),), sequences=det.sequences,
+                        norm=norm, **windows)
+    return getattr(scores, _LENS[req["method_name"]])[:, 0]
+
+
 def _rauq_args(req):
     return (req.get("token_aggregation", "mean_all_tokens"), req.get("head_aggregation", "rollout"),
             req.get("alphas", [0.3]), req.get("ablation", False))
@@ -135,7 +175,8 @@ def compute_uncertainties(model, tokenizer, prompt: str, uncertainty_requests: L
 
     ``uncertainty_requests``: dicts with ``method_name`` in eigen_score, normalized_entropy, semantic_entropy, perplexity,
     generation_entropy, RAUQ, hidden_score, attention_score (LLM-Check at ``"layer"``, default 15; the key gets ``_<layer>``
-    appended for another layer), lexical_similarity, deg, ecc, eigv, num_sets (the last five: sample consistency of the sampled
+    appended for another layer), lens_entropy, lens_log_prob, lens_kl (the logit lens at ``"layer"``, the same key rule; an
+    optional ``"norm"`` names the model's final norm module where it is not ``base_model.norm`` / ``.final_layernorm`` / ``.ln_f``), lexical_similarity, deg, ecc, eigv, num_sets (the last five: sample consistency of the sampled
     ids, ``.consistency``; an optional ``"similarity"`` of ``"rouge_l"`` (default) or ``"jaccard"``, which is appended to the
     key when it is not the default; ``num_sets`` is an int); a RAUQ request also names ``token_aggregation`` and
     ``head_aggregation`` and may give ``alphas`` (default [0.3]) and ``ablation`` (default False).  Returns ``(deterministic_text, scores)``: the text as
@@ -144,6 +185,7 @@ def compute_uncertainties(model, tokenizer, prompt: str, uncertainty_requests: L
     ``"clusters"`` = ``{text: cluster}`` when semantic entropy is requested.  ``entailment``: the NLI ``(model,
     tokenizer)`` for semantic entropy (default: ``microsoft/deberta-v2-xxlarge-mnli`` by name)."""
     names = [_score_name(req) for req in uncertainty_requests]
+    lens_parts = _lens_parts(model, uncertainty_requests)
     inputs = tokenizer(prompt, return_tensors="pt").to(model.device)
     input_length = int(inputs["input_ids"].shape[1])
     nli_model, nli_tokenizer = _entailment_models(entailment, uncertainty_requests)
@@ -174,6 +216,8 @@ def compute_uncertainties(model, tokenizer, prompt: str, uncertainty_requests: L
             scores[name] = RAUQ(det_scores().log_probs, det.attentions, input_length, tok, head, alphas, ablation)
         elif method in _LLM_CHECK:
             scores[name] = float(_llm_check(req, det, input_length=input_length)[0])
+        elif method in _LENS:
+            scores[name] = float(_lens(req, lens_parts, det, input_length=input_length)[0])
         elif method == "normalized_entropy":
             scores[name] = generation_scores(samp.sequences, samp.scores).normalized_entropy
         elif method == "eigen_score":
@@ -225,6 +269,7 @@ def compute_uncertainties_batch(model, tokenizer, prompts: Sequence[str], uncert
     if not prompts or not all(isinstance(p, str) for p in prompts):
         raise ValueError("prompts must be a non-empty sequence of strings")
     names = [_score_name(req) for req in uncertainty_requests]
+    lens_parts = _lens_parts(model, uncertainty_requests)
     B, K = len(prompts), int(num_samples)
     side, pad = tokenizer.padding_side, tokenizer.pad_token
     try:
@@ -285,6 +330,9 @@ def compute_uncertainties_batch(model, tokenizer, prompts: Sequence[str], uncert
         elif method in _LLM_CHECK:
             scores[name] = _llm_check(req, det, input_length=input_length, attention_mask=inputs["attention_mask"],
                                       lengths=det_lengths()).cpu()  # (no pass over the logits)
+        elif method in _LENS:
+            scores[name] = _lens(req, lens_parts, det, input_length=input_length, attention_mask=inputs["attention_mask"],
+                                 lengths=det_lengths()).cpu()
         elif method == "normalized_entropy":
             # per sample row the mean of its finite log-probs (-inf = padding), then -mean over the prompt's K rows
             lp = samp_scores().log_probs

@@ -1754,6 +1754,34 @@ int runia_lens_scores(const void* states, const void* weight, int64_t weight_row
                       float* log_prob, float* top_log_prob, int32_t* top_token, float* kl_final, void* workspace,
                       size_t workspace_bytes, runia_stream_t stream);
 
+/* ---- Embedding-level sample consistency  greedy token matching between a prompt's samples (cons_embed.hip; ---- *
+ * llm_uncertainty/embedding_consistency.py).  Rows are prompt-major: group g is batch rows g*k .. g*k+k-1, the content
+ * of row r the states of ONE layer over its window [s_r, s_r + n_r) of positions (n_r = 0 allowed), read through the step
+ * descriptors of runia_llmcheck_hidden with L = 1.  With center != 0 every token loses m_g, the f64 mean of the group's content
+ * tokens (rounded to f32); x^ = x / |x|, a zero token has cosine 0 with everything.
+ *   cov [groups, k, k] f64:  cov[g, i, j] = (1 / n_i) sum_{a in i} max_{b in j} <x^_a, y^_b>   (i = j included)
+ *   both contents empty: 1; exactly one empty: 0; a state that is NaN or infinite makes every entry of its group NaN and
+ *   changes no other group by a bit.
+ * Five launches: the workspace cleared; the group means (f64 sums in one order); the inverse norms of the centred tokens;
+ * one workgroup per (group, pair i <= j, 128 tokens of i) that sweeps the tokens of j in tiles of 128 - chunks of 64 bytes per
+ * token are centred and scaled in f32, converted to the element type (f16 / bf16: as a hi + lo pair of elements, three products
+ * per pair of operands) and multiplied on the matrix cores (f32 accumulation),
+ * the tile leaves the registers as row maxima (complete in the workgroup) and column maxima (integer atomicMax on ordered
+ * keys across the row blocks); one wave per entry forms the f64 means, pair (j, i) from the column maxima of (i, j).  Nothing
+ * of size T x T or N x d is written.  The same call gives the same bits; a group's bits depend on the group alone.
+ *   rows / host_rows   device / host copies of the groups * k {s_r, n_r} int64 pairs; the host copy is checked: 0 <= n_r <=
+ *                      RUNIA_CONS_EMBED_MAX_T and the window inside the P + n_steps - 1 positions.
+ *   2 <= k <= RUNIA_CONS_MAX_K, groups * k <= 2^20, 1 <= d <= 2^20, dtype 0 f32 / 1 f16 / 2 bf16; RUNIA_E_INVALID otherwise,
+ *   checked on the host before anything else.
+ *   workspace: runia_cons_embed_workspace_bytes(groups, k, max_r n_r, d) bytes, 16-byte aligned (0 outside the limits; the
+ *   query returns int64_t): with Tp = max_r n_r rounded up to 128 (at least 128), 4 bytes per group and feature (d rounded up
+ *   to 32), 4 Tp per row and 8 Tp per (group, pair i <= j). */
+#define RUNIA_CONS_EMBED_MAX_T 1024
+int64_t runia_cons_embed_workspace_bytes(int64_t groups, int64_t k, int64_t T_max, int64_t d);
+int runia_cons_embed(const void* table, const void* rows, const int64_t* host_rows, int dtype, int64_t groups, int64_t k,
+                     int64_t n_steps, int64_t P, int64_t d, int center, double* cov, void* workspace, size_t workspace_bytes,
+                     runia_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

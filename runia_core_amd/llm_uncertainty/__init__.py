@@ -1,6 +1,8 @@
 from .conformal import TokenConformal, TokenSets  # noqa: F401
 from .consistency import (ConsistencyScores, PairCounts, consistency_scores, graph_scores, pairwise_counts,  # noqa: F401
                           pairwise_similarity, word_ids)
+from .embedding_consistency import (EmbeddingSimilarity, embedding_consistency_scores,  # noqa: F401
+                                    embedding_similarity)
 from .llm_check import LLMCheckScores, attention_score, hidden_score, llm_check_scores  # noqa: F401
 from .logit_lens import LogitLensScores, logit_lens  # noqa: F401
 from .logits import GenerationScores, generation_scores, token_entropies, transition_scores  # noqa: F401
@@ -14,4 +16,4 @@ __all__ = ["eigen_score", "semantic_entropy", "rauq_uncertainty", "rauq_uncertai
            "transition_scores", "compute_uncertainties", "compute_uncertainties_batch", "eigen_scores", "TokenConformal",
            "TokenSets", "PairCounts", "ConsistencyScores", "pairwise_counts", "pairwise_similarity", "graph_scores",
            "consistency_scores", "word_ids", "LLMCheckScores", "hidden_score", "attention_score", "llm_check_scores",
-           "LogitLensScores", "logit_lens"]
+           "LogitLensScores", "logit_lens", "EmbeddingSimilarity", "embedding_similarity", "embedding_consistency_scores"]

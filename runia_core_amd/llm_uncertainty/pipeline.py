@@ -16,7 +16,9 @@ made with the same keyword arguments and every score comes from this package's d
 - ``eigen_score``: ``eigen_scores`` (one launch of ``runia_eigen_score_batch`` for every prompt's sample group);
 - ``semantic_entropy``: the host function of ``.scores`` with the NLI model (its forward passes are the cost);
 - ``lexical_similarity``, ``deg``, ``ecc``, ``eigv``, ``num_sets``: the sample-consistency scores of ``.consistency`` from the
-  sampled ids alone (one ``runia_cons_pairs`` call and one ``runia_cons_graph`` launch per call, shared by the requests).
+  sampled ids alone (one ``runia_cons_pairs`` call and one ``runia_cons_graph`` launch per call, shared by the requests), or,
+  with ``"similarity": "embedding"``, from the sampled output's hidden states (``.embedding_consistency``: one
+  ``runia_cons_embed`` call per distinct ``layer``).
 
 ``model.compute_transition_scores`` is not called.  ``entailment=(nli_model, nli_tokenizer)`` is this package's
 addition: without it a ``semantic_entropy`` request loads ``microsoft/deberta-v2-xxlarge-mnli`` by name, as the
@@ -30,6 +32,7 @@ import torch
 
 from .. import _hip
 from .consistency import SIMILARITIES, scores_by_kind
+from .embedding_consistency import embedding_consistency_scores
 from .llm_check import attention_score, hidden_score
 from .logit_lens import logit_lens
 from .logits import generation_scores
@@ -50,6 +53,7 @@ _LENS = {"lens_entropy": "mean_entropy", "lens_log_prob": "mean_log_prob", "lens
 # request name -> field of ConsistencyScores
 _CONSISTENCY = {"lexical_similarity": "lexical_similarity", "deg": "u_deg", "ecc": "u_ecc", "eigv": "u_eigv",
                 "num_sets": "num_sets"}
+_EMBEDDING = "embedding"  # the "similarity" of the consistency requests that is scored from hidden states, at "layer"
 _NLI_MODEL = "microsoft/deberta-v2-xxlarge-mnli"
 
 
@@ -87,6 +91,9 @@ def _score_name(req: Dict[str, Any]) -> str:
         return f"RAUQ_{req['token_aggregation']}_{req['head_aggregation']}"
     if method in _CONSISTENCY:
         similarity = req.get("similarity", SIMILARITIES[0])
+        if similarity == _EMBEDDING:
+            layer = int(req.get("layer", _LLM_CHECK_LAYER))
+            return f"{method}_{similarity}" if layer == _LLM_CHECK_LAYER else f"{method}_{similarity}_{layer}"
         if similarity not in SIMILARITIES:
             raise KeyError(similarity)
         return method if similarity == SIMILARITIES[0] else f"{method}_{similarity}"
@@ -98,9 +105,26 @@ def _score_name(req: Dict[str, Any]) -> str:
 
 def _consistency(requests, samp, input_length: int, num_samples: int, eos):
     """``{similarity: ConsistencyScores}`` of the sampled rows for every similarity the requests name: one count call and
-    one graph launch, whatever the number of requests."""
+    one graph launch, whatever the number of requests (``("embedding", layer)`` keys: see below)."""
     kinds = [req.get("similarity", SIMILARITIES[0]) for req in requests if req["method_name"] in _CONSISTENCY]
-    return scores_by_kind(samp.sequences[:, input_length:], num_samples, kinds, eos_token_id=eos)
+    kinds = [kind for kind in kinds if kind != _EMBEDDING]
+    by_kind = scores_by_kind(samp.sequences[:, input_length:], num_samples, kinds, eos_token_id=eos) if kinds else {}
+    # the embedding similarity: the samples' own states over their generated tokens, one kernel call per distinct layer
+    layers = dict.fromkeys(int(req.get("layer", _LLM_CHECK_LAYER)) for req in requests
+                           if req["method_name"] in _CONSISTENCY and req.get("similarity") == _EMBEDDING)
+    if layers:
+        steps = len(samp.hidden_states)  # = the generated columns, which generated_lengths never exceeds
+        lengths = (generated_lengths(samp.sequences, input_length, eos) if eos is not None
+                   else torch.full((int(samp.sequences.shape[0]),), steps, dtype=torch.int64))
+        for layer in layers:
+            by_kind[_EMBEDDING, layer] = embedding_consistency_scores(samp.hidden_states, num_samples, layer, lengths=lengths)
+    return by_kind
+
+
+def _consistency_of(req, by_kind):
+    """The ConsistencyScores a consistency request reads."""
+    similarity = req.get("similarity", SIMILARITIES[0])
+    return by_kind[(similarity, int(req.get("layer", _LLM_CHECK_LAYER))) if similarity == _EMBEDDING else similarity]
 
 
 def _entailment_models(entailment, requests):
@@ -178,7 +202,8 @@ def compute_uncertainties(model, tokenizer, prompt: str, uncertainty_requests: L
     appended for another layer), lens_entropy, lens_log_prob, lens_kl (the logit lens at ``"layer"``, the same key rule; an
     optional ``"norm"`` names the model's final norm module where it is not ``base_model.norm`` / ``.final_layernorm`` / ``.ln_f``), lexical_similarity, deg, ecc, eigv, num_sets (the last five: sample consistency of the sampled
     ids, ``.consistency``; an optional ``"similarity"`` of ``"rouge_l"`` (default) or ``"jaccard"``, which is appended to the
-    key when it is not the default; ``num_sets`` is an int); a RAUQ request also names ``token_aggregation`` and
+    key when it is not the default, or ``"embedding"``: the greedy token matching of ``.embedding_consistency`` on the samples'
+    hidden states at ``"layer"`` (default 15), key ``<method>_embedding`` or ``<method>_embedding_<layer>``; ``num_sets`` is an int); a RAUQ request also names ``token_aggregation`` and
     ``head_aggregation`` and may give ``alphas`` (default [0.3]) and ``ablation`` (default False).  Returns ``(deterministic_text, scores)``: the text as
     the reference returns it (a list of one string) and ``{key: score}`` with keys ``method_name`` or
     ``RAUQ_<token_aggregation>_<head_aggregation>``, Python floats (a list for RAUQ with ``ablation=True``), plus
@@ -226,7 +251,7 @@ def compute_uncertainties(model, tokenizer, prompt: str, uncertainty_requests: L
             if "cons" not in cache:
                 cache["cons"] = _consistency(uncertainty_requests, samp, input_length, num_samples,
                                              _eos_ids(model, gen_config))
-            value = getattr(cache["cons"][req.get("similarity", SIMILARITIES[0])], _CONSISTENCY[method])[0]
+            value = getattr(_consistency_of(req, cache["cons"]), _CONSISTENCY[method])[0]
             scores[name] = int(value) if method == "num_sets" else float(value)
         else:  # semantic_entropy
             entropy, clusters = semantic_entropy(nli_model, nli_tokenizer, sampled_texts)
@@ -345,7 +370,7 @@ def compute_uncertainties_batch(model, tokenizer, prompts: Sequence[str], uncert
         elif method in _CONSISTENCY:
             if "cons" not in cache:
                 cache["cons"] = _consistency(uncertainty_requests, samp, input_length, K, _eos_ids(model, gen_config))
-            value = getattr(cache["cons"][req.get("similarity", SIMILARITIES[0])], _CONSISTENCY[method]).cpu()
+            value = getattr(_consistency_of(req, cache["cons"]), _CONSISTENCY[method]).cpu()
             scores[name] = value.to(torch.int64) if method == "num_sets" else value
         else:  # semantic_entropy
             ent, groups = [], []
